@@ -1,9 +1,20 @@
 #!/usr/bin/env python3
 """Benchmark of the Splice per-pair optimisation step on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: either under a launcher -- python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
    ... bench.py --gpus N ... -- or bare: the script then starts its own N workers, one per GPU via HIP_VISIBLE_DEVICES)
+
+A plain run does only what the headline needs: set up, W warm-up steps, exactly K timed steps (value / ms_per_step), the
+outputs of the last timed step if --dump-outputs is given, the JSON line.  --full adds everything else the line can carry
+(below): blocks of K steps repeated until >= 1 s is timed, the pairs-per-GPU sweep, the train_model regime, the live-timed
+kernel families (roofline, north_star), the box's copy rate and the CPU baseline.
+
+--dump-outputs DIR (rank 0): after the timed steps, what a caller of the step receives from the last of them, as float32
+DIR/<name>.npy -- losses [P, 8] (the step's return value; one row per ViT scale with --scales), the generator parameters
+after the Adam update, the gradient of that step and the BatchNorm running statistics, each [P, n].  An array above
+DUMP_ARRAY_BYTES is replaced by a fixed seeded sample of its flattened elements.  Inputs and weights are seeded, so runs
+with the same arguments compare output for output (with --full the number of timed blocks, hence of steps, varies).
 
 Workload (config.workload): BASELINE.json configs[1] -- one 224x224 structure/appearance pair,
 DINO ViT-B/8 (T = 785 tokens), bf16 ViT / fp32 generator, reference hyper-parameters
@@ -13,7 +24,7 @@ LossG.forward, backward, Adam (train.py:56-80), nothing cached between steps.  E
 optimises its OWN pair on its own GPU (independent units, no data-path collective): weak scaling;
 value = total steps of all ranks / max-over-ranks time.
 
-Printed JSON (one line, rank 0) additionally carries
+Printed JSON (one line, rank 0) additionally carries (--full; null in a plain run)
   roofline     : the live-timed kernel family with the largest share of the step (no family is excluded: at one 224 pair that is the
                  generator chain, reported per kernel -- its three longest kernels with their own FLOPs / bytes -- and as a roll-up): algorithmic
                  FLOPs of one call / the kernels' own begin-end time stamps; every other family under other_kernels
@@ -288,7 +299,42 @@ def median_block(reduced):
     return order[(len(order) - 1) // 2]
 
 
-def timing_record(K, reduced, first_step, entire_every):
+DUMP_ARRAY_BYTES = 12 << 20   # per dumped array; four arrays stay below 64 MB in all
+
+
+def step_outputs(eng):
+    """Host float32 copies of what a caller of the timed step receives from its last call: the loss rows the step returns, the
+    generator parameters after the update, that step's gradient and the BatchNorm running statistics ([P, n] each)."""
+    import torch
+    e0 = eng.engines[0] if hasattr(eng, "engines") else eng   # MultiScaleEngine: one parameter set, one loss row per scale
+    losses = torch.cat([e.losses_dev for e in eng.engines]) if hasattr(eng, "engines") else eng.losses_dev
+    n, P, stride = e0.gen.numel, e0.P, e0.stride
+    return {"losses": _host(losses),
+            "params": _host(e0.params.view(P, stride)[:, :n]), "grads": _host(e0.grads.view(P, stride)[:, :n]),
+            "bn_running_stats": _host(e0.running)}
+
+
+def _host(t):
+    return t.detach().float().cpu().numpy()
+
+
+def dump_outputs(out_dir, arrays, max_bytes=DUMP_ARRAY_BYTES):
+    """Writes out_dir/<name>.npy; an array above max_bytes becomes a sorted, seeded sample of its flattened elements (the same
+    indices on every run and build for the same shape)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes > max_bytes:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, max_bytes // 4, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = list(a.shape)
+    return written
+
+
+def timing_record(K, reduced, first_step, entire_every, min_seconds=MIN_TIMED_SECONDS):
     mid = median_block(reduced)
     ms = [round(t / K * 1e3, 4) for t in reduced]
     ent = [sum(1 for st in range(first_step + b * K, first_step + (b + 1) * K) if entire_every and st % entire_every == 0) for b in range(len(reduced))]
@@ -296,9 +342,11 @@ def timing_record(K, reduced, first_step, entire_every):
                  "ms_per_step_median_block": ms[mid], "entire_image_steps_total": sum(ent),
                  "ms_per_step_by_block": ms if len(ms) <= 64 else ms[:64] + ["..."], "ms_per_step_min": min(ms), "ms_per_step_max": max(ms),
                  "entire_image_steps_by_block": ent if len(ent) <= 64 else ent[:64] + ["..."],
-                 "rule": f"W warm-up steps, then blocks of exactly K steps (barrier + synchronize on both sides, max over ranks) until >= {MIN_TIMED_SECONDS} s "
-                         "are timed; value / ms_per_step = ALL timed steps / ALL timed seconds (the periodic entire-image steps are in it at their true "
-                         "frequency); the median block is kept as a robustness figure"}
+                 "rule": (f"W warm-up steps, then blocks of exactly K steps (barrier + synchronize on both sides, max over ranks) until >= {min_seconds} s "
+                          "are timed (--full); value / ms_per_step = ALL timed steps / ALL timed seconds (the periodic entire-image steps are in it at their true "
+                          "frequency); the median block is kept as a robustness figure") if min_seconds > 0 else
+                         ("W warm-up steps, then ONE block of exactly K steps (barrier + synchronize on both sides, max over ranks); value / ms_per_step = "
+                          "K / its seconds (the periodic entire-image steps are in it where they fall)")}
 
 
 def train_regime_leg(eng, A, B, steps=120):
@@ -342,8 +390,9 @@ def stub_main(args, ms, world):
     rep = Replicas(backend="gloo", device=None)
     host = pin_worker(rep.local_rank, world, 0)
     eng = StubEngine(ms * (1.0 + 0.5 * rep.rank))   # rank r is slower: the max over ranks must show it
-    local, reduced = time_blocks(eng, None, None, args.steps, args.warmup, rep.barrier, rep, min_seconds=float(os.environ.get("SPLICE_BENCH_STUB_MIN_S", "0.2")))
-    mid, timing = timing_record(args.steps, reduced, args.warmup, 0)
+    min_s = float(os.environ.get("SPLICE_BENCH_STUB_MIN_S", "0.2")) if args.full else 0.0
+    local, reduced = time_blocks(eng, None, None, args.steps, args.warmup, rep.barrier, rep, min_seconds=min_s)
+    mid, timing = timing_record(args.steps, reduced, args.warmup, 0, min_s)
     per_rank = rep.gather_floats(sum(local))
     elapsed = sum(reduced)
     k_total = args.steps * len(reduced)
@@ -372,7 +421,11 @@ def main():
                                                 "graphs replay), every crop resized to --size (224), the entire HxW image through Resize(224, max_size=480); one pair, no sweep")
     ap.add_argument("--model", default="dino_vitb8")
     ap.add_argument("--pairs", type=int, default=1, help="pairs optimised side by side per GPU in the timed region (1 = the reference's unit: the latency form of the metric)")
-    ap.add_argument("--pairs-sweep", default="2,4,8,12,16,32", help="additional pairs-per-GPU settings timed briefly after the main region (throughput form: pairs/hr); '' = off")
+    ap.add_argument("--full", action="store_true", help="besides the headline: timed blocks repeated until >= 1 s, the pairs sweep, the train_model regime, "
+                                                        "the live-timed kernel families (roofline, north_star), the box's copy rate and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's losses, parameters, gradient and BatchNorm "
+                                                                        "statistics as float32 DIR/<name>.npy (rank 0)")
+    ap.add_argument("--pairs-sweep", default="2,4,8,12,16,32", help="(--full) additional pairs-per-GPU settings timed briefly after the main region (throughput form: pairs/hr); '' = off")
     ap.add_argument("--fp8", nargs="?", const="gemm", default=None, choices=("gemm", "attention"),
                     help="fp8 operand path (own, looser tolerance table: an APPROXIMATE mode, tests/test_fp8_gpu.py).  '--fp8' = '--fp8 gemm': e4m3 QKV / fc1 / fc2 "
                          "projections + key self-similarity Gram on the fp8 MFMA (the fastest setting; the config key fp8: True); "
@@ -382,12 +435,14 @@ def main():
                                                  "one fused step per scale + one Adam (MultiScaleEngine); disables the pairs sweep and the train-regime leg")
     ap.add_argument("--full-top-block", action="store_true", help="compute the whole top ViT block (default: behind its QKV projection only the [CLS] rows, "
                                                                   "all the losses read besides the keys)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-train-regime", action="store_true", help="skip the train_model-shaped leg (random crops + augmentations + logging)")
-    ap.add_argument("--prof-kernels", default="4,1,2,9,5,11,3,6,10,7,8", help="kernel families timed live for the roofline leg ('' = off; default: all): 4 fc2 fwd, 1 fc1 fwd, 2 qkv fwd, 9 proj fwd, "
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-train-regime", action="store_true", help="(--full) skip the train_model-shaped leg (random crops + augmentations + logging)")
+    ap.add_argument("--prof-kernels", default="4,1,2,9,5,11,3,6,10,7,8", help="(--full) kernel families timed live for the roofline leg ('' = off; default: all): 4 fc2 fwd, 1 fc1 fwd, 2 qkv fwd, 9 proj fwd, "
                                                                   "5 split-K dgrads, 11 bf16-output dgrads, 3 attention fwd, 6 attention bwd, 10 LayerNorm, 7 generator chain, 8 key self-similarity")
     ap.add_argument("--allow-dev-env", action="store_true", help="run although a debugging / work-skipping SPLICE_* switch is set (the JSON line then carries config.dev_env)")
     args = ap.parse_args()
+    if not args.full:   # a plain run: set up, warm up, the K timed steps, the outputs, the line -- no other leg
+        args.pairs_sweep, args.prof_kernels, args.no_train_regime, args.no_cpu_baseline = "", "", True, True
     fp8_mode = False if not args.fp8 else ("attention" if (args.fp8 == "attention" or args.fp8_attention == "on") else "gemm")   # splice_amd.vit.fp8_mode
     stub_ms = os.environ.get("SPLICE_BENCH_STUB")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -455,8 +510,12 @@ def main():
         rep.barrier()
         torch.cuda.synchronize()
 
-    local_blocks, reduced_blocks = time_blocks(eng, A, B, K, W, barrier, rep, E=E_in)
-    mid, timing = timing_record(K, reduced_blocks, W, eng.cfg["entire_A_every"] if not scales else eng.engines[0].cfg["entire_A_every"])
+    min_s = MIN_TIMED_SECONDS if args.full else 0.0
+    local_blocks, reduced_blocks = time_blocks(eng, A, B, K, W, barrier, rep, min_seconds=min_s, E=E_in)
+    mid, timing = timing_record(K, reduced_blocks, W, eng.cfg["entire_A_every"] if not scales else eng.engines[0].cfg["entire_A_every"], min_s)
+    dumped = None
+    if args.dump_outputs and rank == 0:   # before any other leg steps the same engine on
+        dumped = {"dir": args.dump_outputs, "last_step": eng.step_idx, "arrays": dump_outputs(args.dump_outputs, step_outputs(eng))}
     n_blocks = len(reduced_blocks)
     elapsed = sum(local_blocks)          # this rank's timed seconds over all blocks
     losses = eng.losses() if (P == 1 or scales) else eng.losses(0)
@@ -605,10 +664,12 @@ def main():
                  "gflop_per_step": round(fl / 1e9, 2), "kernel_ms_per_step": round(ms_, 4), "achieved_tflops": round(fl / (ms_ * 1e-3) / 1e12, 1),
                  "peak_tflops": BF16_MFMA_PEAK, "frac": round(fl / (ms_ * 1e-3) / 1e12 / BF16_MFMA_PEAK, 4), "target": 0.40,
                  "by_family": {fams[f][0].split(" ")[0]: round(fams[f][2] / (prof[f][0] / prof[f][1] * 1e-3) / 1e12 / BF16_MFMA_PEAK, 4) for f in (3, 6, 8)}}
-    try:
-        box_copy = hbm_copy_rate(dev)
-    except Exception:
-        box_copy = None
+    box_copy = None
+    if args.full:
+        try:
+            box_copy = hbm_copy_rate(dev)
+        except Exception:
+            pass
     cpu = None
     if not args.no_cpu_baseline and world == 1:
         try:
@@ -635,7 +696,7 @@ def main():
                                                    for k, v in sorted(sweep.items())},
                    "train_model_regime": train_leg,
                    "generator_dtype": "f32", "last_loss": round(losses["loss"], 5), "box_hbm_f32_copy_gb_s": box_copy,
-                   "env": library_env(), "host": host, "timing": timing},
+                   "env": library_env(), "host": host, "timing": timing, "full": args.full, "outputs": dumped},
         "roofline": roof, "north_star": north, "cpu_baseline": cpu,
     }
     if bad:

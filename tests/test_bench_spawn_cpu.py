@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,7 +21,7 @@ def _run(extra_env, *argv):
 
 def test_spawn_two_workers_stub():
     r = _run({"SPLICE_BENCH_STUB": "20", "SPLICE_BENCH_STUB_GPUS": "4", "HIP_VISIBLE_DEVICES": "3,5,6,7", "SPLICE_CONV_TILE": "1"},
-             "--gpus", "2", "--steps", "6", "--warmup", "1")
+             "--gpus", "2", "--steps", "6", "--warmup", "1", "--full")
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout            # rank 0 prints the one line
@@ -37,13 +38,44 @@ def test_spawn_two_workers_stub():
     assert 29.0 < out["ms_per_step"] < 45.0
     assert cfg["host"]["threads"] >= 1
     assert cfg["env"] == {"SPLICE_CONV_TILE": "1"}   # library switches are echoed, bench plumbing is not
-    # VERDICT r3 #9: blocks of exactly K steps repeated until the minimum timed duration (0.2 s for the stub; 1 s for real runs),
+    # VERDICT r3 #9 (--full): blocks of exactly K steps repeated until the minimum timed duration (0.2 s for the stub; 1 s for real runs),
     # round 5: value / ms_per_step are ALL timed steps over ALL timed seconds; the median block is a robustness figure
     t = cfg["timing"]
     assert t["steps_per_block"] == 6 and t["blocks"] >= 2 and t["timed_seconds"] >= 0.2 and len(t["ms_per_step_by_block"]) == t["blocks"]
     assert abs(t["timed_seconds"] / (t["blocks"] * t["steps_per_block"]) * 1e3 - out["ms_per_step"]) < 1e-2
     assert abs(t["ms_per_step_by_block"][t["median_block"]] - t["ms_per_step_median_block"]) < 1e-6
     assert t["ms_per_step_min"] <= out["ms_per_step"] <= t["ms_per_step_max"]
+
+
+def test_plain_run_times_exactly_k_steps_stub():
+    """Without --full the line is the headline alone: one block of exactly --steps steps, no other leg."""
+    # (device ids no GPU box has, as above: the stub workers must never open a real device)
+    r = _run({"SPLICE_BENCH_STUB": "20", "SPLICE_BENCH_STUB_GPUS": "4", "HIP_VISIBLE_DEVICES": "3,5,6,7"}, "--gpus", "2", "--steps", "5", "--warmup", "1")
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    out = json.loads(lines[0])
+    t = out["config"]["timing"]
+    assert out["steps"] == 5 and out["warmup"] == 1 and t["blocks"] == 1 and t["steps_per_block"] == 5
+    assert abs(t["timed_seconds"] / 5 * 1e3 - out["ms_per_step"]) < 2e-2
+    assert 29.0 < out["ms_per_step"] < 45.0        # the slower rank's 30 ms steps
+    assert out["roofline"] is None and out["cpu_baseline"] is None
+
+
+def test_dump_outputs_caps_and_samples_deterministically(tmp_path):
+    sys.path.insert(0, ROOT)
+    import bench
+    big = np.arange(3_000_000, dtype=np.float64).reshape(3, -1)
+    small = np.linspace(0.0, 1.0, 16).reshape(2, 8)
+    cap = 1 << 20
+    w = bench.dump_outputs(str(tmp_path / "a"), {"big": big, "small": small}, max_bytes=cap)
+    bench.dump_outputs(str(tmp_path / "b"), {"big": 2.0 * big, "small": small}, max_bytes=cap)
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float32 and a.shape == (cap // 4,) and w["big"] == [cap // 4]
+    assert np.all(np.diff(a) > 0)                  # distinct elements in their original order
+    assert np.array_equal(b, 2.0 * a)              # the same sample indices for the same shape
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and w["small"] == [2, 8] and np.array_equal(s, small.astype(np.float32))
 
 
 def test_spawn_fails_cleanly_without_enough_gpus():
