@@ -296,6 +296,17 @@ int splice_gen_running_stats_update(void* const* plans, int n_plans, float* runn
  * step counts from 1; zero_grad != 0 also clears grads (optimizer.zero_grad, train.py:56) */
 int splice_adam_step(float* params, float* grads, float* m, float* v, long long n, float lr, float beta1,
                      float beta2, float eps, int step, int zero_grad, splice_stream_t stream);
+/* One step of the optimiser the config names (util/util.py:28-39: optimizer adam / rmsprop / sgd, every other argument at
+ * torch.optim's default) fused over the arena.  kind 0 Adam: hp0 = beta1, hp1 = beta2, step counts from 1 (as splice_adam_step).
+ * kind 1 RMSprop: hp0 = alpha (0.99), v holds square_avg, m is not touched (may be NULL); no momentum, not centred.  kind 2 SGD:
+ * p -= lr * g; m and v are not touched (may be NULL).  zero_grad != 0 also clears grads.  An element's result does not depend on
+ * where it sits in the arena. */
+int splice_optim_step(int kind, float* params, float* grads, float* m, float* v, long long n, float lr, float hp0, float hp1,
+                      float eps, int step, int zero_grad, splice_stream_t stream);
+/* as splice_optim_step, plus g2 (may be NULL): a second gradient arena of n floats folded in first (grads += g2, written back), and
+ * lr_dev (may be NULL): a device float the kernel reads as the learning rate when it runs (lr is then ignored) */
+int splice_optim_step_ex(int kind, float* params, float* grads, const float* g2, float* m, float* v, long long n, float lr,
+                         const float* lr_dev, float hp0, float hp1, float eps, int step, int zero_grad, splice_stream_t stream);
 
 /* live timing of one kernel family (bench.py roofline leg, prof.hip): while a family is armed its kernels are launched with
  * a start / stop event pair each (hipExtLaunchKernelGGL: the kernel's own begin / end time stamps, as rocprofv3 reports them).
@@ -383,6 +394,13 @@ int splice_step_set_crops(void* step, int a_h, int a_w, int b_h, int b_w);
  * parameters untouched; several losses (the same crops at several ViT input scales) are summed that way before ONE
  * splice_adam_step */
 int splice_step_set_mode(void* step, int skip_adam, int accumulate);
+/* The optimiser of the step's update: kind / hp0 / hp1 / eps as splice_optim_step (0 Adam, 1 RMSprop with v = square_avg,
+ * 2 SGD).  Default: Adam with the config's beta1 / beta2 / eps.  A change drops the handle's captured graphs. */
+int splice_step_set_optimizer(void* step, int kind, float hp0, float hp1, float eps);
+/* Learning rate of the next splice_step_run and every later one until the next call (a schedule: the host calls it once per
+ * step).  The value is staged by the step's input-staging launch (phase 1) and the update reads it from device memory, so a
+ * replayed graph uses the lr of its own step.  Before the first call the handle uses the config's lr, as a kernel argument. */
+int splice_step_set_lr(void* step, float lr);
 /* Run part of a step: phases = mask of 1 generator forward (+ input staging), 2 ViT forward / losses / ViT backward down to
  * the gradient of the generated images, 4 generator backward (+ Adam unless splice_step_set_mode disables it); default 7.
  * leader != NULL (phases must be 2; another step handle with the same image shapes): this handle reads the leader's staged

@@ -790,4 +790,34 @@ int splice_adam_step(float* params, float* grads, float* m, float* v, long long 
     RC(adam_launch(params, grads, m, v, (size_t)n, lr, beta1, beta2, eps, step, zero_grad, (hipStream_t)stream));
     return SPLICE_OK;
 }
+
+// One step of the configured optimiser over a flat arena (util/util.py:28-39): kind 0 Adam (hp0 = beta1, hp1 = beta2, step >= 1),
+// 1 RMSprop (hp0 = alpha; v = square_avg, m unused), 2 SGD (m, v unused).  g2 (may be NULL): second gradient arena, g += g2 first.
+// lr_dev (may be NULL): device float read by the kernel instead of lr.
+int splice_optim_step_ex(int kind, float* params, float* grads, const float* g2, float* m, float* v, long long n, float lr, const float* lr_dev,
+                         float hp0, float hp1, float eps, int step, int zero_grad, splice_stream_t stream) {
+    if (!params || !grads || n < 1) return SPLICE_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    switch (kind) {
+    case SPLICE_OPT_ADAM:
+        if (!m || !v) return SPLICE_ERR_ARG;
+        RC(adam_launch(params, grads, m, v, (size_t)n, lr, hp0, hp1, eps, step, zero_grad, s, g2, lr_dev));
+        break;
+    case SPLICE_OPT_RMSPROP:
+        if (!v) return SPLICE_ERR_ARG;
+        RC(rmsprop_launch(params, grads, v, (size_t)n, lr, hp0, eps, zero_grad, s, g2, lr_dev));
+        break;
+    case SPLICE_OPT_SGD:
+        RC(sgd_launch(params, grads, (size_t)n, lr, zero_grad, s, g2, lr_dev));
+        break;
+    default:
+        splice_set_error("splice_optim_step: unknown optimiser kind %d", kind);
+        return SPLICE_ERR_ARG;
+    }
+    return SPLICE_OK;
+}
+int splice_optim_step(int kind, float* params, float* grads, float* m, float* v, long long n, float lr, float hp0, float hp1, float eps, int step,
+                      int zero_grad, splice_stream_t stream) {
+    return splice_optim_step_ex(kind, params, grads, nullptr, m, v, n, lr, nullptr, hp0, hp1, eps, step, zero_grad, stream);
+}
 }

@@ -112,6 +112,11 @@ struct SpliceStep {
     std::vector<void*> allocs;
     int max_crop_h = 0, max_crop_w = 0;
     int* dev_t = nullptr;        // Adam step count on the device
+    float* dev_lr = nullptr;     // learning rate of the step on the device (staged per step once splice_step_set_lr was called)
+    int lr_set = 0;              // 0: the optimiser node takes cfg.lr as a kernel argument (the handle's behaviour before any splice_step_set_lr)
+    float lr = 0.f;              // value staged into dev_lr by the next run
+    int opt_kind = SPLICE_OPT_ADAM;      // splice_step_set_optimizer; hp0 / hp1 / eps start as cfg.beta1 / beta2 / eps
+    float opt_hp0 = 0.f, opt_hp1 = 0.f, opt_eps = 0.f;
     hipStream_t own_stream = nullptr;
     // Cross-stream events, a RING of sets: an eager step records its fork / join events twice and the next step records them again
     // ~2 ms later, while waits on the previous record may still be queued; every record site has an event of its own and a set is
@@ -218,8 +223,9 @@ __global__ __launch_bounds__(320) void total_loss_kernel(float* lbase, size_t ls
     }
 }
 // All per-step inputs in ONE eager launch in front of the graph replay (three copies + the Adam step count were four
-// launches with ~10-30 us of host/queue gaps between them): up to three fp32 buffers and one int.
-struct StageArgs { const float* src[3]; float* dst[3]; unsigned long long n[3]; int* ip; int iv; };
+// launches with ~10-30 us of host/queue gaps between them): up to three fp32 buffers, one int and (fp != null) one float,
+// the scheduled learning rate.
+struct StageArgs { const float* src[3]; float* dst[3]; unsigned long long n[3]; int* ip; int iv; float* fp; float fv; };
 __global__ __launch_bounds__(256) void stage_inputs_kernel(StageArgs a) {
     const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
 #pragma unroll
@@ -236,7 +242,10 @@ __global__ __launch_bounds__(256) void stage_inputs_kernel(StageArgs a) {
             for (size_t i = gid; i < a.n[k]; i += stride) a.dst[k][i] = a.src[k][i];
         }
     }
-    if (gid == 0) *a.ip = a.iv;
+    if (gid == 0) {
+        *a.ip = a.iv;
+        if (a.fp) *a.fp = a.fv;
+    }
 }
 static float* loss_part(SpliceStep* st, int slot) { return st->losses + 8 + (size_t)slot * st->lp; }   // pair 0; pair p at + p * lstride
 
@@ -377,6 +386,8 @@ int splice_step_create(const splice_step_config* cfg, void* vit_ctx_global, void
     }
     if ((rc = salloc(st, &st->losses, P * st->lstride)) != SPLICE_OK) return fail(rc);
     if ((rc = salloc(st, &st->dev_t, 4)) != SPLICE_OK) return fail(rc);
+    if ((rc = salloc(st, &st->dev_lr, 1)) != SPLICE_OK) return fail(rc);
+    st->opt_hp0 = cfg->beta1; st->opt_hp1 = cfg->beta2; st->opt_eps = cfg->eps;
     if (const char* e = getenv("SPLICE_STEP_GRAPH")) st->use_graph = atoi(e);
     if (const char* e = getenv("SPLICE_STEP_SYNC")) st->dbg_sync = atoi(e);
     if (const char* e = getenv("SPLICE_STEP_OVERLAP")) st->overlap = atoi(e);
@@ -437,6 +448,26 @@ int splice_step_set_mode(void* h, int skip_adam, int accumulate) {
     if (!st || (accumulate && !skip_adam)) return SPLICE_ERR_ARG;
     if (st->skip_adam != (skip_adam ? 1 : 0) || st->accumulate != (accumulate ? 1 : 0)) drop_graphs(st);
     st->skip_adam = skip_adam ? 1 : 0; st->accumulate = accumulate ? 1 : 0;
+    return SPLICE_OK;
+}
+// The optimiser of the step's update (util/util.py:28-39): kind 0 Adam (hp0 = beta1, hp1 = beta2), 1 RMSprop (hp0 = alpha; the v arena
+// holds square_avg, m is not touched), 2 SGD (no moment arena).  Default: Adam with cfg.beta1 / beta2 / eps.  A change drops the
+// handle's graphs.
+int splice_step_set_optimizer(void* h, int kind, float hp0, float hp1, float eps) {
+    SpliceStep* st = (SpliceStep*)h;
+    if (!st || kind < SPLICE_OPT_ADAM || kind > SPLICE_OPT_SGD) return SPLICE_ERR_ARG;
+    if (st->opt_kind != kind || st->opt_hp0 != hp0 || st->opt_hp1 != hp1 || st->opt_eps != eps) drop_graphs(st);
+    st->opt_kind = kind; st->opt_hp0 = hp0; st->opt_hp1 = hp1; st->opt_eps = eps;
+    return SPLICE_OK;
+}
+// The learning rate of the next splice_step_run (a schedule: scheduler.step(), train.py:80).  It is staged into device memory by the
+// step's input-staging launch and read by the optimiser kernel, so a captured graph replays with the lr of every step.  Until the
+// first call the handle keeps cfg.lr as a kernel argument; the first call drops the handle's graphs.
+int splice_step_set_lr(void* h, float lr) {
+    SpliceStep* st = (SpliceStep*)h;
+    if (!st) return SPLICE_ERR_ARG;
+    if (!st->lr_set) drop_graphs(st);
+    st->lr_set = 1; st->lr = lr;
     return SPLICE_OK;
 }
 // Run only part of a step: phases is a mask of 1 = generator forward (and input staging), 2 = ViT forward, losses and ViT backward
@@ -631,9 +662,16 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
         if (do_gb) RC(splice_gen_backward(st->plan_e, params, ip.dxe, grads, 1, s));
     }
     if (!loss_summed) { sum_losses(s); RC(track_running(s)); }
-    // ---- optimizer.step() (train.py:79) over every pair's arena; Adam's step count (>= 1) is read from the device at execution time
+    // ---- optimizer.step() (train.py:79) over every pair's arena; Adam's step count (>= 1) and a scheduled lr are read from the device at
+    // execution time
     SPLICE_DEV_REGION(21);
-    if (do_gb && !st->skip_adam) RC(adam_launch_dev(params, grads, m, v, st->astride ? P * st->astride : (size_t)st->nparams, c.lr, c.beta1, c.beta2, c.eps, st->dev_t, 0, s, adam_g2));
+    if (do_gb && !st->skip_adam) {
+        const size_t n_all = st->astride ? P * st->astride : (size_t)st->nparams;
+        const float* lr_dev = st->lr_set ? st->dev_lr : nullptr;
+        if (st->opt_kind == SPLICE_OPT_RMSPROP) RC(rmsprop_launch(params, grads, v, n_all, c.lr, st->opt_hp0, st->opt_eps, 0, s, adam_g2, lr_dev));
+        else if (st->opt_kind == SPLICE_OPT_SGD) RC(sgd_launch(params, grads, n_all, c.lr, 0, s, adam_g2, lr_dev));
+        else RC(adam_launch_dev(params, grads, m, v, n_all, c.lr, st->opt_hp0, st->opt_hp1, st->opt_eps, st->dev_t, 0, s, adam_g2, lr_dev));
+    }
     return SPLICE_OK;
 }
 
@@ -766,6 +804,7 @@ int splice_step_run(void* h, float* params, float* grads, float* m, float* v, co
         sa.src[1] = B_crop; sa.dst[1] = ip.b_in; sa.n[1] = (size_t)st->Pb * 3 * st->cropb_h * st->cropb_w;
         if (entire) { sa.src[2] = A_entire; sa.dst[2] = ip.e_in; sa.n[2] = (size_t)st->Pe * 3 * c.ent_h * c.ent_w; }
         sa.ip = st->dev_t; sa.iv = step_idx + 1;
+        if (st->lr_set) { sa.fp = st->dev_lr; sa.fv = st->lr; }
         SPLICE_LAUNCH(stage_inputs_kernel, dim3(128 * (P > 4 ? 4 : P)), dim3(256), 0, s, sa);
     }
     // Steps whose shapes differ from the previous step's (the reference's random crop sizes) are launched eagerly.  Capturing EVERY such step into a

@@ -12,6 +12,7 @@ import torch
 
 from . import _lib, synth
 from .generator import GeneratorEngine, GeneratorPlan
+from .util import LrSchedule, fused_optimizer
 from .vit import VitContext, VitEngine, fp8_mode
 
 LOSS_KEYS = ["loss", "loss_global_ssim", "loss_entire_ssim", "loss_entire_cls", "loss_global_cls", "loss_global_id_B"]
@@ -62,8 +63,11 @@ class MultiPairEngine:
         self.n_crops = max(nA, nB)
         if self.n_crops > 1 and len(gen_states) != 1:
             raise ValueError("n_crops > 1 is a property of ONE pair: pass a single generator state")
-        if c["optimizer"] != "adam" or c["scheduler_policy"] != "none":
-            raise NotImplementedError("the fused step implements the reference's default optimizer 'adam' with scheduler 'none'")
+        # optimizer adam / rmsprop / sgd and scheduler_policy none / linear / step / cosine (util/util.py:8-39); the lr of every step is
+        # computed on the host and staged on the device (splice_step_set_lr), so a replayed graph runs with the scheduled value
+        self.opt_kind, *self.opt_hp = fused_optimizer(c)
+        self.schedule = LrSchedule(c)
+        self.lr = None   # the lr the last step used
         self.device = torch.device(device)
         self.P = P = len(gen_states)
         self.vit = vit_engine or VitEngine(c["dino_model_name"], device=device).load_state_dict(vit_state)
@@ -133,6 +137,8 @@ class MultiPairEngine:
                                                  self.plan_a.handle, self.plan_b.handle, self.plan_e.handle if self.plan_e else None, C.byref(h)),
                    "step_create")
         self.handle = h
+        if self.opt_kind != 0:
+            _lib.check(_lib.lib().splice_step_set_optimizer(self.handle, self.opt_kind, *self.opt_hp), "step_set_optimizer")
         _lib.check(_lib.lib().splice_step_set_running_stats(self.handle, _lib.ptr(self.running), self.running.stride(0)), "step_set_running_stats")
         self.losses_dev = torch.zeros(P, 8, device=self.device)
         self.step_idx = -1  # data/Dataset.py:57 -- the first step is 0
@@ -153,6 +159,9 @@ class MultiPairEngine:
         ``_repeat``: another phase of the step just run (``splice_step_set_phases``): no bookkeeping."""
         if not _repeat:
             self.step_idx += 1
+            self.lr = self.schedule.lr(self.step_idx)
+            if self.schedule.policy != "none":   # (without a schedule the handle keeps cfg lr as a kernel argument, as before)
+                _lib.check(_lib.lib().splice_step_set_lr(self.handle, self.lr), "step_set_lr")
         for t, n in ((A_crop, self.slots_ab[0]), (B_crop, self.slots_ab[1])):
             assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
             assert t.numel() == n * 3 * t.shape[-2] * t.shape[-1], (tuple(t.shape), n)
@@ -242,11 +251,11 @@ class SpliceEngine(MultiPairEngine):
 class MultiScaleEngine:
     """One pair, every loss term evaluated at SEVERAL ViT input scales (BASELINE configs[4]: 224 / 320 / 448): the same global
     crops are resized to each ``dino_global_patch_size`` in ``scales`` and the reference loss (util/losses.py:46-72) of every
-    scale is summed; one Adam update per step on the summed gradient.  An extension beyond the reference (it has one
+    scale is summed; one update of the configured optimiser (scheduled lr) per step on the summed gradient.  An extension beyond the reference (it has one
     scale).  The generator runs ONCE per step: the first scale's engine (the leader) does the generator forward and its own
     ViT part, the other scales (followers, ``splice_step_set_phases``) run only their ViT part on the leader's images and add
     their image gradients to the leader's, then the leader backpropagates the summed image gradient through the generator
-    (linear in it, so this equals the sum of the per-scale backpropagations) and the fused Adam launch follows."""
+    (linear in it, so this equals the sum of the per-scale backpropagations) and the fused optimiser launch follows."""
 
     def __init__(self, cfg, vit_state, gen_state, crop_hw, entire_hw=None, scales=(224, 320, 448), device="cuda", vit_engine=None, n_crops=1,
                  fp8=False):
@@ -265,18 +274,22 @@ class MultiScaleEngine:
         self.vit, self.gen = self.engines[0].vit, self.engines[0].gen
         self.params, self.grads = self.engines[0].params, self.engines[0].grads
         self.step_idx = -1
+        self.opt_kind, *self.opt_hp = fused_optimizer(self.cfg)
+        self.schedule = LrSchedule(self.cfg)
+        self.lr = None
 
     def step(self, A_crop, B_crop, A_entire=None):
-        from .generator import adam_step
+        from .generator import optim_step
         self.step_idx += 1
-        e0, c, L = self.engines[0], self.cfg, _lib.lib()
+        e0, L = self.engines[0], _lib.lib()
         _lib.check(L.splice_step_set_phases(e0.handle, 1 | 2, None), "step_set_phases")
         e0.step(A_crop, B_crop, A_entire)                    # G forward, the leader's ViT part
         for e in self.engines[1:]:
             e.step(A_crop, B_crop, A_entire)                 # the other scales' ViT parts: d(images) += ...
         _lib.check(L.splice_step_set_phases(e0.handle, 4, None), "step_set_phases")
         e0.step(A_crop, B_crop, A_entire, _repeat=True)      # G backward of the summed image gradient
-        adam_step(e0.params, e0.grads, e0.m, e0.v, c["lr"], c["optimizer_beta1"], c["optimizer_beta2"], 1e-8, self.step_idx + 1)
+        self.lr = self.schedule.lr(self.step_idx)
+        optim_step(self.opt_kind, e0.params, e0.grads, e0.m, e0.v, self.lr, *self.opt_hp, self.step_idx + 1)
 
     def losses(self):
         """Per-scale loss dicts and their sum: ``{"loss": total, "scales": {224: {...}, ...}}``."""

@@ -159,3 +159,27 @@ class GeneratorPlan:
 def adam_step(params, grads, m, v, lr, beta1, beta2, eps, step, zero_grad=False):
     _lib.check(_lib.lib().splice_adam_step(_lib.ptr(params), _lib.ptr(grads), _lib.ptr(m), _lib.ptr(v), params.numel(), lr, beta1, beta2,
                                            eps, step, int(zero_grad), _lib.current_stream()), "adam_step")
+
+
+OPTIMIZER_KINDS = {"adam": 0, "rmsprop": 1, "sgd": 2}   # the `kind` of splice_optim_step
+
+
+def optim_step(kind, params, grads, m, v, lr, hp0, hp1, eps, step, zero_grad=False, g2=None, lr_dev=None):
+    """One fused optimiser step over a flat arena (``splice_optim_step_ex``): kind 0 Adam (hp0 / hp1 = betas, step >= 1),
+    1 RMSprop (hp0 = alpha, ``v`` = square_avg, ``m`` unused), 2 SGD (``m`` / ``v`` unused).  ``g2``: second gradient arena
+    added to ``grads`` first; ``lr_dev``: one-element device tensor read as the learning rate when the kernel runs."""
+    if kind not in OPTIMIZER_KINDS.values():
+        raise ValueError(f"optim_step: unknown optimiser kind {kind}")
+    m = m if kind == 0 else None            # arenas the kind does not touch are not passed
+    v = v if kind in (0, 1) else None
+    n = params.numel()
+    for name, t, needed in (("params", params, True), ("grads", grads, True), ("g2", g2, False), ("m", m, kind == 0), ("v", v, kind in (0, 1))):
+        if t is None and not needed:
+            continue
+        if t is None or not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n):
+            raise ValueError(f"optim_step: {name} must be a contiguous fp32 CUDA tensor of {n} elements")
+    if lr_dev is not None and not (lr_dev.is_cuda and lr_dev.dtype == torch.float32 and lr_dev.numel() >= 1):
+        raise ValueError("optim_step: lr_dev must be a fp32 CUDA tensor")
+    _lib.check(_lib.lib().splice_optim_step_ex(int(kind), _lib.ptr(params), _lib.ptr(grads), _lib.ptr(g2), _lib.ptr(m), _lib.ptr(v), n,
+                                               float(lr), _lib.ptr(lr_dev), float(hp0), float(hp1), float(eps), int(step), int(zero_grad),
+                                               _lib.current_stream()), "optim_step")

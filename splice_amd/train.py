@@ -196,7 +196,7 @@ def train_model(dataroot, callback=None, cfg_overrides=None, vit_state=None, pro
                 if callback is not None:
                     callback(output[0])
             if progress and (epoch % 50 == 0 or epoch == 1):
-                print(f"Epoch {epoch}: loss={engine.losses()['loss']:.4f} lr={cfg['lr']}")
+                print(f"Epoch {epoch}: loss={engine.losses()['loss']:.4f} lr={engine.lr}")
     finally:
         writer.close()
     return engine
@@ -294,7 +294,7 @@ def train_pairs(dataroots, callback=None, cfg_overrides=None, vit_state=None, pr
                     if callback is not None:
                         callback(p, out[0])
             if progress and (epoch % 50 == 0 or epoch == 1):
-                print(f"Epoch {epoch}: loss=" + ", ".join(f"{d['loss']:.4f}" for d in engine.losses()) + f" lr={cfg['lr']}")
+                print(f"Epoch {epoch}: loss=" + ", ".join(f"{d['loss']:.4f}" for d in engine.losses()) + f" lr={engine.lr}")
     finally:
         for w in writers:
             w.close()

@@ -2,6 +2,7 @@
 over the generator's arena-backed parameters), ``tensor2im``, ``save_result``."""
 from pathlib import Path
 
+import math
 import os
 import numpy as np
 import torch
@@ -44,6 +45,74 @@ def get_optimizer(cfg, params):
     if build is None:
         return NotImplementedError('optimizer [%s] is not implemented', cfg['optimizer'])
     return build(cfg, params)
+
+
+# ---- the same on the host for the fused engines -----------------------------------------------------------------------
+# The reference's loop (train.py:79-80) calls optimizer.step() and then scheduler.step() once per step: step k (0-based) runs with
+# the lr the scheduler holds after k calls.  LrSchedule restates torch's recurrences in Python floats, with the arithmetic of the
+# torch.optim.lr_scheduler classes above in the same order (CosineAnnealingLR and StepLR are chainable recurrences, not closed
+# forms), so every value equals torch's float for float; a sequential lr() call costs about a microsecond.
+class LrSchedule:
+    """``lr(k)``: learning rate of optimisation step ``k`` (0-based) under the config's ``scheduler_policy`` with ``lr``,
+    ``n_epochs``, ``scheduler_n_epochs_decay`` and ``scheduler_lr_decay_iters`` (the arguments train.py passes to get_scheduler).
+    Policies: none, linear, step, cosine.  ``plateau`` is refused: the reference calls ``scheduler.step()`` without a metric
+    (train.py:80), which ReduceLROnPlateau rejects, and a plateau rule would need the loss on the host every step."""
+
+    POLICIES = ("none", "linear", "step", "cosine")
+
+    def __init__(self, cfg):
+        self.policy = cfg.get("scheduler_policy", "none")
+        if self.policy == "plateau":
+            raise NotImplementedError("scheduler_policy 'plateau' is not supported: the reference's loop calls scheduler.step() with no metric "
+                                      "(train.py:80), which ReduceLROnPlateau rejects, and a plateau rule would need the loss on the host every step")
+        if self.policy not in self.POLICIES:
+            raise NotImplementedError(f"learning rate policy [{self.policy}] is not implemented")
+        self.base_lr = cfg["lr"]
+        if self.policy == "linear":
+            self.span = float(cfg["scheduler_n_epochs_decay"] + 1)
+        elif self.policy == "step":
+            self.step_size = cfg["scheduler_lr_decay_iters"]
+            if self.step_size is None or self.step_size < 1:
+                raise ValueError("scheduler_policy 'step' needs scheduler_lr_decay_iters >= 1")
+        elif self.policy == "cosine":
+            self.T_max, self.eta_min = cfg["n_epochs"], 0
+            if self.T_max is None or self.T_max < 1:
+                raise ValueError("scheduler_policy 'cosine' needs n_epochs >= 1")
+        self._k, self._lr = 0, self.base_lr   # recurrence state: lr after _k scheduler steps
+
+    def lr(self, k):
+        if self.policy == "none":      # LambdaLR(lambda _: 1)
+            return self.base_lr * 1
+        if self.policy == "linear":    # LambdaLR, closed form
+            return self.base_lr * max(1.0 - max(0, k) / self.span, 0)
+        if k < self._k:
+            self._k, self._lr = 0, self.base_lr
+        while self._k < k:
+            self._k += 1
+            self._lr = self._next(self._k, self._lr)
+        return self._lr
+
+    def _next(self, e, lr):
+        """The lr after the e-th scheduler step from ``lr`` (torch's get_lr with last_epoch = e)."""
+        if self.policy == "step":      # StepLR(step_size=lr_decay_iters, gamma=0.5)
+            return lr if e % self.step_size != 0 else lr * 0.5
+        T, eta = self.T_max, self.eta_min   # CosineAnnealingLR(T_max=n_epochs, eta_min=0)
+        if (e - 1 - T) % (2 * T) == 0:
+            return lr + (self.base_lr - eta) * (1 - math.cos(math.pi / T)) / 2
+        return (1 + math.cos(math.pi * e / T)) / (1 + math.cos(math.pi * (e - 1) / T)) * (lr - eta) + eta
+
+
+def fused_optimizer(cfg):
+    """``(kind, hp0, hp1, eps)`` of the config's ``optimizer`` for the fused update (splice_optim_step): the torch.optim
+    arguments get_optimizer uses, every other one at torch's default."""
+    name = cfg.get("optimizer", "adam")
+    if name == "adam":
+        return 0, cfg["optimizer_beta1"], cfg["optimizer_beta2"], 1e-8
+    if name == "rmsprop":
+        return 1, 0.99, 0.0, 1e-8
+    if name == "sgd":
+        return 2, 0.0, 0.0, 0.0
+    raise NotImplementedError(f"optimizer [{name}] is not implemented")
 
 
 def _to_uint8_hwc(chw):
