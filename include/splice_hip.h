@@ -307,6 +307,12 @@ int splice_optim_step(int kind, float* params, float* grads, float* m, float* v,
  * lr_dev (may be NULL): a device float the kernel reads as the learning rate when it runs (lr is then ignored) */
 int splice_optim_step_ex(int kind, float* params, float* grads, const float* g2, float* m, float* v, long long n, float lr,
                          const float* lr_dev, float hp0, float hp1, float eps, int step, int zero_grad, splice_stream_t stream);
+/* n_pairs arenas in one launch, each with its own learning rate: pair p's n floats start at p * stride (stride >= n, a multiple of 4)
+ * and use lr_dev[p] (device, n_pairs floats).  All n_pairs * stride floats are updated (the padding holds zero gradients); g2, m
+ * and v span the same range.  Bit for bit the result of n_pairs splice_optim_step_ex calls, one per arena with its lr. */
+int splice_optim_step_pairs(int kind, float* params, float* grads, const float* g2, float* m, float* v, int n_pairs, long long stride,
+                            long long n, const float* lr_dev, float hp0, float hp1, float eps, int step, int zero_grad,
+                            splice_stream_t stream);
 
 /* live timing of one kernel family (bench.py roofline leg, prof.hip): while a family is armed its kernels are launched with
  * a start / stop event pair each (hipExtLaunchKernelGGL: the kernel's own begin / end time stamps, as rocprofv3 reports them).
@@ -363,6 +369,8 @@ typedef struct splice_step_config {
                                   * the A crops only -- the reference zips the crop lists (util/losses.py:76,87,98): structure term over the
                                   * A crops, identity term over the B crops, appearance term over min(n_crops, n_crops_b) pairs */
 } splice_step_config;
+/* most pairs of one step handle that can carry a config of their own (splice_step_set_pair_weights / splice_step_set_pair_lr) */
+#define SPLICE_STEP_MAX_PAIR_CFGS 32
 /* gen_plan_a / gen_plan_b: N = P plans at the crop size for the A and the B crops; gen_plan_entire: N = P at the entire size
  * (NULL with ent_h == 0).  Contexts: need_grad, B = 4P / 2P. */
 int splice_step_create(const splice_step_config* cfg, void* vit_ctx_global, void* vit_ctx_entire, void* gen_plan_a, void* gen_plan_b,
@@ -401,6 +409,15 @@ int splice_step_set_optimizer(void* step, int kind, float hp0, float hp1, float 
  * step).  The value is staged by the step's input-staging launch (phase 1) and the update reads it from device memory, so a
  * replayed graph uses the lr of its own step.  Before the first call the handle uses the config's lr, as a kernel argument. */
 int splice_step_set_lr(void* step, float lr);
+/* Per-pair loss weights (pairs mode, P > 1; at most SPLICE_STEP_MAX_PAIR_CFGS pairs): lambdas = host [P][5], per pair
+ * {lambda_global_cls, lambda_global_ssim, lambda_global_identity, lambda_entire_cls, lambda_entire_ssim}; they replace the config's
+ * five lambdas.  The device scale tables are built once, here.  A term is launched when any pair's weight is > 0 (and its gate is
+ * on: cls_warmup, the entire step); a pair whose weight is 0 writes no loss partials and no gradient for it and reports 0, as a
+ * single-pair step that skips the launch.  Drops the handle's graphs. */
+int splice_step_set_pair_weights(void* step, const float* lambdas);
+/* Per-pair learning rates (pairs mode, P > 1): lr = host [P], the per-pair form of splice_step_set_lr (staged by the input-staging
+ * launch, read by the optimiser from device memory: pair p's arena uses lr[p]).  The first call drops the handle's graphs. */
+int splice_step_set_pair_lr(void* step, const float* lr);
 /* Run part of a step: phases = mask of 1 generator forward (+ input staging), 2 ViT forward / losses / ViT backward down to
  * the gradient of the generated images, 4 generator backward (+ Adam unless splice_step_set_mode disables it); default 7.
  * leader != NULL (phases must be 2; another step handle with the same image shapes): this handle reads the leader's staged

@@ -116,6 +116,7 @@ _SIGNATURES = {
     "splice_adam_step": ([_vp, _vp, _vp, _vp, C.c_longlong, _f, _f, _f, _f, _i, _i, _vp], _i),
     "splice_optim_step": ([_i, _vp, _vp, _vp, _vp, C.c_longlong, _f, _f, _f, _f, _i, _i, _vp], _i),
     "splice_optim_step_ex": ([_i, _vp, _vp, _vp, _vp, _vp, C.c_longlong, _f, _vp, _f, _f, _f, _i, _i, _vp], _i),
+    "splice_optim_step_pairs": ([_i, _vp, _vp, _vp, _vp, _vp, _i, C.c_longlong, C.c_longlong, _vp, _f, _f, _f, _i, _i, _vp], _i),
     "splice_prof_begin": ([_i], _i),
     "splice_prof_end": ([C.POINTER(_f), C.POINTER(_i)], _i),
     "splice_prof_end_ex": ([C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)], _i),
@@ -136,6 +137,8 @@ _SIGNATURES = {
     "splice_step_set_mode": ([_vp, _i, _i], _i),
     "splice_step_set_optimizer": ([_vp, _i, _f, _f, _f], _i),
     "splice_step_set_lr": ([_vp, _f], _i),
+    "splice_step_set_pair_weights": ([_vp, _vp], _i),
+    "splice_step_set_pair_lr": ([_vp, _vp], _i),
     "splice_step_set_phases": ([_vp, _i, _vp], _i),
     "splice_gen_buffer_count": ([_vp], C.c_longlong),
     "splice_gen_num_buffers": ([_vp], _i),

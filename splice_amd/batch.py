@@ -20,8 +20,13 @@ Layout::
     root/<pair name>/out/result.json {"pair", "gpu", "steps", "loss", "seconds", ...}
 
     python -m splice_amd.batch --root pairs/ --gpus 8 [--pairs-per-gpu P] [--n_epochs 2000] [--set key=value ...]
+
+A hyper-parameter sweep (``--sweep KEY=V1,V2[,...]``, repeatable): every pair runs the cartesian product of the values as ONE
+``train.train_sweep`` work item (all variants of the pair side by side in one engine); ``result.json`` then lists the variants
+with their losses and ``out/sweep/<k>/`` holds each variant's image.
 """
 import importlib
+import itertools
 import json
 import os
 import sys
@@ -80,6 +85,32 @@ def train_group_runner(pair_dirs, overrides):
     return [{"steps": eng.step_idx + 1, "loss": d["loss"], "seconds": dt, "pairs_in_step": len(pair_dirs)} for d in eng.losses()]
 
 
+def train_sweep_runner(pair_dir, overrides, variants):
+    """Sweep runner: all ``variants`` of one pair in one engine (``train_sweep``)."""
+    from .train import train_sweep
+    t0 = time.perf_counter()
+    eng = train_sweep(pair_dir, variants, cfg_overrides=overrides, progress=False)
+    import torch
+    torch.cuda.synchronize()
+    losses = eng.losses()
+    return {"steps": eng.step_idx + 1, "seconds": round(time.perf_counter() - t0, 3),
+            "variants": [{"index": k, "overrides": v, "loss": d["loss"], "losses": d} for k, (v, d) in enumerate(zip(variants, losses))]}
+
+
+def sweep_variants(specs):
+    """``["KEY=V1,V2", ...]`` (``--sweep``) -> the list of override dicts of the cartesian product, in argument order (the first
+    key varies slowest); every value is parsed as JSON where it can be, as ``--set`` does."""
+    axes = []
+    for spec in specs:
+        key, sep, vals = spec.partition("=")
+        if not sep or not key or not vals:
+            raise ValueError(f"--sweep {spec!r}: expected KEY=V1,V2[,...]")
+        if key in (k for k, _ in axes):
+            raise ValueError(f"--sweep: {key!r} given twice")
+        axes.append((key, [_parse_value(v) for v in vals.split(",")]))
+    return [dict(zip((k for k, _ in axes), combo)) for combo in itertools.product(*(v for _, v in axes))]
+
+
 def _image_sizes(pair_dir):
     from PIL import Image
     out = []
@@ -121,7 +152,8 @@ def _write_result(root, name, res):
     os.replace(tmp, os.path.join(pair_dir, "out", "result.json"))
 
 
-def _worker(gpu, visible_id, root, names, items, head, current, runner, overrides, pin_gpu, group_runner="splice_amd.batch:train_group_runner", redo=None):
+def _worker(gpu, visible_id, root, names, items, head, current, runner, overrides, pin_gpu, group_runner="splice_amd.batch:train_group_runner", redo=None,
+            sweep=None):
     if pin_gpu:   # must happen before the HIP runtime starts in this process
         os.environ["HIP_VISIBLE_DEVICES"] = str(visible_id)
         os.environ.pop("CUDA_VISIBLE_DEVICES", None)
@@ -146,13 +178,14 @@ def _worker(gpu, visible_id, root, names, items, head, current, runner, override
         else:
             run = run or _resolve(runner)
             i = item[0]
-            res = dict(run(os.path.join(root, names[i]), dict(overrides)) or {})
+            args = (os.path.join(root, names[i]), dict(overrides)) + ((list(sweep),) if sweep is not None else ())
+            res = dict(run(*args) or {})
             _write_result(root, names[i], dict(res, pair=names[i], index=i, gpu=gpu))
         current[gpu] = -1
 
 
 def run_batch(root, n_gpus=1, overrides=None, runner="splice_amd.batch:train_runner", pin_gpu=True, visible_ids=None, pairs_per_gpu=1,
-              group_runner=None, sizes=None, max_retries=1):
+              group_runner=None, sizes=None, max_retries=1, sweep=None):
     """Optimise every pair under ``root`` on ``n_gpus`` worker processes; returns the per-pair result dicts in pair order.
 
     ``runner``: ``"module:function"`` (or a picklable callable) ``(pair_dir, overrides) -> dict``; the default trains the
@@ -169,8 +202,19 @@ def run_batch(root, n_gpus=1, overrides=None, runner="splice_amd.batch:train_run
     runtime's handler thread has done that) is replaced by a fresh process on the same GPU and the item it
     was running goes back to the queue, at most ``max_retries`` times per item; a worker that ends with a Python error -- a
     deterministic failure -- or an item out of retries takes the batch down with a RuntimeError naming the pairs it was running and
-    the pairs left undone; the other workers drain the rest of the queue first, and finished pairs keep their ``result.json``."""
+    the pairs left undone; the other workers drain the rest of the queue first, and finished pairs keep their ``result.json``.
+    ``sweep``: a list of variant override dicts, or of ``"KEY=V1,V2"`` specs expanded as ``--sweep`` does (``sweep_variants``): every
+    pair is one work item that runs all the variants (default runner ``train_sweep_runner``; a runner is then called as
+    ``runner(pair_dir, overrides, variants)``).  Refused with ``pairs_per_gpu`` > 1."""
     import multiprocessing as mp
+    if sweep is not None:
+        if int(pairs_per_gpu) > 1:
+            raise ValueError("run_batch: a sweep runs one pair per work item; pairs_per_gpu > 1 is refused")
+        sweep = sweep_variants(sweep) if all(isinstance(v, str) for v in sweep) else [dict(v) for v in sweep]
+        if not sweep:
+            raise ValueError("run_batch: an empty sweep")
+        if runner == "splice_amd.batch:train_runner":
+            runner = "splice_amd.batch:train_sweep_runner"
     if int(pairs_per_gpu) > 1 and group_runner is None:
         if runner != "splice_amd.batch:train_runner":
             raise ValueError("run_batch: pairs_per_gpu > 1 with a custom runner needs a group_runner (pair_dirs, overrides) -> [dict per pair]")
@@ -185,7 +229,7 @@ def run_batch(root, n_gpus=1, overrides=None, runner="splice_amd.batch:train_run
         try:
             sizes = [_image_sizes(os.path.join(root, n)) for n in names]
         except Exception:
-            if int(pairs_per_gpu) > 1 or runner == "splice_amd.batch:train_runner":
+            if int(pairs_per_gpu) > 1 or runner in ("splice_amd.batch:train_runner", "splice_amd.batch:train_sweep_runner"):
                 raise                                  # the default runner trains IMAGES: an unreadable one is an error here, not later in a worker
             sizes = [((0, 0), (0, 0))] * len(names)    # custom (stub) runners on directories without images: index order, one pair per item
     items = work_items(sizes, pairs_per_gpu)
@@ -206,7 +250,8 @@ def run_batch(root, n_gpus=1, overrides=None, runner="splice_amd.batch:train_run
     redo = ctx.Array("i", [0] * len(items), lock=False)   # (guarded by head's lock)
 
     def spawn(g):
-        p = ctx.Process(target=_worker, args=(g, visible_ids[g] if pin_gpu else g, root, names, items, head, current, runner, dict(overrides or {}), pin_gpu, group_runner, redo))
+        p = ctx.Process(target=_worker, args=(g, visible_ids[g] if pin_gpu else g, root, names, items, head, current, runner, dict(overrides or {}), pin_gpu, group_runner, redo,
+                                              sweep))
         p.start()
         return p
 
@@ -296,6 +341,9 @@ def main(argv=None):
                     help="e4m3 operands for the QKV / fc1 / fc2 projections and the self-similarity Gram matrices (config key fp8); "
                          "'--fp8 attention': the attention forward too")
     ap.add_argument("--set", action="append", default=[], metavar="KEY=VALUE", help="config override (conf/default/config.yaml keys)")
+    ap.add_argument("--sweep", action="append", default=[], metavar="KEY=V1,V2",
+                    help="sweep a per-slot key over the values (repeatable: the cartesian product, in argument order); each pair runs all the "
+                         "variants side by side in one engine (train_sweep)")
     ap.add_argument("--max-retries", type=int, default=1, help="times an item goes back to the queue when the worker running it is killed by a signal")
     args = ap.parse_args(argv)
     over = {}
@@ -310,8 +358,16 @@ def main(argv=None):
     for kv in args.set:
         k, _, v = kv.partition("=")
         over[k] = _parse_value(v)
+    sweep = None
+    if args.sweep:
+        if args.pairs_per_gpu > 1:
+            raise SystemExit("--sweep runs one pair per work item (all its variants in one engine); use --pairs-per-gpu 1")
+        try:
+            sweep = sweep_variants(args.sweep)
+        except ValueError as e:
+            raise SystemExit(str(e))
     t0 = time.perf_counter()
-    res = run_batch(args.root, args.gpus, over, pairs_per_gpu=args.pairs_per_gpu, max_retries=args.max_retries)
+    res = run_batch(args.root, args.gpus, over, pairs_per_gpu=args.pairs_per_gpu, max_retries=args.max_retries, sweep=sweep)
     dt = time.perf_counter() - t0
     print(json.dumps({"pairs": len(res), "gpus": args.gpus, "seconds": round(dt, 2), "pairs_per_hour": round(len(res) * 3600 / dt, 2), "results": res}))
 

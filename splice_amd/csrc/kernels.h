@@ -129,6 +129,7 @@ struct SelfSimBatch {
     float* dk;                      // d keys fp32: pair p at + p * dk_pstride, [T][lddk]
     size_t dk_pstride; int lddk;
     float eps, e_scale, loss_scale; // e_scale = 4 lambda / T^2 ; loss_scale = 1 / T^2
+    const float* e_scale_tab;       // optional [pairs] per-pair e_scale (replaces e_scale); a pair whose entry is 0 writes nothing
     int fp8;                        // != 0: the two Gram matrices run on the fp8 MFMA from per-row quantised keys (D % 128 == 0)
     uint8_t *k8_tgt, *k8_x;         // [pairs][Tp][D] e4m3 rows (workspace)
     float *qnorm_tgt, *qnorm_x;     // [pairs][Tp] norms of the quantised rows
@@ -137,8 +138,11 @@ size_t selfsim_batch_ws_bytes(int T, int D, int pairs);
 void selfsim_batch_carve(void* base, int T, int D, int pairs, SelfSimBatch* b);   // fills T, Tp, D, pairs and the workspace pointers
 int selfsim_target_launch(const SelfSimBatch& b, hipStream_t s);   // S* with the row norms taken inside the Gram kernel (1 launch; 2 on the fp8 path)
 int selfsim_loss_launch(const SelfSimBatch& b, hipStream_t s);     // fused S / loss / W (norms in-kernel) + dK (2 launches; 3 on the fp8 path)
+// grad_tab (optional, [pairs]): per-pair gradient weight, the value grad_weight / (rows * cols) takes otherwise; a pair whose entry
+// is 0 writes no partials and no gradient
 int mse_batched_launch(const float* a, int lda, size_t a_ps, const float* b, int ldb, size_t b_ps, int rows, int cols, float loss_weight,
-                       float grad_weight, float* part, size_t part_ps, float* grad, int ldg, size_t g_ps, int pairs, hipStream_t s);
+                       float grad_weight, float* part, size_t part_ps, float* grad, int ldg, size_t g_ps, int pairs, hipStream_t s,
+                       const float* grad_tab = nullptr);
 // 2-D strided MSE: loss_accum[0] += weight * mean((a-b)^2); grad (optional) = weight * 2 (a-b) / (rows*cols)
 int mse_launch(const float* a, int lda, const float* b, int ldb, int rows, int cols, float weight, float* loss_accum,
                float* grad, int ldg, hipStream_t s);

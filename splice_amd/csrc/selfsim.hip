@@ -279,6 +279,7 @@ template <bool FP8>
 __global__ __launch_bounds__(256) void selfsim_tgt_kernel(SelfSimBatch b) {
     extern __shared__ __attribute__((aligned(16))) bf16_t selfsim_smem[];
     const int T = b.T, nt = (T + 63) / 64, pair = blockIdx.y;
+    if (b.e_scale_tab && b.e_scale_tab[pair] == 0.f) return;   // a pair without this term
     int tm, tn;
     tri_tile(xcd_remap(blockIdx.x, gridDim.x), nt, tm, tn);
     const int m0 = tm * 64, n0 = tn * 64;
@@ -318,6 +319,11 @@ template <bool FP8>
 __global__ __launch_bounds__(256) void selfsim_loss_kernel(SelfSimBatch b) {
     extern __shared__ __attribute__((aligned(16))) bf16_t selfsim_smem[];
     const int T = b.T, Tp = b.Tp, nt = Tp / 64, pair = blockIdx.y;
+    float e_scale = b.e_scale;
+    if (b.e_scale_tab) {   // per-pair table: a pair whose entry is 0 does not take part (no partials, no W)
+        e_scale = b.e_scale_tab[pair];
+        if (e_scale == 0.f) return;
+    }
     const int tile_id = xcd_remap(blockIdx.x, gridDim.x);
     int tm, tn;
     tri_tile(tile_id, nt, tm, tn);
@@ -394,7 +400,7 @@ __global__ __launch_bounds__(256) void selfsim_loss_kernel(SelfSimBatch b) {
                 const float s = FP8 ? tile.acc[i][j][r] / fmaxf(qr[i][r] * qc[j], 1e-30f) : tile.acc[i][j][r] / c;
                 const float d = valid ? s - st[i][j][r] : 0.f;
                 lsum += d * d;
-                const float e = b.e_scale * d;                 // (dS + dS^T)_ij = 4 lambda d / T^2
+                const float e = e_scale * d;                   // (dS + dS^T)_ij = 4 lambda d / T^2
                 w4[r] = e / c;
                 const float rd = nn > b.eps ? e * s : 0.f;
                 rs[i][r] += rd;
@@ -437,6 +443,7 @@ __global__ __launch_bounds__(256) void selfsim_dk_kernel(SelfSimBatch b) {
     extern __shared__ __attribute__((aligned(16))) bf16_t selfsim_smem[];
     __shared__ float rdot[64];
     const int T = b.T, Tp = b.Tp, D = b.D, nt = Tp / 64, pair = blockIdx.y;
+    if (b.e_scale_tab && b.e_scale_tab[pair] == 0.f) return;   // a pair without this term: its key gradient is left alone
     const int tiles_n = D / 64;
     const int t = xcd_remap(blockIdx.x, gridDim.x);
     const int m0 = (t / tiles_n) * 64, n0 = (t % tiles_n) * 64;
@@ -520,8 +527,13 @@ void selfsim_batch_carve(void* base, int T, int D, int pairs, SelfSimBatch* b) {
 // ---- batched strided MSE (blockIdx.y = pair): the [CLS] and key-identity terms of P pairs in one launch each
 __global__ __launch_bounds__(256) void mse_batched_kernel(const float* __restrict__ a, int lda, size_t a_ps, const float* __restrict__ bb, int ldb,
                                                           size_t b_ps, int rows, int cols, float wmean, float gmean, float* __restrict__ part,
-                                                          size_t part_ps, float* __restrict__ grad, int ldg, size_t g_ps) {
+                                                          size_t part_ps, float* __restrict__ grad, int ldg, size_t g_ps,
+                                                          const float* __restrict__ gtab) {
     const int pair = blockIdx.y;
+    if (gtab) {   // per-pair gradient weight; a pair whose weight is 0 does not take part
+        gmean = gtab[pair];
+        if (gmean == 0.f) return;
+    }
     a += (size_t)pair * a_ps; bb += (size_t)pair * b_ps; part += (size_t)pair * part_ps;
     if (grad) grad += (size_t)pair * g_ps;
     const size_t n = (size_t)rows * cols;
@@ -539,12 +551,13 @@ __global__ __launch_bounds__(256) void mse_batched_kernel(const float* __restric
     if (threadIdx.x == 0) part[blockIdx.x] = ((red[0] + red[1]) + (red[2] + red[3])) * wmean;
 }
 int mse_batched_launch(const float* a, int lda, size_t a_ps, const float* b, int ldb, size_t b_ps, int rows, int cols, float loss_weight,
-                       float grad_weight, float* part, size_t part_ps, float* grad, int ldg, size_t g_ps, int pairs, hipStream_t s) {
+                       float grad_weight, float* part, size_t part_ps, float* grad, int ldg, size_t g_ps, int pairs, hipStream_t s,
+                       const float* grad_tab) {
     const size_t n = (size_t)rows * cols;
     if (!n || !part || pairs < 1) return SPLICE_ERR_ARG;
     size_t g = (n + 255) / 256;
     if (g > MSE_MAX_WG) g = MSE_MAX_WG;
     SPLICE_LAUNCH(mse_batched_kernel, dim3((unsigned)g, pairs), dim3(256), 0, s, a, lda, a_ps, b, ldb, b_ps, rows, cols, loss_weight / (float)n,
-                       grad_weight / (float)n, part, part_ps, grad, ldg, g_ps);
+                       grad_weight / (float)n, part, part_ps, grad, ldg, g_ps, grad_tab);
     return SPLICE_OK;
 }

@@ -116,6 +116,15 @@ struct SpliceStep {
     int lr_set = 0;              // 0: the optimiser node takes cfg.lr as a kernel argument (the handle's behaviour before any splice_step_set_lr)
     float lr = 0.f;              // value staged into dev_lr by the next run
     int opt_kind = SPLICE_OPT_ADAM;      // splice_step_set_optimizer; hp0 / hp1 / eps start as cfg.beta1 / beta2 / eps
+    // per-pair configs (splice_step_set_pair_weights / splice_step_set_pair_lr; pairs mode only).  pw: device tables, NULL until set --
+    // [P] e_scale of the global / entire structure term, [P] gradient weights of the [CLS], identity and entire [CLS] terms, [P][5] lambdas
+    // of the total in the order of splice_step_set_pair_weights.  pw_any[k]: some pair has lambda k > 0 (the term's launch happens).
+    float* pw = nullptr;
+    float* pw_tab_alloc = nullptr;   // (the tables' memory: allocated at creation for P > 1, switched on as pw by splice_step_set_pair_weights)
+    int pw_any[5] = {0, 0, 0, 0, 0};
+    float* dev_lrs = nullptr;    // [SPLICE_STEP_MAX_PAIR_CFGS] per-pair learning rates, staged per step once splice_step_set_pair_lr was called
+    int pair_lr = 0;
+    float lrs[SPLICE_STEP_MAX_PAIR_CFGS] = {};
     float opt_hp0 = 0.f, opt_hp1 = 0.f, opt_eps = 0.f;
     hipStream_t own_stream = nullptr;
     // Cross-stream events, a RING of sets: an eager step records its fork / join events twice and the next step records them again
@@ -196,8 +205,10 @@ static int view_init(SpliceStep* st, VitView& v, void* ctx, int want_B) {
 // blockIdx.x = pair.  raw_k = fixed-order sum of term k's workgroup partials (no float atomics anywhere: replicas are
 // bit-reproducible); total = sum_k lambda_k * raw_k   (util/losses.py:53-71)
 // n_slots > 1 (crops mode, grid 1): the terms of the n_crops crops are added in crop order (util/losses.py:75-82 `loss +=`).
+// wtab (optional, [pairs][5] in the order of splice_step_set_pair_weights): per-pair lambdas in place of the five weights, gated as the
+// scalar weights are (ssim_on: global structure and identity; entire: the two entire-image terms)
 __global__ __launch_bounds__(320) void total_loss_kernel(float* lbase, size_t lstride, int lp, float w_ssim, float w_essim, float w_ecls, float w_cls,
-                                                         float w_id, float* out8, int n_slots) {
+                                                         float w_id, float* out8, int n_slots, const float* wtab, int ssim_on, int entire) {
     __shared__ float raw[8];
     float* l = lbase + (size_t)blockIdx.x * lstride;
     const int k = 1 + (threadIdx.x >> 6), lane = threadIdx.x & 63;   // wave k-1 owns term k (5 waves)
@@ -212,6 +223,14 @@ __global__ __launch_bounds__(320) void total_loss_kernel(float* lbase, size_t ls
     if (lane == 0) raw[k] = acc;
     __syncthreads();
     if (threadIdx.x == 0) {
+        if (wtab) {
+            const float* w = wtab + (size_t)blockIdx.x * 5;
+            w_cls = w[0];
+            w_ssim = ssim_on ? w[1] : 0.f;
+            w_id = ssim_on ? w[2] : 0.f;
+            w_ecls = entire ? w[3] : 0.f;
+            w_essim = entire ? w[4] : 0.f;
+        }
         for (int t = 1; t <= 5; ++t) l[t] = raw[t];
         l[L_TOTAL] = w_ssim * raw[L_GLOBAL_SSIM] + w_essim * raw[L_ENTIRE_SSIM] + w_ecls * raw[L_ENTIRE_CLS] + w_cls * raw[L_GLOBAL_CLS] + w_id * raw[L_GLOBAL_ID];
         if (out8) {   // the caller's losses buffer, written here instead of by a copy behind the step
@@ -223,9 +242,9 @@ __global__ __launch_bounds__(320) void total_loss_kernel(float* lbase, size_t ls
     }
 }
 // All per-step inputs in ONE eager launch in front of the graph replay (three copies + the Adam step count were four
-// launches with ~10-30 us of host/queue gaps between them): up to three fp32 buffers, one int and (fp != null) one float,
-// the scheduled learning rate.
-struct StageArgs { const float* src[3]; float* dst[3]; unsigned long long n[3]; int* ip; int iv; float* fp; float fv; };
+// launches with ~10-30 us of host/queue gaps between them): up to three fp32 buffers, one int and (fp != null) nf floats, the
+// scheduled learning rate (nf = 1) or one per pair (splice_step_set_pair_lr).
+struct StageArgs { const float* src[3]; float* dst[3]; unsigned long long n[3]; int* ip; int iv; float* fp; int nf; float fv[SPLICE_STEP_MAX_PAIR_CFGS]; };
 __global__ __launch_bounds__(256) void stage_inputs_kernel(StageArgs a) {
     const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
 #pragma unroll
@@ -244,7 +263,11 @@ __global__ __launch_bounds__(256) void stage_inputs_kernel(StageArgs a) {
     }
     if (gid == 0) {
         *a.ip = a.iv;
-        if (a.fp) *a.fp = a.fv;
+        if (a.fp) {
+#pragma unroll
+            for (int k = 0; k < SPLICE_STEP_MAX_PAIR_CFGS; ++k)
+                if (k < a.nf) a.fp[k] = a.fv[k];
+        }
     }
 }
 static float* loss_part(SpliceStep* st, int slot) { return st->losses + 8 + (size_t)slot * st->lp; }   // pair 0; pair p at + p * lstride
@@ -317,6 +340,7 @@ static int ssim_batch(SpliceStep* st, VitView& v, int pass_tgt, int pass_x, int 
     b->fp8 = st->cfg.fp8_selfsim && v.D % 128 == 0;
     b->loss_scale = 1.0f / ((float)v.T * (float)v.T);
     b->e_scale = 4.0f * lambda * b->loss_scale;
+    if (st->pw) b->e_scale_tab = st->pw + (slot == L_ENTIRE_SSIM ? st->P : 0);   // (per-pair configs: the tables of splice_step_set_pair_weights)
     return SPLICE_OK;
 }
 
@@ -387,6 +411,10 @@ int splice_step_create(const splice_step_config* cfg, void* vit_ctx_global, void
     if ((rc = salloc(st, &st->losses, P * st->lstride)) != SPLICE_OK) return fail(rc);
     if ((rc = salloc(st, &st->dev_t, 4)) != SPLICE_OK) return fail(rc);
     if ((rc = salloc(st, &st->dev_lr, 1)) != SPLICE_OK) return fail(rc);
+    if (P > 1 && !st->crops_mode) {
+        if ((rc = salloc(st, &st->dev_lrs, SPLICE_STEP_MAX_PAIR_CFGS)) != SPLICE_OK) return fail(rc);
+        if ((rc = salloc(st, &st->pw_tab_alloc, (size_t)10 * P)) != SPLICE_OK) return fail(rc);
+    }
     st->opt_hp0 = cfg->beta1; st->opt_hp1 = cfg->beta2; st->opt_eps = cfg->eps;
     if (const char* e = getenv("SPLICE_STEP_GRAPH")) st->use_graph = atoi(e);
     if (const char* e = getenv("SPLICE_STEP_SYNC")) st->dbg_sync = atoi(e);
@@ -470,6 +498,56 @@ int splice_step_set_lr(void* h, float lr) {
     st->lr_set = 1; st->lr = lr;
     return SPLICE_OK;
 }
+static int pair_cfgs_ok(SpliceStep* st, const void* host, const char* who) {
+    if (!st || !host) return SPLICE_ERR_ARG;
+    if (st->P < 2 || st->crops_mode || !st->pw_tab_alloc || st->P > SPLICE_STEP_MAX_PAIR_CFGS) {
+        splice_set_error("%s: per-pair configs need 2 .. %d pairs (pairs mode, not n_crops)", who, SPLICE_STEP_MAX_PAIR_CFGS);
+        return SPLICE_ERR_ARG;
+    }
+    return SPLICE_OK;
+}
+// Per-pair loss weights: lambdas = host [P][5] {global_cls, global_ssim, global_identity, entire_cls, entire_ssim}.  The device tables
+// hold what the scalar path computes from cfg, with the same fp32 expressions in the same order: e_scale = 4 lambda * loss_scale of the
+// view (ssim_batch), lambda / (float)(rows * cols) of each MSE term (mse_batched_launch), and the lambdas of the total.
+int splice_step_set_pair_weights(void* h, const float* lambdas) {
+    SpliceStep* st = (SpliceStep*)h;
+    RC(pair_cfgs_ok(st, lambdas, "splice_step_set_pair_weights"));
+    const int P = st->P;
+    for (int i = 0; i < 5 * P; ++i)
+        if (!(lambdas[i] >= 0.f)) { splice_set_error("splice_step_set_pair_weights: lambdas must be >= 0"); return SPLICE_ERR_ARG; }
+    std::vector<float> t((size_t)10 * P, 0.f);
+    const VitView &vg = st->vg, &ve = st->ve;
+    const float ls_g = 1.0f / ((float)vg.T * (float)vg.T);
+    const float ls_e = st->plan_e ? 1.0f / ((float)ve.T * (float)ve.T) : 0.f;
+    const size_t n_cls = (size_t)1 * vg.D, n_id = (size_t)vg.T * vg.D, n_ecls = (size_t)1 * ve.D;
+    for (int k = 0; k < 5; ++k) st->pw_any[k] = 0;
+    for (int p = 0; p < P; ++p) {
+        const float* l = lambdas + (size_t)p * 5;
+        for (int k = 0; k < 5; ++k) st->pw_any[k] |= l[k] > 0.f;
+        t[p] = 4.0f * l[1] * ls_g;                              // global structure term
+        if (st->plan_e) t[P + p] = 4.0f * l[4] * ls_e;          // entire structure term
+        t[2 * P + p] = l[0] / (float)n_cls;                     // [CLS]
+        t[3 * P + p] = l[2] / (float)n_id;                      // identity (keys)
+        if (st->plan_e) t[4 * P + p] = l[3] / (float)n_ecls;    // entire [CLS]
+        for (int k = 0; k < 5; ++k) t[5 * P + (size_t)p * 5 + k] = l[k];
+    }
+    drop_graphs(st);
+    HIPCHK(hipDeviceSynchronize());   // (a running step may still read the tables)
+    HIPCHK(hipMemcpy(st->pw_tab_alloc, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
+    st->pw = st->pw_tab_alloc;
+    return SPLICE_OK;
+}
+// Per-pair learning rates of the next splice_step_run and every later one until the next call (the per-pair form of splice_step_set_lr):
+// staged by the input-staging launch, read by the optimiser as lr[element / arena_stride].  The first call drops the handle's graphs.
+int splice_step_set_pair_lr(void* h, const float* lr) {
+    SpliceStep* st = (SpliceStep*)h;
+    RC(pair_cfgs_ok(st, lr, "splice_step_set_pair_lr"));
+    if (st->astride % 4) { splice_set_error("splice_step_set_pair_lr: the arena stride must be a multiple of 4"); return SPLICE_ERR_ARG; }
+    if (!st->pair_lr) drop_graphs(st);
+    st->pair_lr = 1;
+    for (int p = 0; p < st->P; ++p) st->lrs[p] = lr[p];
+    return SPLICE_OK;
+}
 // Run only part of a step: phases is a mask of 1 = generator forward (and input staging), 2 = ViT forward, losses and ViT backward
 // down to the gradient of the generated images, 4 = generator backward (+ Adam unless splice_step_set_mode says otherwise).
 // With `leader` (another step handle, same image shapes; phases must be 2) this handle is a FOLLOWER: it reads the leader's
@@ -503,6 +581,13 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
     const float l_ssim = ssim_on ? c.lambda_global_ssim : 0.f, l_id = ssim_on ? c.lambda_global_identity : 0.f;
     const float l_cls = c.lambda_global_cls;
     const float l_essim = entire ? c.lambda_entire_ssim : 0.f, l_ecls = entire ? c.lambda_entire_cls : 0.f;
+    // which terms launch: with per-pair weights, when any pair needs them (a pair whose weight is 0 returns early in the kernel)
+    const float* pw = st->pw;
+    const bool on_cls = pw ? st->pw_any[0] != 0 : l_cls > 0.f;
+    const bool on_ssim = pw ? ssim_on && st->pw_any[1] : l_ssim > 0.f;
+    const bool on_id = pw ? ssim_on && st->pw_any[2] : l_id > 0.f;
+    const bool on_ecls = pw ? entire && st->pw_any[3] : l_ecls > 0.f;
+    const bool on_essim = pw ? entire && st->pw_any[4] : l_essim > 0.f;
     const size_t vimg = (size_t)3 * vg.H * vg.W;
     const StepPtrs ip = step_ptrs(st);
     // a follower (splice_step_set_phases) sees the leader's images and adds its image gradients to the leader's
@@ -545,7 +630,7 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
         RC(dev_zero_launch(st->losses, (size_t)P * st->lstride * sizeof(float), s2));
         RC(dev_zero_launch(vg.d_block + pX * passD, (size_t)(Pa + Pb) * passD * sizeof(float), s2));
         RC(dev_zero_launch(vg.d_keys + pX * passD, (size_t)(Pa + Pb) * passD * sizeof(float), s2));
-        if (l_ssim > 0.f) {   // target self-similarity S* of A' (util/losses.py:79)
+        if (on_ssim) {   // target self-similarity S* of A' (util/losses.py:79)
             RC(ssim_batch(st, vg, pA, pX, Pa, l_ssim, L_GLOBAL_SSIM, &sb));
             RC(selfsim_target_launch(sb, s2));
         }
@@ -564,13 +649,13 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
     if (overlap) HIPCHK(hipStreamWaitEvent(s, st->ev(SpliceStep::EV_JOIN), 0));
     // ---- losses on the global batch
     if (do_v) {
-        if (l_ssim > 0.f) RC(selfsim_loss_launch(sb, s));
-        if (l_cls > 0.f)   // [CLS] of block 11, before the final LayerNorm (util/losses.py:90-93)
+        if (on_ssim) RC(selfsim_loss_launch(sb, s));
+        if (on_cls)   // [CLS] of block 11, before the final LayerNorm (util/losses.py:90-93)
             RC(mse_batched_launch(blk_g + pX * passD, vg.D, passD, blk_g + pB * passD, vg.D, passD, 1, vg.D, 1.0f, l_cls, loss_part(st, L_GLOBAL_CLS),
-                                  st->lstride, vg.d_block + pX * passD, vg.D, passD, Pc, s));
-        if (l_id > 0.f)    // keys of y' against keys of B' (util/losses.py:96-105): mean over h*T*d = T*D
+                                  st->lstride, vg.d_block + pX * passD, vg.D, passD, Pc, s, pw ? pw + 2 * P : nullptr));
+        if (on_id)    // keys of y' against keys of B' (util/losses.py:96-105): mean over h*T*d = T*D
             RC(mse_batched_launch(keys_ptr(vg, qkv_g, pY), 3 * vg.D, 3 * passD, keys_ptr(vg, qkv_g, pB), 3 * vg.D, 3 * passD, vg.T, vg.D, 1.0f, l_id,
-                                  loss_part(st, L_GLOBAL_ID), st->lstride, vg.d_keys + pY * passD, vg.D, passD, Pb, s));
+                                  loss_part(st, L_GLOBAL_ID), st->lstride, vg.d_keys + pY * passD, vg.D, passD, Pb, s, pw ? pw + 3 * P : nullptr));
     }
     // ---- entire-image branch (every entire_every-th step): passes [0, Pe) A_entire', [Pe, 2 Pe) x_entire'
     const int Pe = st->Pe;
@@ -587,15 +672,15 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
             const size_t epassD = (size_t)ve.Tld * ve.D;
             RC(dev_zero_launch(ve.d_block + Pe * epassD, (size_t)Pe * epassD * sizeof(float), s));
             RC(dev_zero_launch(ve.d_keys + Pe * epassD, (size_t)Pe * epassD * sizeof(float), s));
-            if (l_essim > 0.f) {
+            if (on_essim) {
                 SelfSimBatch se = {};
                 RC(ssim_batch(st, ve, 0, Pe, Pe, l_essim, L_ENTIRE_SSIM, &se));
                 RC(selfsim_target_launch(se, s));
                 RC(selfsim_loss_launch(se, s));
             }
-            if (l_ecls > 0.f)   // target is the B_global crop's CLS (util/losses.py:60; with n_crops > 1 the zip pairs x_entire with the FIRST crop)
+            if (on_ecls)   // target is the B_global crop's CLS (util/losses.py:60; with n_crops > 1 the zip pairs x_entire with the FIRST crop)
                 RC(mse_batched_launch(blk_e + Pe * epassD, ve.D, epassD, blk_g + pB * passD, vg.D, passD, 1, ve.D, 1.0f, l_ecls, loss_part(st, L_ENTIRE_CLS),
-                                      st->lstride, ve.d_block + Pe * epassD, ve.D, epassD, Pe, s));
+                                      st->lstride, ve.d_block + Pe * epassD, ve.D, epassD, Pe, s, pw ? pw + 4 * P : nullptr));
         }
     }
     // ---- backward (train.py:78): ViT dgrad for the generated images only, then the generator
@@ -605,7 +690,7 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
     auto sum_losses = [&](hipStream_t q) {
         if (!do_v) return;
         SPLICE_LAUNCH(total_loss_kernel, dim3(st->crops_mode ? 1 : P), dim3(320), 0, q, st->losses, st->lstride, (int)st->lp, l_ssim, l_essim, l_ecls, l_cls, l_id,
-                           st->losses_out, st->crops_mode ? P : 1);
+                           st->losses_out, st->crops_mode ? P : 1, pw ? pw + 5 * P : nullptr, (int)ssim_on, (int)entire);
     };
     auto track_running = [&](hipStream_t q) -> int {   // BatchNorm running statistics in the reference's call order
         if (!st->running || (st->ablate & 1) || !do_gf) return SPLICE_OK;
@@ -667,10 +752,12 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
     SPLICE_DEV_REGION(21);
     if (do_gb && !st->skip_adam) {
         const size_t n_all = st->astride ? P * st->astride : (size_t)st->nparams;
-        const float* lr_dev = st->lr_set ? st->dev_lr : nullptr;
-        if (st->opt_kind == SPLICE_OPT_RMSPROP) RC(rmsprop_launch(params, grads, v, n_all, c.lr, st->opt_hp0, st->opt_eps, 0, s, adam_g2, lr_dev));
-        else if (st->opt_kind == SPLICE_OPT_SGD) RC(sgd_launch(params, grads, n_all, c.lr, 0, s, adam_g2, lr_dev));
-        else RC(adam_launch_dev(params, grads, m, v, n_all, c.lr, st->opt_hp0, st->opt_hp1, st->opt_eps, st->dev_t, 0, s, adam_g2, lr_dev));
+        // per-pair lrs (splice_step_set_pair_lr): pair p's arena reads dev_lrs[p]
+        const float* lr_dev = st->pair_lr ? st->dev_lrs : st->lr_set ? st->dev_lr : nullptr;
+        const size_t lr_stride = st->pair_lr ? st->astride : 0;
+        if (st->opt_kind == SPLICE_OPT_RMSPROP) RC(rmsprop_launch(params, grads, v, n_all, c.lr, st->opt_hp0, st->opt_eps, 0, s, adam_g2, lr_dev, lr_stride));
+        else if (st->opt_kind == SPLICE_OPT_SGD) RC(sgd_launch(params, grads, n_all, c.lr, 0, s, adam_g2, lr_dev, lr_stride));
+        else RC(adam_launch_dev(params, grads, m, v, n_all, c.lr, st->opt_hp0, st->opt_hp1, st->opt_eps, st->dev_t, 0, s, adam_g2, lr_dev, lr_stride));
     }
     return SPLICE_OK;
 }
@@ -804,7 +891,12 @@ int splice_step_run(void* h, float* params, float* grads, float* m, float* v, co
         sa.src[1] = B_crop; sa.dst[1] = ip.b_in; sa.n[1] = (size_t)st->Pb * 3 * st->cropb_h * st->cropb_w;
         if (entire) { sa.src[2] = A_entire; sa.dst[2] = ip.e_in; sa.n[2] = (size_t)st->Pe * 3 * c.ent_h * c.ent_w; }
         sa.ip = st->dev_t; sa.iv = step_idx + 1;
-        if (st->lr_set) { sa.fp = st->dev_lr; sa.fv = st->lr; }
+        if (st->pair_lr) {
+            sa.fp = st->dev_lrs; sa.nf = P;
+            for (int p = 0; p < P; ++p) sa.fv[p] = st->lrs[p];
+        } else if (st->lr_set) {
+            sa.fp = st->dev_lr; sa.nf = 1; sa.fv[0] = st->lr;
+        }
         SPLICE_LAUNCH(stage_inputs_kernel, dim3(128 * (P > 4 ? 4 : P)), dim3(256), 0, s, sa);
     }
     // Steps whose shapes differ from the previous step's (the reference's random crop sizes) are launched eagerly.  Capturing EVERY such step into a

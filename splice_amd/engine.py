@@ -27,6 +27,51 @@ DEFAULT_CFG = dict(  # conf/default/config.yaml of the reference
     log_images_freq=10)
 
 
+# Per-slot keys of a sweep (MultiPairEngine(pair_cfgs=...), train.train_sweep): the five loss weights in the order of
+# splice_step_set_pair_weights, the learning rate and its schedule, and what only the host-side generator initialisation reads.
+# Every other key is shared by the slots of one engine.
+PAIR_LAMBDA_KEYS = ("lambda_global_cls", "lambda_global_ssim", "lambda_global_identity", "lambda_entire_cls", "lambda_entire_ssim")
+PAIR_LR_KEYS = ("lr", "scheduler_policy", "scheduler_n_epochs_decay", "scheduler_lr_decay_iters")
+PAIR_INIT_KEYS = ("seed", "init_type", "init_gain")
+PAIR_KEYS = PAIR_LAMBDA_KEYS + PAIR_LR_KEYS + PAIR_INIT_KEYS
+MAX_PAIR_CFGS = 32   # SPLICE_STEP_MAX_PAIR_CFGS
+
+
+def _entire_branch(c):
+    return c["lambda_entire_ssim"] > 0 or c["lambda_entire_cls"] > 0
+
+
+def merge_pair_cfgs(cfg, pair_cfgs):
+    """The per-slot configs of a sweep: ``cfg`` (base) merged with each override dict of ``pair_cfgs``.  Checked on the host
+    alone (nothing touches the GPU): at most MAX_PAIR_CFGS slots; a variant may set only PAIR_KEYS (a shared key only to the
+    base value); every slot's optimiser / schedule must be valid; all slots must agree on whether the entire-image branch
+    exists (a slot without it makes no G(A) call, so its BatchNorm statistics would not be its single run's).  Raises
+    ValueError naming the offending key."""
+    base = dict(DEFAULT_CFG, **cfg)
+    pair_cfgs = list(pair_cfgs)
+    if not pair_cfgs:
+        raise ValueError("pair_cfgs: at least one variant")
+    if len(pair_cfgs) > MAX_PAIR_CFGS:
+        raise ValueError(f"pair_cfgs: {len(pair_cfgs)} variants, at most {MAX_PAIR_CFGS} slots per engine")
+    out = []
+    for k, over in enumerate(pair_cfgs):
+        if not isinstance(over, dict):
+            raise ValueError(f"pair_cfgs[{k}]: a dict of per-slot overrides")
+        for key, val in over.items():
+            if key not in PAIR_KEYS and (key not in base or base[key] != val):
+                raise ValueError(f"pair_cfgs[{k}]: '{key}' is shared by every slot of a sweep (per-slot keys: {', '.join(PAIR_KEYS)})")
+        c = dict(base, **over)
+        for key in PAIR_LAMBDA_KEYS:
+            if not c[key] >= 0:
+                raise ValueError(f"pair_cfgs[{k}]: '{key}' must be >= 0")
+        LrSchedule(c)   # (refuses plateau / unknown policies with the reason)
+        out.append(c)
+    if len({_entire_branch(c) for c in out}) > 1:
+        raise ValueError("pair_cfgs: the variants disagree on whether the entire-image branch exists (lambda_entire_cls / lambda_entire_ssim > 0): "
+                         "a slot without it makes no G(A) call and its BatchNorm statistics would differ from its single run")
+    return out
+
+
 def resize_output_size(h, w, size, max_size=480):
     """Output (h, w) of torchvision-0.10 ``Resize(size, max_size)`` (util/losses.py:20): shorter
     edge -> size, aspect kept (long edge truncated), both shrunk if the long edge exceeds max_size;
@@ -48,13 +93,36 @@ class MultiPairEngine:
     bit-identical whichever batch it rides in (tests/test_multipair_gpu.py).  All pairs of a batch share the image and
     crop sizes."""
 
-    def __init__(self, cfg, vit_state, gen_states, crop_hw, entire_hw=None, device="cuda", vit_engine=None, n_crops=1, fp8=False, top_cls_only=True):
+    def __init__(self, cfg, vit_state, gen_states, crop_hw, entire_hw=None, device="cuda", vit_engine=None, n_crops=1, fp8=False, top_cls_only=True,
+                 pair_cfgs=None):
         """cfg: reference config keys (conf/default/config.yaml); vit_state: DINO state dict; gen_states: list of P generator
         state dicts (reference names); crop_hw: (h, w) of the (largest) global crops; entire_hw: (H, W) of the whole
         structure image or None to disable the entire branch.  ``n_crops`` > 1 (one pair only): the reference's
         ``global_{A,B}_crops_n_crops`` -- every step takes ``[n_crops,3,h,w]`` crops of the pair, netG sees them as ONE batch
-        (BatchNorm statistics over the crops), every loss term is summed over the crops."""
+        (BatchNorm statistics over the crops), every loss term is summed over the crops.
+        ``pair_cfgs``: one dict of per-slot overrides per pair (a sweep: PAIR_KEYS -- the five lambdas, lr and its schedule; the
+        init keys are the caller's business), checked by ``merge_pair_cfgs``.  Slot p then runs, bit for bit, as a
+        ``SpliceEngine`` with ``cfgs[p]`` would; ``lr`` becomes a list of P values."""
         self.cfg = dict(DEFAULT_CFG, **cfg)
+        P_in = len(gen_states)
+        self.cfgs = [self.cfg] * P_in
+        self._pair_lambdas = self._pair_lr = False
+        if pair_cfgs is not None:
+            if len(pair_cfgs) != P_in:
+                raise ValueError(f"pair_cfgs: {len(pair_cfgs)} variants for {P_in} generator states")
+            if (int(n_crops) if isinstance(n_crops, int) else max(int(n) for n in n_crops)) > 1:
+                raise ValueError("pair_cfgs: a sweep takes one global crop per image (n_crops > 1 is not supported)")
+            self.cfgs = merge_pair_cfgs(self.cfg, pair_cfgs)
+            # a group of keys that is equal over the slots stays on the scalar path (no per-pair table, today's launches)
+            self._pair_lambdas = len({tuple(cp[k] for k in PAIR_LAMBDA_KEYS) for cp in self.cfgs}) > 1
+            self._pair_lr = len({tuple(cp.get(k) for k in PAIR_LR_KEYS) for cp in self.cfgs}) > 1
+            c0 = self.cfgs[0]
+            if self._pair_lambdas:   # (scalar fields: the largest weight of each term -- > 0 exactly where some slot needs the term)
+                self.cfg.update({k: max(cp[k] for cp in self.cfgs) for k in PAIR_LAMBDA_KEYS})
+            else:
+                self.cfg.update({k: c0[k] for k in PAIR_LAMBDA_KEYS})
+            if not self._pair_lr:
+                self.cfg.update({k: c0[k] for k in PAIR_LR_KEYS if k in c0})
         c = self.cfg
         # n_crops: int, or (nA, nB) = (global_A_crops_n_crops, global_B_crops_n_crops) -- the reference zips the crop lists
         # (util/losses.py:76,87,98): structure term over the A crops, identity term over the B crops, appearance term over min pairs
@@ -67,7 +135,10 @@ class MultiPairEngine:
         # computed on the host and staged on the device (splice_step_set_lr), so a replayed graph runs with the scheduled value
         self.opt_kind, *self.opt_hp = fused_optimizer(c)
         self.schedule = LrSchedule(c)
-        self.lr = None   # the lr the last step used
+        self.schedules = [LrSchedule(cp) for cp in self.cfgs] if self._pair_lr else None
+        self._lr_staged = None
+        self.lr = None   # the lr the last step used (a list of P values with pair_cfgs)
+        self._lr_list = pair_cfgs is not None
         self.device = torch.device(device)
         self.P = P = len(gen_states)
         self.vit = vit_engine or VitEngine(c["dino_model_name"], device=device).load_state_dict(vit_state)
@@ -140,6 +211,9 @@ class MultiPairEngine:
         if self.opt_kind != 0:
             _lib.check(_lib.lib().splice_step_set_optimizer(self.handle, self.opt_kind, *self.opt_hp), "step_set_optimizer")
         _lib.check(_lib.lib().splice_step_set_running_stats(self.handle, _lib.ptr(self.running), self.running.stride(0)), "step_set_running_stats")
+        if self._pair_lambdas:
+            lam = (C.c_float * (5 * P))(*[float(cp[k]) for cp in self.cfgs for k in PAIR_LAMBDA_KEYS])
+            _lib.check(_lib.lib().splice_step_set_pair_weights(self.handle, lam), "step_set_pair_weights")
         self.losses_dev = torch.zeros(P, 8, device=self.device)
         self.step_idx = -1  # data/Dataset.py:57 -- the first step is 0
         self._cur_crops = (ch, cw, ch, cw)
@@ -159,9 +233,17 @@ class MultiPairEngine:
         ``_repeat``: another phase of the step just run (``splice_step_set_phases``): no bookkeeping."""
         if not _repeat:
             self.step_idx += 1
-            self.lr = self.schedule.lr(self.step_idx)
-            if self.schedule.policy != "none":   # (without a schedule the handle keeps cfg lr as a kernel argument, as before)
-                _lib.check(_lib.lib().splice_step_set_lr(self.handle, self.lr), "step_set_lr")
+            if self._pair_lr:   # every slot's own schedule; staged per step, re-sent only when a value changes
+                self.lr = [sch.lr(self.step_idx) for sch in self.schedules]
+                if self.lr != self._lr_staged:
+                    _lib.check(_lib.lib().splice_step_set_pair_lr(self.handle, (C.c_float * self.P)(*self.lr)), "step_set_pair_lr")
+                    self._lr_staged = list(self.lr)
+            else:
+                self.lr = self.schedule.lr(self.step_idx)
+                if self.schedule.policy != "none":   # (without a schedule the handle keeps cfg lr as a kernel argument, as before)
+                    _lib.check(_lib.lib().splice_step_set_lr(self.handle, self.lr), "step_set_lr")
+                if self._lr_list:
+                    self.lr = [self.lr] * self.P
         for t, n in ((A_crop, self.slots_ab[0]), (B_crop, self.slots_ab[1])):
             assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
             assert t.numel() == n * 3 * t.shape[-2] * t.shape[-1], (tuple(t.shape), n)
@@ -183,13 +265,16 @@ class MultiPairEngine:
         """Host dict(s) of the last step's losses with the reference's keys (inactive terms omitted): one dict for ``pair``,
         a list over the pairs for ``pair=None``."""
         rows = self.losses_dev.cpu().tolist()
-        c, s = self.cfg, self.step_idx
-        on = s >= c["cls_warmup"]
-        ent = self.plan_e is not None and s % c["entire_A_every"] == 0
-        active = {"loss": True, "loss_global_ssim": on and c["lambda_global_ssim"] > 0, "loss_entire_ssim": ent and c["lambda_entire_ssim"] > 0,
-                  "loss_entire_cls": ent and c["lambda_entire_cls"] > 0, "loss_global_cls": c["lambda_global_cls"] > 0,
-                  "loss_global_id_B": on and c["lambda_global_identity"] > 0}
-        dicts = [{k: vals[i] for i, k in enumerate(LOSS_KEYS) if active[k]} for vals in rows]
+        s = self.step_idx
+        on = s >= self.cfg["cls_warmup"]
+        ent = self.plan_e is not None and s % self.cfg["entire_A_every"] == 0
+
+        def active(c):   # (a slot's terms follow that slot's own lambdas)
+            return {"loss": True, "loss_global_ssim": on and c["lambda_global_ssim"] > 0, "loss_entire_ssim": ent and c["lambda_entire_ssim"] > 0,
+                    "loss_entire_cls": ent and c["lambda_entire_cls"] > 0, "loss_global_cls": c["lambda_global_cls"] > 0,
+                    "loss_global_id_B": on and c["lambda_global_identity"] > 0}
+        acts = [active(c) for c in (self.cfgs if len(self.cfgs) == len(rows) else [self.cfg] * len(rows))]
+        dicts = [{k: vals[i] for i, k in enumerate(LOSS_KEYS) if act[k]} for vals, act in zip(rows, acts)]
         return dicts if pair is None else dicts[pair]
 
     def pair_params(self, pair=0):

@@ -12,6 +12,7 @@ Here the images live on the GPU and the same pipelines run on device tensors (``
 structure image = h-flip(0.5), ColorJitter(.4,.4,.2,.1)@0.5, GaussianBlur(3)@0.2; texture image = h-flip(0.5);
 then one random square crop covering >= ``min_cover`` of the height (``data/transforms.py:7-41``).
 """
+import json
 import os
 import random
 from argparse import ArgumentParser
@@ -298,6 +299,102 @@ def train_pairs(dataroots, callback=None, cfg_overrides=None, vit_state=None, pr
     finally:
         for w in writers:
             w.close()
+    return engine
+
+
+def _sweep_checks(cfg, variants):
+    """Host-side refusals of ``train_sweep`` (before anything touches the GPU); returns the per-slot configs."""
+    from .engine import merge_pair_cfgs
+    if int(cfg['global_A_crops_n_crops']) != 1 or int(cfg['global_B_crops_n_crops']) != 1:
+        raise NotImplementedError("train_sweep: a sweep takes one global crop per image (global_{A,B}_crops_n_crops > 1 is not supported)")
+    if len(cfg.get('dino_global_scales') or []) > 1:
+        raise NotImplementedError("train_sweep: dino_global_scales with several entries is not supported (the slots of a sweep share one ViT scale)")
+    return merge_pair_cfgs(cfg, variants)
+
+
+def train_sweep(dataroot, variants, cfg_overrides=None, vit_state=None, callback=None, progress=True):
+    """One pair, K settings (``variants``: K dicts of per-slot overrides, ``engine.PAIR_KEYS``: the loss weights, lr and its
+    schedule, seed / init_type / init_gain) optimised side by side in ONE ``MultiPairEngine``.  Every slot sees the same crops
+    and augmentations each step (one data feed, the crops stacked K times); slot k's generator is ``define_G`` under its own
+    seed.  The random state right after variant 0's ``define_G`` drives the loop, so when the variants share the seed every
+    slot is, bit for bit, the ``train_model`` run of its merged config, random crops included (``seed: -1`` draws one seed for
+    every variant that has it).  Writes ``<dataroot>/out/sweep/<k>/output.png`` and ``variant.json`` (overrides, seed, final
+    losses); ``callback(k, image)``.  Returns the engine."""
+    from .engine import MultiPairEngine
+    cfg_path = "conf/default/config.yaml" if os.path.exists("conf/default/config.yaml") else _PKG_CFG
+    with open(cfg_path, "r") as f:
+        cfg = yaml.safe_load(f)
+    if dataroot is not None:
+        cfg['dataroot'] = dataroot
+    cfg.update(cfg_overrides or {})
+    variants = [dict(v) for v in variants]
+    cfgs = _sweep_checks(cfg, variants)
+    if device.type != 'cuda':
+        raise RuntimeError("train_sweep needs an MI355X: the product path has no CPU fallback")
+    K = len(variants)
+    drawn = None
+    seeds = []
+    for c in cfgs:
+        seed = c['seed']
+        if seed == -1:
+            if drawn is None:
+                drawn = np.random.randint(2 ** 32 - 1, dtype=np.int64)
+            seed = drawn
+        seeds.append(int(seed))
+    random.seed(seeds[0])
+    np.random.seed(seeds[0] % (2 ** 32))
+    torch.manual_seed(seeds[0])
+    print(f'running a sweep of {K} variants with seeds: {seeds}.')
+
+    A = _load_image(_first_file(os.path.join(cfg['dataroot'], 'A')), cfg['A_resize'])
+    B = _load_image(_first_file(os.path.join(cfg['dataroot'], 'B')), cfg['B_resize'])
+    if cfg['direction'] == 'BtoA':
+        A, B = B, A
+    feed = DeviceDataFeed(cfg, A, B)
+    vit_engine = None if vit_state is not None else _shared_vit_engine(cfg['dino_model_name'], "train_sweep")
+    from .networks import define_G
+    gen_states, rng = [], None
+    for k, c in enumerate(cfgs):
+        if k > 0:
+            torch.manual_seed(seeds[k])
+        netG = define_G(c['init_type'], c['init_gain'], device=device)
+        gen_states.append({n: t.detach().clone() for n, t in netG.state_dict().items() if n in netG.engine.table})
+        del netG
+        if k == 0:   # the state train_model's loop starts from (variant 0's)
+            rng = (random.getstate(), np.random.get_state(), torch.get_rng_state(), torch.cuda.get_rng_state_all())
+    random.setstate(rng[0])
+    np.random.set_state(rng[1])
+    torch.set_rng_state(rng[2])
+    torch.cuda.set_rng_state_all(rng[3])
+    if cfg.get('dino_global_scales'):
+        cfg['dino_global_patch_size'] = int(cfg['dino_global_scales'][0])   # one entry: the ViT input size, as in train_model
+    crop_max = max(min(A.shape[1], A.shape[2]), min(B.shape[1], B.shape[2]))
+    engine = MultiPairEngine(cfg, vit_state, gen_states, (crop_max, crop_max), tuple(A.shape[1:]), device=device, vit_engine=vit_engine,
+                             fp8=fp8_mode(cfg), pair_cfgs=variants)
+    out_dirs = [os.path.join(cfg['dataroot'], 'out', 'sweep', str(k)) for k in range(K)]
+    writers = [AsyncResultWriter(cfg['dataroot'], out_dir=d) for d in out_dirs]
+    try:
+        for epoch in range(1, cfg['n_epochs'] + 1):
+            inputs = feed.next()
+            log = epoch % cfg['log_images_freq'] == 0
+            outputs = [engine.generate(feed.get_A(), pair=k) for k in range(K)] if log else None
+            A_entire = inputs['A'].expand(K, -1, -1, -1).contiguous() if 'A' in inputs else None
+            engine.step(inputs['A_global'].expand(K, -1, -1, -1).contiguous(), inputs['B_global'].expand(K, -1, -1, -1).contiguous(), A_entire)
+            if log:
+                engine.book_logged_forward()
+                for k, out in enumerate(outputs):
+                    writers[k].submit(out[0], force=epoch + cfg['log_images_freq'] > cfg['n_epochs'])
+                    if callback is not None:
+                        callback(k, out[0])
+            if progress and (epoch % 50 == 0 or epoch == 1):
+                print(f"Epoch {epoch}: loss=" + ", ".join(f"{d['loss']:.4f}" for d in engine.losses()) + f" lr={engine.lr}")
+    finally:
+        for w in writers:
+            w.close()
+    losses = engine.losses() if engine.step_idx >= 0 else [{} for _ in range(K)]
+    for k in range(K):
+        with open(os.path.join(out_dirs[k], 'variant.json'), 'w') as f:
+            json.dump({"index": k, "overrides": variants[k], "seed": seeds[k], "losses": losses[k]}, f)
     return engine
 
 

@@ -149,10 +149,11 @@ class AsyncResultWriter:
     overwrites the file later, as the reference does.  ``close()`` drains the queue (called at the end of
     ``train_model`` so the final PNG is on disk when it returns)."""
 
-    def __init__(self, dataroot, slots=2):
+    def __init__(self, dataroot, slots=2, out_dir=None):
+        """``out_dir``: where output.png goes (default ``<dataroot>/out``; a sweep writes ``<dataroot>/out/sweep/<k>``)."""
         import queue
         import threading
-        self.dir = Path(f"{dataroot}/out")
+        self.dir = Path(out_dir) if out_dir is not None else Path(f"{dataroot}/out")
         self.dir.mkdir(exist_ok=True, parents=True)
         self._q = queue.Queue()
         self._free = queue.Queue()
