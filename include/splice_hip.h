@@ -336,6 +336,11 @@ int splice_gen_plan_set_arena_stride(void* plan, long long stride);
  * BatchNorm statistics over the whole batch as nn.BatchNorm2d takes them; gradients summed over the images.  Default 0:
  * N separate batch-1 calls. */
 int splice_gen_plan_set_batch_stats(void* plan, int on);
+/* groups of images per netG call: images [k*g, (k+1)*g) are ONE call on a batch of g images (the n_crops crops of pair k) --
+ * BatchNorm statistics over those g images, parameters / gradients at + k*stride (splice_gen_plan_set_arena_stride first when
+ * there is more than one group).  Group k is bit-identical to a batch-statistics plan of g images on its images.  g = 1: N
+ * independent images; g = N: splice_gen_plan_set_batch_stats.  Needs N % g == 0 and 1 <= g <= 8. */
+int splice_gen_plan_set_groups(void* plan, int images_per_group);
 /* re-target a plan to a smaller input without reallocating (per-step random crop sizes,
  * data/transforms.py:21-22) */
 int splice_gen_plan_resize(void* plan, int H, int W);
@@ -361,16 +366,21 @@ typedef struct splice_step_config {
     int fp8_selfsim;             /* != 0: the key self-similarity Gram matrices on the fp8 MFMA (per-row e4m3 keys; dim % 128 == 0) */
     int top_cls_only;            /* != 0: the step switches its ViT contexts to splice_vit_ctx_set_top_cls_only (the Python engine's default;
                                   * results differ from the full top block by rounding only) */
-    int n_crops;                 /* > 1 (with pairs <= 1): global_{A,B}_crops_n_crops of conf/default/config.yaml -- the step works on
-                                  * n_crops crops of ONE pair: A_crop / B_crop are [n_crops][3][h][w], the generator plans hold n_crops
-                                  * images in batch-statistics mode (splice_gen_plan_set_batch_stats: netG sees the stacked crops,
-                                  * data/transforms.py:27), each loss term is summed over the crops (util/losses.py:75-105), one arena */
+    int n_crops;                 /* > 1: global_{A,B}_crops_n_crops of conf/default/config.yaml -- the step works on n_crops crops of
+                                  * each pair: A_crop / B_crop are [pairs * n_crops][3][h][w] (pair-major), the generator plans hold
+                                  * pairs * n_crops images in batch-statistics mode, one netG call per pair (one pair:
+                                  * splice_gen_plan_set_batch_stats; several: splice_gen_plan_set_groups(n_crops) after the arena stride;
+                                  * netG sees the stacked crops, data/transforms.py:27), each loss term is summed over a pair's crops
+                                  * (util/losses.py:75-105), one arena per pair.  With pairs > 1: at most SPLICE_STEP_MAX_GROUP_IMAGES
+                                  * images per side; the entire-image plan holds `pairs` independent images */
     int n_crops_b;               /* 0: global_B_crops_n_crops == n_crops.  > 0: the B-crop plan holds n_crops_b images and n_crops counts
                                   * the A crops only -- the reference zips the crop lists (util/losses.py:76,87,98): structure term over the
                                   * A crops, identity term over the B crops, appearance term over min(n_crops, n_crops_b) pairs */
 } splice_step_config;
 /* most pairs of one step handle that can carry a config of their own (splice_step_set_pair_weights / splice_step_set_pair_lr) */
 #define SPLICE_STEP_MAX_PAIR_CFGS 32
+/* most images per side (pairs * max(n_crops, n_crops_b)) of a step handle with pairs > 1 and n_crops > 1 */
+#define SPLICE_STEP_MAX_GROUP_IMAGES 32
 /* gen_plan_a / gen_plan_b: N = P plans at the crop size for the A and the B crops; gen_plan_entire: N = P at the entire size
  * (NULL with ent_h == 0).  Contexts: need_grad, B = 4P / 2P. */
 int splice_step_create(const splice_step_config* cfg, void* vit_ctx_global, void* vit_ctx_entire, void* gen_plan_a, void* gen_plan_b,

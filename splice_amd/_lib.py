@@ -147,6 +147,7 @@ _SIGNATURES = {
     "splice_gen_plan_resize": ([_vp, _i, _i], _i),
     "splice_gen_plan_set_arena_stride": ([_vp, C.c_longlong], _i),
     "splice_gen_plan_set_batch_stats": ([_vp, _i], _i),
+    "splice_gen_plan_set_groups": ([_vp, _i], _i),
 }
 
 

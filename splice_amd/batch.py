@@ -21,6 +21,9 @@ Layout::
 
     python -m splice_amd.batch --root pairs/ --gpus 8 [--pairs-per-gpu P] [--n_epochs 2000] [--set key=value ...]
 
+``--pairs-per-gpu P`` works with ``--set global_A_crops_n_crops=n`` (and ``global_B_crops_n_crops``): each pair's n crops are one
+netG call inside the group's shared launches (``train_pairs``); a group holds at most 32 // n pairs (32 images per side).
+
 A hyper-parameter sweep (``--sweep KEY=V1,V2[,...]``, repeatable): every pair runs the cartesian product of the values as ONE
 ``train.train_sweep`` work item (all variants of the pair side by side in one engine); ``result.json`` then lists the variants
 with their losses and ``out/sweep/<k>/`` holds each variant's image.
@@ -232,6 +235,10 @@ def run_batch(root, n_gpus=1, overrides=None, runner="splice_amd.batch:train_run
             if int(pairs_per_gpu) > 1 or runner in ("splice_amd.batch:train_runner", "splice_amd.batch:train_sweep_runner"):
                 raise                                  # the default runner trains IMAGES: an unreadable one is an error here, not later in a worker
             sizes = [((0, 0), (0, 0))] * len(names)    # custom (stub) runners on directories without images: index order, one pair per item
+    # several pairs with n_crops > 1 crops each: at most 32 images per side ride one engine (train_pairs refuses more)
+    n_max = max(int((overrides or {}).get(k, 1)) for k in ("global_A_crops_n_crops", "global_B_crops_n_crops"))
+    if int(pairs_per_gpu) > 1 and n_max > 1:
+        pairs_per_gpu = max(1, min(int(pairs_per_gpu), 32 // n_max))
     items = work_items(sizes, pairs_per_gpu)
     n_gpus = max(1, min(int(n_gpus), len(items)))
     if visible_ids is None:

@@ -81,7 +81,8 @@ struct SpliceGenPlan {
     SpliceGen* gen = nullptr;
     int N = 0, H = 0, W = 0, need_grad = 0, maxH = 0, maxW = 0;
     size_t p_nstride = 0;                 // > 0: the N images are independent generators -- image n uses params / grads + n * p_nstride
-    int batch_stats = 0;                  // != 0: ONE netG call on a batch of N images -- BatchNorm statistics over the whole batch
+    int batch_stats = 0;                  // != 0: netG calls on batches of `group` images -- BatchNorm statistics over each batch
+    int group = 1;                        // images per netG call: N (splice_gen_plan_set_batch_stats) or set by splice_gen_plan_set_groups
     int h[MAXS + 1], w[MAXS + 1];         // spatial size at scale i (h[0] = H)
     std::vector<void*> allocs;
     // per scale
@@ -111,6 +112,11 @@ struct SpliceGenPlan {
     int forward_saved = 0;
 };
 
+// the BatchNorm kernels' `batch` argument (images per statistics group, 0: per image) and the conv launches' images per parameter arena
+static inline int bn_batch(const SpliceGenPlan* p) { return p->batch_stats ? p->group : 0; }
+static inline int conv_group(const SpliceGenPlan* p) { return p->batch_stats && p->p_nstride ? p->group : 0; }
+// parameter arenas of the plan's images (the wgrad / head-bias reductions: one per image or per group; 1 without a stride)
+static inline int plan_arenas(const SpliceGenPlan* p) { return p->batch_stats ? p->N / p->group : p->N; }
 static void build_table(const GenArch& A, ParamTable& t, size_t* offs /* [MAXS][6 units][4] */, size_t* head, ParamTable* bufs = nullptr,
                         size_t* roffs /* [MAXS][6] */ = nullptr) {
     // a conv is nn.Sequential([ReflectionPad2d,] Conv2d): the Conv2d is child "1" behind a padder, child "0" otherwise (models/unet/common.py:113-124)
@@ -235,7 +241,7 @@ static ConvArgs unit_conv_args(const SpliceGenPlan* p, const Unit& u, const floa
     ConvArgs a = {};
     a.in = u.in; a.w = params + u.w_off; a.bias = params + u.b_off; a.out = u.y;
     a.in_nstride = u.in_ns; a.in_cstride = (size_t)u.Hi * u.Wi; a.out_nstride = u.y_ns; a.out_cstride = (size_t)u.Ho * u.Wo;
-    a.w_jstride = (size_t)u.Cin * u.ks * u.ks; a.w_cstride = (size_t)u.ks * u.ks; a.p_nstride = p->p_nstride;
+    a.w_jstride = (size_t)u.Cin * u.ks * u.ks; a.w_cstride = (size_t)u.ks * u.ks; a.p_nstride = p->p_nstride; a.p_group = conv_group(p);
     a.N = p->N; a.Cin = u.Cin; a.Hi = u.Hi; a.Wi = u.Wi; a.Cout = u.Cout; a.Ho = u.Ho; a.Wo = u.Wo;
     a.ks = u.ks; a.stride = u.stride; a.pad = (u.ks - 1) / 2; a.reflect = p->gen->arch.reflect && u.ks > 1;
     a.ws = ws; a.ws_floats = ws_floats;
@@ -270,7 +276,7 @@ static int unit_bn_forward(const SpliceGenPlan* p, const Unit& u, const float* p
         up = nullptr;
     }
     RC(bn_fwd_launch(y, y_ns, u.out, u.out_ns, N, u.Cout, u.Ho * u.Wo, params + u.g_off, params + u.be_off, BN_EPS, u.s1, u.mean, u.rstd, u.slope, s, up,
-                     p->p_nstride, p->batch_stats, pre));
+                     p->p_nstride, bn_batch(p), pre));
     return SPLICE_OK;
 }
 static int unit_forward(const SpliceGenPlan* p, const Unit& u, const float* params, hipStream_t s, const BnUpsample* up = nullptr, const BnPre* pre = nullptr) {
@@ -320,7 +326,7 @@ static int unit_backward_bn(const SpliceGenPlan* p, const Unit& u, const float* 
         if (pend.target) { sl.slabs = pend.slabs; sl.ksplit = pend.ksplit; sl.accumulate = pend.accumulate; pend.target = nullptr; }
         SPLICE_DEV_REGION(14);
         RC(bn_bwd_launch(u.d_out, u.d_out_ns, u.out, u.out_ns, y, y_ns, dy, dy_ns, N, u.Cout, HW, params + u.g_off, u.mean, u.rstd, u.slope,
-                         u.s1, grads + u.g_off, grads + u.be_off, acc, s, p->batch_stats ? nullptr : up, p->p_nstride, p->batch_stats, pre, &sl, params + u.be_off));
+                         u.s1, grads + u.g_off, grads + u.be_off, acc, s, p->batch_stats ? nullptr : up, p->p_nstride, bn_batch(p), pre, &sl, params + u.be_off));
     }
     if (!u.ks) return SPLICE_OK;
     // The bias of a conv that feeds a train-mode BatchNorm has an analytically ZERO gradient (BN subtracts the
@@ -352,7 +358,7 @@ static ConvArgs unit_dgrad_args(const SpliceGenPlan* p, const Unit& u, const flo
     ConvArgs a = {};
     a.in = u.dy; a.w = params + u.w_off; a.bias = nullptr; a.out = u.d_in;
     a.in_nstride = u.y_ns; a.in_cstride = (size_t)HW; a.out_nstride = u.d_in_ns; a.out_cstride = (size_t)u.Hi * u.Wi;
-    a.w_jstride = (size_t)u.ks * u.ks; a.w_cstride = (size_t)u.Cin * u.ks * u.ks; a.p_nstride = p->p_nstride;
+    a.w_jstride = (size_t)u.ks * u.ks; a.w_cstride = (size_t)u.Cin * u.ks * u.ks; a.p_nstride = p->p_nstride; a.p_group = conv_group(p);
     a.N = p->N; a.Cin = u.Cout; a.Hi = u.Ho; a.Wi = u.Wo; a.Cout = u.Cin; a.Ho = u.Hi; a.Wo = u.Wi;
     a.ks = u.ks; a.stride = u.stride; a.pad = (u.ks - 1) / 2; a.transposed = 1; a.accumulate = accumulate;
     a.ws = ws; a.ws_floats = ws_floats;
@@ -551,6 +557,28 @@ int splice_gen_plan_set_batch_stats(void* plan, int on) {
         return SPLICE_ERR_ARG;
     }
     p->batch_stats = on ? 1 : 0;
+    p->group = on ? p->N : 1;
+    plan_configure(p, p->H, p->W);
+    return SPLICE_OK;
+}
+
+// Groups of images per netG call: images [k g, (k + 1) g) are ONE call (the n_crops crops of pair k) -- BatchNorm statistics over those g
+// images in image order, parameters and gradients in arena k (k * arena stride).  Every sum and launch policy of a group is the one
+// of a plan of g images with batch statistics, so group k's results are bit for bit those of that plan on its images.  g = 1: N
+// separate calls (independent images with a stride); g = N: batch statistics (splice_gen_plan_set_batch_stats).  Needs N % g == 0,
+// 1 <= g <= 8, and an arena stride when there is more than one group (set it first).
+int splice_gen_plan_set_groups(void* plan, int images_per_group) {
+    SpliceGenPlan* p = (SpliceGenPlan*)plan;
+    const int g = images_per_group;
+    if (!p) { splice_set_error("splice_gen_plan_set_groups: null plan"); return SPLICE_ERR_ARG; }
+    if (g < 1 || g > 8) { splice_set_error("splice_gen_plan_set_groups: images_per_group %d outside 1..8", g); return SPLICE_ERR_ARG; }
+    if (p->N % g) { splice_set_error("splice_gen_plan_set_groups: %d images are not a multiple of images_per_group %d", p->N, g); return SPLICE_ERR_ARG; }
+    if (g > 1 && g < p->N && !p->p_nstride) {
+        splice_set_error("splice_gen_plan_set_groups: %d groups need an arena stride (splice_gen_plan_set_arena_stride first)", p->N / g);
+        return SPLICE_ERR_ARG;
+    }
+    p->batch_stats = g > 1 ? 1 : 0;
+    p->group = g;
     plan_configure(p, p->H, p->W);
     return SPLICE_OK;
 }
@@ -588,13 +616,15 @@ int splice_gen_running_stats_update(void* const* plans, int n_plans, float* runn
     for (int k = 0; k < n_plans; ++k) {
         SpliceGenPlan* p = (SpliceGenPlan*)plans[k];
         if (!p) return SPLICE_ERR_ARG;
-        t.N[k] = p->batch_stats ? 1 : p->N; t.indep[k] = p->p_nstride ? 1 : 0;   // a batch call is ONE update with the batch statistics
-        if (t.indep[k] && p->N > max_images) max_images = p->N;
+        // a batch call is ONE update with the batch statistics; grouped plans: one per group, from its first image's (= the group's) statistics
+        t.N[k] = p->batch_stats ? p->N / p->group : p->N; t.indep[k] = p->p_nstride ? 1 : 0;
+        t.img_step[k] = p->batch_stats ? p->group : 1;
+        if (t.indep[k] && t.N[k] > max_images) max_images = t.N[k];
         int bn = 0;
         for (int i = 0; i < p->gen->arch.n_scales; ++i)
             for (Unit* u : {&p->u_skip[i], &p->u_da[i], &p->u_db[i], &p->u_cat[i], &p->u_up3[i], &p->u_up1[i]}) {
                 if (k == 0) { t.C[bn] = u->Cout; t.r_off[bn] = (int)u->r_off; }
-                t.HW[k][bn] = u->Ho * u->Wo * (p->batch_stats ? p->N : 1); t.mean[k][bn] = u->mean; t.rstd[k][bn] = u->rstd;
+                t.HW[k][bn] = u->Ho * u->Wo * (p->batch_stats ? p->group : 1); t.mean[k][bn] = u->mean; t.rstd[k][bn] = u->rstd;
                 ++bn;
             }
     }
@@ -652,7 +682,7 @@ static int gen_forward_impl(void* plan, const float* params, const float* x, flo
         a.in = u.out; a.w = params + p->head_w; a.bias = params + p->head_b; a.out = y;
         const int OC = p->gen->arch.out_channels, U0 = p->gen->arch.up[0];
         a.in_nstride = u.out_ns; a.in_cstride = (size_t)p->H * p->W; a.out_nstride = (size_t)OC * p->H * p->W; a.out_cstride = (size_t)p->H * p->W;
-        a.w_jstride = U0; a.w_cstride = 1; a.p_nstride = p->p_nstride;
+        a.w_jstride = U0; a.w_cstride = 1; a.p_nstride = p->p_nstride; a.p_group = conv_group(p);
         a.N = p->N; a.Cin = U0; a.Hi = p->H; a.Wi = p->W; a.Cout = OC; a.Ho = p->H; a.Wo = p->W; a.ks = 1; a.stride = 1; a.pad = 0; a.act = 1;
         RC(conv_launch(a, s));
     }
@@ -742,7 +772,7 @@ int splice_gen_backward(void* plan, const float* params, const float* dy, float*
     (void)npix;
     {
         int chunks = 0;
-        RC(sigmoid_bwd_bias_launch(dy, p->y_saved, p->d_head_pre, p->N, OC, HW, p->wgrad_ws + p->head_bias_off, s, p->p_nstride, &chunks));
+        RC(sigmoid_bwd_bias_launch(dy, p->y_saved, p->d_head_pre, p->N, OC, HW, p->wgrad_ws + p->head_bias_off, s, p->p_nstride, &chunks, conv_group(p)));
         WgradReduceAll& r = p->red;
         const int li = r.count++;
         r.n[li] = OC; r.chunks[li] = chunks; r.ws_off[li] = (long long)p->head_bias_off; r.dw_off[li] = (long long)p->head_b;
@@ -763,7 +793,7 @@ int splice_gen_backward(void* plan, const float* params, const float* dy, float*
         ConvArgs a = {};
         a.in = p->d_head_pre; a.w = params + p->head_w; a.out = u.d_out;
         a.in_nstride = (size_t)OC * HW; a.in_cstride = (size_t)HW; a.out_nstride = u.d_out_ns; a.out_cstride = (size_t)HW;
-        a.w_jstride = 1; a.w_cstride = U0; a.p_nstride = p->p_nstride;
+        a.w_jstride = 1; a.w_cstride = U0; a.p_nstride = p->p_nstride; a.p_group = conv_group(p);
         a.N = p->N; a.Cin = OC; a.Hi = p->H; a.Wi = p->W; a.Cout = U0; a.Ho = p->H; a.Wo = p->W; a.ks = 1; a.stride = 1; a.pad = 0; a.transposed = 1;
         RC(conv_launch(a, s));
     }
@@ -776,7 +806,7 @@ int splice_gen_backward(void* plan, const float* params, const float* dy, float*
         r.prefix[0] = 0;
         for (int i = 0; i < r.count; ++i) r.prefix[i + 1] = r.prefix[i] + r.n[i];
         r.total = r.prefix[r.count];
-        RC(wgrad_reduce_all_launch(r, p->wgrad_ws, grads, accumulate, s, p->N, p->p_nstride));
+        RC(wgrad_reduce_all_launch(r, p->wgrad_ws, grads, accumulate, s, plan_arenas(p), p->p_nstride));
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { splice_set_error("splice_gen_backward: %s", hipGetErrorString(e)); return SPLICE_ERR_HIP; }

@@ -19,6 +19,7 @@ struct ConvArgs {
     float* ws;        // optional split-K scratch (ws_floats floats); null disables split-K
     size_t ws_floats;
     int ksplit;       // set by the launcher
+    int p_group;      // > 1 (with p_nstride): grouped images -- image n reads the arena of group n / p_group; launch policies read one group
     int defer_reduce; // split-K: leave the raw slabs in ws (ksplit_out tells how many); the consumer adds bias + slabs in slice order
 };
 int conv_launch(const ConvArgs& a, hipStream_t s, int* ksplit_out = nullptr);
@@ -108,7 +109,8 @@ bool bn_bwd_fuses_upsample(int HW, int h, int w);
 bool bn_bwd_fuses_upsample_ex(int HW, int h, int w, int N, size_t p_nstride, int batch);   // incl. the one-launch form of the middle planes
 int bn_fwd_launch(const float* y, size_t y_nstride, float* out, size_t out_nstride, int N, int C, int HW, const float* gamma,
                   const float* beta, float eps, float* part, float* mean, float* rstd, float slope, hipStream_t s, const BnUpsample* up = nullptr,
-                  size_t p_nstride = 0, int batch = 0, const BnPre* pre = nullptr);   // batch != 0: statistics over all N images (nn.BatchNorm2d on a batch), N <= 8
+                  size_t p_nstride = 0, int batch = 0, const BnPre* pre = nullptr);   // batch > 0: statistics over groups of `batch` images (nn.BatchNorm2d on a
+                                                                                          // batch), batch <= 8; batch < N needs p_nstride (one arena per group)
 // same, fused with the split-K reduction of the convolution that feeds it (small planes only: HW <= bn_small_hw()):
 // y = bias + sum_k slabs[k] is formed, stored (the backward reads it) and normalised in one launch
 int bn_small_hw();
@@ -126,7 +128,8 @@ int upsample2x_bwd_launch(const float* dout, size_t dout_nstride, float* din, si
 int sigmoid_bwd_launch(const float* dout, const float* sout, float* dpre, size_t n, hipStream_t s);
 // sigmoid backward of the [N][C][HW] head + per-channel sums of the result (the head's bias gradient) in two
 // deterministic stages; part = C * 64 floats of scratch
-int sigmoid_bwd_bias_launch(const float* dout, const float* sout, float* dpre, int N, int C, int HW, float* part, hipStream_t s, size_t p_nstride, int* chunks);
+int sigmoid_bwd_bias_launch(const float* dout, const float* sout, float* dpre, int N, int C, int HW, float* part, hipStream_t s, size_t p_nstride, int* chunks,
+                            int group = 1);
 int sigmoid_bias_part_floats(int N, int C);   // floats of `part`: [image][segment][channel], summed by wgrad_reduce_all_launch
 // Fused optimiser updates over a flat arena (torch.optim as util/util.py:28-39 builds them).  g2 (optional): a second gradient
 // arena folded in as g += g2 (written back when g2 or zero_grad is set).  lr_dev (optional): the learning rate is read from
@@ -149,6 +152,7 @@ struct RunStatTable {
     int n_plans, n_bn;
     int C[RUNSTAT_MAX_BN], r_off[RUNSTAT_MAX_BN];      // channels; offset of running_mean in the buffer arena (running_var follows at + C)
     int N[RUNSTAT_MAX_PLANS], indep[RUNSTAT_MAX_PLANS];
+    int img_step[RUNSTAT_MAX_PLANS];                   // grouped plans: images per update (the group's first image holds its statistics); 0 / 1 otherwise
     int HW[RUNSTAT_MAX_PLANS][RUNSTAT_MAX_BN];
     const float* mean[RUNSTAT_MAX_PLANS][RUNSTAT_MAX_BN];   // [N][C] batch statistics saved by the forward
     const float* rstd[RUNSTAT_MAX_PLANS][RUNSTAT_MAX_BN];

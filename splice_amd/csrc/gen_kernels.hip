@@ -61,6 +61,8 @@ struct ConvTile {   // LDS geometry of one instantiation (shared by the kernel w
 // ConvTile<..>::A_FLOATS / W_FLOATS floats of LDS.  Called from conv_igemm_kernel (one convolution per launch) and from
 // conv_pair_kernel (two independent convolutions -- e.g. the 1x1 skip branch and the 3x3 stride-2 encoder convolution of one
 // scale, which read the same input -- sharing one launch: a launch less on a latency-bound chain).
+// offset of image img's parameter arena: its own (p_nstride > 0), its group's (p_group > 1 images per arena) or the one arena
+__device__ __forceinline__ size_t conv_arena(const ConvArgs& a, int img) { return (size_t)(a.p_group > 1 ? img / a.p_group : img) * a.p_nstride; }
 template <int KS, bool TRANSPOSED, int FN, int CK, int NG>
 __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, int bx, int by, int bz, float* As, float* Ws) {
     constexpr int T = KS * KS;
@@ -82,9 +84,10 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, int bx, int b
     const int m0 = bx * BM;
     const int HWo = a.Ho * a.Wo;
     const float* in = a.in + (size_t)img * a.in_nstride;
-    // independent images (several pairs optimised side by side): image n convolves with ITS OWN parameter arena
-    const float* wgt = a.w + (size_t)img * a.p_nstride;
-    const float* bias = a.bias ? a.bias + (size_t)img * a.p_nstride : nullptr;
+    // independent images (several pairs optimised side by side): image n convolves with ITS OWN parameter arena (grouped
+    // images: the arena of its group)
+    const float* wgt = a.w + conv_arena(a, img);
+    const float* bias = a.bias ? a.bias + conv_arena(a, img) : nullptr;
     const int pl = tid & 63;
     const int p = m0 + pl;
     const bool pvalid = p < HWo;
@@ -322,7 +325,7 @@ __global__ void conv_splitk_reduce_kernel(ConvArgs a, int ksplit) {
         const int pp = i % HWo;
         const int n = (i / HWo) % a.Cout;
         const int img = i / ((size_t)HWo * a.Cout);
-        float v = a.bias ? a.bias[(size_t)img * a.p_nstride + n] : 0.f;
+        float v = a.bias ? a.bias[conv_arena(a, img) + n] : 0.f;
         float* q = a.out + (size_t)img * a.out_nstride + (size_t)n * a.out_cstride + pp;
         const float prev = a.accumulate ? *q : 0.f;
         int k = 0;
@@ -367,7 +370,7 @@ static ConvPolicy conv_policy(const ConvArgs& a, int KS, int CK) {
     const int nt_run = cdiv(a.Cout, 16 * fn_run);
     // launch policy (split-K, 8-wave workgroups) from the workgroups of ONE image when the images are independent pairs:
     // split-K changes the summation order, and a pair's result must not depend on how many pairs share the launch
-    const int npol = a.p_nstride ? 1 : a.N;
+    const int npol = a.p_nstride ? (a.p_group > 1 ? a.p_group : 1) : a.N;
     const int wgs = mt * nt * npol;
     int ksplit = 1;
     const int ktiles = cdiv(a.Cin, CK);
@@ -402,7 +405,7 @@ static void conv_splitk_reduce_launch(const ConvArgs& a, int ksplit, hipStream_t
 static inline void conv_note_work(const ConvArgs& a) {
     if (g_splice_prof_open <= 0) return;
     const double outs = (double)a.N * a.Cout * a.Ho * a.Wo, red = (double)a.Cin * a.ks * a.ks;
-    splice_prof_note(2.0 * outs * red, 4.0 * (outs + (double)a.N * a.Cin * a.Hi * a.Wi + (double)a.Cout * red * (a.p_nstride ? a.N : 1)));
+    splice_prof_note(2.0 * outs * red, 4.0 * (outs + (double)a.N * a.Cin * a.Hi * a.Wi + (double)a.Cout * red * (a.p_nstride ? a.N / (a.p_group > 1 ? a.p_group : 1) : 1)));
 }
 template <int KS, bool TR, int CK>
 static void conv_launch_fn(ConvArgs a, hipStream_t s, int* ksplit_out) {
@@ -508,8 +511,8 @@ __global__ __launch_bounds__(256) void conv3x3_tile_kernel(ConvArgs a, int tiles
     const int x0 = (blockIdx.x % tiles_x) * CT_TW, y0 = (blockIdx.x / tiles_x) * CT_TH;
     const int n0 = blockIdx.y * BN;
     const float* in = a.in + (size_t)img * a.in_nstride;
-    const float* wgt = a.w + (size_t)img * a.p_nstride;
-    const float* bias = a.bias ? a.bias + (size_t)img * a.p_nstride : nullptr;
+    const float* wgt = a.w + conv_arena(a, img);
+    const float* bias = a.bias ? a.bias + conv_arena(a, img) : nullptr;
     // source coordinates of the patch origin: forward sy = oy - pad + ky, data gradient sy = oy + pad - ky (ky = 0 .. 2)
     const int sy0 = TRANSPOSED ? y0 + a.pad - 2 : y0 - a.pad, sx0 = TRANSPOSED ? x0 + a.pad - 2 : x0 - a.pad;
     // ---- staging descriptors: patch element e = tid + 256 j = (channel, patch row, patch column); fixed for the kernel, the chunk enters as the scalar offset
@@ -1506,6 +1509,10 @@ __device__ __forceinline__ void bn_combine_wave_raw(const float* part, int PB, i
     mean = __shfl(m, 0, 64);
     M2out = __shfl(M2, 0, 64);
 }
+// The BatchNorm kernels' `batch`: 0 = per-image statistics; > 0 = statistics over groups of `batch` consecutive images (one netG call on
+// the crops of one pair: batch = N for a single pair, n_crops per pair for several pairs side by side).  Image img reads its parameters at
+// + bn_arena(...): its own arena (independent images), its group's arena (grouped images) or the one arena (p_nstride == 0).
+__device__ __forceinline__ size_t bn_arena(int img, size_t p_nstride, int batch) { return (size_t)(batch ? img / batch : img) * p_nstride; }
 // batch statistics (nn.BatchNorm2d over a batch of N images, models/unet/common.py:95-96 when netG is fed n_crops > 1
 // crops at once): Chan merge of the N planes' (mean, M2) in image order
 __device__ __forceinline__ void bn_combine_batch(const float* part_c0 /* image 0, channel c */, size_t img_stride, int N, int PB, int HW, float eps,
@@ -1534,10 +1541,10 @@ __global__ __launch_bounds__(256) void bn_act_kernel(const float* __restrict__ y
                                                      float* __restrict__ mean_o, float* __restrict__ rstd_o, float slope, size_t p_nstride, int batch) {
     __shared__ float st[2];
     const int c = blockIdx.y, img = blockIdx.z;
-    gamma += (size_t)img * p_nstride; beta += (size_t)img * p_nstride;
+    gamma += bn_arena(img, p_nstride, batch); beta += bn_arena(img, p_nstride, batch);
     if (threadIdx.x < 64) {
         float m, r;
-        if (batch) bn_combine_batch(part + (size_t)c * PB * 2, (size_t)C * PB * 2, gridDim.z, PB, HW, eps, m, r);
+        if (batch) bn_combine_batch(part + ((size_t)(img / batch * batch) * C + c) * PB * 2, (size_t)C * PB * 2, batch, PB, HW, eps, m, r);
         else bn_combine_wave(part + ((size_t)img * C + c) * PB * 2, PB, HW, eps, m, r);
         if (threadIdx.x == 0) {
             st[0] = m; st[1] = r;
@@ -1634,14 +1641,14 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
                                                            const float* __restrict__ beta) {
     __shared__ float st[2];
     const int c = blockIdx.y, img = blockIdx.z;
-    gamma += (size_t)img * p_nstride;
+    gamma += bn_arena(img, p_nstride, batch);
     if (threadIdx.x < 64) {   // one wave: lane k holds segment k (PB <= 64), fixed-order tree sums
         const int lane = threadIdx.x;
         const float* pp = part + ((size_t)img * C + c) * PB * 2;
         const float a = part_sum(pp, PB, 0, lane), b = part_sum(pp, PB, 1, lane);
         if (lane == 0) { st[0] = a; st[1] = b; }
-        if (p_nstride) {   // independent images: every image owns its parameter gradients (the sums of the N = 1 path: 0 + x)
-            if (blockIdx.x == 0 && lane == 0) {
+        if (p_nstride) {   // independent images: every image owns its parameter gradients (the sums of the N = 1 path: 0 + x); grouped: below
+            if (!batch && blockIdx.x == 0 && lane == 0) {
                 float* dg = dgamma + (size_t)img * p_nstride + c;
                 float* db = dbeta + (size_t)img * p_nstride + c;
                 const float g = 0.f + b, be = 0.f + a;
@@ -1661,19 +1668,27 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
             }
         }
     }
-    if (batch && threadIdx.x < 64) {   // batch statistics: the two sums run over every image of the batch (image order)
-        const int lane = threadIdx.x;
+    if (batch && threadIdx.x < 64) {   // batch statistics: the two sums run over every image of the batch / group (image order)
+        const int lane = threadIdx.x, n0 = img / batch * batch;
         float a = 0.f, b = 0.f;
-        for (int n = 0; n < N; ++n) {
-            const float* pn = part + ((size_t)n * C + c) * PB * 2;
+        for (int n = 0; n < batch; ++n) {
+            const float* pn = part + ((size_t)(n0 + n) * C + c) * PB * 2;
             a += part_sum(pn, PB, 0, lane);
             b += part_sum(pn, PB, 1, lane);
         }
-        if (lane == 0) { st[0] = a; st[1] = b; }
+        if (lane == 0) {
+            st[0] = a; st[1] = b;
+            if (p_nstride && img == n0 && blockIdx.x == 0) {   // grouped: the group's parameter gradients are these sums (those of the one-group path)
+                float* dg = dgamma + bn_arena(img, p_nstride, batch) + c;
+                float* db = dbeta + bn_arena(img, p_nstride, batch) + c;
+                *dg = accumulate ? *dg + b : b;
+                *db = accumulate ? *db + a : a;
+            }
+        }
     }
     __syncthreads();
     const float m = mean[img * C + c], r = rstd[img * C + c];
-    const float cnt = batch ? (float)HW * (float)N : (float)HW;
+    const float cnt = batch ? (float)HW * (float)batch : (float)HW;
     const float k1 = st[0] / cnt, k2 = st[1] / cnt;
     const float gr = gamma[c] * r;
     const float* pd = da + (size_t)img * da_nstride + (size_t)c * HW;
@@ -1691,7 +1706,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
             ld_run(py, i, hi, yy[k]);
             if (act && !from_y) ld_run(pa, i, hi, a[k]);
         }
-        const float sc = gr, sh = from_y ? bn_shift(beta[(size_t)img * p_nstride + c], m, sc) : 0.f;
+        const float sc = gr, sh = from_y ? bn_shift(beta[bn_arena(img, p_nstride, batch) + c], m, sc) : 0.f;
 #pragma unroll
         for (int k = 0; k < BN_V_CH; ++k) {
             const int i = lo + 4 * (threadIdx.x + 256 * k);
@@ -1770,8 +1785,8 @@ __global__ __launch_bounds__(256) void bn_small_fwd_kernel(const float* y, size_
     __shared__ float red[8];
     __shared__ float up_src_s[BN_UP_SRC];
     const int c = blockIdx.x, img = blockIdx.y;
-    gamma += (size_t)img * p_nstride; beta += (size_t)img * p_nstride;
-    if (bias) bias += (size_t)img * p_nstride;
+    gamma += bn_arena(img, p_nstride, batch); beta += bn_arena(img, p_nstride, batch);
+    if (bias) bias += bn_arena(img, p_nstride, batch);
     const float* p = y + (size_t)img * y_nstride + (size_t)c * HW;
     float* q = out + (size_t)img * out_nstride + (size_t)c * HW;
     // loads are issued branch-free (wave-uniform guards only; a thread past the end of the plane re-reads element 0 and
@@ -1931,12 +1946,13 @@ __global__ __launch_bounds__(256) void bn_small_fwd_kernel(const float* y, size_
     dummy = 0.f;
     float cnt = (float)HW;
     if (batch) {
-        // batch statistics: every workgroup of channel c walks all N planes in image order (same bits in each); the other
-        // planes are re-read (small, L2-resident); slabs / fused upsampling are not combined with this mode
-        const int N = gridDim.y;
+        // batch statistics: every workgroup of channel c walks all N planes of its batch / group in image order (same bits in each);
+        // the other planes are re-read (small, L2-resident); slabs / fused upsampling are not combined with this mode
+        const int N = batch;
+        const float* yg = y + (size_t)(img / batch * batch) * y_nstride;
         float tot = 0.f;
         for (int n = 0; n < N; ++n) {
-            const float* pn = y + (size_t)n * y_nstride + (size_t)c * HW;
+            const float* pn = yg + (size_t)n * y_nstride + (size_t)c * HW;
             float sn = 0.f, d2 = 0.f;
 #pragma unroll
             for (int k = 0; k < PER; ++k) {
@@ -1949,7 +1965,7 @@ __global__ __launch_bounds__(256) void bn_small_fwd_kernel(const float* y, size_
         cnt = (float)HW * (float)N;
         m = tot / cnt;
         for (int n = 0; n < N; ++n) {
-            const float* pn = y + (size_t)n * y_nstride + (size_t)c * HW;
+            const float* pn = yg + (size_t)n * y_nstride + (size_t)c * HW;
             float qn = 0.f, d2 = 0.f;
 #pragma unroll
             for (int k = 0; k < PER; ++k) {
@@ -2057,7 +2073,8 @@ __global__ __launch_bounds__(256) void bn_small_bwd_kernel(const float* __restri
     __shared__ float red[8];
     __shared__ float up_grad_s[BN_SMALL_HW];   // fused upsampling adjoint: this plane's input gradient
     const int c = blockIdx.x, img = blockIdx.y;
-    gamma += (size_t)img * p_nstride;
+    gamma += bn_arena(img, p_nstride, batch);
+    const int n0 = batch ? img / batch * batch : 0;   // first image of the batch / group
     float dz[PER], xh[PER];
     float s1, s2;
     const bool chained = pre.y && c < pre.C;   // workgroup-uniform: a skip-branch BatchNorm sits in front of this channel (BnPre)
@@ -2069,21 +2086,22 @@ __global__ __launch_bounds__(256) void bn_small_bwd_kernel(const float* __restri
 #pragma unroll
             for (int n = 0; n < BN_MAX_BATCH; ++n) {
                 t1s[n] = 0.f; t2s[n] = 0.f;
-                if (n < N && n != img)
-                    bn_small_bwd_sums<PER>(da + (size_t)n * da_nstride + (size_t)c * HW, aout + (size_t)n * a_nstride + (size_t)c * HW,
-                                      y + (size_t)n * y_nstride + (size_t)c * HW, HW, mean[n * C + c], rstd[n * C + c], slope, dz, xh, t1s[n], t2s[n], red);
+                const int gn = n0 + n;
+                if (n < batch && gn != img)
+                    bn_small_bwd_sums<PER>(da + (size_t)gn * da_nstride + (size_t)c * HW, aout + (size_t)gn * a_nstride + (size_t)c * HW,
+                                      y + (size_t)gn * y_nstride + (size_t)c * HW, HW, mean[gn * C + c], rstd[gn * C + c], slope, dz, xh, t1s[n], t2s[n], red);
             }
             bn_small_bwd_sums<PER>(da + (size_t)img * da_nstride + (size_t)c * HW, aout + (size_t)img * a_nstride + (size_t)c * HW,
                               y + (size_t)img * y_nstride + (size_t)c * HW, HW, m, r, slope, dz, xh, s1, s2, red);
 #pragma unroll
             for (int n = 0; n < BN_MAX_BATCH; ++n)
-                if (n < N) { b1 += n == img ? s1 : t1s[n]; b2 += n == img ? s2 : t2s[n]; }
+                if (n < batch) { b1 += n0 + n == img ? s1 : t1s[n]; b2 += n0 + n == img ? s2 : t2s[n]; }
         } else {
             bn_small_bwd_sums<PER>(da + (size_t)img * da_nstride + (size_t)c * HW, aout + (size_t)img * a_nstride + (size_t)c * HW,
                               y + (size_t)img * y_nstride + (size_t)c * HW, HW, m, r, slope, dz, xh, s1, s2, red,
                               sl.slabs ? sl.slabs + ((size_t)img * C + c) * HW : nullptr, (size_t)gridDim.y * C * HW, sl.ksplit, sl.accumulate);
         }
-        const float cnt = batch ? (float)HW * (float)N : (float)HW;
+        const float cnt = batch ? (float)HW * (float)batch : (float)HW;
         const float k1 = (batch ? b1 : s1) / cnt, k2 = (batch ? b2 : s2) / cnt;
         if (batch) { s1 = b1; s2 = b2; }   // the parameter gradients are exactly these sums
         const float gr = gamma[c] * r;
@@ -2149,10 +2167,10 @@ __global__ __launch_bounds__(256) void bn_small_bwd_kernel(const float* __restri
                 qd[e] = up_adjoint_value((const float*)up_grad_s, up.h, up.w, up.Ho, up.Wo, e / up.w, e % up.w);
         }
     }
-    if (p_nstride) {   // independent images: every image owns its parameter gradients
-        if (threadIdx.x == 0) {
-            float* dg = dgamma + (size_t)img * p_nstride + c;
-            float* db = dbeta + (size_t)img * p_nstride + c;
+    if (p_nstride) {   // independent images: every image owns its parameter gradients; grouped: the group's first image writes its sums
+        if (threadIdx.x == 0 && (!batch || img == n0)) {
+            float* dg = dgamma + bn_arena(img, p_nstride, batch) + c;
+            float* db = dbeta + bn_arena(img, p_nstride, batch) + c;
             *dg = accumulate ? *dg + s2 : s2;
             *db = accumulate ? *db + s1 : s1;
         }
@@ -2437,7 +2455,7 @@ int bn_fwd_launch(const float* y, size_t y_nstride, float* out, size_t out_nstri
                   int batch, const BnPre* pre) {
     const BnUpsample u = up ? *up : BnUpsample{};
     const BnPre pr = pre ? *pre : BnPre{};
-    if (batch && (N > BN_MAX_BATCH || u.src || p_nstride)) return SPLICE_ERR_ARG;
+    if (batch && (batch > BN_MAX_BATCH || N % batch || u.src || (N != batch && !p_nstride))) return SPLICE_ERR_ARG;
     if (pre && !bn_pre_supported(HW, N, p_nstride, batch)) return SPLICE_ERR_ARG;
     if (HW <= BN_SMALL_HW) {
         BN_SMALL_DISPATCH(HW, bn_small_fwd_kernel, dim3(C, N), s, y, y_nstride, out, out_nstride, C, HW, gamma, beta, eps, mean, rstd, slope,
@@ -2472,7 +2490,7 @@ int bn_bwd_launch(const float* da, size_t da_nstride, const float* aout, size_t 
                   size_t dy_nstride, int N, int C, int HW, const float* gamma, const float* mean, const float* rstd, float slope,
                   float* part, float* dgamma, float* dbeta, int accumulate, hipStream_t s, const BnUpsample* up, size_t p_nstride, int batch, const BnPre* pre,
                   const BnSlabs* slabs, const float* beta) {
-    if (batch && (N > BN_MAX_BATCH || p_nstride)) return SPLICE_ERR_ARG;
+    if (batch && (batch > BN_MAX_BATCH || N % batch || (N != batch && !p_nstride))) return SPLICE_ERR_ARG;
     if (pre && !bn_pre_supported(HW, N, p_nstride, batch)) return SPLICE_ERR_ARG;
     if (slabs && slabs->slabs && !bn_bwd_takes_slabs(HW, N, p_nstride, batch)) return SPLICE_ERR_ARG;
     const BnPre pr = pre ? *pre : BnPre{};
@@ -2563,12 +2581,12 @@ __global__ void sigmoid_bwd_kernel(const float* __restrict__ dout, const float* 
 // wgrad_reduce_all launch sums them with everything else (round 4: the bias had a reduce launch of its own).
 __global__ __launch_bounds__(256) void sigmoid_bwd_bias_kernel(const float* __restrict__ dout, const float* __restrict__ sout,
                                                                float* __restrict__ dpre, int N, int C, int HW, int PB,
-                                                               float* __restrict__ part) {
+                                                               float* __restrict__ part, int per) {
     __shared__ float red[8];
     const int pb = blockIdx.x, c = blockIdx.y;
     const int seg = seg_len(HW, PB), lo = pb * seg, hi = min(lo + seg, HW);
     float acc = 0.f, dummy = 0.f;
-    const int n_lo = gridDim.z > 1 ? blockIdx.z : 0, n_hi = gridDim.z > 1 ? blockIdx.z + 1 : N;
+    const int n_lo = gridDim.z > 1 ? blockIdx.z * per : 0, n_hi = gridDim.z > 1 ? n_lo + per : N;
     part += (size_t)(gridDim.z > 1 ? blockIdx.z : 0) * C * PB;
     for (int n = n_lo; n < n_hi; ++n) {
         const size_t base = ((size_t)n * C + c) * HW;
@@ -2582,11 +2600,14 @@ __global__ __launch_bounds__(256) void sigmoid_bwd_bias_kernel(const float* __re
     block_sum2(acc, dummy, red);
     if (threadIdx.x == 0) part[pb * C + c] = acc;
 }
-// returns the number of partial "chunks" per parameter (for the reduce entry): PB, or N * PB for independent images
-int sigmoid_bwd_bias_launch(const float* dout, const float* sout, float* dpre, int N, int C, int HW, float* part, hipStream_t s, size_t p_nstride, int* chunks) {
+// returns the number of partial "chunks" per parameter (for the reduce entry): PB, or N / group * PB for independent images / groups
+// of `group` images (blockIdx.z = group: its images in image order, as the one-group path walks them)
+int sigmoid_bwd_bias_launch(const float* dout, const float* sout, float* dpre, int N, int C, int HW, float* part, hipStream_t s, size_t p_nstride, int* chunks,
+                            int group) {
     const int PB = plane_blocks(HW);
-    const int nz = p_nstride ? N : 1;
-    SPLICE_LAUNCH(sigmoid_bwd_bias_kernel, dim3(PB, C, nz), dim3(256), 0, s, dout, sout, dpre, N, C, HW, PB, part);
+    const int per = group > 1 ? group : 1;
+    const int nz = p_nstride ? N / per : 1;
+    SPLICE_LAUNCH(sigmoid_bwd_bias_kernel, dim3(PB, C, nz), dim3(256), 0, s, dout, sout, dpre, N, C, HW, PB, part, per);
     if (chunks) *chunks = PB * nz;
     return SPLICE_OK;
 }
@@ -2787,11 +2808,12 @@ __global__ __launch_bounds__(256) void bn_running_update_kernel(RunStatTable t, 
         if (indep && (int)blockIdx.y >= t.N[p]) continue;
         if (!indep && blockIdx.y != 0) continue;
         const int n_lo = indep ? blockIdx.y : 0, n_hi = indep ? blockIdx.y + 1 : t.N[p];
+        const int step = t.img_step[p] > 1 ? t.img_step[p] : 1;   // grouped plans: update n reads the statistics of its group's first image
         float* arena = running + (indep ? (size_t)blockIdx.y * r_nstride : 0) + t.r_off[bn];
         const float hw = (float)t.HW[p][bn];
         const float unbias = hw > 1.f ? hw / (hw - 1.f) : 1.f;
         for (int n = n_lo; n < n_hi; ++n) {
-            const float m = t.mean[p][bn][n * t.C[bn] + c], r = t.rstd[p][bn][n * t.C[bn] + c];
+            const float m = t.mean[p][bn][n * step * t.C[bn] + c], r = t.rstd[p][bn][n * step * t.C[bn] + c];
             const float var = fmaxf(1.0f / (r * r) - eps, 0.f) * unbias;
             arena[c] = (1.f - momentum) * arena[c] + momentum * m;
             arena[t.C[bn] + c] = (1.f - momentum) * arena[t.C[bn] + c] + momentum * var;

@@ -92,7 +92,10 @@ struct SpliceStep {
     int P = 1;                   // pairs optimised side by side -- or, in crops mode, the n_crops global crops of ONE pair (max of the two counts)
     int Pa = 1, Pb = 1;          // images of the A-crop / B-crop plans: P in pairs mode; global_A_crops_n_crops / global_B_crops_n_crops in crops mode
     int Pe = 1;                  // images of the entire-image branch: P in pairs mode, 1 in crops mode (netG(A) is one image there)
-    int crops_mode = 0;          // the P slots are crops of one pair: one generator (batch-statistics plans), losses summed over the crops
+    int crops_mode = 0;          // n_crops > 1: the slots are crops -- pair p's na A crops / nb B crops are images p * na + i / p * nb + i (pair-major)
+                                 // of plans in grouped batch-statistics mode (one netG call and one arena per pair), losses summed over a pair's crops
+    int pairs = 1;               // pairs (parameter arenas, rows of the loss table): cfg.pairs; P = pairs * max(na, nb) slots
+    int na = 1, nb = 1;          // A / B crops per pair (1 in pairs mode)
     size_t astride = 0;          // floats between the pairs' parameter / gradient / moment arenas (P > 1, pairs mode)
     VitView vg, ve;
     void *plan_a = nullptr, *plan_b = nullptr, *plan_e = nullptr;   // generator plans: P independent images each
@@ -204,17 +207,21 @@ static int view_init(SpliceStep* st, VitView& v, void* ctx, int want_B) {
 
 // blockIdx.x = pair.  raw_k = fixed-order sum of term k's workgroup partials (no float atomics anywhere: replicas are
 // bit-reproducible); total = sum_k lambda_k * raw_k   (util/losses.py:53-71)
-// n_slots > 1 (crops mode, grid 1): the terms of the n_crops crops are added in crop order (util/losses.py:75-82 `loss +=`).
+// n_a / n_b / n_c / n_e > 1 (crops mode): pair p's structure / identity / appearance / entire-image terms are the slots [p n, (p + 1) n) of the
+// term's images, added in crop order (util/losses.py:75-82 `loss +=`); one pair: n_a = n_b = n_c = n_e = the slot count.
 // wtab (optional, [pairs][5] in the order of splice_step_set_pair_weights): per-pair lambdas in place of the five weights, gated as the
 // scalar weights are (ssim_on: global structure and identity; entire: the two entire-image terms)
 __global__ __launch_bounds__(320) void total_loss_kernel(float* lbase, size_t lstride, int lp, float w_ssim, float w_essim, float w_ecls, float w_cls,
-                                                         float w_id, float* out8, int n_slots, const float* wtab, int ssim_on, int entire) {
+                                                         float w_id, float* out8, int n_a, int n_b, int n_c, int n_e, const float* wtab, int ssim_on,
+                                                         int entire) {
     __shared__ float raw[8];
     float* l = lbase + (size_t)blockIdx.x * lstride;
     const int k = 1 + (threadIdx.x >> 6), lane = threadIdx.x & 63;   // wave k-1 owns term k (5 waves)
+    const int n_slots = k == L_GLOBAL_SSIM ? n_a : k == L_GLOBAL_ID ? n_b : k == L_GLOBAL_CLS ? n_c : n_e;
+    const float* lp0 = lbase + (size_t)blockIdx.x * n_slots * lstride;   // the pair's first slot of this term
     float tot = 0.f;
     for (int slot = 0; slot < n_slots; ++slot) {
-        const float* part = l + (size_t)slot * lstride + 8 + (size_t)k * lp;
+        const float* part = lp0 + (size_t)slot * lstride + 8 + (size_t)k * lp;
         float acc = 0.f;
         for (int i = lane; i < lp; i += 64) acc += part[i];
         tot += wave_sum(acc);
@@ -351,17 +358,25 @@ int splice_step_create(const splice_step_config* cfg, void* vit_ctx_global, void
     if (!cfg || !vit_ctx_global || !gen_plan_a || !gen_plan_b || !out) return SPLICE_ERR_ARG;
     SpliceStep* st = new SpliceStep();
     st->cfg = *cfg;
-    if ((cfg->n_crops > 1 || cfg->n_crops_b > 1) && cfg->pairs > 1) { splice_set_error("splice_step_create: n_crops > 1 and pairs > 1 cannot be combined"); delete st; return SPLICE_ERR_ARG; }
     st->crops_mode = cfg->n_crops > 1 || cfg->n_crops_b > 1;
+    const int pairs = st->pairs = cfg->pairs > 1 ? cfg->pairs : 1;
     // crops mode: the reference zips the crop lists (util/losses.py:76,87,98) -- the structure term runs over the A crops, the
     // identity term over the B crops, the appearance term over min(nA, nB) pairs -- while netG's BatchNorm sees every crop of
     // its call (models/model.py:15-23): the two plans may hold different numbers of images
     const int nb_crops = cfg->n_crops_b > 0 ? cfg->n_crops_b : cfg->n_crops;
     if (st->crops_mode && (nb_crops < 1 || nb_crops > 8 || cfg->n_crops > 8)) { splice_set_error("splice_step_create: 1..8 crops per side"); delete st; return SPLICE_ERR_ARG; }
-    const int Pa = st->Pa = st->crops_mode ? cfg->n_crops : cfg->pairs > 1 ? cfg->pairs : 1;
-    const int Pb = st->Pb = st->crops_mode ? nb_crops : Pa;
+    // several pairs with n_crops > 1 each: pair p's crops are images [p n, (p + 1) n) of each side, one netG call per pair (grouped plans)
+    const int na = st->na = st->crops_mode ? cfg->n_crops : 1, nb = st->nb = st->crops_mode ? nb_crops : 1;
+    if (st->crops_mode && pairs > 1 && pairs * (na > nb ? na : nb) > SPLICE_STEP_MAX_GROUP_IMAGES) {
+        splice_set_error("splice_step_create: %d pairs x %d crops = %d images per side, at most %d", pairs, na > nb ? na : nb, pairs * (na > nb ? na : nb),
+                         SPLICE_STEP_MAX_GROUP_IMAGES);
+        delete st;
+        return SPLICE_ERR_ARG;
+    }
+    const int Pa = st->Pa = pairs * na;
+    const int Pb = st->Pb = pairs * nb;
     const int P = st->P = Pa > Pb ? Pa : Pb;
-    const int Pe = st->Pe = st->crops_mode ? 1 : P;
+    const int Pe = st->Pe = pairs;
     st->max_crop_h = cfg->crop_h; st->max_crop_w = cfg->crop_w;
     st->cropb_h = cfg->crop_h; st->cropb_w = cfg->crop_w;
     int rc = SPLICE_OK;
@@ -376,17 +391,17 @@ int splice_step_create(const splice_step_config* cfg, void* vit_ctx_global, void
         if (n != want || h != cfg->crop_h || w != cfg->crop_w) { splice_set_error("splice_step_create: the crop generator plans must hold %d / %d image(s) at the crop size", Pa, Pb); return fail(SPLICE_ERR_ARG); }
     }
     st->plan_a = gen_plan_a; st->plan_b = gen_plan_b;
-    if (P > 1 && !st->crops_mode) {
+    if (pairs > 1) {
         if (cfg->arena_stride < st->nparams) { splice_set_error("splice_step_create: pairs > 1 needs arena_stride >= the parameter count"); return fail(SPLICE_ERR_ARG); }
         st->astride = (size_t)cfg->arena_stride;
     }
     const size_t crop = (size_t)3 * cfg->crop_h * cfg->crop_w;
     for (float** q : {&st->gen_in, &st->in_b, &st->gen_out, &st->gen_out_b, &st->d_gen_out, &st->d_gen_out_b})
         if ((rc = salloc(st, q, P * crop)) != SPLICE_OK) return fail(rc);
-    if ((rc = salloc(st, &st->grads_b, st->astride ? P * st->astride : (size_t)st->nparams)) != SPLICE_OK) return fail(rc);
+    if ((rc = salloc(st, &st->grads_b, st->astride ? pairs * st->astride : (size_t)st->nparams)) != SPLICE_OK) return fail(rc);
     // the backward writes nparams floats per pair; the <= 63 floats of padding between two arenas are read by the whole-range
     // add / Adam and must never hold garbage
-    if (hipMemset(st->grads_b, 0, (st->astride ? P * st->astride : (size_t)st->nparams) * sizeof(float)) != hipSuccess) return fail(SPLICE_ERR_HIP);
+    if (hipMemset(st->grads_b, 0, (st->astride ? pairs * st->astride : (size_t)st->nparams) * sizeof(float)) != hipSuccess) return fail(SPLICE_ERR_HIP);
     int Tmax = st->vg.T;
     if (cfg->ent_h > 0) {
         if (!vit_ctx_entire || !gen_plan_entire) { splice_set_error("splice_step_create: entire-image branch needs its ViT context and generator plan"); return fail(SPLICE_ERR_ARG); }
@@ -577,7 +592,8 @@ int splice_step_set_running_stats(void* h, float* running, long long stride) {
 static int step_body(SpliceStep* st, float* params, float* grads, float* m, float* v, bool ssim_on, bool entire, hipStream_t s) {
     const splice_step_config& c = st->cfg;
     VitView& vg = st->vg;
-    const int P = st->P, Pa = st->Pa, Pb = st->Pb, Pc = Pa < Pb ? Pa : Pb;   // Pc: pairs of the appearance term (zip of x' and B')
+    const int P = st->P, Pa = st->Pa, Pb = st->Pb, pairs = st->pairs;
+    const int nc = st->na < st->nb ? st->na : st->nb, Pc = pairs * nc;   // Pc: pairs of the appearance term (zip of x' and B' within each pair)
     const float l_ssim = ssim_on ? c.lambda_global_ssim : 0.f, l_id = ssim_on ? c.lambda_global_identity : 0.f;
     const float l_cls = c.lambda_global_cls;
     const float l_essim = entire ? c.lambda_entire_ssim : 0.f, l_ecls = entire ? c.lambda_entire_cls : 0.f;
@@ -650,9 +666,19 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
     // ---- losses on the global batch
     if (do_v) {
         if (on_ssim) RC(selfsim_loss_launch(sb, s));
-        if (on_cls)   // [CLS] of block 11, before the final LayerNorm (util/losses.py:90-93)
-            RC(mse_batched_launch(blk_g + pX * passD, vg.D, passD, blk_g + pB * passD, vg.D, passD, 1, vg.D, 1.0f, l_cls, loss_part(st, L_GLOBAL_CLS),
-                                  st->lstride, vg.d_block + pX * passD, vg.D, passD, Pc, s, pw ? pw + 2 * P : nullptr));
+        if (on_cls) {   // [CLS] of block 11, before the final LayerNorm (util/losses.py:90-93)
+            if (pairs > 1 && st->na != st->nb) {
+                // several pairs with nA != nB crops: one launch per crop index i (pair p's x'_i against its B'_i into slot p nc + i); every
+                // pair-crop is its own workgroups, as in one launch
+                for (int i = 0; i < nc; ++i)
+                    RC(mse_batched_launch(blk_g + (pX + i) * passD, vg.D, st->na * passD, blk_g + (pB + i) * passD, vg.D, st->nb * passD, 1, vg.D, 1.0f, l_cls,
+                                          loss_part(st, L_GLOBAL_CLS) + (size_t)i * st->lstride, (size_t)nc * st->lstride, vg.d_block + (pX + i) * passD, vg.D,
+                                          st->na * passD, pairs, s, nullptr));
+            } else {
+                RC(mse_batched_launch(blk_g + pX * passD, vg.D, passD, blk_g + pB * passD, vg.D, passD, 1, vg.D, 1.0f, l_cls, loss_part(st, L_GLOBAL_CLS),
+                                      st->lstride, vg.d_block + pX * passD, vg.D, passD, Pc, s, pw ? pw + 2 * P : nullptr));
+            }
+        }
         if (on_id)    // keys of y' against keys of B' (util/losses.py:96-105): mean over h*T*d = T*D
             RC(mse_batched_launch(keys_ptr(vg, qkv_g, pY), 3 * vg.D, 3 * passD, keys_ptr(vg, qkv_g, pB), 3 * vg.D, 3 * passD, vg.T, vg.D, 1.0f, l_id,
                                   loss_part(st, L_GLOBAL_ID), st->lstride, vg.d_keys + pY * passD, vg.D, passD, Pb, s, pw ? pw + 3 * P : nullptr));
@@ -678,8 +704,8 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
                 RC(selfsim_target_launch(se, s));
                 RC(selfsim_loss_launch(se, s));
             }
-            if (on_ecls)   // target is the B_global crop's CLS (util/losses.py:60; with n_crops > 1 the zip pairs x_entire with the FIRST crop)
-                RC(mse_batched_launch(blk_e + Pe * epassD, ve.D, epassD, blk_g + pB * passD, vg.D, passD, 1, ve.D, 1.0f, l_ecls, loss_part(st, L_ENTIRE_CLS),
+            if (on_ecls)   // target is the B_global crop's CLS (util/losses.py:60; with n_crops > 1 the zip pairs x_entire with the FIRST crop of its pair)
+                RC(mse_batched_launch(blk_e + Pe * epassD, ve.D, epassD, blk_g + pB * passD, vg.D, st->nb * passD, 1, ve.D, 1.0f, l_ecls, loss_part(st, L_ENTIRE_CLS),
                                       st->lstride, ve.d_block + Pe * epassD, ve.D, epassD, Pe, s, pw ? pw + 4 * P : nullptr));
         }
     }
@@ -689,8 +715,13 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
     bool loss_summed = false;
     auto sum_losses = [&](hipStream_t q) {
         if (!do_v) return;
-        SPLICE_LAUNCH(total_loss_kernel, dim3(st->crops_mode ? 1 : P), dim3(320), 0, q, st->losses, st->lstride, (int)st->lp, l_ssim, l_essim, l_ecls, l_cls, l_id,
-                           st->losses_out, st->crops_mode ? P : 1, pw ? pw + 5 * P : nullptr, (int)ssim_on, (int)entire);
+        // slots per pair and term: 1 (pairs mode); the slot count for every term (one pair with n_crops: unused slots hold zeros); the term's crops
+        // per pair (several pairs with n_crops)
+        const bool grouped = st->crops_mode && pairs > 1;
+        const int n1 = st->crops_mode ? P : 1;
+        SPLICE_LAUNCH(total_loss_kernel, dim3(pairs), dim3(320), 0, q, st->losses, st->lstride, (int)st->lp, l_ssim, l_essim, l_ecls, l_cls, l_id,
+                           st->losses_out, grouped ? st->na : n1, grouped ? st->nb : n1, grouped ? nc : n1, grouped ? 1 : n1, pw ? pw + 5 * P : nullptr,
+                           (int)ssim_on, (int)entire);
     };
     auto track_running = [&](hipStream_t q) -> int {   // BatchNorm running statistics in the reference's call order
         if (!st->running || (st->ablate & 1) || !do_gf) return SPLICE_OK;
@@ -732,7 +763,7 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
         // grads = g(A) + g(B): folded into the Adam kernel on ordinary steps; a separate add when the entire-image branch
         // still has to accumulate into the sum (same association order either way)
         if (do_gb && !(st->ablate & 2)) {
-            if (entire || st->skip_adam) RC(add_f32_launch(grads, st->grads_b, st->astride ? P * st->astride : (size_t)st->nparams, s));
+            if (entire || st->skip_adam) RC(add_f32_launch(grads, st->grads_b, st->astride ? pairs * st->astride : (size_t)st->nparams, s));
             else adam_g2 = st->grads_b;
         }
     }
@@ -751,7 +782,7 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
     // execution time
     SPLICE_DEV_REGION(21);
     if (do_gb && !st->skip_adam) {
-        const size_t n_all = st->astride ? P * st->astride : (size_t)st->nparams;
+        const size_t n_all = st->astride ? pairs * st->astride : (size_t)st->nparams;
         // per-pair lrs (splice_step_set_pair_lr): pair p's arena reads dev_lrs[p]
         const float* lr_dev = st->pair_lr ? st->dev_lrs : st->lr_set ? st->dev_lr : nullptr;
         const size_t lr_stride = st->pair_lr ? st->astride : 0;
@@ -919,6 +950,10 @@ int splice_step_run(void* h, float* params, float* grads, float* m, float* v, co
             }
             GraphSig sig;
             const bool have_sig = graph_signature(g, &sig);
+            if (have_sig && st->crops_mode && st->pairs > 1) {   // several pairs with n_crops: the layout is part of the key (other keys unchanged)
+                sig.mix(0x67726f7570ull);
+                sig.mix(((unsigned long long)st->pairs << 32) | ((unsigned long long)st->na << 16) | (unsigned long long)st->nb);
+            }
             hipGraphExec_t ex = nullptr;
             hipGraphExec_t spare = nullptr;
             if (have_sig) {

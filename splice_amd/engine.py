@@ -35,6 +35,7 @@ PAIR_LR_KEYS = ("lr", "scheduler_policy", "scheduler_n_epochs_decay", "scheduler
 PAIR_INIT_KEYS = ("seed", "init_type", "init_gain")
 PAIR_KEYS = PAIR_LAMBDA_KEYS + PAIR_LR_KEYS + PAIR_INIT_KEYS
 MAX_PAIR_CFGS = 32   # SPLICE_STEP_MAX_PAIR_CFGS
+MAX_GROUP_IMAGES = 32   # SPLICE_STEP_MAX_GROUP_IMAGES: images per side (pairs x n_crops) of several pairs with n_crops > 1
 
 
 def _entire_branch(c):
@@ -97,9 +98,10 @@ class MultiPairEngine:
                  pair_cfgs=None):
         """cfg: reference config keys (conf/default/config.yaml); vit_state: DINO state dict; gen_states: list of P generator
         state dicts (reference names); crop_hw: (h, w) of the (largest) global crops; entire_hw: (H, W) of the whole
-        structure image or None to disable the entire branch.  ``n_crops`` > 1 (one pair only): the reference's
-        ``global_{A,B}_crops_n_crops`` -- every step takes ``[n_crops,3,h,w]`` crops of the pair, netG sees them as ONE batch
-        (BatchNorm statistics over the crops), every loss term is summed over the crops.
+        structure image or None to disable the entire branch.  ``n_crops`` > 1: the reference's ``global_{A,B}_crops_n_crops``
+        -- every step takes ``[P*n_crops,3,h,w]`` crops (pair-major; ``[P,n_crops,3,h,w]`` is the same memory), netG sees each
+        pair's crops as ONE batch (BatchNorm statistics over the pair's crops), every loss term is summed over the pair's crops.
+        Pair p is bit for bit the ``SpliceEngine(n_crops=...)`` run of that pair.
         ``pair_cfgs``: one dict of per-slot overrides per pair (a sweep: PAIR_KEYS -- the five lambdas, lr and its schedule; the
         init keys are the caller's business), checked by ``merge_pair_cfgs``.  Slot p then runs, bit for bit, as a
         ``SpliceEngine`` with ``cfgs[p]`` would; ``lr`` becomes a list of P values."""
@@ -129,8 +131,12 @@ class MultiPairEngine:
         nA, nB = (int(n_crops), int(n_crops)) if isinstance(n_crops, int) else (int(n_crops[0]), int(n_crops[1]))
         self.n_crops_ab = (nA, nB)
         self.n_crops = max(nA, nB)
-        if self.n_crops > 1 and len(gen_states) != 1:
-            raise ValueError("n_crops > 1 is a property of ONE pair: pass a single generator state")
+        if self.n_crops > 1 and len(gen_states) > 1:
+            if min(nA, nB) < 1 or self.n_crops > 8:
+                raise ValueError(f"n_crops: 1..8 crops per side, got {(nA, nB)}")
+            if len(gen_states) * self.n_crops > MAX_GROUP_IMAGES:
+                raise ValueError(f"n_crops: {len(gen_states)} pairs x {self.n_crops} crops = {len(gen_states) * self.n_crops} images per side, "
+                                 f"at most {MAX_GROUP_IMAGES}")
         # optimizer adam / rmsprop / sgd and scheduler_policy none / linear / step / cosine (util/util.py:8-39); the lr of every step is
         # computed on the host and staged on the device (splice_step_set_lr), so a replayed graph runs with the scheduled value
         self.opt_kind, *self.opt_hp = fused_optimizer(c)
@@ -168,8 +174,8 @@ class MultiPairEngine:
         ch, cw = crop_hw
         vh, vw = resize_output_size(ch, cw, Pz, 480)
         self.crop_hw, self.vit_hw = (ch, cw), (vh, vw)
-        slots = self.slots = self.n_crops if self.n_crops > 1 else P    # images per generator plan / per ViT pass group (maximum of the two sides)
-        sa, sb = (nA, nB) if self.n_crops > 1 else (P, P)
+        slots = self.slots = P * self.n_crops    # images per generator plan / per ViT pass group (maximum of the two sides)
+        sa, sb = (P * nA, P * nB) if self.n_crops > 1 else (P, P)
         self.slots_ab = (sa, sb)
         batch = self.n_crops > 1
         # A step engine's contexts are PRIVATE, never taken from the shape-keyed cache of ``VitEngine.context()``: with an identity
@@ -179,8 +185,12 @@ class MultiPairEngine:
         self.ctx_g = VitContext(self.vit, 2 * (sa + sb), vh, vw, True, fp8=self.fp8)
         arena_stride = self.stride if P > 1 else 0
         # private plan objects (the shape-keyed plan cache could hand out one plan twice)
-        self.plan_a = GeneratorPlan(self.gen, sa, ch, cw, True, arena_stride, batch_stats=batch and sa > 1)
-        self.plan_b = GeneratorPlan(self.gen, sb, ch, cw, True, arena_stride, batch_stats=batch and sb > 1)
+        if batch and P > 1:   # several pairs: one netG call per pair's crops (grouped plans, arena per pair)
+            self.plan_a = GeneratorPlan(self.gen, sa, ch, cw, True, arena_stride, groups=nA)
+            self.plan_b = GeneratorPlan(self.gen, sb, ch, cw, True, arena_stride, groups=nB)
+        else:
+            self.plan_a = GeneratorPlan(self.gen, sa, ch, cw, True, arena_stride, batch_stats=batch and sa > 1)
+            self.plan_b = GeneratorPlan(self.gen, sb, ch, cw, True, arena_stride, batch_stats=batch and sb > 1)
         sc = _lib.StepConfig()
         sc.crop_h, sc.crop_w, sc.vit_h, sc.vit_w = ch, cw, vh, vw
         sc.pairs, sc.arena_stride, sc.fp8_selfsim = P, arena_stride, int(bool(self.fp8))
@@ -195,7 +205,7 @@ class MultiPairEngine:
         if use_entire:
             eh, ew = entire_hw
             evh, evw = resize_output_size(eh, ew, Pz, 480)
-            self.ctx_e = VitContext(self.vit, 2 * P, evh, evw, True, fp8=self.fp8)   # (P = 1 in crops mode)
+            self.ctx_e = VitContext(self.vit, 2 * P, evh, evw, True, fp8=self.fp8)   # (one entire image per pair, whatever n_crops)
             self.plan_e = GeneratorPlan(self.gen, P, eh, ew, True, arena_stride)
             sc.ent_h, sc.ent_w, sc.ent_vit_h, sc.ent_vit_w = eh, ew, evh, evw
         sc.lambda_global_cls, sc.lambda_global_ssim = c["lambda_global_cls"], c["lambda_global_ssim"]

@@ -120,9 +120,11 @@ class GeneratorEngine:
 
 
 class GeneratorPlan:
-    def __init__(self, engine, N, H, W, need_grad, arena_stride=0, batch_stats=False):
+    def __init__(self, engine, N, H, W, need_grad, arena_stride=0, batch_stats=False, groups=0):
         """``arena_stride`` > 0: the N images are INDEPENDENT generators -- image n uses ``params[n * stride:]`` and its
-        gradient goes to ``grads[n * stride:]`` (several pairs in one launch); 0: one generator applied to N images."""
+        gradient goes to ``grads[n * stride:]`` (several pairs in one launch); 0: one generator applied to N images.
+        ``groups`` = g > 0 (``splice_gen_plan_set_groups``): images ``[k*g, (k+1)*g)`` are ONE netG call -- BatchNorm statistics
+        over those g images, parameters / gradients in arena k (several pairs with n_crops > 1 crops each)."""
         self.engine, self.N, self.H, self.W, self.need_grad, self.arena_stride = engine, N, H, W, need_grad, arena_stride
         h = C.c_void_p()
         _lib.check(_lib.lib().splice_gen_plan_create(engine.handle, N, H, W, int(need_grad), C.byref(h)), "gen_plan_create")
@@ -132,6 +134,10 @@ class GeneratorPlan:
         self.batch_stats = bool(batch_stats)
         if batch_stats:   # ONE netG call on the batch: BatchNorm statistics over all N images (the reference with n_crops > 1)
             _lib.check(_lib.lib().splice_gen_plan_set_batch_stats(h, 1), "gen_plan_set_batch_stats")
+        self.groups = int(groups)
+        if groups:
+            _lib.check(_lib.lib().splice_gen_plan_set_groups(h, int(groups)), "gen_plan_set_groups")
+            self.batch_stats = groups > 1
 
     def __del__(self):
         try:
@@ -150,7 +156,8 @@ class GeneratorPlan:
     def backward(self, params, dy, grads=None, accumulate=False):
         assert dy.is_cuda and dy.dtype == torch.float32 and dy.is_contiguous() and tuple(dy.shape) == (self.N, self.engine.out_channels, self.H, self.W)
         if grads is None:
-            grads = torch.zeros(self.N * self.arena_stride if self.arena_stride else self.engine.numel, device=self.engine.device)
+            arenas = self.N // self.groups if self.groups else self.N
+            grads = torch.zeros(arenas * self.arena_stride if self.arena_stride else self.engine.numel, device=self.engine.device)
         _lib.check(_lib.lib().splice_gen_backward(self.handle, _lib.ptr(params), _lib.ptr(dy), _lib.ptr(grads), int(accumulate),
                                                   _lib.current_stream()), "gen_backward")
         return grads

@@ -205,22 +205,24 @@ def train_model(dataroot, callback=None, cfg_overrides=None, vit_state=None, pro
 
 class PairBatchFeed:
     """Device data feed of P pairs that share image sizes: per step ONE crop size per side (A / B), as ``Global_crops`` draws it
-    (data/transforms.py:21), and one random position per pair; augmentations per pair.  Every pair sees the reference's marginal
-    distribution of crops; the sizes are shared so that the P crops stack into one ``[P,3,s,s]`` batch."""
+    (data/transforms.py:21), and ``global_{A,B}_crops_n_crops`` random positions per pair; augmentations once per pair image, before
+    cropping (data/Dataset.py:67-68, as ``DeviceDataFeed``).  Every pair sees the reference's marginal distribution of crops; the sizes
+    are shared so that the crops stack into one ``[P*n,3,s,s]`` batch, pair-major (pair p's crops are rows ``[p*n, (p+1)*n)``)."""
 
-    def __init__(self, cfg, As, Bs):
+    def __init__(self, cfg, As, Bs, device=device):
         if len({tuple(a.shape) for a in As}) != 1 or len({tuple(b.shape) for b in Bs}) != 1:
             raise ValueError("pairs optimised side by side must share the structure-image size and the appearance-image size")
         self.cfg, self.A, self.B = cfg, [a.to(device) for a in As], [b.to(device) for b in Bs]
+        self.n_crops = (int(cfg.get('global_A_crops_n_crops', 1)), int(cfg.get('global_B_crops_n_crops', 1)))
         self.step = -1
 
     def get_A(self, pair):
         return self.A[pair][None]
 
-    def _crops(self, imgs, min_cover):
+    def _crops(self, imgs, min_cover, n):
         _, h, w = imgs[0].shape
-        size, boxes = augment.global_crop_boxes(h, w, min_cover, len(imgs))
-        return torch.stack([im[:, t:t + size, l:l + size] for im, (t, l) in zip(imgs, boxes)]).contiguous()
+        size, boxes = augment.global_crop_boxes(h, w, min_cover, len(imgs) * n)
+        return torch.stack([imgs[k // n][:, t:t + size, l:l + size] for k, (t, l) in enumerate(boxes)]).contiguous()
 
     def next(self):
         self.step += 1
@@ -228,8 +230,8 @@ class PairBatchFeed:
         sample = {'step': self.step}
         if self.step % self.cfg['entire_A_every'] == 0:
             sample['A'] = torch.stack(self.A).contiguous()
-        sample['A_global'] = self._crops([augment.structure_transforms(a) if aug else a for a in self.A], self.cfg['global_A_crops_min_cover'])
-        sample['B_global'] = self._crops([augment.texture_transforms(b) if aug else b for b in self.B], self.cfg['global_B_crops_min_cover'])
+        sample['A_global'] = self._crops([augment.structure_transforms(a) if aug else a for a in self.A], self.cfg['global_A_crops_min_cover'], self.n_crops[0])
+        sample['B_global'] = self._crops([augment.texture_transforms(b) if aug else b for b in self.B], self.cfg['global_B_crops_min_cover'], self.n_crops[1])
         return sample
 
 
@@ -239,15 +241,20 @@ def train_pairs(dataroots, callback=None, cfg_overrides=None, vit_state=None, pr
     P directories with ``A/`` and ``B/``; all structure images must share one size and all appearance images one size
     (``A_resize`` / ``B_resize`` apply).  Every pair's generator is initialised as its own ``train_model`` run would
     (the seed is re-applied before each ``define_G``); writes ``<dataroot>/out/output.png`` per pair; ``callback(pair, image)``.
+    ``global_{A,B}_crops_n_crops`` (1..8, equal or not) run as one netG call per pair's crops (at most 32 images per side).
     With deterministic full crops (``use_augmentations: False``, ``min_cover: 1``) the result of every pair is bit-identical to
     its single ``train_model`` run."""
-    from .engine import MultiPairEngine
+    from .engine import MAX_GROUP_IMAGES, MultiPairEngine
     cfg_path = "conf/default/config.yaml" if os.path.exists("conf/default/config.yaml") else _PKG_CFG
     with open(cfg_path, "r") as f:
         cfg = yaml.safe_load(f)
     cfg.update(cfg_overrides or {})
-    if int(cfg['global_A_crops_n_crops']) != 1 or int(cfg['global_B_crops_n_crops']) != 1:
-        raise NotImplementedError("train_pairs: several pairs per step take one global crop per image (n_crops is a single-pair option)")
+    n_crops = (int(cfg['global_A_crops_n_crops']), int(cfg['global_B_crops_n_crops']))
+    if not all(1 <= n <= 8 for n in n_crops):
+        raise NotImplementedError("train_pairs: the fused engine takes 1..8 global crops per image (global_{A,B}_crops_n_crops)")
+    if len(dataroots) * max(n_crops) > MAX_GROUP_IMAGES:
+        raise NotImplementedError(f"train_pairs: {len(dataroots)} pairs x {max(n_crops)} global crops = {len(dataroots) * max(n_crops)} images per side, "
+                                  f"at most {MAX_GROUP_IMAGES} (global_{{A,B}}_crops_n_crops)")
     if len(cfg.get('dino_global_scales') or []) > 1:
         raise NotImplementedError("train_pairs: dino_global_scales with several entries is a single-pair option (train_model / MultiScaleEngine); "
                                   "grouped pairs would silently train single-scale")
@@ -280,7 +287,8 @@ def train_pairs(dataroots, callback=None, cfg_overrides=None, vit_state=None, pr
         cfg['dino_global_patch_size'] = int(cfg['dino_global_scales'][0])   # one entry: the ViT input size, as in train_model
     A0, B0 = As[0], Bs[0]
     crop_max = max(min(A0.shape[1], A0.shape[2]), min(B0.shape[1], B0.shape[2]))
-    engine = MultiPairEngine(cfg, vit_state, gen_states, (crop_max, crop_max), tuple(A0.shape[1:]), device=device, vit_engine=vit_engine, fp8=fp8_mode(cfg))
+    engine = MultiPairEngine(cfg, vit_state, gen_states, (crop_max, crop_max), tuple(A0.shape[1:]), device=device, vit_engine=vit_engine, fp8=fp8_mode(cfg),
+                             n_crops=n_crops[0] if n_crops[0] == n_crops[1] else n_crops)
     writers = [AsyncResultWriter(root) for root in dataroots]
     try:
         for epoch in range(1, cfg['n_epochs'] + 1):
