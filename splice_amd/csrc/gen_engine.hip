@@ -812,71 +812,4 @@ int splice_gen_backward(void* plan, const float* params, const float* dy, float*
     if (e != hipSuccess) { splice_set_error("splice_gen_backward: %s", hipGetErrorString(e)); return SPLICE_ERR_HIP; }
     return SPLICE_OK;
 }
-
-// torch.optim.Adam step over a flat arena (util/util.py:28-32); zero_grad != 0 also clears g.
-int splice_adam_step(float* params, float* grads, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps,
-                     int step, int zero_grad, splice_stream_t stream) {
-    if (!params || !grads || !m || !v || n < 1) return SPLICE_ERR_ARG;
-    RC(adam_launch(params, grads, m, v, (size_t)n, lr, beta1, beta2, eps, step, zero_grad, (hipStream_t)stream));
-    return SPLICE_OK;
-}
-
-// One step of the configured optimiser over a flat arena (util/util.py:28-39): kind 0 Adam (hp0 = beta1, hp1 = beta2, step >= 1),
-// 1 RMSprop (hp0 = alpha; v = square_avg, m unused), 2 SGD (m, v unused).  g2 (may be NULL): second gradient arena, g += g2 first.
-// lr_dev (may be NULL): device float read by the kernel instead of lr.
-int splice_optim_step_ex(int kind, float* params, float* grads, const float* g2, float* m, float* v, long long n, float lr, const float* lr_dev,
-                         float hp0, float hp1, float eps, int step, int zero_grad, splice_stream_t stream) {
-    if (!params || !grads || n < 1) return SPLICE_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    switch (kind) {
-    case SPLICE_OPT_ADAM:
-        if (!m || !v) return SPLICE_ERR_ARG;
-        RC(adam_launch(params, grads, m, v, (size_t)n, lr, hp0, hp1, eps, step, zero_grad, s, g2, lr_dev));
-        break;
-    case SPLICE_OPT_RMSPROP:
-        if (!v) return SPLICE_ERR_ARG;
-        RC(rmsprop_launch(params, grads, v, (size_t)n, lr, hp0, eps, zero_grad, s, g2, lr_dev));
-        break;
-    case SPLICE_OPT_SGD:
-        RC(sgd_launch(params, grads, (size_t)n, lr, zero_grad, s, g2, lr_dev));
-        break;
-    default:
-        splice_set_error("splice_optim_step: unknown optimiser kind %d", kind);
-        return SPLICE_ERR_ARG;
-    }
-    return SPLICE_OK;
-}
-int splice_optim_step(int kind, float* params, float* grads, float* m, float* v, long long n, float lr, float hp0, float hp1, float eps, int step,
-                      int zero_grad, splice_stream_t stream) {
-    return splice_optim_step_ex(kind, params, grads, nullptr, m, v, n, lr, nullptr, hp0, hp1, eps, step, zero_grad, stream);
-}
-// The update of n_pairs generators in one launch, each pair with its own learning rate: pair p's arena is [p * stride, p * stride + n),
-// its lr is lr_dev[p] (device, n_pairs floats).  The whole range n_pairs * stride is updated, the padding floats between two arenas
-// included (they hold zero gradients, so they stay as they are).  stride must be a multiple of 4 (a float4 never straddles two pairs).
-int splice_optim_step_pairs(int kind, float* params, float* grads, const float* g2, float* m, float* v, int n_pairs, long long stride, long long n,
-                            const float* lr_dev, float hp0, float hp1, float eps, int step, int zero_grad, splice_stream_t stream) {
-    if (!params || !grads || !lr_dev || n_pairs < 1 || n < 1 || stride < n || stride % 4) {
-        splice_set_error("splice_optim_step_pairs: needs a device lr table, n_pairs >= 1 and 1 <= n <= stride with stride a multiple of 4");
-        return SPLICE_ERR_ARG;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    const size_t n_all = (size_t)n_pairs * (size_t)stride;
-    switch (kind) {
-    case SPLICE_OPT_ADAM:
-        if (!m || !v) return SPLICE_ERR_ARG;
-        RC(adam_launch(params, grads, m, v, n_all, 0.f, hp0, hp1, eps, step, zero_grad, s, g2, lr_dev, (size_t)stride));
-        break;
-    case SPLICE_OPT_RMSPROP:
-        if (!v) return SPLICE_ERR_ARG;
-        RC(rmsprop_launch(params, grads, v, n_all, 0.f, hp0, eps, zero_grad, s, g2, lr_dev, (size_t)stride));
-        break;
-    case SPLICE_OPT_SGD:
-        RC(sgd_launch(params, grads, n_all, 0.f, zero_grad, s, g2, lr_dev, (size_t)stride));
-        break;
-    default:
-        splice_set_error("splice_optim_step_pairs: unknown optimiser kind %d", kind);
-        return SPLICE_ERR_ARG;
-    }
-    return SPLICE_OK;
-}
 }

@@ -131,20 +131,6 @@ int sigmoid_bwd_launch(const float* dout, const float* sout, float* dpre, size_t
 int sigmoid_bwd_bias_launch(const float* dout, const float* sout, float* dpre, int N, int C, int HW, float* part, hipStream_t s, size_t p_nstride, int* chunks,
                             int group = 1);
 int sigmoid_bias_part_floats(int N, int C);   // floats of `part`: [image][segment][channel], summed by wgrad_reduce_all_launch
-// Fused optimiser updates over a flat arena (torch.optim as util/util.py:28-39 builds them).  g2 (optional): a second gradient
-// arena folded in as g += g2 (written back when g2 or zero_grad is set).  lr_dev (optional): the learning rate is read from
-// device memory when the kernel runs (a schedule under graph replay); null: the lr argument.  lr_stride (optional, a multiple of 4):
-// per-pair learning rates, element i of the arena uses lr_dev[i / lr_stride] (0: the one value above).
-enum { SPLICE_OPT_ADAM = 0, SPLICE_OPT_RMSPROP = 1, SPLICE_OPT_SGD = 2 };
-int adam_launch(float* p, float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps, int step, int zero_grad, hipStream_t s,
-                const float* g2 = nullptr, const float* lr_dev = nullptr, size_t lr_stride = 0);
-int adam_launch_dev(float* p, float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps, const int* step_dev,
-                    int zero_grad, hipStream_t s, const float* g2 = nullptr, const float* lr_dev = nullptr, size_t lr_stride = 0);
-// RMSprop (alpha, eps; v = square_avg) and plain SGD
-int rmsprop_launch(float* p, float* g, float* v, size_t n, float lr, float alpha, float eps, int zero_grad, hipStream_t s, const float* g2 = nullptr,
-                   const float* lr_dev = nullptr, size_t lr_stride = 0);
-int sgd_launch(float* p, float* g, size_t n, float lr, int zero_grad, hipStream_t s, const float* g2 = nullptr, const float* lr_dev = nullptr,
-               size_t lr_stride = 0);
 int set_int_launch(int* p, int v, hipStream_t s);
 // BatchNorm running statistics of up to 3 generator calls (in call order) in one launch; see gen_kernels.hip
 constexpr int RUNSTAT_MAX_PLANS = 3, RUNSTAT_MAX_BN = 36;

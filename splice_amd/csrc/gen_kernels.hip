@@ -2619,181 +2619,6 @@ int sigmoid_bwd_launch(const float* dout, const float* sout, float* dpre, size_t
     return SPLICE_OK;
 }
 
-// one element of the update; contraction is OFF so that the vector body and the scalar tail of the kernel round alike (an
-// element's result must not depend on where in an arena it sits: P pairs per step == P single runs, bit for bit)
-__device__ __forceinline__ void adam_update(float& pi, float& gi, float& mi_, float& vi_, float g2i, bool has_g2, float b1, float b2, float eps, float lr,
-                                            float bc1, float bc2_sqrt, int zero_grad) {
-#pragma clang fp contract(off)
-    if (has_g2) gi += g2i;   // second gradient arena (the B-crop plan): g = g + g2, as a separate add would leave it
-    const float mi = b1 * mi_ + (1.f - b1) * gi;
-    const float vi = b2 * vi_ + (1.f - b2) * gi * gi;
-    mi_ = mi;
-    vi_ = vi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    pi -= (lr / bc1) * (mi / denom);
-    if (zero_grad) gi = 0.f;
-}
-// ---------------------------------------------------------------------------------------
-// Fused multi-tensor Adam over the flat parameter arena (K19; torch.optim.Adam as configured by
-// util/util.py:28-32: no weight decay / amsgrad, eps added after sqrt(v_hat)).  Also clears the
-// gradient (optimizer.zero_grad, train.py:56) when zero_grad != 0.
-// PAIR_LR: every pair of the arena has its own learning rate, lr_ptr[element / lr_stride] (lr_stride = the arena stride, a multiple
-// of 4: a float4 never straddles two pairs); the PAIR_LR = false instance is the single-lr kernel, unchanged
-template <bool PAIR_LR>
-__global__ void adam_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, size_t n, float lr,
-                            float b1, float b2, float eps, float bc1, float bc2_sqrt, int zero_grad, const int* __restrict__ step_ptr,
-                            const float* __restrict__ g2, const float* __restrict__ lr_ptr, unsigned lr_stride) {
-    if (!PAIR_LR && lr_ptr) lr = *lr_ptr;   // learning rate on the device (a schedule under graph replay); null: the argument
-    if (step_ptr) {   // step count lives on the device (graph replay): bias corrections computed here
-        const float t = (float)*step_ptr;
-        bc1 = 1.0f - powf(b1, t);
-        bc2_sqrt = sqrtf(1.0f - powf(b2, t));
-    }
-    // one float4 per thread and (at the generator's size) ONE pass: the five operand vectors of an element group are a single
-    // memory round trip; the kernel is the last node of the step's critical chain
-    auto upd = [&](float& pi, float& gi, float& mi_, float& vi_, float g2i) {
-        adam_update(pi, gi, mi_, vi_, g2i, g2 != nullptr, b1, b2, eps, lr, bc1, bc2_sqrt, zero_grad);
-    };
-    const unsigned lr_stride4 = lr_stride / 4;
-    const size_t n4 = ((reinterpret_cast<size_t>(p) | reinterpret_cast<size_t>(g) | reinterpret_cast<size_t>(m) | reinterpret_cast<size_t>(v) |
-                        reinterpret_cast<size_t>(g2)) & 15) ? 0 : n / 4;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-        float4 pv = reinterpret_cast<float4*>(p)[i], gv = reinterpret_cast<float4*>(g)[i], mv = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
-        const float4 g2v = g2 ? reinterpret_cast<const float4*>(g2)[i] : float4{0.f, 0.f, 0.f, 0.f};
-        if (PAIR_LR) lr = lr_ptr[(unsigned)i / lr_stride4];
-        upd(pv.x, gv.x, mv.x, vv.x, g2v.x); upd(pv.y, gv.y, mv.y, vv.y, g2v.y); upd(pv.z, gv.z, mv.z, vv.z, g2v.z); upd(pv.w, gv.w, mv.w, vv.w, g2v.w);
-        reinterpret_cast<float4*>(p)[i] = pv; reinterpret_cast<float4*>(m)[i] = mv; reinterpret_cast<float4*>(v)[i] = vv;
-        if (g2 || zero_grad) reinterpret_cast<float4*>(g)[i] = gv;
-    }
-    for (size_t i = n4 * 4 + (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        float pi = p[i], gi = g[i], mi = m[i], vi = v[i];
-        if (PAIR_LR) lr = lr_ptr[(unsigned)i / lr_stride];
-        upd(pi, gi, mi, vi, g2 ? g2[i] : 0.f);
-        p[i] = pi; m[i] = mi; v[i] = vi;
-        if (g2 || zero_grad) g[i] = gi;
-    }
-}
-static unsigned optim_grid(size_t n) {
-    size_t g_ = (n / 4 + 255) / 256 + 1;
-    return (unsigned)(g_ > 2048 ? 2048 : g_);
-}
-void splice_set_error(const char* fmt, ...);
-// lr_stride != 0 (per-pair learning rates, lr_dev[pair]): a multiple of 4, and the element index must fit 32 bits
-static bool pair_lr_ok(size_t n, const float* lr_dev, size_t lr_stride) {
-    if (!lr_stride) return true;
-    if (!lr_dev || lr_stride % 4 || n > 0xFFFFFFFFull || lr_stride > 0xFFFFFFFFull) {
-        splice_set_error("optimiser: per-pair lr needs a device lr table, an arena stride that is a multiple of 4 and < 2^32 elements");
-        return false;
-    }
-    return true;
-}
-int adam_launch(float* p, float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps, int step, int zero_grad, hipStream_t s,
-                const float* g2, const float* lr_dev, size_t lr_stride) {
-    if (step < 1 || !pair_lr_ok(n, lr_dev, lr_stride)) return SPLICE_ERR_ARG;
-    const float bc1 = 1.0f - powf(b1, (float)step);
-    const float bc2 = 1.0f - powf(b2, (float)step);
-    if (lr_stride)
-        SPLICE_LAUNCH(adam_kernel<true>, dim3(optim_grid(n)), dim3(256), 0, s, p, g, m, v, n, lr, b1, b2, eps, bc1, sqrtf(bc2), zero_grad, (const int*)nullptr, g2,
-                      lr_dev, (unsigned)lr_stride);
-    else
-        SPLICE_LAUNCH(adam_kernel<false>, dim3(optim_grid(n)), dim3(256), 0, s, p, g, m, v, n, lr, b1, b2, eps, bc1, sqrtf(bc2), zero_grad, (const int*)nullptr, g2,
-                      lr_dev, 0u);
-    return SPLICE_OK;
-}
-// same, the step count t (>= 1) read from device memory at execution time
-int adam_launch_dev(float* p, float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps, const int* step_dev,
-                    int zero_grad, hipStream_t s, const float* g2, const float* lr_dev, size_t lr_stride) {
-    if (!pair_lr_ok(n, lr_dev, lr_stride)) return SPLICE_ERR_ARG;
-    if (lr_stride)
-        SPLICE_LAUNCH(adam_kernel<true>, dim3(optim_grid(n)), dim3(256), 0, s, p, g, m, v, n, lr, b1, b2, eps, 1.f, 1.f, zero_grad, step_dev, g2, lr_dev,
-                      (unsigned)lr_stride);
-    else
-        SPLICE_LAUNCH(adam_kernel<false>, dim3(optim_grid(n)), dim3(256), 0, s, p, g, m, v, n, lr, b1, b2, eps, 1.f, 1.f, zero_grad, step_dev, g2, lr_dev, 0u);
-    return SPLICE_OK;
-}
-
-// torch.optim.RMSprop(lr) as util/util.py:35 builds it (alpha 0.99, eps 1e-8; no momentum, not centred, no weight decay):
-// v = alpha v + (1 - alpha) g^2, p -= lr g / (sqrt(v) + eps).  Same element rules as adam_update (contraction off, g2 folded in).
-__device__ __forceinline__ void rmsprop_update(float& pi, float& gi, float& vi_, float g2i, bool has_g2, float alpha, float eps, float lr, int zero_grad) {
-#pragma clang fp contract(off)
-    if (has_g2) gi += g2i;
-    const float vi = alpha * vi_ + (1.f - alpha) * gi * gi;
-    vi_ = vi;
-    pi -= lr * (gi / (sqrtf(vi) + eps));
-    if (zero_grad) gi = 0.f;
-}
-// the v arena holds square_avg; m is not touched
-template <bool PAIR_LR>   // (as adam_kernel)
-__global__ void rmsprop_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ v, size_t n, float lr, float alpha, float eps,
-                               int zero_grad, const float* __restrict__ g2, const float* __restrict__ lr_ptr, unsigned lr_stride) {
-    if (!PAIR_LR && lr_ptr) lr = *lr_ptr;
-    auto upd = [&](float& pi, float& gi, float& vi_, float g2i) { rmsprop_update(pi, gi, vi_, g2i, g2 != nullptr, alpha, eps, lr, zero_grad); };
-    const unsigned lr_stride4 = lr_stride / 4;
-    const size_t n4 = ((reinterpret_cast<size_t>(p) | reinterpret_cast<size_t>(g) | reinterpret_cast<size_t>(v) | reinterpret_cast<size_t>(g2)) & 15) ? 0 : n / 4;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-        float4 pv = reinterpret_cast<float4*>(p)[i], gv = reinterpret_cast<float4*>(g)[i], vv = reinterpret_cast<float4*>(v)[i];
-        const float4 g2v = g2 ? reinterpret_cast<const float4*>(g2)[i] : float4{0.f, 0.f, 0.f, 0.f};
-        if (PAIR_LR) lr = lr_ptr[(unsigned)i / lr_stride4];
-        upd(pv.x, gv.x, vv.x, g2v.x); upd(pv.y, gv.y, vv.y, g2v.y); upd(pv.z, gv.z, vv.z, g2v.z); upd(pv.w, gv.w, vv.w, g2v.w);
-        reinterpret_cast<float4*>(p)[i] = pv; reinterpret_cast<float4*>(v)[i] = vv;
-        if (g2 || zero_grad) reinterpret_cast<float4*>(g)[i] = gv;
-    }
-    for (size_t i = n4 * 4 + (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        float pi = p[i], gi = g[i], vi = v[i];
-        if (PAIR_LR) lr = lr_ptr[(unsigned)i / lr_stride];
-        upd(pi, gi, vi, g2 ? g2[i] : 0.f);
-        p[i] = pi; v[i] = vi;
-        if (g2 || zero_grad) g[i] = gi;
-    }
-}
-int rmsprop_launch(float* p, float* g, float* v, size_t n, float lr, float alpha, float eps, int zero_grad, hipStream_t s, const float* g2,
-                   const float* lr_dev, size_t lr_stride) {
-    if (!pair_lr_ok(n, lr_dev, lr_stride)) return SPLICE_ERR_ARG;
-    if (lr_stride)
-        SPLICE_LAUNCH(rmsprop_kernel<true>, dim3(optim_grid(n)), dim3(256), 0, s, p, g, v, n, lr, alpha, eps, zero_grad, g2, lr_dev, (unsigned)lr_stride);
-    else
-        SPLICE_LAUNCH(rmsprop_kernel<false>, dim3(optim_grid(n)), dim3(256), 0, s, p, g, v, n, lr, alpha, eps, zero_grad, g2, lr_dev, 0u);
-    return SPLICE_OK;
-}
-
-// torch.optim.SGD(lr) as util/util.py:36 builds it (no momentum, dampening, nesterov or weight decay): p -= lr g.  No moment arena.
-__device__ __forceinline__ void sgd_update(float& pi, float& gi, float g2i, bool has_g2, float lr, int zero_grad) {
-#pragma clang fp contract(off)
-    if (has_g2) gi += g2i;
-    pi -= lr * gi;
-    if (zero_grad) gi = 0.f;
-}
-template <bool PAIR_LR>   // (as adam_kernel)
-__global__ void sgd_kernel(float* __restrict__ p, float* __restrict__ g, size_t n, float lr, int zero_grad, const float* __restrict__ g2,
-                           const float* __restrict__ lr_ptr, unsigned lr_stride) {
-    if (!PAIR_LR && lr_ptr) lr = *lr_ptr;
-    auto upd = [&](float& pi, float& gi, float g2i) { sgd_update(pi, gi, g2i, g2 != nullptr, lr, zero_grad); };
-    const unsigned lr_stride4 = lr_stride / 4;
-    const size_t n4 = ((reinterpret_cast<size_t>(p) | reinterpret_cast<size_t>(g) | reinterpret_cast<size_t>(g2)) & 15) ? 0 : n / 4;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-        float4 pv = reinterpret_cast<float4*>(p)[i], gv = reinterpret_cast<float4*>(g)[i];
-        const float4 g2v = g2 ? reinterpret_cast<const float4*>(g2)[i] : float4{0.f, 0.f, 0.f, 0.f};
-        if (PAIR_LR) lr = lr_ptr[(unsigned)i / lr_stride4];
-        upd(pv.x, gv.x, g2v.x); upd(pv.y, gv.y, g2v.y); upd(pv.z, gv.z, g2v.z); upd(pv.w, gv.w, g2v.w);
-        reinterpret_cast<float4*>(p)[i] = pv;
-        if (g2 || zero_grad) reinterpret_cast<float4*>(g)[i] = gv;
-    }
-    for (size_t i = n4 * 4 + (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        float pi = p[i], gi = g[i];
-        if (PAIR_LR) lr = lr_ptr[(unsigned)i / lr_stride];
-        upd(pi, gi, g2 ? g2[i] : 0.f);
-        p[i] = pi;
-        if (g2 || zero_grad) g[i] = gi;
-    }
-}
-int sgd_launch(float* p, float* g, size_t n, float lr, int zero_grad, hipStream_t s, const float* g2, const float* lr_dev, size_t lr_stride) {
-    if (!pair_lr_ok(n, lr_dev, lr_stride)) return SPLICE_ERR_ARG;
-    if (lr_stride)
-        SPLICE_LAUNCH(sgd_kernel<true>, dim3(optim_grid(n)), dim3(256), 0, s, p, g, n, lr, zero_grad, g2, lr_dev, (unsigned)lr_stride);
-    else
-        SPLICE_LAUNCH(sgd_kernel<false>, dim3(optim_grid(n)), dim3(256), 0, s, p, g, n, lr, zero_grad, g2, lr_dev, 0u);
-    return SPLICE_OK;
-}
 // ---------------------------------------------------------------------------------------
 // nn.BatchNorm2d bookkeeping (models/unet/common.py:95-96: every netG call in train mode moves running_mean / running_var
 // with momentum 0.1; nothing ever reads them, but they are part of netG.state_dict()).  One launch covers every

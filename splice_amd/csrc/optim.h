@@ -1,0 +1,20 @@
+// The fused optimiser update over a flat arena (optim.hip; torch.optim as util/util.py:28-39 builds them).
+#pragma once
+#include "common.h"
+
+enum { SPLICE_OPT_ADAM = 0, SPLICE_OPT_RMSPROP = 1, SPLICE_OPT_SGD = 2 };
+struct OptimArgs {
+    int kind;              // SPLICE_OPT_*
+    float *p, *g;
+    const float* g2;       // optional: a second gradient arena folded in as g += g2 (g is written back when g2 or zero_grad is set)
+    float *m, *v;          // Adam: m and v; RMSprop: v = square_avg; an arena the kind does not use is never touched (may be null)
+    size_t n;
+    float lr;
+    const float* lr_dev;   // optional: the learning rate is read from device memory when the kernel runs (a schedule under graph replay)
+    size_t lr_stride;      // != 0 (a multiple of 4): per-pair learning rates, element i of the arena uses lr_dev[i / lr_stride]
+    float hp0, hp1, eps;   // Adam: beta1, beta2; RMSprop: alpha
+    int step;              // Adam's step count (>= 1); the bias corrections are then computed on the host ...
+    const int* step_dev;   // ... unless this is set: the count is read, and they are computed, on the device (graph replay)
+    int zero_grad;
+};
+int optim_launch(const OptimArgs& a, hipStream_t s);

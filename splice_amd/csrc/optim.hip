@@ -1,0 +1,163 @@
+// Fused multi-tensor optimiser update over the flat parameter arena (K19): torch.optim.Adam / RMSprop / SGD as util/util.py:28-39
+// configures them, plus optimizer.zero_grad (train.py:56) when zero_grad != 0.  One walk over the arena (optim_kernel), one element
+// rule per optimiser, one launcher that validates and selects the instance.
+#include "optim.h"
+
+void splice_set_error(const char* fmt, ...);
+
+// ---- element rules.  Contraction is OFF so that the vector body and the scalar tail of the kernel round alike (an element's result
+// must not depend on where in an arena it sits: P pairs per step == P single runs, bit for bit).  USES_M / USES_V: the moment arenas
+// the rule reads and writes; the walk does not touch (or alignment-test) the others.
+// Adam: no weight decay / amsgrad, eps added after sqrt(v_hat)
+struct AdamRule {
+    static constexpr bool USES_M = true, USES_V = true;
+    float b1, b2, eps, bc1, bc2_sqrt;
+    __device__ __forceinline__ AdamRule(float hp0, float hp1, float eps_, float bc1_, float bc2_sqrt_) : b1(hp0), b2(hp1), eps(eps_), bc1(bc1_), bc2_sqrt(bc2_sqrt_) {}
+    __device__ __forceinline__ void update(float& pi, float& gi, float& mi_, float& vi_, float g2i, bool has_g2, float lr, int zero_grad) const {
+#pragma clang fp contract(off)
+        if (has_g2) gi += g2i;   // second gradient arena (the B-crop plan): g = g + g2, as a separate add would leave it
+        const float mi = b1 * mi_ + (1.f - b1) * gi;
+        const float vi = b2 * vi_ + (1.f - b2) * gi * gi;
+        mi_ = mi;
+        vi_ = vi;
+        const float denom = sqrtf(vi) / bc2_sqrt + eps;
+        pi -= (lr / bc1) * (mi / denom);
+        if (zero_grad) gi = 0.f;
+    }
+};
+// RMSprop (alpha 0.99, eps 1e-8; no momentum, not centred, no weight decay): v = alpha v + (1 - alpha) g^2, p -= lr g / (sqrt(v) + eps);
+// the v arena holds square_avg
+struct RmspropRule {
+    static constexpr bool USES_M = false, USES_V = true;
+    float alpha, eps;
+    __device__ __forceinline__ RmspropRule(float hp0, float, float eps_, float, float) : alpha(hp0), eps(eps_) {}
+    __device__ __forceinline__ void update(float& pi, float& gi, float&, float& vi_, float g2i, bool has_g2, float lr, int zero_grad) const {
+#pragma clang fp contract(off)
+        if (has_g2) gi += g2i;
+        const float vi = alpha * vi_ + (1.f - alpha) * gi * gi;
+        vi_ = vi;
+        pi -= lr * (gi / (sqrtf(vi) + eps));
+        if (zero_grad) gi = 0.f;
+    }
+};
+// SGD (no momentum, dampening, nesterov or weight decay): p -= lr g
+struct SgdRule {
+    static constexpr bool USES_M = false, USES_V = false;
+    __device__ __forceinline__ SgdRule(float, float, float, float, float) {}
+    __device__ __forceinline__ void update(float& pi, float& gi, float&, float&, float g2i, bool has_g2, float lr, int zero_grad) const {
+#pragma clang fp contract(off)
+        if (has_g2) gi += g2i;
+        pi -= lr * gi;
+        if (zero_grad) gi = 0.f;
+    }
+};
+
+// ---- the walk.  One float4 per thread and (at the generator's size) ONE pass: the operand vectors of an element group are a single
+// memory round trip; the kernel is the last node of the step's critical chain.
+// PAIR_LR: every pair of the arena has its own learning rate, lr_ptr[element / lr_stride] (lr_stride = the arena stride, a multiple
+// of 4: a float4 never straddles two pairs).
+// The argument list is the same for every rule (a rule ignores what it does not use) and keeps Adam's order: the pointers and Adam's
+// scalars fill the 16 preloaded kernel-argument SGPRs.  RMSprop and SGD pay for the shared list: their g2 / lr_ptr / zero_grad lie
+// behind the preloaded 16 and cost one scalar load at the kernel's head (SGD +0.3 us, RMSprop +0.1 us per launch at one pair, nothing
+// measurable at eight).  Argument lists of their own need the walk in an inlined function, which the compiler
+// schedules differently (the per-pair-lr instances then take 1-2 VGPRs more than before): not done.
+template <class Rule, bool PAIR_LR>
+__global__ void optim_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, size_t n, float lr,
+                             float hp0, float hp1, float eps, float bc1, float bc2_sqrt, int zero_grad, const int* __restrict__ step_ptr,
+                             const float* __restrict__ g2, const float* __restrict__ lr_ptr, unsigned lr_stride) {
+    if (!PAIR_LR && lr_ptr) lr = *lr_ptr;   // learning rate on the device (a schedule under graph replay); null: the argument
+    if (step_ptr) {   // Adam's step count lives on the device (graph replay): bias corrections computed here
+        const float t = (float)*step_ptr;
+        bc1 = 1.0f - powf(hp0, t);
+        bc2_sqrt = sqrtf(1.0f - powf(hp1, t));
+    }
+    const Rule rule(hp0, hp1, eps, bc1, bc2_sqrt);
+    auto upd = [&](float& pi, float& gi, float& mi, float& vi, float g2i) { rule.update(pi, gi, mi, vi, g2i, g2 != nullptr, lr, zero_grad); };
+    const unsigned lr_stride4 = lr_stride / 4;
+    const size_t align = reinterpret_cast<size_t>(p) | reinterpret_cast<size_t>(g) | (Rule::USES_M ? reinterpret_cast<size_t>(m) : 0) |
+                         (Rule::USES_V ? reinterpret_cast<size_t>(v) : 0) | reinterpret_cast<size_t>(g2);
+    const size_t n4 = (align & 15) ? 0 : n / 4;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+        float4 pv = reinterpret_cast<float4*>(p)[i], gv = reinterpret_cast<float4*>(g)[i], mv = {}, vv = {};
+        if (Rule::USES_M) mv = reinterpret_cast<float4*>(m)[i];
+        if (Rule::USES_V) vv = reinterpret_cast<float4*>(v)[i];
+        const float4 g2v = g2 ? reinterpret_cast<const float4*>(g2)[i] : float4{0.f, 0.f, 0.f, 0.f};
+        if (PAIR_LR) lr = lr_ptr[(unsigned)i / lr_stride4];
+        upd(pv.x, gv.x, mv.x, vv.x, g2v.x); upd(pv.y, gv.y, mv.y, vv.y, g2v.y); upd(pv.z, gv.z, mv.z, vv.z, g2v.z); upd(pv.w, gv.w, mv.w, vv.w, g2v.w);
+        reinterpret_cast<float4*>(p)[i] = pv;
+        if (Rule::USES_M) reinterpret_cast<float4*>(m)[i] = mv;
+        if (Rule::USES_V) reinterpret_cast<float4*>(v)[i] = vv;
+        if (g2 || zero_grad) reinterpret_cast<float4*>(g)[i] = gv;
+    }
+    for (size_t i = n4 * 4 + (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        float pi = p[i], gi = g[i], mi = 0.f, vi = 0.f;
+        if (Rule::USES_M) mi = m[i];
+        if (Rule::USES_V) vi = v[i];
+        if (PAIR_LR) lr = lr_ptr[(unsigned)i / lr_stride];
+        upd(pi, gi, mi, vi, g2 ? g2[i] : 0.f);
+        p[i] = pi;
+        if (Rule::USES_M) m[i] = mi;
+        if (Rule::USES_V) v[i] = vi;
+        if (g2 || zero_grad) g[i] = gi;
+    }
+}
+static unsigned optim_grid(size_t n) {
+    size_t g_ = (n / 4 + 255) / 256 + 1;
+    return (unsigned)(g_ > 2048 ? 2048 : g_);
+}
+
+int optim_launch(const OptimArgs& a, hipStream_t s) {
+    static constexpr decltype(&optim_kernel<AdamRule, false>) kernels[3][2] = {{optim_kernel<AdamRule, false>, optim_kernel<AdamRule, true>},
+                                                                               {optim_kernel<RmspropRule, false>, optim_kernel<RmspropRule, true>},
+                                                                               {optim_kernel<SgdRule, false>, optim_kernel<SgdRule, true>}};
+    if (a.kind < SPLICE_OPT_ADAM || a.kind > SPLICE_OPT_SGD) {
+        splice_set_error("optimiser: unknown optimiser kind %d", a.kind);
+        return SPLICE_ERR_ARG;
+    }
+    const bool adam = a.kind == SPLICE_OPT_ADAM, host_step = adam && !a.step_dev;
+    if (!a.p || !a.g || a.n < 1 || (adam && !a.m) || (a.kind != SPLICE_OPT_SGD && !a.v) || (host_step && a.step < 1)) return SPLICE_ERR_ARG;
+    // per-pair learning rates index lr_dev with a 32-bit element index
+    if (a.lr_stride && (!a.lr_dev || a.lr_stride % 4 || a.n > 0xFFFFFFFFull || a.lr_stride > 0xFFFFFFFFull)) {
+        splice_set_error("optimiser: per-pair lr needs a device lr table, an arena stride that is a multiple of 4 and < 2^32 elements");
+        return SPLICE_ERR_ARG;
+    }
+    // a host step count: the bias corrections come from the HOST's powf (host and device powf need not agree to the bit, so a caller
+    // stays with the form it has)
+    const float bc1 = host_step ? 1.0f - powf(a.hp0, (float)a.step) : 1.f;
+    const float bc2_sqrt = host_step ? sqrtf(1.0f - powf(a.hp1, (float)a.step)) : 1.f;
+    const auto kernel = kernels[a.kind][a.lr_stride != 0];
+    SPLICE_LAUNCH(kernel, dim3(optim_grid(a.n)), dim3(256), 0, s, a.p, a.g, a.m, a.v, a.n, a.lr, a.hp0, a.hp1, a.eps, bc1, bc2_sqrt, a.zero_grad,
+                  adam ? a.step_dev : nullptr, a.g2, a.lr_dev, (unsigned)a.lr_stride);
+    return SPLICE_OK;
+}
+
+// ---- exports (include/splice_hip.h): fillers of OptimArgs
+static OptimArgs optim_args(int kind, float* params, float* grads, const float* g2, float* m, float* v, long long n, float lr, const float* lr_dev,
+                            size_t lr_stride, float hp0, float hp1, float eps, int step, int zero_grad) {
+    return OptimArgs{kind, params, grads, g2, m, v, n < 1 ? 0 : (size_t)n, lr, lr_dev, lr_stride, hp0, hp1, eps, step, nullptr, zero_grad};
+}
+extern "C" {
+int splice_adam_step(float* params, float* grads, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps, int step,
+                     int zero_grad, splice_stream_t stream) {
+    return optim_launch(optim_args(SPLICE_OPT_ADAM, params, grads, nullptr, m, v, n, lr, nullptr, 0, beta1, beta2, eps, step, zero_grad), (hipStream_t)stream);
+}
+int splice_optim_step_ex(int kind, float* params, float* grads, const float* g2, float* m, float* v, long long n, float lr, const float* lr_dev,
+                         float hp0, float hp1, float eps, int step, int zero_grad, splice_stream_t stream) {
+    return optim_launch(optim_args(kind, params, grads, g2, m, v, n, lr, lr_dev, 0, hp0, hp1, eps, step, zero_grad), (hipStream_t)stream);
+}
+int splice_optim_step(int kind, float* params, float* grads, float* m, float* v, long long n, float lr, float hp0, float hp1, float eps, int step,
+                      int zero_grad, splice_stream_t stream) {
+    return splice_optim_step_ex(kind, params, grads, nullptr, m, v, n, lr, nullptr, hp0, hp1, eps, step, zero_grad, stream);
+}
+// The whole range n_pairs * stride is updated, the padding floats between two arenas included (they hold zero gradients, so they stay
+// as they are).
+int splice_optim_step_pairs(int kind, float* params, float* grads, const float* g2, float* m, float* v, int n_pairs, long long stride, long long n,
+                            const float* lr_dev, float hp0, float hp1, float eps, int step, int zero_grad, splice_stream_t stream) {
+    if (!params || !grads || !lr_dev || n_pairs < 1 || n < 1 || stride < n || stride % 4) {
+        splice_set_error("splice_optim_step_pairs: needs a device lr table, n_pairs >= 1 and 1 <= n <= stride with stride a multiple of 4");
+        return SPLICE_ERR_ARG;
+    }
+    return optim_launch(optim_args(kind, params, grads, g2, m, v, (long long)n_pairs * stride, 0.f, lr_dev, (size_t)stride, hp0, hp1, eps, step, zero_grad),
+                        (hipStream_t)stream);
+}
+}

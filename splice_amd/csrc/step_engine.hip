@@ -25,6 +25,7 @@
 
 #include "gen_kernels.h"
 #include "kernels.h"
+#include "optim.h"
 
 void splice_set_error(const char* fmt, ...);
 extern "C" {
@@ -45,8 +46,6 @@ int splice_gen_plan_dims(void* plan, int* N, int* H, int* W, long long* nparams)
 int splice_gen_plan_resize(void* plan, int H, int W);
 int splice_gen_forward(void* plan, const float* params, const float* x, float* y, splice_stream_t stream);
 int splice_gen_backward(void* plan, const float* params, const float* dy, float* grads, int accumulate, splice_stream_t stream);
-int splice_adam_step(float* params, float* grads, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps,
-                     int step, int zero_grad, splice_stream_t stream);
 int splice_prof_active(void);
 }
 
@@ -782,13 +781,14 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
     // execution time
     SPLICE_DEV_REGION(21);
     if (do_gb && !st->skip_adam) {
-        const size_t n_all = st->astride ? pairs * st->astride : (size_t)st->nparams;
+        OptimArgs a = {};
+        a.kind = st->opt_kind; a.p = params; a.g = grads; a.g2 = adam_g2; a.m = m; a.v = v;
+        a.n = st->astride ? pairs * st->astride : (size_t)st->nparams;
+        a.lr = c.lr; a.hp0 = st->opt_hp0; a.hp1 = st->opt_hp1; a.eps = st->opt_eps; a.step_dev = st->dev_t;
         // per-pair lrs (splice_step_set_pair_lr): pair p's arena reads dev_lrs[p]
-        const float* lr_dev = st->pair_lr ? st->dev_lrs : st->lr_set ? st->dev_lr : nullptr;
-        const size_t lr_stride = st->pair_lr ? st->astride : 0;
-        if (st->opt_kind == SPLICE_OPT_RMSPROP) RC(rmsprop_launch(params, grads, v, n_all, c.lr, st->opt_hp0, st->opt_eps, 0, s, adam_g2, lr_dev, lr_stride));
-        else if (st->opt_kind == SPLICE_OPT_SGD) RC(sgd_launch(params, grads, n_all, c.lr, 0, s, adam_g2, lr_dev, lr_stride));
-        else RC(adam_launch_dev(params, grads, m, v, n_all, c.lr, st->opt_hp0, st->opt_hp1, st->opt_eps, st->dev_t, 0, s, adam_g2, lr_dev, lr_stride));
+        a.lr_dev = st->pair_lr ? st->dev_lrs : st->lr_set ? st->dev_lr : nullptr;
+        a.lr_stride = st->pair_lr ? st->astride : 0;
+        RC(optim_launch(a, s));
     }
     return SPLICE_OK;
 }
