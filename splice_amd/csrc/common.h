@@ -7,6 +7,26 @@
 
 typedef uint16_t bf16_t;  // raw bf16 storage
 
+// ---- host-side error plumbing of the engines: the message behind splice_last_error (capi.hip), and "return on failure" for
+// the library's own status codes (RC) and for HIP runtime calls (HIPCHK)
+void splice_set_error(const char* fmt, ...);
+#define RC(x)                                                                                     \
+    do {                                                                                          \
+        int rc_ = (x);                                                                            \
+        if (rc_ != SPLICE_OK) {                                                                   \
+            splice_set_error("%s:%d %s failed (%d)", __FILE__, __LINE__, #x, rc_);                \
+            return rc_;                                                                           \
+        }                                                                                         \
+    } while (0)
+#define HIPCHK(x)                                                                                 \
+    do {                                                                                          \
+        hipError_t e_ = (x);                                                                      \
+        if (e_ != hipSuccess) {                                                                   \
+            splice_set_error("%s:%d %s -> %s", __FILE__, __LINE__, #x, hipGetErrorString(e_));    \
+            return SPLICE_ERR_HIP;                                                                \
+        }                                                                                         \
+    } while (0)
+
 // ---- every kernel launch of the library goes through SPLICE_LAUNCH.  While bench.py's roofline leg has a kernel family
 // armed (splice_prof_begin) and one of its host calls is open (SpliceProfScope), the launch goes out as hipExtLaunchKernelGGL
 // with a start / stop event pair of its own: the pair carries the kernel's begin and end time stamps (what rocprofv3's

@@ -11,19 +11,7 @@
 #include <vector>
 
 #include "gen_kernels.h"
-
-int dev_copy_launch(void* dst, const void* src, size_t bytes, hipStream_t s);
-
-void splice_set_error(const char* fmt, ...);
-
-#define RC(x)                                                                                     \
-    do {                                                                                          \
-        int rc_ = (x);                                                                            \
-        if (rc_ != SPLICE_OK) {                                                                   \
-            splice_set_error("%s:%d %s failed (%d)", __FILE__, __LINE__, #x, rc_);                \
-            return rc_;                                                                           \
-        }                                                                                         \
-    } while (0)
+#include "kernels.h"
 
 // Architecture of a skip() network (models/unet/skip.py:4-11): define_G builds the default one; the feature-inversion
 // experiment (inversion.py:21-25) asks for 6 scales, 7/7/5/5/3/3 filters, reflection padding and 32 input channels.
@@ -61,7 +49,9 @@ struct Unit {
     const float* in = nullptr; size_t in_ns = 0;
     float* y = nullptr; size_t y_ns = 0;
     float* out = nullptr; size_t out_ns = 0;
-    float *mean = nullptr, *rstd = nullptr, *s1 = nullptr, *s2 = nullptr;
+    float *mean = nullptr, *rstd = nullptr, *s1 = nullptr;
+    // how the unit's BatchNorm runs (plane Ho x Wo), and the BatchNorm that reads the unit's input gradient (plane Hi x Wi): plan_configure
+    BnForm bn = {}, bn_in = {};
     // gradients
     float* d_out = nullptr; size_t d_out_ns = 0;   // grad w.r.t. `out` (provided by the consumer)
     float* dy = nullptr;                            // grad w.r.t. y (same shape/stride as y)
@@ -74,6 +64,7 @@ struct Unit {
 struct SpliceGen {
     GenArch arch;
     ParamTable table;
+    size_t offs[MAXS * 6 * 4], head[4], roffs[MAXS * 6];   // build_table's offsets: [scale][unit][w, b, gamma, beta], the head's, [scale][unit] running_mean
     ParamTable buffers;   // BatchNorm running statistics in state_dict order: "<bn>.running_mean" (C floats) then "<bn>.running_var" (C floats)
 };
 
@@ -95,7 +86,6 @@ struct SpliceGenPlan {
     int skip_ks[MAXS];                    // slabs left by the last forward (<= 1: none, u_skip.y is complete)
     struct { const float* target = nullptr; const float* slabs = nullptr; int ksplit = 0, accumulate = 0; } pend;   // backward: slabs of the next BatchNorm's output gradient
     float* pad_scratch = nullptr;         // reflection padding: padded-domain data gradient of one layer (largest layer)
-    float* head_y = nullptr;              // unused (sigmoid fused)
     size_t head_w = 0, head_b = 0;
     float* d_head_pre = nullptr;          // [N][3][H][W]
     float* d_u0 = nullptr;                // grad w.r.t. u_0 (scale-0 output)
@@ -117,8 +107,7 @@ static inline int bn_batch(const SpliceGenPlan* p) { return p->batch_stats ? p->
 static inline int conv_group(const SpliceGenPlan* p) { return p->batch_stats && p->p_nstride ? p->group : 0; }
 // parameter arenas of the plan's images (the wgrad / head-bias reductions: one per image or per group; 1 without a stride)
 static inline int plan_arenas(const SpliceGenPlan* p) { return p->batch_stats ? p->N / p->group : p->N; }
-static void build_table(const GenArch& A, ParamTable& t, size_t* offs /* [MAXS][6 units][4] */, size_t* head, ParamTable* bufs = nullptr,
-                        size_t* roffs /* [MAXS][6] */ = nullptr) {
+static void build_table(const GenArch& A, ParamTable& t, size_t* offs /* [MAXS][6 units][4] */, size_t* head, ParamTable* bufs, size_t* roffs /* [MAXS][6] */) {
     // a conv is nn.Sequential([ReflectionPad2d,] Conv2d): the Conv2d is child "1" behind a padder, child "0" otherwise (models/unet/common.py:113-124)
     const std::string cv = A.reflect ? ".1" : ".0";
     auto conv = [&](const std::string& n, int co, int ci, int k, size_t* o) {
@@ -202,16 +191,18 @@ static void plan_configure(SpliceGenPlan* p, int H, int W) {
         const size_t catC = A.skip[i] + p->kch[i];
         const size_t cat_ns = catC * hi * wi;
         Unit &sk = p->u_skip[i], &da = p->u_da[i], &db = p->u_db[i], &ct = p->u_cat[i], &u3 = p->u_up3[i], &u1 = p->u_up1[i];
-        auto dims = [](Unit& u, int Hi, int Wi, int Ho, int Wo) {
+        auto dims = [p](Unit& u, int Hi, int Wi, int Ho, int Wo) {
             u.Hi = Hi; u.Wi = Wi; u.Ho = Ho; u.Wo = Wo;
+            u.bn = bn_form(Ho * Wo, p->N, p->p_nstride, bn_batch(p));
+            u.bn_in = bn_form(Hi * Wi, p->N, p->p_nstride, bn_batch(p));
             u.y_ns = (size_t)u.Cout * Ho * Wo;
             if (u.own_out) { u.out_ns = u.y_ns; u.d_out_ns = u.y_ns; }
         };
-        // the skip branch's BatchNorm rides in the concat BatchNorm's kernels where those own whole planes (BnPre)
-        p->chain[i] = A.skip[i] > 0 && bn_pre_supported(hi * wi, p->N, p->p_nstride, p->batch_stats);
         p->skip_ks[i] = 1;
         dims(sk, hi, wi, hi, wi); dims(da, hi, wi, hd, wd); dims(db, hd, wd, hd, wd);
         dims(ct, hi, wi, hi, wi); dims(u3, hi, wi, hi, wi); dims(u1, hi, wi, hi, wi);
+        // the skip branch's BatchNorm rides in the concat BatchNorm's kernels where those own whole planes (BnPre)
+        p->chain[i] = A.skip[i] > 0 && ct.bn.hosts_pre;
         sk.out = p->cat[i]; sk.out_ns = cat_ns;
         if (ng) { sk.d_out = p->d_cat[i]; sk.d_out_ns = cat_ns; }
         ct.in = p->cat[i]; ct.in_ns = cat_ns;
@@ -245,8 +236,7 @@ static ConvArgs unit_conv_args(const SpliceGenPlan* p, const Unit& u, const floa
     a.N = p->N; a.Cin = u.Cin; a.Hi = u.Hi; a.Wi = u.Wi; a.Cout = u.Cout; a.Ho = u.Ho; a.Wo = u.Wo;
     a.ks = u.ks; a.stride = u.stride; a.pad = (u.ks - 1) / 2; a.reflect = p->gen->arch.reflect && u.ks > 1;
     a.ws = ws; a.ws_floats = ws_floats;
-    // small planes: a split-K convolution leaves its slabs for the BatchNorm kernel, which adds them while it loads the plane
-    a.defer_reduce = !p->batch_stats && u.Ho * u.Wo <= bn_small_hw();
+    a.defer_reduce = u.bn.fwd_takes_slabs;   // a split-K convolution leaves its slabs for the BatchNorm kernel
     return a;
 }
 // the skip unit of a scale as the BnPre of that scale's concat BatchNorm
@@ -261,30 +251,42 @@ static BnPre skip_pre(const SpliceGenPlan* p, int i, const float* params, float*
     else if (p->skip_ks[i] > 1) { pr.slabs = p->skip_ws[i]; pr.ksplit = p->skip_ks[i]; pr.bias = params + sk.b_off; }
     return pr;
 }
+// the BatchNorm of a unit as BnArgs, forward direction; unit_bn_bwd_args adds the backward's tensors
+static BnArgs unit_bn_args(const SpliceGenPlan* p, const Unit& u, const float* params, const BnUpsample* up, const BnPre* pre) {
+    BnArgs a;
+    a.y = u.ks ? u.y : u.in; a.y_nstride = u.ks ? u.y_ns : u.in_ns;   // BN-only unit: normalises its input
+    a.out = u.out; a.out_nstride = u.out_ns;
+    a.N = p->N; a.C = u.Cout; a.HW = u.Ho * u.Wo;
+    a.gamma = params + u.g_off; a.beta = params + u.be_off; a.eps = BN_EPS; a.slope = u.slope;
+    a.p_nstride = p->p_nstride; a.batch = bn_batch(p);
+    a.part = u.s1; a.mean = u.mean; a.rstd = u.rstd;
+    a.up = up; a.pre = pre;
+    return a;
+}
+static BnArgs unit_bn_bwd_args(const SpliceGenPlan* p, const Unit& u, const float* params, float* grads, int acc, const BnUpsample* up, const BnPre* pre,
+                               const BnSlabs* slabs) {
+    BnArgs a = unit_bn_args(p, u, params, up, pre);
+    a.da = u.d_out; a.da_nstride = u.d_out_ns;
+    a.dy = u.ks ? u.dy : u.d_in; a.dy_nstride = u.ks ? u.y_ns : u.d_in_ns;   // BN-only unit: dy IS the input gradient
+    a.dgamma = grads + u.g_off; a.dbeta = grads + u.be_off; a.accumulate = acc;
+    a.da_slabs = slabs;
+    return a;
+}
 // BatchNorm + activation of a unit behind its convolution (ksplit > 1 with a deferred reduction: the slabs at `slabs` are summed here)
-static int unit_bn_forward(const SpliceGenPlan* p, const Unit& u, const float* params, const float* y, size_t y_ns, const float* slabs, int ksplit,
-                           bool deferred, hipStream_t s, const BnUpsample* up, const BnPre* pre = nullptr) {
+static int unit_bn_forward(const SpliceGenPlan* p, const Unit& u, const float* params, const float* slabs, int ksplit, bool deferred, hipStream_t s,
+                           const BnUpsample* up, const BnPre* pre = nullptr) {
     SPLICE_DEV_REGION(13);
-    const int N = p->N;
-    if (deferred && ksplit > 1) {
-        RC(bn_fwd_slabs_launch(slabs, ksplit, params + u.b_off, u.y, u.y_ns, u.out, u.out_ns, N, u.Cout, u.Ho * u.Wo, params + u.g_off,
-                               params + u.be_off, BN_EPS, u.mean, u.rstd, u.slope, s, p->p_nstride));
-        return SPLICE_OK;
-    }
-    if (p->batch_stats && up) {   // batch statistics: the upsampled channels are materialised first (no fusion with the statistics pass)
-        RC(upsample2x_fwd_launch(up->src, up->src_ns, const_cast<float*>(y) + (size_t)up->c0 * u.Ho * u.Wo, y_ns, N, u.Cout - up->c0, up->h, up->w, up->Ho, up->Wo, s));
-        up = nullptr;
-    }
-    RC(bn_fwd_launch(y, y_ns, u.out, u.out_ns, N, u.Cout, u.Ho * u.Wo, params + u.g_off, params + u.be_off, BN_EPS, u.s1, u.mean, u.rstd, u.slope, s, up,
-                     p->p_nstride, bn_batch(p), pre));
+    BnArgs a = unit_bn_args(p, u, params, up, pre);
+    if (deferred && ksplit > 1) { a.slabs = slabs; a.ksplit = ksplit; a.bias = params + u.b_off; }
+    RC(bn_fwd_launch(a, s));
     return SPLICE_OK;
 }
 static int unit_forward(const SpliceGenPlan* p, const Unit& u, const float* params, hipStream_t s, const BnUpsample* up = nullptr, const BnPre* pre = nullptr) {
-    if (!u.ks) return unit_bn_forward(p, u, params, u.in, u.in_ns, nullptr, 1, false, s, up, pre);
+    if (!u.ks) return unit_bn_forward(p, u, params, nullptr, 1, false, s, up, pre);
     const ConvArgs a = unit_conv_args(p, u, params, p->conv_ws, p->conv_ws_floats);
     int ksplit = 1;
     RC(conv_launch(a, s, &ksplit));
-    return unit_bn_forward(p, u, params, u.y, u.y_ns, p->conv_ws, ksplit, a.defer_reduce != 0, s, up);
+    return unit_bn_forward(p, u, params, p->conv_ws, ksplit, a.defer_reduce != 0, s, up);
 }
 // two units that read the same input and do not depend on each other (the skip branch and the first encoder convolution of a
 // scale): their convolutions share one launch (conv_pair_launch); a = the 1x1 unit
@@ -301,22 +303,24 @@ static int unit_pair_forward(SpliceGenPlan* p, int scale, const Unit& ua, const 
     int ksa = 1, ksb = 1;
     RC(conv_pair_launch(a, b, s, &ksa, &ksb));
     p->skip_ks[scale] = a_bn_later && a.defer_reduce ? ksa : 1;
-    if (!a_bn_later) RC(unit_bn_forward(p, ua, params, ua.y, ua.y_ns, a.ws, ksa, a.defer_reduce != 0, s, nullptr));
-    RC(unit_bn_forward(p, ub, params, ub.y, ub.y_ns, b.ws, ksb, b.defer_reduce != 0, s, nullptr));
+    if (!a_bn_later) RC(unit_bn_forward(p, ua, params, a.ws, ksa, a.defer_reduce != 0, s, nullptr));
+    RC(unit_bn_forward(p, ub, params, b.ws, ksb, b.defer_reduce != 0, s, nullptr));
     return SPLICE_OK;
 }
 
+// one entry of the backward's single reduction: n gradient elements at dw_off of the arena = the sum of `chunks` partials at ws_off of the
+// weight-gradient workspace (chunks == 0: exact zeros)
+static void reduce_entry(SpliceGenPlan* p, int n, int chunks, size_t ws_off, size_t dw_off) {
+    WgradReduceAll& r = p->red;
+    const int li = r.count++;
+    r.n[li] = n; r.chunks[li] = chunks; r.ws_off[li] = (long long)ws_off; r.dw_off[li] = (long long)dw_off;
+}
 // backward of one unit, first part: BatchNorm backward (consumes u.d_out, leaves dy), the conv bias gradient (exact zero) and the
 // weight-gradient work item
 // bn_done: the BatchNorm backward of this unit has already run inside another kernel (BnPre)
-static int unit_backward_bn(const SpliceGenPlan* p, const Unit& u, const float* params, float* grads, int acc, hipStream_t s,
+static int unit_backward_bn(SpliceGenPlan* p, const Unit& u, const float* params, float* grads, int acc, hipStream_t s,
                             const BnUpsample* up = nullptr, const BnPre* pre = nullptr, bool bn_done = false) {
-    const int N = p->N, HW = u.Ho * u.Wo;
-    const float* y = u.ks ? u.y : u.in;
-    const size_t y_ns = u.ks ? u.y_ns : u.in_ns;
-    float* dy = u.ks ? u.dy : u.d_in;          // BN-only unit: dy IS the input gradient
-    const size_t dy_ns = u.ks ? u.y_ns : u.d_in_ns;
-    auto& pend = const_cast<SpliceGenPlan*>(p)->pend;
+    auto& pend = p->pend;
     if (pend.target && (bn_done || pend.target != u.d_out)) {
         splice_set_error("generator backward: split-K slabs pending for a gradient that the next BatchNorm does not read");
         return SPLICE_ERR_STATE;
@@ -325,31 +329,22 @@ static int unit_backward_bn(const SpliceGenPlan* p, const Unit& u, const float* 
         BnSlabs sl;
         if (pend.target) { sl.slabs = pend.slabs; sl.ksplit = pend.ksplit; sl.accumulate = pend.accumulate; pend.target = nullptr; }
         SPLICE_DEV_REGION(14);
-        RC(bn_bwd_launch(u.d_out, u.d_out_ns, u.out, u.out_ns, y, y_ns, dy, dy_ns, N, u.Cout, HW, params + u.g_off, u.mean, u.rstd, u.slope,
-                         u.s1, grads + u.g_off, grads + u.be_off, acc, s, p->batch_stats ? nullptr : up, p->p_nstride, bn_batch(p), pre, &sl, params + u.be_off));
+        RC(bn_bwd_launch(unit_bn_bwd_args(p, u, params, grads, acc, up, pre, &sl), s));
     }
     if (!u.ks) return SPLICE_OK;
     // The bias of a conv that feeds a train-mode BatchNorm has an analytically ZERO gradient (BN subtracts the
     // per-channel mean, sum_p dy = 0); the reference's autograd returns fp32 rounding noise there.  We write the
     // exact value and skip the reduction.
-    {
-        WgradReduceAll& r = const_cast<SpliceGenPlan*>(p)->red;
-        const int li = r.count++;
-        r.n[li] = u.Cout; r.chunks[li] = 0; r.ws_off[li] = 0; r.dw_off[li] = (long long)u.b_off;
-    }
-    {
-        WgradArgs a = {};
-        a.x = u.in; a.dy = u.dy;
-        a.x_nstride = u.in_ns; a.x_cstride = (size_t)u.Hi * u.Wi; a.dy_nstride = u.y_ns; a.dy_cstride = (size_t)HW;
-        a.N = N; a.Cin = u.Cin; a.Hi = u.Hi; a.Wi = u.Wi; a.Cout = u.Cout; a.Ho = u.Ho; a.Wo = u.Wo;
-        a.ks = u.ks; a.stride = u.stride; a.pad = (u.ks - 1) / 2; a.reflect = p->gen->arch.reflect && u.ks > 1;
-        a.ws = p->wgrad_ws + u.wg_off;
-        int chunks = 0;
-        RC(conv_wgrad_add(&const_cast<SpliceGenPlan*>(p)->wg, a, &chunks));
-        WgradReduceAll& r = const_cast<SpliceGenPlan*>(p)->red;
-        const int li = r.count++;
-        r.n[li] = u.Cout * u.Cin * u.ks * u.ks; r.chunks[li] = chunks; r.ws_off[li] = (long long)u.wg_off; r.dw_off[li] = (long long)u.w_off;
-    }
+    reduce_entry(p, u.Cout, 0, 0, u.b_off);
+    WgradArgs a = {};
+    a.x = u.in; a.dy = u.dy;
+    a.x_nstride = u.in_ns; a.x_cstride = (size_t)u.Hi * u.Wi; a.dy_nstride = u.y_ns; a.dy_cstride = (size_t)u.Ho * u.Wo;
+    a.N = p->N; a.Cin = u.Cin; a.Hi = u.Hi; a.Wi = u.Wi; a.Cout = u.Cout; a.Ho = u.Ho; a.Wo = u.Wo;
+    a.ks = u.ks; a.stride = u.stride; a.pad = (u.ks - 1) / 2; a.reflect = p->gen->arch.reflect && u.ks > 1;
+    a.ws = p->wgrad_ws + u.wg_off;
+    int chunks = 0;
+    RC(conv_wgrad_add(&p->wg, a, &chunks));
+    reduce_entry(p, u.Cout * u.Cin * u.ks * u.ks, chunks, u.wg_off, u.w_off);
     return SPLICE_OK;
 }
 // the data-gradient convolution of a unit (dy -> d_in) in data-gradient form; accumulate: 1 = add into d_in
@@ -369,15 +364,15 @@ static ConvArgs unit_dgrad_args(const SpliceGenPlan* p, const Unit& u, const flo
 // last_writer: no other convolution adds to d_in after this one.
 static bool dgrad_may_defer(const SpliceGenPlan* p, const Unit& u, bool last_writer) {
     return last_writer && u.ks && u.d_in && !(p->gen->arch.reflect && u.ks > 1) && u.d_in_ns == (size_t)u.Cin * u.Hi * u.Wi &&
-           bn_bwd_takes_slabs(u.Hi * u.Wi, p->N, p->p_nstride, p->batch_stats);
+           u.bn_in.bwd_takes_slabs;
 }
-static void dgrad_note_slabs(const SpliceGenPlan* p, const ConvArgs& a, int ksplit) {
+static void dgrad_note_slabs(SpliceGenPlan* p, const ConvArgs& a, int ksplit) {
     if (!a.defer_reduce || ksplit <= 1) return;
-    auto& pend = const_cast<SpliceGenPlan*>(p)->pend;
+    auto& pend = p->pend;
     pend.target = a.out; pend.slabs = a.ws; pend.ksplit = ksplit; pend.accumulate = a.accumulate;
 }
 // second part: the data gradient (if the unit's input needs one)
-static int unit_backward_dgrad(const SpliceGenPlan* p, const Unit& u, const float* params, int accumulate, hipStream_t s, bool last_writer = false) {
+static int unit_backward_dgrad(SpliceGenPlan* p, const Unit& u, const float* params, int accumulate, hipStream_t s, bool last_writer = false) {
     if (!u.ks || !u.d_in) return SPLICE_OK;
     ConvArgs a = unit_dgrad_args(p, u, params, accumulate, p->conv_ws, p->conv_ws_floats);
     if (p->gen->arch.reflect && u.ks > 1) { RC(conv_reflect_dgrad_launch(a, p->pad_scratch, s)); return SPLICE_OK; }
@@ -389,7 +384,7 @@ static int unit_backward_dgrad(const SpliceGenPlan* p, const Unit& u, const floa
 }
 // backward of one unit: consumes u.d_out, produces parameter grads and (optionally) u.d_in
 // last_writer: the unit's data gradient is the only (or the last) contribution to d_in and the BatchNorm backward that reads d_in runs next
-static int unit_backward(const SpliceGenPlan* p, const Unit& u, const float* params, float* grads, int acc, hipStream_t s,
+static int unit_backward(SpliceGenPlan* p, const Unit& u, const float* params, float* grads, int acc, hipStream_t s,
                          const BnUpsample* up = nullptr, const BnPre* pre = nullptr, bool bn_done = false, bool last_writer = false) {
     RC(unit_backward_bn(p, u, params, grads, acc, s, up, pre, bn_done));
     return unit_backward_dgrad(p, u, params, u.d_in_accumulate, s, last_writer);
@@ -422,8 +417,7 @@ int splice_gen_create_arch(const splice_gen_arch* arch, void** out) {
         delete g;
         return SPLICE_ERR_ARG;
     }
-    size_t offs[MAXS * 6 * 4], head[4], roffs[MAXS * 6];
-    build_table(g->arch, g->table, offs, head, &g->buffers, roffs);
+    build_table(g->arch, g->table, g->offs, g->head, &g->buffers, g->roffs);
     *out = g;
     return SPLICE_OK;
 }
@@ -455,10 +449,7 @@ int splice_gen_plan_create(void* h, int N, int H, int W, int need_grad, void** o
     p->gen = g; p->N = N; p->H = H; p->W = W; p->maxH = H; p->maxW = W; p->need_grad = need_grad;
     p->h[0] = H; p->w[0] = W;
     for (int i = 1; i <= S; ++i) { p->h[i] = (p->h[i - 1] + 1) / 2; p->w[i] = (p->w[i - 1] + 1) / 2; }
-    size_t offs[MAXS * 6 * 4], head[4], roffs[MAXS * 6];
-    ParamTable tmp, tmpb;
-    build_table(A, tmp, offs, head, &tmpb, roffs);
-    p->head_w = head[0]; p->head_b = head[1];
+    p->head_w = g->head[0]; p->head_b = g->head[1];
     int rc = SPLICE_OK;
     auto fail = [&]() { for (void* q : p->allocs) (void)hipFree(q); delete p; return rc; };
     size_t ws_need = 0, pad_need = 0;
@@ -476,14 +467,15 @@ int splice_gen_plan_create(void* h, int N, int H, int W, int need_grad, void** o
             for (size_t c : cand) if (N * c > pad_need) pad_need = N * c;
         }
         p->skip_ws[i] = nullptr; p->skip_ws_floats[i] = 0;
-        if (hi * wi <= bn_small_hw() && A.skip[i] > 0) {   // split-K slabs of a chained skip convolution (up to 16 slices)
+        // split-K slabs of a chained skip convolution (up to 16 slices); the layout setters come later: every form that can take slabs
+        if (A.skip[i] > 0 && bn_form(hi * wi, N, 0, 0).fwd_takes_slabs) {
             p->skip_ws_floats[i] = (size_t)16 * N * A.skip[i] * hi * wi;
             if ((rc = palloc(p, &p->skip_ws[i], p->skip_ws_floats[i])) != SPLICE_OK) break;
         }
         if ((rc = palloc(p, &p->cat[i], (size_t)N * catC * hi * wi)) != SPLICE_OK) break;
         if (need_grad && (rc = palloc(p, &p->d_cat[i], (size_t)N * catC * hi * wi)) != SPLICE_OK) break;
-        size_t* o = offs + (size_t)i * 6 * 4;
-        auto setp = [&](Unit& u, int idx) { u.w_off = o[idx * 4 + 0]; u.b_off = o[idx * 4 + 1]; u.g_off = o[idx * 4 + 2]; u.be_off = o[idx * 4 + 3]; u.r_off = roffs[i * 6 + idx]; };
+        const size_t* o = g->offs + (size_t)i * 6 * 4;
+        auto setp = [&](Unit& u, int idx) { u.w_off = o[idx * 4 + 0]; u.b_off = o[idx * 4 + 1]; u.g_off = o[idx * 4 + 2]; u.be_off = o[idx * 4 + 3]; u.r_off = g->roffs[i * 6 + idx]; };
         auto mk = [&](Unit& u, int idx, int ks, int stride, int ci, int co, int Hi, int Wi, int Ho, int Wo, bool own) {
             u.ks = ks; u.stride = stride; u.Cin = ci; u.Cout = co; u.Hi = Hi; u.Wi = Wi; u.Ho = Ho; u.Wo = Wo;
             setp(u, idx);
@@ -652,7 +644,7 @@ static int scale_forward(SpliceGenPlan* p, int i, const float* params, hipStream
     }
     const int hi = p->h[i], wi = p->w[i];
     // nn.Upsample(x2, bilinear) of the deeper branch into channels SKIPC.. of the concat: produced inside the concat's
-    // BatchNorm kernels (bn_fwd_launch with a BnUpsample), not by a launch of its own
+    // BatchNorm kernels where their form fuses it (bn_fwd_launch with a BnUpsample), else by a launch of its own in front of them
     BnUpsample up;
     up.src = deep; up.src_ns = deep_ns; up.c0 = SKIPC; up.h = p->h[i + 1]; up.w = p->w[i + 1]; up.Ho = hi; up.Wo = wi;
     const BnPre pre = skip_pre(p, i, params, nullptr);
@@ -717,15 +709,13 @@ static int scale_backward(SpliceGenPlan* p, int i, const float* params, float* g
     const GenArch& A = p->gen->arch;
     const int SKIPC = A.skip[i];
     Unit& deep = i < A.n_scales - 1 ? p->u_up1[i + 1] : p->u_db[i];
-    // small planes: the upsampled channels' gradient goes through the adjoint inside the concat's BatchNorm backward
+    // the upsampled channels' gradient goes through the adjoint inside the concat's BatchNorm backward where its form fuses it, else
+    // in a launch of its own behind it (bn_bwd_launch with a BnUpsample)
     BnUpsample up;
     up.d_src = deep.d_out; up.d_src_ns = deep.d_out_ns; up.c0 = SKIPC; up.h = p->h[i + 1]; up.w = p->w[i + 1]; up.Ho = hi; up.Wo = wi;
     const BnPre pre = skip_pre(p, i, params, grads);
     const bool chained = p->chain[i];
     RC(unit_backward(p, p->u_cat[i], params, grads, acc, s, &up, chained ? &pre : nullptr));   // -> d_cat[i] (chained: the skip channels' gradient goes on into u_skip[i].dy)
-    if (p->batch_stats || !bn_bwd_fuses_upsample_ex(hi * wi, up.h, up.w, p->N, p->p_nstride, p->batch_stats))
-        RC(upsample2x_bwd_launch(p->d_cat[i] + (size_t)SKIPC * hi * wi, p->u_skip[i].d_out_ns, deep.d_out, deep.d_out_ns, p->N, p->kch[i],
-                                 p->h[i + 1], p->w[i + 1], hi, wi, s));
     // The skip branch's backward depends on nothing deeper: where its input needs a gradient (every scale but the first) and a
     // deeper scale exists, it runs NOW, and its 1x1 data gradient shares a launch with the 1x1 data gradient of the deeper
     // scale's decoder output unit (two independent convolutions, conv_pair_launch).  It is then the FIRST writer of d x_i and
@@ -761,7 +751,6 @@ int splice_gen_backward(void* plan, const float* params, const float* dy, float*
     hipStream_t s = (hipStream_t)stream;
     SpliceProfScope prof_scope(7); SPLICE_DEV_REGION(16);
     const int OC = p->gen->arch.out_channels, U0 = p->gen->arch.up[0];
-    const size_t npix = (size_t)p->N * OC * p->H * p->W;
     p->red.count = 0;
     p->pend.target = nullptr;   // (a backward that failed half-way must not leave slabs pending for this one)
     p->wg.small.count = p->wg.small.total_wgs = 0;
@@ -769,13 +758,10 @@ int splice_gen_backward(void* plan, const float* params, const float* dy, float*
     p->wg.tile.count = p->wg.tile.total_wgs = 0;
     const Unit& u = p->u_up1[0];
     const int HW = p->H * p->W;
-    (void)npix;
     {
         int chunks = 0;
         RC(sigmoid_bwd_bias_launch(dy, p->y_saved, p->d_head_pre, p->N, OC, HW, p->wgrad_ws + p->head_bias_off, s, p->p_nstride, &chunks, conv_group(p)));
-        WgradReduceAll& r = p->red;
-        const int li = r.count++;
-        r.n[li] = OC; r.chunks[li] = chunks; r.ws_off[li] = (long long)p->head_bias_off; r.dw_off[li] = (long long)p->head_b;
+        reduce_entry(p, OC, chunks, p->head_bias_off, p->head_b);
     }
     {
         WgradArgs a = {};
@@ -785,9 +771,7 @@ int splice_gen_backward(void* plan, const float* params, const float* dy, float*
         a.ws = p->wgrad_ws + p->head_wg_off;
         int chunks = 0;
         RC(conv_wgrad_add(&p->wg, a, &chunks));
-        WgradReduceAll& r = p->red;
-        const int li = r.count++;
-        r.n[li] = OC * U0; r.chunks[li] = chunks; r.ws_off[li] = (long long)p->head_wg_off; r.dw_off[li] = (long long)p->head_w;
+        reduce_entry(p, OC * U0, chunks, p->head_wg_off, p->head_w);
     }
     {
         ConvArgs a = {};

@@ -1,4 +1,4 @@
-// Launchers of the generator kernels (gen_kernels.hip).
+// Launchers of the generator kernels: the host-side interface of gen_conv.hip, gen_wgrad.hip, gen_bn.hip and gen_pointwise.hip.
 #pragma once
 #include "common.h"
 
@@ -26,7 +26,7 @@ int conv_launch(const ConvArgs& a, hipStream_t s, int* ksplit_out = nullptr);
 // two independent convolutions (a: 1x1, stride 1) in ONE launch where an instantiation exists, else two launches; same results
 // as two conv_launch calls up to the summation order of `a` (it adopts b's wave groups)
 int conv_pair_launch(ConvArgs a, ConvArgs b, hipStream_t s, int* ksplit_a = nullptr, int* ksplit_b = nullptr);
-// data gradient of a reflection-padded convolution (transposed conv on the padded domain + mirror fold); see gen_kernels.hip
+// data gradient of a reflection-padded convolution (transposed conv on the padded domain + mirror fold); see gen_conv.hip
 int conv_reflect_dgrad_launch(ConvArgs a, float* pad_scratch, hipStream_t s);
 
 struct WgradArgs {
@@ -73,7 +73,8 @@ int bn_part_floats(int N, int C);
 // Optional fusion of the decoder's x2 bilinear upsampling (models/unet/skip.py: nn.Upsample in front of the concat's
 // BatchNorm) into the BatchNorm kernels of the concat unit: channels >= c0 of the normalised tensor ARE the upsampling of
 // `src`.  Forward: they are computed on the fly (and stored into y for the backward) instead of by a launch of their
-// own; backward (planes <= bn_small_hw() only): their input gradient goes straight through the adjoint into d_src.
+// own; backward: their input gradient goes straight through the adjoint into d_src.  A form that does not fuse a direction
+// (BnForm) gets the stand-alone upsampling launch from the BatchNorm launcher: same tensors either way.
 struct BnUpsample {
     const float* src = nullptr; size_t src_ns = 0;   // [N][C - c0][h][w]
     float* d_src = nullptr; size_t d_src_ns = 0;
@@ -103,36 +104,56 @@ struct BnSlabs {
     const float* slabs = nullptr;   // [ksplit][N][C][HW]
     int ksplit = 0, accumulate = 0;
 };
-bool bn_bwd_takes_slabs(int HW, int N, size_t p_nstride, int batch);
-bool bn_pre_supported(int HW, int N, size_t p_nstride, int batch);   // the concat BatchNorm of this size runs as ONE launch that can host a BnPre
-bool bn_bwd_fuses_upsample(int HW, int h, int w);
-bool bn_bwd_fuses_upsample_ex(int HW, int h, int w, int N, size_t p_nstride, int batch);   // incl. the one-launch form of the middle planes
-int bn_fwd_launch(const float* y, size_t y_nstride, float* out, size_t out_nstride, int N, int C, int HW, const float* gamma,
-                  const float* beta, float eps, float* part, float* mean, float* rstd, float slope, hipStream_t s, const BnUpsample* up = nullptr,
-                  size_t p_nstride = 0, int batch = 0, const BnPre* pre = nullptr);   // batch > 0: statistics over groups of `batch` images (nn.BatchNorm2d on a
-                                                                                          // batch), batch <= 8; batch < N needs p_nstride (one arena per group)
-// same, fused with the split-K reduction of the convolution that feeds it (small planes only: HW <= bn_small_hw()):
-// y = bias + sum_k slabs[k] is formed, stored (the backward reads it) and normalised in one launch
-int bn_small_hw();
-int bn_fwd_slabs_launch(const float* slabs, int ksplit, const float* bias, float* y, size_t y_nstride, float* out, size_t out_nstride, int N,
-                        int C, int HW, const float* gamma, const float* beta, float eps, float* mean, float* rstd, float slope, hipStream_t s,
-                        size_t p_nstride = 0);
-int bn_bwd_launch(const float* da, size_t da_nstride, const float* aout, size_t a_nstride, const float* y, size_t y_nstride, float* dy,
-                  size_t dy_nstride, int N, int C, int HW, const float* gamma, const float* mean, const float* rstd, float slope,
-                  float* part, float* dgamma, float* dbeta, int accumulate, hipStream_t s, const BnUpsample* up = nullptr, size_t p_nstride = 0,
-                  int batch = 0, const BnPre* pre = nullptr, const BnSlabs* slabs = nullptr, const float* beta = nullptr);
-int fill_zero_launch(float* p, int n, hipStream_t s);
-int channel_sum_launch(const float* dy, size_t nstride, int N, int C, int HW, float* db, int accumulate, hipStream_t s);
+// Which kernel form a BatchNorm plane runs in and what that form absorbs: THE table of forms -- bn_fwd_launch / bn_bwd_launch dispatch on
+// it, the engine plans with it (which convolutions may leave split-K slabs, which skip branch is chained, which workspaces to keep).
+//   SMALL          HW <= 4096                                      one launch, the plane in registers
+//   MID            HW <= 16384, per-image statistics, own arena     one launch, the plane in LDS
+//   TWO_STAGE      everything else                                  partials + apply, <= 64 scalar segments
+//   TWO_STAGE_VEC  65536 < HW <= 1.31 M                             partials + apply, <= 256 segments in 16-byte runs
+// batch: images per statistics group (0: per image); p_nstride: images (groups) with parameter arenas of their own.
+struct BnForm {
+    enum Kind { SMALL, MID, TWO_STAGE, TWO_STAGE_VEC } kind;
+    bool hosts_pre;            // a BnPre can ride in this launch (SPLICE_BN_CHAIN=0: never)
+    bool fwd_takes_slabs;      // forward sums the feeding convolution's split-K slabs (BnArgs::slabs)
+    bool bwd_takes_slabs;      // backward sums the feeding data gradient's split-K slabs (BnSlabs; SPLICE_BN_BWD_SLABS=0: never)
+    bool fwd_fuses_upsample;   // forward produces the upsampled channels itself (else the launcher runs upsample2x_fwd_kernel in front)
+    bool bwd_fuses_upsample;   // backward sends them through the adjoint itself (else the launcher runs upsample2x_bwd_kernel behind)
+    bool sign_from_y;          // backward re-forms the activation's sign from y and beta (SPLICE_BN_SIGN_FROM_Y=0: never)
+};
+BnForm bn_form(int HW, int N, size_t p_nstride, int batch);
+// One BatchNorm (+ LeakyReLU when slope != 1) launch, either direction.  batch > 0: statistics over groups of `batch` images
+// (nn.BatchNorm2d on a batch), batch <= 8; batch < N needs p_nstride (one arena per group).
+struct BnArgs {
+    const float* y = nullptr; size_t y_nstride = 0;       // the BatchNorm's input [N][C][HW] (forward with slabs or a non-fused upsampling: formed here first)
+    float* out = nullptr; size_t out_nstride = 0;         // the activated output (backward: read)
+    int N = 0, C = 0, HW = 0;
+    const float* gamma = nullptr; const float* beta = nullptr;   // image n at + n * p_nstride
+    float eps = 0.f, slope = 1.f;
+    size_t p_nstride = 0;
+    int batch = 0;
+    float* part = nullptr;                                // bn_part_floats(N, C) floats of scratch (two-stage forms)
+    float* mean = nullptr; float* rstd = nullptr;         // saved statistics [N][C] (forward: written)
+    const BnUpsample* up = nullptr;                       // channels >= up->c0 are an upsampling (forward: of up->src; backward: gradient to up->d_src)
+    const BnPre* pre = nullptr;                           // needs a form that hosts_pre
+    // forward only: y = bias + sum_k slabs[k] is formed, stored (the backward reads it) and normalised in one launch (needs fwd_takes_slabs, ksplit >= 2)
+    const float* slabs = nullptr; int ksplit = 0; const float* bias = nullptr;
+    // backward only
+    const float* da = nullptr; size_t da_nstride = 0;     // gradient w.r.t. out
+    float* dy = nullptr; size_t dy_nstride = 0;           // gradient w.r.t. y
+    float* dgamma = nullptr; float* dbeta = nullptr;
+    int accumulate = 0;                                   // dgamma / dbeta += result
+    const BnSlabs* da_slabs = nullptr;                    // needs bwd_takes_slabs
+};
+int bn_fwd_launch(const BnArgs& a, hipStream_t s);
+int bn_bwd_launch(const BnArgs& a, hipStream_t s);
 int upsample2x_fwd_launch(const float* in, size_t in_nstride, float* out, size_t out_nstride, int N, int C, int h, int w, int Ho, int Wo, hipStream_t s);
 int upsample2x_bwd_launch(const float* dout, size_t dout_nstride, float* din, size_t din_nstride, int N, int C, int h, int w, int Ho, int Wo, hipStream_t s);
-int sigmoid_bwd_launch(const float* dout, const float* sout, float* dpre, size_t n, hipStream_t s);
 // sigmoid backward of the [N][C][HW] head + per-channel sums of the result (the head's bias gradient) in two
 // deterministic stages; part = C * 64 floats of scratch
 int sigmoid_bwd_bias_launch(const float* dout, const float* sout, float* dpre, int N, int C, int HW, float* part, hipStream_t s, size_t p_nstride, int* chunks,
                             int group = 1);
 int sigmoid_bias_part_floats(int N, int C);   // floats of `part`: [image][segment][channel], summed by wgrad_reduce_all_launch
-int set_int_launch(int* p, int v, hipStream_t s);
-// BatchNorm running statistics of up to 3 generator calls (in call order) in one launch; see gen_kernels.hip
+// BatchNorm running statistics of up to 3 generator calls (in call order) in one launch; see gen_bn.hip
 constexpr int RUNSTAT_MAX_PLANS = 3, RUNSTAT_MAX_BN = 36;
 struct RunStatTable {
     int n_plans, n_bn;

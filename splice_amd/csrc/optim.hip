@@ -3,8 +3,6 @@
 // rule per optimiser, one launcher that validates and selects the instance.
 #include "optim.h"
 
-void splice_set_error(const char* fmt, ...);
-
 // ---- element rules.  Contraction is OFF so that the vector body and the scalar tail of the kernel round alike (an element's result
 // must not depend on where in an arena it sits: P pairs per step == P single runs, bit for bit).  USES_M / USES_V: the moment arenas
 // the rule reads and writes; the walk does not touch (or alignment-test) the others.

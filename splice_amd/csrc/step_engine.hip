@@ -27,45 +27,6 @@
 #include "kernels.h"
 #include "optim.h"
 
-void splice_set_error(const char* fmt, ...);
-extern "C" {
-int splice_vit_ctx_info(void* ctx, int* T, int* Tld, int* rows);
-int splice_vit_ctx_dims(void* ctx, int* B, int* H, int* W, int* D, int* depth, int* heads, int* patch);
-int splice_vit_ctx_set_top_cls_only(void* ctx, int on);
-int splice_vit_forward(void* ctx, const float* img, int normalize, splice_stream_t stream);
-int splice_vit_forward_ex(void* ctx, const float* img, int normalize, int grad_pass_begin, splice_stream_t stream);
-int splice_vit_get_tensor(void* ctx, int kind, int layer, void** out);
-int splice_vit_backward(void* ctx, int pass_begin, int pass_end, const float* const* d_block, const float* const* d_qkv,
-                        const float* const* d_keys, float* d_img, int normalize, splice_stream_t stream);
-int splice_gen_forward_borrowed(void* plan, const float* params, const float* x, float* y, splice_stream_t stream);
-int splice_gen_running_stats_update(void* const* plans, int n_plans, float* running, long long running_stride, float momentum,
-                                    splice_stream_t stream);
-int splice_vit_forward_passes(void* ctx, const float* img, int normalize, int grad_pass_begin, int pass_begin, int pass_end,
-                              splice_stream_t stream);
-int splice_gen_plan_dims(void* plan, int* N, int* H, int* W, long long* nparams);
-int splice_gen_plan_resize(void* plan, int H, int W);
-int splice_gen_forward(void* plan, const float* params, const float* x, float* y, splice_stream_t stream);
-int splice_gen_backward(void* plan, const float* params, const float* dy, float* grads, int accumulate, splice_stream_t stream);
-int splice_prof_active(void);
-}
-
-#define RC(x)                                                                                     \
-    do {                                                                                          \
-        int rc_ = (x);                                                                            \
-        if (rc_ != SPLICE_OK) {                                                                   \
-            splice_set_error("%s:%d %s failed (%d)", __FILE__, __LINE__, #x, rc_);                \
-            return rc_;                                                                           \
-        }                                                                                         \
-    } while (0)
-#define HIPCHK(x)                                                                                 \
-    do {                                                                                          \
-        hipError_t e_ = (x);                                                                      \
-        if (e_ != hipSuccess) {                                                                   \
-            splice_set_error("%s:%d %s -> %s", __FILE__, __LINE__, #x, hipGetErrorString(e_));    \
-            return SPLICE_ERR_HIP;                                                                \
-        }                                                                                         \
-    } while (0)
-
 enum { L_TOTAL = 0, L_GLOBAL_SSIM = 1, L_ENTIRE_SSIM = 2, L_ENTIRE_CLS = 3, L_GLOBAL_CLS = 4, L_GLOBAL_ID = 5 };
 
 struct VitView {

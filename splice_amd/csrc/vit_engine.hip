@@ -14,26 +14,6 @@
 
 #include "kernels.h"
 
-void splice_set_error(const char* fmt, ...);
-extern "C" int splice_vit_params_complete(void* vit);
-
-#define HIPCHK(x)                                                                                 \
-    do {                                                                                          \
-        hipError_t e_ = (x);                                                                      \
-        if (e_ != hipSuccess) {                                                                   \
-            splice_set_error("%s:%d %s -> %s", __FILE__, __LINE__, #x, hipGetErrorString(e_));    \
-            return SPLICE_ERR_HIP;                                                                \
-        }                                                                                         \
-    } while (0)
-#define RC(x)                                                                                     \
-    do {                                                                                          \
-        int rc_ = (x);                                                                            \
-        if (rc_ != SPLICE_OK) {                                                                   \
-            splice_set_error("%s:%d %s failed (%d)", __FILE__, __LINE__, #x, rc_);                \
-            return rc_;                                                                           \
-        }                                                                                         \
-    } while (0)
-
 // (live timing of one kernel family for the roofline leg: SpliceProfScope, prof.hip)
 
 struct Linear {

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Timing-only ablations of the generator's implicit-GEMM convolution (results are garbage): builds gen_kernels.o with -DCONV_ABL=<m> for each m
+# Timing-only ablations of the generator's implicit-GEMM convolution (results are garbage): builds gen_conv.o with -DCONV_ABL=<m> for each m
 # (0 = as shipped, 1 = no MFMA, 2 = no gather after the first channel tile, 3 = one k step per tile), links it against the other objects of the
 # current build and prints the kernel-trace averages of the conv kernels for bench.py's --image 900x1200 leg with each library.
 #   here (no GPU):   bash tools/conv_ablate.sh build "0 1 2 3"
@@ -9,10 +9,10 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -mllvm -amdgpu-mfma-vgpr-form=1 -mllvm -amdgpu-kernarg-preload-count=16 -I$ROOT/include -Wno-unused-result"
 if [ "$mode" = build ]; then
   mkdir -p $ROOT/build/abl
-  others=$(ls $ROOT/build/csrc/*.o | grep -v gen_kernels.o)
+  others=$(ls $ROOT/build/csrc/*.o | grep -v gen_conv.o)
   for m in $masks; do
-    ( /opt/rocm/bin/hipcc $FLAGS -DCONV_ABL=$m -c $ROOT/splice_amd/csrc/gen_kernels.hip -o $ROOT/build/abl/gen_kernels_$m.o &&
-      /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $ROOT/build/abl/libconv_$m.so $others $ROOT/build/abl/gen_kernels_$m.o ) &
+    ( /opt/rocm/bin/hipcc $FLAGS -DCONV_ABL=$m -c $ROOT/splice_amd/csrc/gen_conv.hip -o $ROOT/build/abl/gen_conv_$m.o &&
+      /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $ROOT/build/abl/libconv_$m.so $others $ROOT/build/abl/gen_conv_$m.o ) &
   done
   wait; ls -la $ROOT/build/abl/libconv_*.so
 else

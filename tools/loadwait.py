@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per kernel: global loads vs vmcnt waits in the gfx950 ISA (tools/isa.sh <unit> first).  A ratio near 1 means the
-loads are serialised (guarded loads each followed by a wait): python tools/loadwait.py gen_kernels"""
+loads are serialised (guarded loads each followed by a wait): python tools/loadwait.py gen_bn"""
 import re, sys
 s = open(f"/tmp/isa/{sys.argv[1]}.s").read()
 for m in re.finditer(r"^(_Z\w+):.*\n", s, re.M):
