@@ -440,6 +440,32 @@ int splice_step_set_phases(void* step, int phases, void* leader);
  * caller's buffer arena(s): layout splice_gen_buffer_info, pair p at running + p * stride.  NULL = not tracked. */
 int splice_step_set_running_stats(void* step, float* running, long long stride);
 
+/* ------------------------------------------------------------------ plateau stop rule (an extension: the reference runs a fixed n_epochs,
+ * train.py:51).  Per slot (pair) and in device memory: window means of the loss over `window` COUNTED steps (step_idx >= cls_warmup and
+ * not an entire-image step -- the steps whose loss is composed alike).  A window is better when mean < best * (1 - rel); the slot stops
+ * at the close of the `patience`-th consecutive window that is not better, if that step's index is >= min_steps.  A slot that stopped at
+ * step k is FROZEN from step k + 1 on: its parameters, optimiser moments and BatchNorm running statistics are no longer written (its
+ * work still rides in the launches, its reported losses are meaningless), and they equal, bit for bit, those of the same pair after
+ * exactly k + 1 steps without the rule.  fp32, one rounding per operation. */
+typedef struct splice_stop_state {
+    float sum;        /* of the open window's losses */
+    int count;        /* counted steps in the open window */
+    int windows;      /* windows closed */
+    float best;       /* best window mean so far (valid when windows > 0) */
+    int bad;          /* consecutive closed windows that were not better */
+    int stop_step;    /* step index the slot stopped at; -1 while it runs */
+} splice_stop_state;
+/* Switch the rule on for every pair of the handle (window > 0; 0 < rel < 1; patience >= 1; min_steps >= 0) or leave it off (window 0).
+ * Before the first splice_step_run only; refused on a handle in gradient-only (splice_step_set_mode) or phase mode
+ * (splice_step_set_phases), which the rule in turn bars.  The state starts as zeros with stop_step -1. */
+int splice_step_set_stop_rule(void* step, int window, float rel, int patience, int min_steps);
+/* copies the handle's [pairs] state records to host memory `out` (synchronises `stream`); all zero / -1 while the rule is off */
+int splice_step_stop_state(void* step, splice_stop_state* out, splice_stream_t stream);
+/* The rule alone, as the step's loss kernel runs it: one step of `pairs` slots.  state: device [pairs] records (the caller starts them
+ * as zeros with stop_step -1); losses8: device [pairs][8], element 0 of a row is the slot's loss; counted == 0: nothing happens. */
+int splice_plateau_update(splice_stop_state* state, const float* losses8, int pairs, int window, float rel, int patience, int min_steps,
+                          int step_idx, int counted, splice_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

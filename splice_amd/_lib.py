@@ -48,6 +48,10 @@ class StepConfig(C.Structure):
     ]
 
 
+class StopState(C.Structure):   # splice_stop_state
+    _fields_ = [("sum", C.c_float), ("count", C.c_int), ("windows", C.c_int), ("best", C.c_float), ("bad", C.c_int), ("stop_step", C.c_int)]
+
+
 EPI_BIAS, EPI_RESID, EPI_OUT_F32, EPI_OUT_BF, EPI_OUT_T = 1, 2, 4, 8, 16
 EPI_GELU, EPI_GELU_GRAD, EPI_COLS_F32, EPI_ALPHA, EPI_ROWDOT, EPI_SCALE_RC, EPI_OUT_F8, EPI_OUT_F8T = 32, 64, 128, 256, 512, 1024, 2048, 4096
 
@@ -140,6 +144,10 @@ _SIGNATURES = {
     "splice_step_set_pair_weights": ([_vp, _vp], _i),
     "splice_step_set_pair_lr": ([_vp, _vp], _i),
     "splice_step_set_phases": ([_vp, _i, _vp], _i),
+    # plateau stop rule
+    "splice_step_set_stop_rule": ([_vp, _i, _f, _i, _i], _i),
+    "splice_step_stop_state": ([_vp, _vp, _vp], _i),
+    "splice_plateau_update": ([_vp, _vp, _i, _i, _f, _i, _i, _i, _i, _vp], _i),
     "splice_gen_buffer_count": ([_vp], C.c_longlong),
     "splice_gen_num_buffers": ([_vp], _i),
     "splice_gen_buffer_info": ([_vp, _i, C.POINTER(C.c_char_p), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)], _i),

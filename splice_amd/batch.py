@@ -17,7 +17,11 @@ Layout::
     root/<pair name>/A/<image>      structure image      (what ``train_model(dataroot)`` expects as dataroot)
     root/<pair name>/B/<image>      appearance image
     root/<pair name>/out/output.png written by the run
-    root/<pair name>/out/result.json {"pair", "gpu", "steps", "loss", "seconds", ...}
+    root/<pair name>/out/result.json {"pair", "gpu", "steps", "loss", "seconds", "steps_run", "stopped_at", ...}
+
+``--set stop_window=W`` (with ``stop_rel`` / ``stop_patience`` / ``stop_min_steps``) switches the plateau stop rule on: a pair ends when its
+window-mean loss stops improving; ``stopped_at`` is the step index it stopped at (null: it ran every step), ``steps_run`` the steps that
+updated it.  A group or a sweep ends when all of its slots have stopped; a loss reported for a slot behind its stop step means nothing.
 
     python -m splice_amd.batch --root pairs/ --gpus 8 [--pairs-per-gpu P] [--n_epochs 2000] [--set key=value ...]
 
@@ -67,6 +71,12 @@ def work_items(sizes, pairs_per_gpu=1):
     return sorted(items, key=lambda it: (-cost(it), it[0]))
 
 
+def _stop_fields(eng, slot=None):
+    """``steps_run`` (steps that updated the slot) and ``stopped_at`` (the step index the plateau stop rule stopped it at, or None)."""
+    at = eng.stopped_at if slot is None else eng.stopped_at[slot]
+    return {"steps_run": eng.step_idx + 1 if at is None else at + 1, "stopped_at": at}
+
+
 def train_runner(pair_dir, overrides):
     """Default runner: the drop-in ``train_model`` on the pair's directory."""
     from .train import train_model
@@ -74,7 +84,7 @@ def train_runner(pair_dir, overrides):
     eng = train_model(pair_dir, cfg_overrides=overrides, progress=False)
     import torch
     torch.cuda.synchronize()
-    return {"steps": eng.step_idx + 1, "loss": eng.losses()["loss"], "seconds": round(time.perf_counter() - t0, 3)}
+    return {"steps": eng.step_idx + 1, "loss": eng.losses()["loss"], "seconds": round(time.perf_counter() - t0, 3), **_stop_fields(eng)}
 
 
 def train_group_runner(pair_dirs, overrides):
@@ -85,7 +95,7 @@ def train_group_runner(pair_dirs, overrides):
     import torch
     torch.cuda.synchronize()
     dt = round(time.perf_counter() - t0, 3)
-    return [{"steps": eng.step_idx + 1, "loss": d["loss"], "seconds": dt, "pairs_in_step": len(pair_dirs)} for d in eng.losses()]
+    return [{"steps": eng.step_idx + 1, "loss": d["loss"], "seconds": dt, "pairs_in_step": len(pair_dirs), **_stop_fields(eng, p)} for p, d in enumerate(eng.losses())]
 
 
 def train_sweep_runner(pair_dir, overrides, variants):
@@ -97,7 +107,7 @@ def train_sweep_runner(pair_dir, overrides, variants):
     torch.cuda.synchronize()
     losses = eng.losses()
     return {"steps": eng.step_idx + 1, "seconds": round(time.perf_counter() - t0, 3),
-            "variants": [{"index": k, "overrides": v, "loss": d["loss"], "losses": d} for k, (v, d) in enumerate(zip(variants, losses))]}
+            "variants": [{"index": k, "overrides": v, "loss": d["loss"], "losses": d, **_stop_fields(eng, k)} for k, (v, d) in enumerate(zip(variants, losses))]}
 
 
 def sweep_variants(specs):

@@ -1,6 +1,7 @@
 // Train-mode BatchNorm (+ LeakyReLU) of the generator, forward and backward, in four kernel forms by plane size (bn_form), and the
 // running-statistics update (see gen_conv.hip for the family overview).
 #include "gen_device.h"
+#include "plateau.h"
 #include <atomic>
 #include <cstdlib>
 
@@ -1189,13 +1190,20 @@ int bn_bwd_launch(const BnArgs& a, hipStream_t s) {
 // BatchNorm of up to RUNSTAT_MAX_PLANS generator calls IN CALL ORDER: thread (bn, channel) walks the plans in order (the
 // updates of one buffer do not commute exactly), and the images of a plan in order unless they are independent
 // generators (blockIdx.y = image = its own buffer arena).  var_unbiased is rebuilt from the saved rstd.
-__global__ __launch_bounds__(256) void bn_running_update_kernel(RunStatTable t, float* __restrict__ running, size_t r_nstride, float momentum, float eps) {
+// MASKED (the plateau stop rule, plateau.h): the buffer arena of a slot that is frozen at this step (index *mask_step - 1) is not
+// touched.  The slot is the arena: blockIdx.y for independent images and for grouped plans (t.N counts a grouped plan's groups, so
+// this is image / group size), 0 for a plan that is one generator.
+template <bool MASKED>
+__global__ __launch_bounds__(256) void bn_running_update_kernel(RunStatTable t, float* __restrict__ running, size_t r_nstride, float momentum, float eps,
+                                                                const splice_stop_state* __restrict__ mask, const int* __restrict__ mask_step) {
     const int bn = blockIdx.x, c = threadIdx.x;
     if (c >= t.C[bn]) return;
+    const int step_idx = MASKED ? *mask_step - 1 : 0;
     for (int p = 0; p < t.n_plans; ++p) {
         const bool indep = t.indep[p] != 0;
         if (indep && (int)blockIdx.y >= t.N[p]) continue;
         if (!indep && blockIdx.y != 0) continue;
+        if (MASKED && stop_frozen(mask + (indep ? blockIdx.y : 0), step_idx)) continue;
         const int n_lo = indep ? blockIdx.y : 0, n_hi = indep ? blockIdx.y + 1 : t.N[p];
         const int step = t.img_step[p] > 1 ? t.img_step[p] : 1;   // grouped plans: update n reads the statistics of its group's first image
         float* arena = running + (indep ? (size_t)blockIdx.y * r_nstride : 0) + t.r_off[bn];
@@ -1209,9 +1217,11 @@ __global__ __launch_bounds__(256) void bn_running_update_kernel(RunStatTable t, 
         }
     }
 }
-int bn_running_update_launch(const RunStatTable& t, float* running, size_t r_nstride, float momentum, float eps, int max_images, hipStream_t s) {
-    if (t.n_plans < 1 || t.n_plans > RUNSTAT_MAX_PLANS || t.n_bn < 1 || t.n_bn > RUNSTAT_MAX_BN) return SPLICE_ERR_ARG;
+int bn_running_update_launch(const RunStatTable& t, float* running, size_t r_nstride, float momentum, float eps, int max_images, hipStream_t s,
+                             const splice_stop_state* mask, const int* mask_step) {
+    if (t.n_plans < 1 || t.n_plans > RUNSTAT_MAX_PLANS || t.n_bn < 1 || t.n_bn > RUNSTAT_MAX_BN || (mask && !mask_step)) return SPLICE_ERR_ARG;
     // one thread per channel: the concat BatchNorm of an architecture within arch_check has up to 128 + 128 = 256 channels
-    SPLICE_LAUNCH(bn_running_update_kernel, dim3(t.n_bn, max_images), dim3(256), 0, s, t, running, r_nstride, momentum, eps);
+    if (mask) SPLICE_LAUNCH(bn_running_update_kernel<true>, dim3(t.n_bn, max_images), dim3(256), 0, s, t, running, r_nstride, momentum, eps, mask, mask_step);
+    else SPLICE_LAUNCH(bn_running_update_kernel<false>, dim3(t.n_bn, max_images), dim3(256), 0, s, t, running, r_nstride, momentum, eps, mask, mask_step);
     return SPLICE_OK;
 }

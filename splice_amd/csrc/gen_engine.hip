@@ -601,6 +601,11 @@ int splice_gen_buffer_info(void* h, int i, const char** name, long long* offset,
 }
 int splice_gen_running_stats_update(void* const* plans, int n_plans, float* running, long long running_stride, float momentum,
                                     splice_stream_t stream) {
+    return gen_running_stats_update(plans, n_plans, running, running_stride, momentum, nullptr, nullptr, (hipStream_t)stream);
+}
+}   // extern "C"
+int gen_running_stats_update(void* const* plans, int n_plans, float* running, long long running_stride, float momentum, const splice_stop_state* mask,
+                             const int* mask_step, hipStream_t stream) {
     if (!plans || n_plans < 1 || n_plans > RUNSTAT_MAX_PLANS || !running) return SPLICE_ERR_ARG;
     RunStatTable t = {};
     t.n_plans = n_plans; t.n_bn = 6 * ((SpliceGenPlan*)plans[0])->gen->arch.n_scales;
@@ -620,9 +625,10 @@ int splice_gen_running_stats_update(void* const* plans, int n_plans, float* runn
                 ++bn;
             }
     }
-    RC(bn_running_update_launch(t, running, (size_t)running_stride, momentum, BN_EPS, max_images, (hipStream_t)stream));
+    RC(bn_running_update_launch(t, running, (size_t)running_stride, momentum, BN_EPS, max_images, stream, mask, mask_step));
     return SPLICE_OK;
 }
+extern "C" {
 
 void splice_gen_plan_destroy(void* plan) {
     SpliceGenPlan* p = (SpliceGenPlan*)plan;

@@ -164,4 +164,9 @@ struct RunStatTable {
     const float* mean[RUNSTAT_MAX_PLANS][RUNSTAT_MAX_BN];   // [N][C] batch statistics saved by the forward
     const float* rstd[RUNSTAT_MAX_PLANS][RUNSTAT_MAX_BN];
 };
-int bn_running_update_launch(const RunStatTable& t, float* running, size_t r_nstride, float momentum, float eps, int max_images, hipStream_t s);
+// mask / mask_step (optional, the plateau stop rule): the arena of a slot frozen at step *mask_step - 1 is left alone
+int bn_running_update_launch(const RunStatTable& t, float* running, size_t r_nstride, float momentum, float eps, int max_images, hipStream_t s,
+                             const splice_stop_state* mask = nullptr, const int* mask_step = nullptr);
+// splice_gen_running_stats_update with that mask (gen_engine.hip; the step engine's bookkeeping)
+int gen_running_stats_update(void* const* plans, int n_plans, float* running, long long running_stride, float momentum, const splice_stop_state* mask,
+                             const int* mask_step, hipStream_t s);

@@ -16,5 +16,10 @@ struct OptimArgs {
     int step;              // Adam's step count (>= 1); the bias corrections are then computed on the host ...
     const int* step_dev;   // ... unless this is set: the count is read, and they are computed, on the device (graph replay)
     int zero_grad;
+    // optional (the plateau stop rule, plateau.h): [slots] records; a slot that is frozen at step *mask_step - 1 is skipped entirely.
+    // Element i belongs to slot i / mask_stride (a multiple of 4); mask_stride 0: the one arena is slot 0.
+    const splice_stop_state* mask = nullptr;
+    const int* mask_step = nullptr;   // device: step index + 1 (the step's Adam count)
+    size_t mask_stride = 0;
 };
 int optim_launch(const OptimArgs& a, hipStream_t s);

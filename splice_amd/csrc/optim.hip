@@ -2,6 +2,7 @@
 // configures them, plus optimizer.zero_grad (train.py:56) when zero_grad != 0.  One walk over the arena (optim_kernel), one element
 // rule per optimiser, one launcher that validates and selects the instance.
 #include "optim.h"
+#include "plateau.h"
 
 // ---- element rules.  Contraction is OFF so that the vector body and the scalar tail of the kernel round alike (an element's result
 // must not depend on where in an arena it sits: P pairs per step == P single runs, bit for bit).  USES_M / USES_V: the moment arenas
@@ -59,10 +60,22 @@ struct SgdRule {
 // behind the preloaded 16 and cost one scalar load at the kernel's head (SGD +0.3 us, RMSprop +0.1 us per launch at one pair, nothing
 // measurable at eight).  Argument lists of their own need the walk in an inlined function, which the compiler
 // schedules differently (the per-pair-lr instances then take 1-2 VGPRs more than before): not done.
-template <class Rule, bool PAIR_LR>
+// MASKED (the plateau stop rule): element i belongs to slot i / mask_stride (mask_stride 0: the one arena is slot 0), and the elements
+// of a slot that is frozen at this step (stop_frozen; the step index is *mask_step - 1) are SKIPPED: no write to p, m or v, and no
+// write-back of g either -- neither the g += g2 sum nor zero_grad.  A frozen slot's gradient arena may therefore hold anything
+// (the sum of an earlier step, this step's backward output): nothing reads it, the next step's backward overwrites it.  The three
+// arguments lie behind the existing list; the instances without MASKED do not read them and compile to what they were (same
+// VGPR / SGPR counts, no scratch).
+template <class Rule, bool PAIR_LR, bool MASKED>
 __global__ void optim_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, size_t n, float lr,
                              float hp0, float hp1, float eps, float bc1, float bc2_sqrt, int zero_grad, const int* __restrict__ step_ptr,
-                             const float* __restrict__ g2, const float* __restrict__ lr_ptr, unsigned lr_stride) {
+                             const float* __restrict__ g2, const float* __restrict__ lr_ptr, unsigned lr_stride,
+                             const splice_stop_state* __restrict__ mask, const int* __restrict__ mask_step, unsigned mask_stride) {
+    int step_idx = 0;
+    if (MASKED) {
+        step_idx = *mask_step - 1;
+        if (!mask_stride && stop_frozen(mask, step_idx)) return;
+    }
     if (!PAIR_LR && lr_ptr) lr = *lr_ptr;   // learning rate on the device (a schedule under graph replay); null: the argument
     if (step_ptr) {   // Adam's step count lives on the device (graph replay): bias corrections computed here
         const float t = (float)*step_ptr;
@@ -71,11 +84,12 @@ __global__ void optim_kernel(float* __restrict__ p, float* __restrict__ g, float
     }
     const Rule rule(hp0, hp1, eps, bc1, bc2_sqrt);
     auto upd = [&](float& pi, float& gi, float& mi, float& vi, float g2i) { rule.update(pi, gi, mi, vi, g2i, g2 != nullptr, lr, zero_grad); };
-    const unsigned lr_stride4 = lr_stride / 4;
+    const unsigned lr_stride4 = lr_stride / 4, mask_stride4 = mask_stride / 4;
     const size_t align = reinterpret_cast<size_t>(p) | reinterpret_cast<size_t>(g) | (Rule::USES_M ? reinterpret_cast<size_t>(m) : 0) |
                          (Rule::USES_V ? reinterpret_cast<size_t>(v) : 0) | reinterpret_cast<size_t>(g2);
     const size_t n4 = (align & 15) ? 0 : n / 4;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+        if (MASKED && mask_stride && stop_frozen(mask + (unsigned)i / mask_stride4, step_idx)) continue;
         float4 pv = reinterpret_cast<float4*>(p)[i], gv = reinterpret_cast<float4*>(g)[i], mv = {}, vv = {};
         if (Rule::USES_M) mv = reinterpret_cast<float4*>(m)[i];
         if (Rule::USES_V) vv = reinterpret_cast<float4*>(v)[i];
@@ -88,6 +102,7 @@ __global__ void optim_kernel(float* __restrict__ p, float* __restrict__ g, float
         if (g2 || zero_grad) reinterpret_cast<float4*>(g)[i] = gv;
     }
     for (size_t i = n4 * 4 + (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        if (MASKED && mask_stride && stop_frozen(mask + (unsigned)i / mask_stride, step_idx)) continue;
         float pi = p[i], gi = g[i], mi = 0.f, vi = 0.f;
         if (Rule::USES_M) mi = m[i];
         if (Rule::USES_V) vi = v[i];
@@ -105,9 +120,10 @@ static unsigned optim_grid(size_t n) {
 }
 
 int optim_launch(const OptimArgs& a, hipStream_t s) {
-    static constexpr decltype(&optim_kernel<AdamRule, false>) kernels[3][2] = {{optim_kernel<AdamRule, false>, optim_kernel<AdamRule, true>},
-                                                                               {optim_kernel<RmspropRule, false>, optim_kernel<RmspropRule, true>},
-                                                                               {optim_kernel<SgdRule, false>, optim_kernel<SgdRule, true>}};
+#define OPTIM_INSTANCES(Rule) {{optim_kernel<Rule, false, false>, optim_kernel<Rule, false, true>}, {optim_kernel<Rule, true, false>, optim_kernel<Rule, true, true>}}
+    static constexpr decltype(&optim_kernel<AdamRule, false, false>) kernels[3][2][2] = {OPTIM_INSTANCES(AdamRule), OPTIM_INSTANCES(RmspropRule),
+                                                                                         OPTIM_INSTANCES(SgdRule)};   // [kind][PAIR_LR][MASKED]
+#undef OPTIM_INSTANCES
     if (a.kind < SPLICE_OPT_ADAM || a.kind > SPLICE_OPT_SGD) {
         splice_set_error("optimiser: unknown optimiser kind %d", a.kind);
         return SPLICE_ERR_ARG;
@@ -119,20 +135,25 @@ int optim_launch(const OptimArgs& a, hipStream_t s) {
         splice_set_error("optimiser: per-pair lr needs a device lr table, an arena stride that is a multiple of 4 and < 2^32 elements");
         return SPLICE_ERR_ARG;
     }
+    // a masked update indexes the state records with a 32-bit element index too
+    if (a.mask && (!a.mask_step || a.mask_stride % 4 || a.n > 0xFFFFFFFFull || a.mask_stride > 0xFFFFFFFFull || (a.lr_stride && a.mask_stride != a.lr_stride))) {
+        splice_set_error("optimiser: a masked update needs the device step count, a slot stride that is a multiple of 4 (the per-pair lr stride where both are set) and < 2^32 elements");
+        return SPLICE_ERR_ARG;
+    }
     // a host step count: the bias corrections come from the HOST's powf (host and device powf need not agree to the bit, so a caller
     // stays with the form it has)
     const float bc1 = host_step ? 1.0f - powf(a.hp0, (float)a.step) : 1.f;
     const float bc2_sqrt = host_step ? sqrtf(1.0f - powf(a.hp1, (float)a.step)) : 1.f;
-    const auto kernel = kernels[a.kind][a.lr_stride != 0];
+    const auto kernel = kernels[a.kind][a.lr_stride != 0][a.mask != nullptr];
     SPLICE_LAUNCH(kernel, dim3(optim_grid(a.n)), dim3(256), 0, s, a.p, a.g, a.m, a.v, a.n, a.lr, a.hp0, a.hp1, a.eps, bc1, bc2_sqrt, a.zero_grad,
-                  adam ? a.step_dev : nullptr, a.g2, a.lr_dev, (unsigned)a.lr_stride);
+                  adam ? a.step_dev : nullptr, a.g2, a.lr_dev, (unsigned)a.lr_stride, a.mask, a.mask_step, (unsigned)a.mask_stride);
     return SPLICE_OK;
 }
 
 // ---- exports (include/splice_hip.h): fillers of OptimArgs
 static OptimArgs optim_args(int kind, float* params, float* grads, const float* g2, float* m, float* v, long long n, float lr, const float* lr_dev,
                             size_t lr_stride, float hp0, float hp1, float eps, int step, int zero_grad) {
-    return OptimArgs{kind, params, grads, g2, m, v, n < 1 ? 0 : (size_t)n, lr, lr_dev, lr_stride, hp0, hp1, eps, step, nullptr, zero_grad};
+    return OptimArgs{kind, params, grads, g2, m, v, n < 1 ? 0 : (size_t)n, lr, lr_dev, lr_stride, hp0, hp1, eps, step, nullptr, zero_grad, nullptr, nullptr, 0};
 }
 extern "C" {
 int splice_adam_step(float* params, float* grads, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps, int step,

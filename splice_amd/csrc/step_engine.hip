@@ -21,6 +21,7 @@
 #include "gen_kernels.h"
 #include "kernels.h"
 #include "optim.h"
+#include "plateau.h"
 #include "step_graph.h"
 
 // The loss terms.  L_*: slot of a term in the losses buffer, and the order of total_loss_kernel's five weights.  LAM_*: column of a term in
@@ -111,6 +112,10 @@ struct SpliceStep {
     long long running_stride = 0;
     int phases = 7;              // splice_step_set_phases: 1 generator forward, 2 ViT forward / losses / ViT backward, 4 generator backward (+ Adam)
     SpliceStep* leader = nullptr;   // the handle whose staged inputs / generator outputs this one reads and whose image gradients it adds to
+    // the plateau stop rule (splice_step_set_stop_rule; plateau.h): [pairs] state records on the device, allocated at creation (zeros, stop_step -1)
+    splice_stop_state* stop = nullptr;
+    StopRule stop_rule = {0, 0.f, 0, 0};   // window 0: off -- the step launches what it always did
+    int runs = 0;                          // splice_step_run calls so far (the rule is set before the first)
 };
 
 static size_t arena_floats(const SpliceStep* st) { return st->astride ? st->pairs * st->astride : (size_t)st->nparams; }   // of all pairs' arenas
@@ -162,9 +167,13 @@ static int view_init(SpliceStep* st, VitView& v, void* ctx, int want_B) {
 // term's images, added in crop order (util/losses.py:75-82 `loss +=`); one pair: n_a = n_b = n_c = n_e = the slot count.
 // wtab (optional, [pairs][5] in the order of splice_step_set_pair_weights): per-pair lambdas in place of the five weights, gated as the
 // scalar weights are (ssim_on: global structure and identity; entire: the two entire-image terms)
+// MONITOR (the plateau stop rule, plateau.h): thread 0 then runs the rule for its pair on the total it has just written, on counted steps
+// -- ssim_on && !entire, both baked per graph variant -- with the step index read from dev_t (step_idx + 1: a replayed graph sees its own
+// step).  The instance without MONITOR does not read the three trailing arguments: its code is what it was.
+template <bool MONITOR>
 __global__ __launch_bounds__(320) void total_loss_kernel(float* lbase, size_t lstride, int lp, float w_ssim, float w_essim, float w_ecls, float w_cls,
                                                          float w_id, float* out8, int n_a, int n_b, int n_c, int n_e, const float* wtab, int ssim_on,
-                                                         int entire) {
+                                                         int entire, splice_stop_state* stop, const int* dev_t, StopRule rule) {
     __shared__ float raw[8];
     float* l = lbase + (size_t)blockIdx.x * lstride;
     const int k = 1 + (threadIdx.x >> 6), lane = threadIdx.x & 63;   // wave k-1 owns term k (5 waves)
@@ -197,7 +206,18 @@ __global__ __launch_bounds__(320) void total_loss_kernel(float* lbase, size_t ls
             for (int t = 1; t <= 5; ++t) o[t] = raw[t];
             o[6] = 0.f; o[7] = 0.f;
         }
+        if (MONITOR && ssim_on && !entire) plateau_update(stop + blockIdx.x, l[L_TOTAL], rule, *dev_t - 1);
     }
+}
+// the rule alone on a caller's [pairs][8] losses (splice_plateau_update): one thread per slot
+__global__ __launch_bounds__(64) void plateau_update_kernel(splice_stop_state* stop, const float* losses8, int pairs, StopRule rule, int step_idx) {
+    const int p = blockIdx.x * 64 + threadIdx.x;
+    if (p < pairs) plateau_update(stop + p, losses8[(size_t)p * 8], rule, step_idx);
+}
+static bool stop_rule_ok(int window, float rel, int patience, int min_steps, const char* who) {
+    if (window >= 0 && rel > 0.f && rel < 1.f && patience >= 1 && min_steps >= 0) return true;
+    splice_set_error("%s: needs window >= 0, 0 < rel < 1, patience >= 1 and min_steps >= 0", who);
+    return false;
 }
 // All per-step inputs in ONE eager launch in front of the graph replay (three copies + the Adam step count were four
 // launches with ~10-30 us of host/queue gaps between them): up to three fp32 buffers, one int and (fp != null) nf floats, the
@@ -391,6 +411,11 @@ int splice_step_create(const splice_step_config* cfg, void* vit_ctx_global, void
     if ((rc = salloc(st, &st->losses, P * st->lstride)) != SPLICE_OK) return rc;
     if ((rc = salloc(st, &st->dev_t, 4)) != SPLICE_OK) return rc;
     if ((rc = salloc(st, &st->dev_lr, 1)) != SPLICE_OK) return rc;
+    if ((rc = salloc(st, &st->stop, (size_t)pairs)) != SPLICE_OK) return rc;
+    {
+        const std::vector<splice_stop_state> z((size_t)pairs, splice_stop_state{0.f, 0, 0, 0.f, 0, -1});
+        if (hipMemcpy(st->stop, z.data(), z.size() * sizeof(splice_stop_state), hipMemcpyHostToDevice) != hipSuccess) return SPLICE_ERR_HIP;
+    }
     if (P > 1 && !st->crops_mode) {
         if ((rc = salloc(st, &st->dev_lrs, SPLICE_STEP_MAX_PAIR_CFGS)) != SPLICE_OK) return rc;
         if ((rc = salloc(st, &st->pw_tab_alloc, (size_t)PW_ROWS * P)) != SPLICE_OK) return rc;
@@ -455,6 +480,7 @@ int splice_step_set_crops(void* h, int a_h, int a_w, int b_h, int b_w) {
 int splice_step_set_mode(void* h, int skip_adam, int accumulate) {
     SpliceStep* st = (SpliceStep*)h;
     if (!st || (accumulate && !skip_adam)) return SPLICE_ERR_ARG;
+    if (skip_adam && st->stop_rule.window > 0) { splice_set_error("splice_step_set_mode: a handle with a stop rule runs whole steps (no gradient-only mode)"); return SPLICE_ERR_STATE; }
     if (st->skip_adam != (skip_adam ? 1 : 0) || st->accumulate != (accumulate ? 1 : 0)) st->graphs.retire();
     st->skip_adam = skip_adam ? 1 : 0; st->accumulate = accumulate ? 1 : 0;
     return SPLICE_OK;
@@ -538,9 +564,41 @@ int splice_step_set_pair_lr(void* h, const float* lr) {
 int splice_step_set_phases(void* h, int phases, void* leader) {
     SpliceStep* st = (SpliceStep*)h;
     if (!st || phases <= 0 || phases > 7 || leader == h || (leader && phases != 2) || (leader && ((SpliceStep*)leader)->leader)) return SPLICE_ERR_ARG;
+    if ((phases != 7 || leader) && st->stop_rule.window > 0) { splice_set_error("splice_step_set_phases: a handle with a stop rule runs whole steps (no phase mode)"); return SPLICE_ERR_STATE; }
     if (st->leader != (SpliceStep*)leader) st->graphs.retire();
     st->phases = phases;
     st->leader = (SpliceStep*)leader;
+    return SPLICE_OK;
+}
+
+// The plateau stop rule of every pair of the handle (plateau.h; include/splice_hip.h has the rule).  Before the first step only: the state
+// records belong to a run from step 0.  Not on a gradient-only or phase-mode handle: the update the rule freezes is not this handle's.
+int splice_step_set_stop_rule(void* h, int window, float rel, int patience, int min_steps) {
+    SpliceStep* st = (SpliceStep*)h;
+    if (!st) return SPLICE_ERR_ARG;
+    if (!stop_rule_ok(window, rel, patience, min_steps, "splice_step_set_stop_rule")) return SPLICE_ERR_ARG;
+    if (st->runs > 0) { splice_set_error("splice_step_set_stop_rule: the rule is set before the first step"); return SPLICE_ERR_STATE; }
+    if (st->skip_adam || st->phases != 7 || st->leader) {
+        splice_set_error("splice_step_set_stop_rule: not on a handle in gradient-only (splice_step_set_mode) or phase mode (splice_step_set_phases)");
+        return SPLICE_ERR_STATE;
+    }
+    if ((window > 0) != (st->stop_rule.window > 0)) st->graphs.retire();
+    st->stop_rule = StopRule{window, rel, patience, min_steps};
+    return SPLICE_OK;
+}
+int splice_step_stop_state(void* h, splice_stop_state* out, splice_stream_t stream) {
+    SpliceStep* st = (SpliceStep*)h;
+    if (!st || !out) return SPLICE_ERR_ARG;
+    HIPCHK(hipMemcpyAsync(out, st->stop, (size_t)st->pairs * sizeof(splice_stop_state), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    return SPLICE_OK;
+}
+int splice_plateau_update(splice_stop_state* state, const float* losses8, int pairs, int window, float rel, int patience, int min_steps, int step_idx,
+                          int counted, splice_stream_t stream) {
+    if (!state || !losses8 || pairs < 1 || step_idx < 0) return SPLICE_ERR_ARG;
+    if (!stop_rule_ok(window, rel, patience, min_steps, "splice_plateau_update")) return SPLICE_ERR_ARG;
+    if (!counted || window == 0) return SPLICE_OK;
+    SPLICE_LAUNCH(plateau_update_kernel, dim3((pairs + 63) / 64), dim3(64), 0, (hipStream_t)stream, state, losses8, pairs, StopRule{window, rel, patience, min_steps}, step_idx);
     return SPLICE_OK;
 }
 
@@ -680,20 +738,23 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
     }
     // The reported loss values and the BatchNorm running statistics (reference's call order) depend on nothing downstream: with a side
     // stream they run at the tail of its chain instead of between the generator backward and Adam on the critical one, else at the end.
+    const bool stop_on = st->stop_rule.window > 0;   // the plateau stop rule: monitor in the loss kernel, frozen slots masked out of the two updates
     auto bookkeeping = [&](hipStream_t q) -> int {
         if (do_v) {
             // slots per pair and term: 1 (pairs mode); the slot count for every term (one pair with n_crops: unused slots hold zeros); the
             // term's crops per pair (several pairs with n_crops)
             const bool grouped = st->crops_mode && pairs > 1;
             const int n1 = st->crops_mode ? P : 1;
-            SPLICE_LAUNCH(total_loss_kernel, dim3(pairs), dim3(320), 0, q, st->losses, st->lstride, (int)st->lp, t[L_GLOBAL_SSIM].lambda, t[L_ENTIRE_SSIM].lambda,
+            const auto kernel = stop_on ? total_loss_kernel<true> : total_loss_kernel<false>;   // (the rule rides in the launch: no node more)
+            SPLICE_LAUNCH(kernel, dim3(pairs), dim3(320), 0, q, st->losses, st->lstride, (int)st->lp, t[L_GLOBAL_SSIM].lambda, t[L_ENTIRE_SSIM].lambda,
                           t[L_ENTIRE_CLS].lambda, t[L_GLOBAL_CLS].lambda, t[L_GLOBAL_ID].lambda, st->losses_out, grouped ? st->na : n1, grouped ? st->nb : n1, grouped ? nc : n1,
-                          grouped ? 1 : n1, st->pw ? st->pw + (size_t)PW_LAMBDAS * P : nullptr, (int)ssim_on, (int)entire);
+                          grouped ? 1 : n1, st->pw ? st->pw + (size_t)PW_LAMBDAS * P : nullptr, (int)ssim_on, (int)entire, st->stop, st->dev_t, st->stop_rule);
         }
         if (!st->running || !gen_fwd) return SPLICE_OK;
         void* plans[3] = {st->plan_a, st->plan_b, nullptr};
         if (entire) { plans[1] = st->plan_e; plans[2] = st->plan_b; }   // (A_global, A on entire steps, B_global)
-        return splice_gen_running_stats_update(plans, entire ? 3 : 2, st->running, st->running_stride, 0.1f, q);
+        // (a slot that stops at THIS step is not frozen yet: the order against the loss kernel above does not matter)
+        return gen_running_stats_update(plans, entire ? 3 : 2, st->running, st->running_stride, 0.1f, stop_on ? st->stop : nullptr, st->dev_t, q);
     };
     // ---- backward (train.py:78): ViT dgrad for the generated images only, then the generator
     // the x' and y' passes are independent chains until the generator: one per stream (every launch of a
@@ -733,6 +794,7 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
         // per-pair lrs (splice_step_set_pair_lr): pair p's arena reads dev_lrs[p]
         a.lr_dev = st->pair_lr ? st->dev_lrs : st->lr_set ? st->dev_lr : nullptr;
         a.lr_stride = st->pair_lr ? st->astride : 0;
+        if (stop_on) { a.mask = st->stop; a.mask_step = st->dev_t; a.mask_stride = st->astride; }
         RC(optim_launch(a, s));
     }
     return SPLICE_OK;
@@ -756,6 +818,7 @@ int splice_step_run(void* h, float* params, float* grads, float* m, float* v, co
     const splice_step_config& c = st->cfg;
     const int P = st->P;
     st->ev_slot = (st->ev_slot + 1) % SpliceStep::EV_RING;   // this call's set of cross-stream events
+    ++st->runs;
     // ---- lambda schedule (util/losses.py:34-44)
     if (step_idx == c.cls_warmup) st->ssim_id_on = 1;
     const bool entire = c.ent_h > 0 && c.entire_every > 0 && (step_idx % c.entire_every == 0);
@@ -835,7 +898,10 @@ int splice_step_run(void* h, float* params, float* grads, float* m, float* v, co
             }
             // several pairs with n_crops: the layout is part of the pool key (other keys unchanged)
             const bool grouped = st->crops_mode && st->pairs > 1;
-            ex = st->graphs.adopt(variant, g, grouped ? ((unsigned long long)st->pairs << 32) | ((unsigned long long)st->na << 16) | (unsigned long long)st->nb : 0);
+            // ... and so is the stop rule: its loss-kernel and update nodes are other kernels than those of a handle without it
+            const unsigned long long salt = (grouped ? ((unsigned long long)st->pairs << 32) | ((unsigned long long)st->na << 16) | (unsigned long long)st->nb : 0) |
+                                            (st->stop_rule.window > 0 ? 1ull << 63 : 0);
+            ex = st->graphs.adopt(variant, g, salt);
             if (!ex) return SPLICE_ERR_HIP;
         }
         HIPCHK(hipGraphLaunch(ex, s));

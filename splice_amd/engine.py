@@ -24,7 +24,9 @@ DEFAULT_CFG = dict(  # conf/default/config.yaml of the reference
     dino_model_name="dino_vitb8", dino_global_patch_size=224,
     cls_warmup=1, n_epochs=10000, scheduler_policy="none",
     optimizer="adam", optimizer_beta1=0.0, optimizer_beta2=0.99, lr=0.002,
-    log_images_freq=10)
+    log_images_freq=10,
+    # extensions (absent from the reference's config): the plateau stop rule, off by default
+    stop_window=0, stop_rel=0.01, stop_patience=2, stop_min_steps=0)
 
 
 # Per-slot keys of a sweep (MultiPairEngine(pair_cfgs=...), train.train_sweep): the five loss weights in the order of
@@ -36,6 +38,43 @@ PAIR_INIT_KEYS = ("seed", "init_type", "init_gain")
 PAIR_KEYS = PAIR_LAMBDA_KEYS + PAIR_LR_KEYS + PAIR_INIT_KEYS
 MAX_PAIR_CFGS = 32   # SPLICE_STEP_MAX_PAIR_CFGS
 MAX_GROUP_IMAGES = 32   # SPLICE_STEP_MAX_GROUP_IMAGES: images per side (pairs x n_crops) of several pairs with n_crops > 1
+
+
+def stop_rule(c):
+    """``(window, rel, patience, min_steps)`` of the plateau stop rule in config ``c``, checked on the host:
+    ``stop_window >= 0`` (0: the rule is off), ``0 < stop_rel < 1``, ``stop_patience >= 1``, ``stop_min_steps >= 0``.  Raises
+    ValueError naming the key."""
+    def integer(key, lo):
+        v = c.get(key, DEFAULT_CFG[key])
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo:
+            raise ValueError(f"'{key}' must be an integer >= {lo}, got {v!r}")
+        return int(v)
+    rel = c.get("stop_rel", DEFAULT_CFG["stop_rel"])
+    if isinstance(rel, bool) or not isinstance(rel, (int, float, np.floating)) or not 0 < rel < 1:
+        raise ValueError(f"'stop_rel' must be a number in (0, 1), got {rel!r}")
+    return integer("stop_window", 0), float(rel), integer("stop_patience", 1), integer("stop_min_steps", 0)
+
+
+def counted_steps(step_idx, cls_warmup, entire_every=0):
+    """Steps among 0 .. ``step_idx`` that the stop rule counts: ``step >= cls_warmup`` and not an entire-image step
+    (``step % entire_every == 0``; ``entire_every`` 0: the engine has no entire-image branch).  These are the steps whose loss is
+    composed alike."""
+    w, e = int(cls_warmup), int(entire_every)
+    if step_idx < w or step_idx < 0:
+        return 0
+    lo = max(w, 0)
+    n = step_idx - lo + 1
+    if e > 0:
+        n -= step_idx // e - (lo - 1) // e   # multiples of e in [lo, step_idx]
+    return n
+
+
+def stop_window_closes(step_idx, window, cls_warmup, entire_every=0):
+    """True when step ``step_idx`` is counted and closes a window of ``window`` counted steps (host arithmetic only)."""
+    if window <= 0 or step_idx < 0:
+        return False
+    n = counted_steps(step_idx, cls_warmup, entire_every)
+    return n > counted_steps(step_idx - 1, cls_warmup, entire_every) and n % window == 0
 
 
 def _entire_branch(c):
@@ -106,6 +145,7 @@ class MultiPairEngine:
         init keys are the caller's business), checked by ``merge_pair_cfgs``.  Slot p then runs, bit for bit, as a
         ``SpliceEngine`` with ``cfgs[p]`` would; ``lr`` becomes a list of P values."""
         self.cfg = dict(DEFAULT_CFG, **cfg)
+        self.stop_rule = stop_rule(self.cfg)   # (host checks first: nothing below this line has touched a GPU yet)
         P_in = len(gen_states)
         self.cfgs = [self.cfg] * P_in
         self._pair_lambdas = self._pair_lr = False
@@ -221,6 +261,11 @@ class MultiPairEngine:
         if self.opt_kind != 0:
             _lib.check(_lib.lib().splice_step_set_optimizer(self.handle, self.opt_kind, *self.opt_hp), "step_set_optimizer")
         _lib.check(_lib.lib().splice_step_set_running_stats(self.handle, _lib.ptr(self.running), self.running.stride(0)), "step_set_running_stats")
+        # the plateau stop rule (shared by the slots; decided per slot on the device): before the first step
+        if self.stop_rule[0] > 0:
+            _lib.check(_lib.lib().splice_step_set_stop_rule(self.handle, *self.stop_rule), "step_set_stop_rule")
+        self._stopped = [None] * P   # the host's copy of every slot's stop step, refreshed by stop_state()
+        self._stop_dirty = False     # a window has closed since the last stop_state(): the copy may be behind
         if self._pair_lambdas:
             lam = (C.c_float * (5 * P))(*[float(cp[k]) for cp in self.cfgs for k in PAIR_LAMBDA_KEYS])
             _lib.check(_lib.lib().splice_step_set_pair_weights(self.handle, lam), "step_set_pair_weights")
@@ -269,7 +314,42 @@ class MultiPairEngine:
                                               _lib.ptr(self.losses_dev), _lib.current_stream()), "step_run")
         if not _repeat:
             self.generator_calls = [n + (3 if entire else 2) for n in self.generator_calls]   # models/model.py:15-23: G(A_global) [, G(A)], G(B_global)
+            if self.stop_rule[0] > 0 and self.window_closes(self.step_idx):
+                self._stop_dirty = True
         return self.losses_dev
+
+    # ---- the plateau stop rule: decided per slot on the device; the host asks only where the answer can change
+    def window_closes(self, step_idx):
+        """True when step ``step_idx`` closes a window of the stop rule (host arithmetic only): the only steps at which a slot can
+        stop, so the only ones after which ``stop_state()`` is worth a device-to-host copy."""
+        return stop_window_closes(step_idx, self.stop_rule[0], self.cfg["cls_warmup"], self.cfg["entire_A_every"] if self.plan_e is not None else 0)
+
+    def stop_state(self):
+        """One dict per slot -- ``stopped_at`` (step index, or None while the slot runs), ``windows`` closed, ``best`` window mean,
+        ``bad`` consecutive windows that were not better -- copied from the device (waits for the current stream)."""
+        rec = (_lib.StopState * self.P)()
+        _lib.check(_lib.lib().splice_step_stop_state(self.handle, rec, _lib.current_stream()), "step_stop_state")
+        self._stopped = [r.stop_step if r.stop_step >= 0 else None for r in rec]
+        self._stop_dirty = False
+        return [dict(stopped_at=k, windows=r.windows, best=r.best, bad=r.bad) for k, r in zip(self._stopped, rec)]
+
+    def _stops(self):
+        if self._stop_dirty:   # (asks the device only if a window closed since the last answer)
+            self.stop_state()
+        return self._stopped
+
+    @property
+    def stopped_at(self):
+        """Per slot: the step index it stopped at, or None."""
+        return list(self._stops())
+
+    def all_stopped(self):
+        """Every slot has stopped (never true with the rule off)."""
+        return self.stop_rule[0] > 0 and all(k is not None for k in self._stops())
+
+    def _frozen(self, pair):
+        k = self._stops()[pair] if self.stop_rule[0] > 0 else None
+        return k is not None and self.step_idx > k
 
     def losses(self, pair=None):
         """Host dict(s) of the last step's losses with the reference's keys (inactive terms omitted): one dict for ``pair``,
@@ -319,6 +399,8 @@ class MultiPairEngine:
         self._logged = []
 
     def book_running_stats(self, plan, pair=0):
+        if self._frozen(pair):   # (a slot that stopped at an earlier step: its buffers stay those of its last own step)
+            return
         plans = (C.c_void_p * 1)(plan.handle)
         _lib.check(_lib.lib().splice_gen_running_stats_update(plans, 1, _lib.ptr(self.running[pair]), 0, 0.1, _lib.current_stream()), "running_stats_update")
         self.generator_calls[pair] += 1
@@ -326,10 +408,14 @@ class MultiPairEngine:
     def state_dict(self, pair=0):
         """``netG.state_dict()`` of one pair: parameters, BatchNorm running statistics and ``num_batches_tracked``."""
         out = {k: v.clone() for k, v in self.gen.unflatten(self.pair_params(pair)).items()}
+        calls = self.generator_calls[pair]
+        if self._frozen(pair):   # the netG calls of the steps behind its stop step did not move this slot's buffers
+            step_calls = lambda k: 2 * (k + 1) + (k // int(self.cfg["entire_A_every"]) + 1 if self.plan_e is not None else 0)
+            calls -= step_calls(self.step_idx) - step_calls(self._stops()[pair])
         for name, (off, cnt) in self.gen.buffer_table.items():
             out[name] = self.running[pair, off:off + cnt].clone()
             if name.endswith("running_var"):
-                out[name[:-len("running_var")] + "num_batches_tracked"] = torch.tensor(self.generator_calls[pair], dtype=torch.long, device=self.device)
+                out[name[:-len("running_var")] + "num_batches_tracked"] = torch.tensor(calls, dtype=torch.long, device=self.device)
         return out
 
 
@@ -341,6 +427,11 @@ class SpliceEngine(MultiPairEngine):
 
     def losses(self):
         return super().losses(0)
+
+    @property
+    def stopped_at(self):
+        """The step index the pair stopped at (the plateau stop rule), or None."""
+        return self._stops()[0]
 
 
 class MultiScaleEngine:
@@ -355,6 +446,8 @@ class MultiScaleEngine:
     def __init__(self, cfg, vit_state, gen_state, crop_hw, entire_hw=None, scales=(224, 320, 448), device="cuda", vit_engine=None, n_crops=1,
                  fp8=False):
         self.cfg = dict(DEFAULT_CFG, **cfg)
+        if stop_rule(self.cfg)[0] > 0:
+            raise NotImplementedError("stop_window > 0: the plateau stop rule lives in the fused step's own update; MultiScaleEngine updates outside the step")
         self.scales = tuple(scales)
         self.engines = []
         for k, sz in enumerate(self.scales):
@@ -396,6 +489,11 @@ class MultiScaleEngine:
 
     def book_logged_forward(self):
         self.engines[0].book_logged_forward()
+
+    stopped_at = None   # (no stop rule here)
+
+    def window_closes(self, step_idx):
+        return False
 
     def state_dict(self, pair=0):
         return self.engines[0].state_dict(pair)

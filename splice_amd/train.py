@@ -198,6 +198,16 @@ def train_model(dataroot, callback=None, cfg_overrides=None, vit_state=None, pro
                     callback(output[0])
             if progress and (epoch % 50 == 0 or epoch == 1):
                 print(f"Epoch {epoch}: loss={engine.losses()['loss']:.4f} lr={engine.lr}")
+            # the plateau stop rule (stop_window > 0; decided on the device): the host asks only after a step that closes a window -- no
+            # other step can stop the pair -- and ends the run with an image of the final parameters
+            if engine.window_closes(engine.step_idx) and engine.all_stopped():
+                output = engine.generate(feed.get_A())
+                writer.submit(output[0], force=True)
+                if callback is not None:
+                    callback(output[0])
+                if progress:
+                    print(f"Epoch {epoch}: the loss has plateaued, stopping")
+                break
     finally:
         writer.close()
     return engine
@@ -233,6 +243,15 @@ class PairBatchFeed:
         sample['A_global'] = self._crops([augment.structure_transforms(a) if aug else a for a in self.A], self.cfg['global_A_crops_min_cover'], self.n_crops[0])
         sample['B_global'] = self._crops([augment.texture_transforms(b) if aug else b for b in self.B], self.cfg['global_B_crops_min_cover'], self.n_crops[1])
         return sample
+
+
+def _final_images(engine, writers, As, callback):
+    """Every slot has stopped (the plateau stop rule): one image per slot from its final parameters, always written."""
+    for p, A in enumerate(As):
+        out = engine.generate(A, pair=p)
+        writers[p].submit(out[0], force=True)
+        if callback is not None:
+            callback(p, out[0])
 
 
 def train_pairs(dataroots, callback=None, cfg_overrides=None, vit_state=None, progress=True):
@@ -304,6 +323,9 @@ def train_pairs(dataroots, callback=None, cfg_overrides=None, vit_state=None, pr
                         callback(p, out[0])
             if progress and (epoch % 50 == 0 or epoch == 1):
                 print(f"Epoch {epoch}: loss=" + ", ".join(f"{d['loss']:.4f}" for d in engine.losses()) + f" lr={engine.lr}")
+            if engine.window_closes(engine.step_idx) and engine.all_stopped():   # every pair has plateaued (see train_model)
+                _final_images(engine, writers, [feed.get_A(p) for p in range(len(dataroots))], callback)
+                break
     finally:
         for w in writers:
             w.close()
@@ -396,13 +418,16 @@ def train_sweep(dataroot, variants, cfg_overrides=None, vit_state=None, callback
                         callback(k, out[0])
             if progress and (epoch % 50 == 0 or epoch == 1):
                 print(f"Epoch {epoch}: loss=" + ", ".join(f"{d['loss']:.4f}" for d in engine.losses()) + f" lr={engine.lr}")
+            if engine.window_closes(engine.step_idx) and engine.all_stopped():   # every variant has plateaued (see train_model)
+                _final_images(engine, writers, [feed.get_A()] * K, callback)
+                break
     finally:
         for w in writers:
             w.close()
     losses = engine.losses() if engine.step_idx >= 0 else [{} for _ in range(K)]
     for k in range(K):
         with open(os.path.join(out_dirs[k], 'variant.json'), 'w') as f:
-            json.dump({"index": k, "overrides": variants[k], "seed": seeds[k], "losses": losses[k]}, f)
+            json.dump({"index": k, "overrides": variants[k], "seed": seeds[k], "losses": losses[k], "stopped_at": engine.stopped_at[k]}, f)
     return engine
 
 
