@@ -313,6 +313,13 @@ int splice_optim_step_ex(int kind, float* params, float* grads, const float* g2,
 int splice_optim_step_pairs(int kind, float* params, float* grads, const float* g2, float* m, float* v, int n_pairs, long long stride,
                             long long n, const float* lr_dev, float hp0, float hp1, float eps, int step, int zero_grad,
                             splice_stream_t stream);
+/* Weight average (an extension; the reference keeps none): as splice_optim_step_ex, plus `ema`, an arena of n floats written in the same
+ * walk behind the parameter of the element.  With p' the parameter just written and step the update's count (>= 1, for every kind):
+ * step <= ema_start: ema = p'; later ema = ema_decay * ema + (1 - ema_decay) * p' (fp32, one rounding per operation).  0 < ema_decay < 1,
+ * ema_start >= 0.  params, m and v are, bit for bit, those of the same call to splice_optim_step_ex. */
+int splice_optim_step_ema(int kind, float* params, float* grads, const float* g2, float* m, float* v, float* ema, long long n, float lr,
+                          const float* lr_dev, float hp0, float hp1, float eps, int step, int zero_grad, float ema_decay, int ema_start,
+                          splice_stream_t stream);
 
 /* live timing of one kernel family (bench.py roofline leg, prof.hip): while a family is armed its kernels are launched with
  * a start / stop event pair each (hipExtLaunchKernelGGL: the kernel's own begin / end time stamps, as rocprofv3 reports them).
@@ -465,6 +472,21 @@ int splice_step_stop_state(void* step, splice_stop_state* out, splice_stream_t s
  * as zeros with stop_step -1); losses8: device [pairs][8], element 0 of a row is the slot's loss; counted == 0: nothing happens. */
 int splice_plateau_update(splice_stop_state* state, const float* losses8, int pairs, int window, float rel, int patience, int min_steps,
                           int step_idx, int counted, splice_stream_t stream);
+
+/* ------------------------------------------------------------------ weight average (an extension: the reference writes the weights of its
+ * last step).  ema: [P][arena_stride] like `params`, the caller's (it starts as a copy of the parameters); the step's optimiser launch
+ * writes it by the rule of splice_optim_step_ema with the step's own count (step_idx + 1) -- no launch more, and params / m / v / losses
+ * are what they are without it.  A slot frozen by the stop rule keeps the average of its stop step.  Before the first splice_step_run
+ * only; refused on a handle in gradient-only (splice_step_set_mode) or phase mode (splice_step_set_phases), which the average in turn
+ * bars.  0 < decay < 1, start >= 0. */
+int splice_step_set_ema(void* step, float* ema, float decay, int start);
+/* as splice_optim_step_pairs with the weight average `ema` ([n_pairs][stride] like params), in the form the fused step launches: the
+ * step count is read from device memory (step_dev, one int >= 1; Adam's bias corrections are then computed on the device), and with
+ * `stop` (may be NULL; device, [n_pairs] records) a pair that is frozen at step index *step_dev - 1 is skipped entirely: params, grads,
+ * m, v and ema of that pair are not written. */
+int splice_optim_step_pairs_ema(int kind, float* params, float* grads, const float* g2, float* m, float* v, float* ema, int n_pairs,
+                                long long stride, long long n, const float* lr_dev, float hp0, float hp1, float eps, const int* step_dev,
+                                const splice_stop_state* stop, int zero_grad, float ema_decay, int ema_start, splice_stream_t stream);
 
 #ifdef __cplusplus
 }

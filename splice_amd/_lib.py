@@ -121,6 +121,10 @@ _SIGNATURES = {
     "splice_optim_step": ([_i, _vp, _vp, _vp, _vp, C.c_longlong, _f, _f, _f, _f, _i, _i, _vp], _i),
     "splice_optim_step_ex": ([_i, _vp, _vp, _vp, _vp, _vp, C.c_longlong, _f, _vp, _f, _f, _f, _i, _i, _vp], _i),
     "splice_optim_step_pairs": ([_i, _vp, _vp, _vp, _vp, _vp, _i, C.c_longlong, C.c_longlong, _vp, _f, _f, _f, _i, _i, _vp], _i),
+    # weight average
+    "splice_optim_step_ema": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, _f, _vp, _f, _f, _f, _i, _i, _f, _i, _vp], _i),
+    "splice_optim_step_pairs_ema": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_longlong, C.c_longlong, _vp, _f, _f, _f, _vp, _vp, _i, _f, _i, _vp], _i),
+    "splice_step_set_ema": ([_vp, _vp, _f, _i], _i),
     "splice_prof_begin": ([_i], _i),
     "splice_prof_end": ([C.POINTER(_f), C.POINTER(_i)], _i),
     "splice_prof_end_ex": ([C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)], _i),

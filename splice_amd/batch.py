@@ -23,6 +23,9 @@ Layout::
 window-mean loss stops improving; ``stopped_at`` is the step index it stopped at (null: it ran every step), ``steps_run`` the steps that
 updated it.  A group or a sweep ends when all of its slots have stopped; a loss reported for a slot behind its stop step means nothing.
 
+``--set ema_decay=0.999`` (with ``ema_start``) keeps an exponential moving average of every pair's generator weights inside the fused
+update; the run then also writes ``out/output_ema.png`` from the averaged weights, and ``result.json`` carries ``ema_decay``.
+
     python -m splice_amd.batch --root pairs/ --gpus 8 [--pairs-per-gpu P] [--n_epochs 2000] [--set key=value ...]
 
 ``--pairs-per-gpu P`` works with ``--set global_A_crops_n_crops=n`` (and ``global_B_crops_n_crops``): each pair's n crops are one
@@ -77,6 +80,11 @@ def _stop_fields(eng, slot=None):
     return {"steps_run": eng.step_idx + 1 if at is None else at + 1, "stopped_at": at}
 
 
+def _ema_fields(eng):
+    """``ema_decay`` of the run's weight average (0: none was kept, there is no ``output_ema.png``)."""
+    return {"ema_decay": eng.ema_rule[0]}
+
+
 def train_runner(pair_dir, overrides):
     """Default runner: the drop-in ``train_model`` on the pair's directory."""
     from .train import train_model
@@ -84,7 +92,7 @@ def train_runner(pair_dir, overrides):
     eng = train_model(pair_dir, cfg_overrides=overrides, progress=False)
     import torch
     torch.cuda.synchronize()
-    return {"steps": eng.step_idx + 1, "loss": eng.losses()["loss"], "seconds": round(time.perf_counter() - t0, 3), **_stop_fields(eng)}
+    return {"steps": eng.step_idx + 1, "loss": eng.losses()["loss"], "seconds": round(time.perf_counter() - t0, 3), **_stop_fields(eng), **_ema_fields(eng)}
 
 
 def train_group_runner(pair_dirs, overrides):
@@ -95,7 +103,7 @@ def train_group_runner(pair_dirs, overrides):
     import torch
     torch.cuda.synchronize()
     dt = round(time.perf_counter() - t0, 3)
-    return [{"steps": eng.step_idx + 1, "loss": d["loss"], "seconds": dt, "pairs_in_step": len(pair_dirs), **_stop_fields(eng, p)} for p, d in enumerate(eng.losses())]
+    return [{"steps": eng.step_idx + 1, "loss": d["loss"], "seconds": dt, "pairs_in_step": len(pair_dirs), **_stop_fields(eng, p), **_ema_fields(eng)} for p, d in enumerate(eng.losses())]
 
 
 def train_sweep_runner(pair_dir, overrides, variants):
@@ -106,7 +114,7 @@ def train_sweep_runner(pair_dir, overrides, variants):
     import torch
     torch.cuda.synchronize()
     losses = eng.losses()
-    return {"steps": eng.step_idx + 1, "seconds": round(time.perf_counter() - t0, 3),
+    return {"steps": eng.step_idx + 1, "seconds": round(time.perf_counter() - t0, 3), **_ema_fields(eng),
             "variants": [{"index": k, "overrides": v, "loss": d["loss"], "losses": d, **_stop_fields(eng, k)} for k, (v, d) in enumerate(zip(variants, losses))]}
 
 

@@ -21,5 +21,10 @@ struct OptimArgs {
     const splice_stop_state* mask = nullptr;
     const int* mask_step = nullptr;   // device: step index + 1 (the step's Adam count)
     size_t mask_stride = 0;
+    // optional (the weight average): an arena laid out like p, written behind p in the same walk.  t = the update's step count (step_dev,
+    // else mask_step, else step -- every kind needs one): t <= ema_start: e = p', later e = ema_decay e + (1 - ema_decay) p'
+    float* ema = nullptr;
+    float ema_decay = 0.f;
+    int ema_start = 0;
 };
 int optim_launch(const OptimArgs& a, hipStream_t s);

@@ -51,6 +51,13 @@ struct SgdRule {
     }
 };
 
+// The weight average (OptimArgs::ema): e follows the parameter just written.  track: the update's step count is <= ema_start, the average
+// still copies the weights.  Afterwards e = d e + (1 - d) p', three roundings like the moment rules.
+__device__ __forceinline__ float ema_update(float ei, float pi, float d, bool track) {
+#pragma clang fp contract(off)
+    return track ? pi : d * ei + (1.f - d) * pi;
+}
+
 // ---- the walk.  One float4 per thread and (at the generator's size) ONE pass: the operand vectors of an element group are a single
 // memory round trip; the kernel is the last node of the step's critical chain.
 // PAIR_LR: every pair of the arena has its own learning rate, lr_ptr[element / lr_stride] (lr_stride = the arena stride, a multiple
@@ -66,11 +73,16 @@ struct SgdRule {
 // (the sum of an earlier step, this step's backward output): nothing reads it, the next step's backward overwrites it.  The three
 // arguments lie behind the existing list; the instances without MASKED do not read them and compile to what they were (same
 // VGPR / SGPR counts, no scratch).
-template <class Rule, bool PAIR_LR, bool MASKED>
+// EMA (the weight average): a fifth arena e with p's layout, written in the same walk behind the parameter of the element (ema_update).
+// The step count is *ema_step_ptr where set (the fused step's device count), else the host's ema_step; every rule reads it here, RMSprop
+// and SGD too.  An unaligned e sends the call down the scalar path like any other arena; a frozen slot's e is skipped with the rest of
+// it.  The five arguments lie behind the masked ones, and the instances without EMA do not read them.
+template <class Rule, bool PAIR_LR, bool MASKED, bool EMA>
 __global__ void optim_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, size_t n, float lr,
                              float hp0, float hp1, float eps, float bc1, float bc2_sqrt, int zero_grad, const int* __restrict__ step_ptr,
                              const float* __restrict__ g2, const float* __restrict__ lr_ptr, unsigned lr_stride,
-                             const splice_stop_state* __restrict__ mask, const int* __restrict__ mask_step, unsigned mask_stride) {
+                             const splice_stop_state* __restrict__ mask, const int* __restrict__ mask_step, unsigned mask_stride,
+                             float* __restrict__ e, float ema_decay, int ema_start, const int* __restrict__ ema_step_ptr, int ema_step) {
     int step_idx = 0;
     if (MASKED) {
         step_idx = *mask_step - 1;
@@ -82,11 +94,13 @@ __global__ void optim_kernel(float* __restrict__ p, float* __restrict__ g, float
         bc1 = 1.0f - powf(hp0, t);
         bc2_sqrt = sqrtf(1.0f - powf(hp1, t));
     }
+    bool ema_track = false;
+    if (EMA) ema_track = (ema_step_ptr ? *ema_step_ptr : ema_step) <= ema_start;
     const Rule rule(hp0, hp1, eps, bc1, bc2_sqrt);
     auto upd = [&](float& pi, float& gi, float& mi, float& vi, float g2i) { rule.update(pi, gi, mi, vi, g2i, g2 != nullptr, lr, zero_grad); };
     const unsigned lr_stride4 = lr_stride / 4, mask_stride4 = mask_stride / 4;
     const size_t align = reinterpret_cast<size_t>(p) | reinterpret_cast<size_t>(g) | (Rule::USES_M ? reinterpret_cast<size_t>(m) : 0) |
-                         (Rule::USES_V ? reinterpret_cast<size_t>(v) : 0) | reinterpret_cast<size_t>(g2);
+                         (Rule::USES_V ? reinterpret_cast<size_t>(v) : 0) | reinterpret_cast<size_t>(g2) | (EMA ? reinterpret_cast<size_t>(e) : 0);
     const size_t n4 = (align & 15) ? 0 : n / 4;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
         if (MASKED && mask_stride && stop_frozen(mask + (unsigned)i / mask_stride4, step_idx)) continue;
@@ -97,6 +111,13 @@ __global__ void optim_kernel(float* __restrict__ p, float* __restrict__ g, float
         if (PAIR_LR) lr = lr_ptr[(unsigned)i / lr_stride4];
         upd(pv.x, gv.x, mv.x, vv.x, g2v.x); upd(pv.y, gv.y, mv.y, vv.y, g2v.y); upd(pv.z, gv.z, mv.z, vv.z, g2v.z); upd(pv.w, gv.w, mv.w, vv.w, g2v.w);
         reinterpret_cast<float4*>(p)[i] = pv;
+        if (EMA) {
+            float4 ev = pv;   // (a tracking average is the parameter: e is not read)
+            if (!ema_track) ev = reinterpret_cast<float4*>(e)[i];
+            ev.x = ema_update(ev.x, pv.x, ema_decay, ema_track); ev.y = ema_update(ev.y, pv.y, ema_decay, ema_track);
+            ev.z = ema_update(ev.z, pv.z, ema_decay, ema_track); ev.w = ema_update(ev.w, pv.w, ema_decay, ema_track);
+            reinterpret_cast<float4*>(e)[i] = ev;
+        }
         if (Rule::USES_M) reinterpret_cast<float4*>(m)[i] = mv;
         if (Rule::USES_V) reinterpret_cast<float4*>(v)[i] = vv;
         if (g2 || zero_grad) reinterpret_cast<float4*>(g)[i] = gv;
@@ -109,6 +130,7 @@ __global__ void optim_kernel(float* __restrict__ p, float* __restrict__ g, float
         if (PAIR_LR) lr = lr_ptr[(unsigned)i / lr_stride];
         upd(pi, gi, mi, vi, g2 ? g2[i] : 0.f);
         p[i] = pi;
+        if (EMA) e[i] = ema_update(ema_track ? pi : e[i], pi, ema_decay, ema_track);
         if (Rule::USES_M) m[i] = mi;
         if (Rule::USES_V) v[i] = vi;
         if (g2 || zero_grad) g[i] = gi;
@@ -120,10 +142,12 @@ static unsigned optim_grid(size_t n) {
 }
 
 int optim_launch(const OptimArgs& a, hipStream_t s) {
-#define OPTIM_INSTANCES(Rule) {{optim_kernel<Rule, false, false>, optim_kernel<Rule, false, true>}, {optim_kernel<Rule, true, false>, optim_kernel<Rule, true, true>}}
-    static constexpr decltype(&optim_kernel<AdamRule, false, false>) kernels[3][2][2] = {OPTIM_INSTANCES(AdamRule), OPTIM_INSTANCES(RmspropRule),
-                                                                                         OPTIM_INSTANCES(SgdRule)};   // [kind][PAIR_LR][MASKED]
+#define OPTIM_EMA(Rule, PAIR_LR, MASKED) {optim_kernel<Rule, PAIR_LR, MASKED, false>, optim_kernel<Rule, PAIR_LR, MASKED, true>}
+#define OPTIM_INSTANCES(Rule) {{OPTIM_EMA(Rule, false, false), OPTIM_EMA(Rule, false, true)}, {OPTIM_EMA(Rule, true, false), OPTIM_EMA(Rule, true, true)}}
+    static constexpr decltype(&optim_kernel<AdamRule, false, false, false>) kernels[3][2][2][2] = {
+        OPTIM_INSTANCES(AdamRule), OPTIM_INSTANCES(RmspropRule), OPTIM_INSTANCES(SgdRule)};   // [kind][PAIR_LR][MASKED][EMA]
 #undef OPTIM_INSTANCES
+#undef OPTIM_EMA
     if (a.kind < SPLICE_OPT_ADAM || a.kind > SPLICE_OPT_SGD) {
         splice_set_error("optimiser: unknown optimiser kind %d", a.kind);
         return SPLICE_ERR_ARG;
@@ -140,13 +164,20 @@ int optim_launch(const OptimArgs& a, hipStream_t s) {
         splice_set_error("optimiser: a masked update needs the device step count, a slot stride that is a multiple of 4 (the per-pair lr stride where both are set) and < 2^32 elements");
         return SPLICE_ERR_ARG;
     }
+    // the weight average counts the update's steps: the device count of the fused step, or the host's
+    const int* ema_step_dev = a.step_dev ? a.step_dev : a.mask_step;
+    if (a.ema && (!(a.ema_decay > 0.f && a.ema_decay < 1.f) || a.ema_start < 0 || (!ema_step_dev && a.step < 1))) {
+        splice_set_error("optimiser: a weight average needs 0 < ema_decay < 1, ema_start >= 0 and a step count (on the device, or step >= 1)");
+        return SPLICE_ERR_ARG;
+    }
     // a host step count: the bias corrections come from the HOST's powf (host and device powf need not agree to the bit, so a caller
     // stays with the form it has)
     const float bc1 = host_step ? 1.0f - powf(a.hp0, (float)a.step) : 1.f;
     const float bc2_sqrt = host_step ? sqrtf(1.0f - powf(a.hp1, (float)a.step)) : 1.f;
-    const auto kernel = kernels[a.kind][a.lr_stride != 0][a.mask != nullptr];
+    const auto kernel = kernels[a.kind][a.lr_stride != 0][a.mask != nullptr][a.ema != nullptr];
     SPLICE_LAUNCH(kernel, dim3(optim_grid(a.n)), dim3(256), 0, s, a.p, a.g, a.m, a.v, a.n, a.lr, a.hp0, a.hp1, a.eps, bc1, bc2_sqrt, a.zero_grad,
-                  adam ? a.step_dev : nullptr, a.g2, a.lr_dev, (unsigned)a.lr_stride, a.mask, a.mask_step, (unsigned)a.mask_stride);
+                  adam ? a.step_dev : nullptr, a.g2, a.lr_dev, (unsigned)a.lr_stride, a.mask, a.mask_step, (unsigned)a.mask_stride,
+                  a.ema, a.ema_decay, a.ema_start, ema_step_dev, a.step);
     return SPLICE_OK;
 }
 
@@ -164,6 +195,15 @@ int splice_optim_step_ex(int kind, float* params, float* grads, const float* g2,
                          float hp0, float hp1, float eps, int step, int zero_grad, splice_stream_t stream) {
     return optim_launch(optim_args(kind, params, grads, g2, m, v, n, lr, lr_dev, 0, hp0, hp1, eps, step, zero_grad), (hipStream_t)stream);
 }
+// as splice_optim_step_ex with the weight average `ema` updated in the same walk; step >= 1 for every kind (the average counts it)
+int splice_optim_step_ema(int kind, float* params, float* grads, const float* g2, float* m, float* v, float* ema, long long n, float lr,
+                          const float* lr_dev, float hp0, float hp1, float eps, int step, int zero_grad, float ema_decay, int ema_start,
+                          splice_stream_t stream) {
+    if (!ema) { splice_set_error("splice_optim_step_ema: needs the ema arena"); return SPLICE_ERR_ARG; }
+    OptimArgs a = optim_args(kind, params, grads, g2, m, v, n, lr, lr_dev, 0, hp0, hp1, eps, step, zero_grad);
+    a.ema = ema; a.ema_decay = ema_decay; a.ema_start = ema_start;
+    return optim_launch(a, (hipStream_t)stream);
+}
 int splice_optim_step(int kind, float* params, float* grads, float* m, float* v, long long n, float lr, float hp0, float hp1, float eps, int step,
                       int zero_grad, splice_stream_t stream) {
     return splice_optim_step_ex(kind, params, grads, nullptr, m, v, n, lr, nullptr, hp0, hp1, eps, step, zero_grad, stream);
@@ -178,5 +218,20 @@ int splice_optim_step_pairs(int kind, float* params, float* grads, const float* 
     }
     return optim_launch(optim_args(kind, params, grads, g2, m, v, (long long)n_pairs * stride, 0.f, lr_dev, (size_t)stride, hp0, hp1, eps, step, zero_grad),
                         (hipStream_t)stream);
+}
+// as splice_optim_step_pairs with the weight average, the fused step's form of the launch: the step count is read from the device
+// (step_dev), and with `stop` ([n_pairs] records) a pair that is frozen at step *step_dev - 1 is skipped -- its ema with the rest of it
+int splice_optim_step_pairs_ema(int kind, float* params, float* grads, const float* g2, float* m, float* v, float* ema, int n_pairs, long long stride,
+                                long long n, const float* lr_dev, float hp0, float hp1, float eps, const int* step_dev, const splice_stop_state* stop,
+                                int zero_grad, float ema_decay, int ema_start, splice_stream_t stream) {
+    if (!params || !grads || !ema || !lr_dev || !step_dev || n_pairs < 1 || n < 1 || stride < n || stride % 4) {
+        splice_set_error("splice_optim_step_pairs_ema: needs the ema arena, a device lr table and step count, n_pairs >= 1 and 1 <= n <= stride with stride a multiple of 4");
+        return SPLICE_ERR_ARG;
+    }
+    OptimArgs a = optim_args(kind, params, grads, g2, m, v, (long long)n_pairs * stride, 0.f, lr_dev, (size_t)stride, hp0, hp1, eps, 0, zero_grad);
+    a.step_dev = step_dev;
+    if (stop) { a.mask = stop; a.mask_step = step_dev; a.mask_stride = (size_t)stride; }
+    a.ema = ema; a.ema_decay = ema_decay; a.ema_start = ema_start;
+    return optim_launch(a, (hipStream_t)stream);
 }
 }

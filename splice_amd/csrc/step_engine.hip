@@ -116,6 +116,10 @@ struct SpliceStep {
     splice_stop_state* stop = nullptr;
     StopRule stop_rule = {0, 0.f, 0, 0};   // window 0: off -- the step launches what it always did
     int runs = 0;                          // splice_step_run calls so far (the rule is set before the first)
+    // the weight average (splice_step_set_ema): the caller's arena(s), laid out like params; null: off -- the step launches what it always did
+    float* ema = nullptr;
+    float ema_decay = 0.f;
+    int ema_start = 0;
 };
 
 static size_t arena_floats(const SpliceStep* st) { return st->astride ? st->pairs * st->astride : (size_t)st->nparams; }   // of all pairs' arenas
@@ -481,6 +485,7 @@ int splice_step_set_mode(void* h, int skip_adam, int accumulate) {
     SpliceStep* st = (SpliceStep*)h;
     if (!st || (accumulate && !skip_adam)) return SPLICE_ERR_ARG;
     if (skip_adam && st->stop_rule.window > 0) { splice_set_error("splice_step_set_mode: a handle with a stop rule runs whole steps (no gradient-only mode)"); return SPLICE_ERR_STATE; }
+    if (skip_adam && st->ema) { splice_set_error("splice_step_set_mode: a handle with a weight average runs whole steps (no gradient-only mode)"); return SPLICE_ERR_STATE; }
     if (st->skip_adam != (skip_adam ? 1 : 0) || st->accumulate != (accumulate ? 1 : 0)) st->graphs.retire();
     st->skip_adam = skip_adam ? 1 : 0; st->accumulate = accumulate ? 1 : 0;
     return SPLICE_OK;
@@ -565,6 +570,7 @@ int splice_step_set_phases(void* h, int phases, void* leader) {
     SpliceStep* st = (SpliceStep*)h;
     if (!st || phases <= 0 || phases > 7 || leader == h || (leader && phases != 2) || (leader && ((SpliceStep*)leader)->leader)) return SPLICE_ERR_ARG;
     if ((phases != 7 || leader) && st->stop_rule.window > 0) { splice_set_error("splice_step_set_phases: a handle with a stop rule runs whole steps (no phase mode)"); return SPLICE_ERR_STATE; }
+    if ((phases != 7 || leader) && st->ema) { splice_set_error("splice_step_set_phases: a handle with a weight average runs whole steps (no phase mode)"); return SPLICE_ERR_STATE; }
     if (st->leader != (SpliceStep*)leader) st->graphs.retire();
     st->phases = phases;
     st->leader = (SpliceStep*)leader;
@@ -584,6 +590,25 @@ int splice_step_set_stop_rule(void* h, int window, float rel, int patience, int 
     }
     if ((window > 0) != (st->stop_rule.window > 0)) st->graphs.retire();
     st->stop_rule = StopRule{window, rel, patience, min_steps};
+    return SPLICE_OK;
+}
+// The weight average of every pair of the handle (include/splice_hip.h has the rule): `ema` is written by the step's optimiser launch.  Before
+// the first step only: the average belongs to a run from step 0.  Not on a gradient-only or phase-mode handle: the update it rides in is
+// not this handle's.
+int splice_step_set_ema(void* h, float* ema, float decay, int start) {
+    SpliceStep* st = (SpliceStep*)h;
+    if (!st) return SPLICE_ERR_ARG;
+    if (!ema || !(decay > 0.f && decay < 1.f) || start < 0) {
+        splice_set_error("splice_step_set_ema: needs the ema arena, 0 < decay < 1 and start >= 0");
+        return SPLICE_ERR_ARG;
+    }
+    if (st->runs > 0) { splice_set_error("splice_step_set_ema: the average is set before the first step"); return SPLICE_ERR_STATE; }
+    if (st->skip_adam || st->phases != 7 || st->leader) {
+        splice_set_error("splice_step_set_ema: not on a handle in gradient-only (splice_step_set_mode) or phase mode (splice_step_set_phases)");
+        return SPLICE_ERR_STATE;
+    }
+    st->graphs.retire();
+    st->ema = ema; st->ema_decay = decay; st->ema_start = start;
     return SPLICE_OK;
 }
 int splice_step_stop_state(void* h, splice_stop_state* out, splice_stream_t stream) {
@@ -795,6 +820,7 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
         a.lr_dev = st->pair_lr ? st->dev_lrs : st->lr_set ? st->dev_lr : nullptr;
         a.lr_stride = st->pair_lr ? st->astride : 0;
         if (stop_on) { a.mask = st->stop; a.mask_step = st->dev_t; a.mask_stride = st->astride; }
+        if (st->ema) { a.ema = st->ema; a.ema_decay = st->ema_decay; a.ema_start = st->ema_start; }   // (another kernel: the graph pool keys on it)
         RC(optim_launch(a, s));
     }
     return SPLICE_OK;

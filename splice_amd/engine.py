@@ -26,7 +26,9 @@ DEFAULT_CFG = dict(  # conf/default/config.yaml of the reference
     optimizer="adam", optimizer_beta1=0.0, optimizer_beta2=0.99, lr=0.002,
     log_images_freq=10,
     # extensions (absent from the reference's config): the plateau stop rule, off by default
-    stop_window=0, stop_rel=0.01, stop_patience=2, stop_min_steps=0)
+    stop_window=0, stop_rel=0.01, stop_patience=2, stop_min_steps=0,
+    # ... and the weight average kept by the fused update, off by default
+    ema_decay=0.0, ema_start=0)
 
 
 # Per-slot keys of a sweep (MultiPairEngine(pair_cfgs=...), train.train_sweep): the five loss weights in the order of
@@ -53,6 +55,29 @@ def stop_rule(c):
     if isinstance(rel, bool) or not isinstance(rel, (int, float, np.floating)) or not 0 < rel < 1:
         raise ValueError(f"'stop_rel' must be a number in (0, 1), got {rel!r}")
     return integer("stop_window", 0), float(rel), integer("stop_patience", 1), integer("stop_min_steps", 0)
+
+
+def ema_rule(c):
+    """``(decay, start)`` of the weight average in config ``c``, checked on the host: ``0 <= ema_decay < 1``
+    (0: no average is kept) and an integer ``ema_start >= 0``, the number of updates the average merely copies the weights for.
+    Raises ValueError naming the key."""
+    d = c.get("ema_decay", DEFAULT_CFG["ema_decay"])
+    if isinstance(d, bool) or not isinstance(d, (int, float, np.floating, np.integer)) or not 0 <= d < 1:
+        raise ValueError(f"'ema_decay' must be a number in [0, 1), got {d!r}")
+    s = c.get("ema_start", DEFAULT_CFG["ema_start"])
+    if isinstance(s, bool) or not isinstance(s, (int, np.integer)) or s < 0:
+        raise ValueError(f"'ema_start' must be an integer >= 0, got {s!r}")
+    return float(d), int(s)
+
+
+def np_ema(e, p, step, decay, start):
+    """The rule of the weight average restated in NumPy float32, one rounding per operation: ``e`` after the update number
+    ``step`` (1-based) that wrote the parameters ``p``."""
+    f = np.float32
+    if step <= start:
+        return np.array(p, dtype=f)
+    d = f(decay)
+    return (d * np.asarray(e, dtype=f) + (f(1) - d) * np.asarray(p, dtype=f)).astype(f)
 
 
 def counted_steps(step_idx, cls_warmup, entire_every=0):
@@ -146,6 +171,8 @@ class MultiPairEngine:
         ``SpliceEngine`` with ``cfgs[p]`` would; ``lr`` becomes a list of P values."""
         self.cfg = dict(DEFAULT_CFG, **cfg)
         self.stop_rule = stop_rule(self.cfg)   # (host checks first: nothing below this line has touched a GPU yet)
+        self.ema_rule = ema_rule(self.cfg)
+        self.ema = None
         P_in = len(gen_states)
         self.cfgs = [self.cfg] * P_in
         self._pair_lambdas = self._pair_lr = False
@@ -264,6 +291,10 @@ class MultiPairEngine:
         # the plateau stop rule (shared by the slots; decided per slot on the device): before the first step
         if self.stop_rule[0] > 0:
             _lib.check(_lib.lib().splice_step_set_stop_rule(self.handle, *self.stop_rule), "step_set_stop_rule")
+        # the weight average (shared by the slots): an arena like params, written by the step's own optimiser launch; before the first step
+        if self.ema_rule[0] > 0:
+            self.ema = self.params.clone()
+            _lib.check(_lib.lib().splice_step_set_ema(self.handle, _lib.ptr(self.ema), *self.ema_rule), "step_set_ema")
         self._stopped = [None] * P   # the host's copy of every slot's stop step, refreshed by stop_state()
         self._stop_dirty = False     # a window has closed since the last stop_state(): the copy may be behind
         if self._pair_lambdas:
@@ -374,11 +405,24 @@ class MultiPairEngine:
     def pair_grads(self, pair=0):
         return self.grads[pair * self.stride: pair * self.stride + self.gen.numel]
 
-    def generate(self, img, pair=0, track_running_stats=False):
+    def pair_ema(self, pair=0):
+        """View of one pair's weight average (``ema_decay > 0``), laid out like ``pair_params``."""
+        if self.ema is None:
+            raise RuntimeError("pair_ema: no weight average is kept (ema_decay == 0)")
+        return self.ema[pair * self.stride: pair * self.stride + self.gen.numel]
+
+    def generate(self, img, pair=0, track_running_stats=False, ema=False):
         """netG_pair(img) under no_grad (the logging forward of train.py:70-73); img ``[n,3,H,W]``.  The reference's net
         is in train mode there too, so the call also moves the BatchNorm running statistics: pass
-        ``track_running_stats=True`` to book that (train_model does, after the step whose forwards precede it)."""
+        ``track_running_stats=True`` to book that (train_model does, after the step whose forwards precede it).
+        ``ema=True``: the forward with the averaged weights (a plan of its own); the reference has no such call, so it never
+        books BatchNorm statistics and is not among the logged forwards."""
         n, _, h, w = img.shape
+        if ema:
+            key = ("ema", pair, n, h, w)
+            if key not in self._log_plans:
+                self._log_plans[key] = GeneratorPlan(self.gen, n, h, w, False, batch_stats=n > 1)
+            return self._log_plans[key].forward(self.pair_ema(pair), img.contiguous())
         key = (pair, n, h, w)   # one plan per pair: a plan holds the BatchNorm statistics of its last forward until they are booked
         if key not in self._log_plans:
             self._log_plans[key] = GeneratorPlan(self.gen, n, h, w, False, batch_stats=n > 1)   # ONE netG call on n images: batch statistics, as nn.BatchNorm2d
@@ -405,9 +449,10 @@ class MultiPairEngine:
         _lib.check(_lib.lib().splice_gen_running_stats_update(plans, 1, _lib.ptr(self.running[pair]), 0, 0.1, _lib.current_stream()), "running_stats_update")
         self.generator_calls[pair] += 1
 
-    def state_dict(self, pair=0):
-        """``netG.state_dict()`` of one pair: parameters, BatchNorm running statistics and ``num_batches_tracked``."""
-        out = {k: v.clone() for k, v in self.gen.unflatten(self.pair_params(pair)).items()}
+    def state_dict(self, pair=0, ema=False):
+        """``netG.state_dict()`` of one pair: parameters, BatchNorm running statistics and ``num_batches_tracked``.
+        ``ema=True``: the averaged parameters with the live buffers."""
+        out = {k: v.clone() for k, v in self.gen.unflatten(self.pair_ema(pair) if ema else self.pair_params(pair)).items()}
         calls = self.generator_calls[pair]
         if self._frozen(pair):   # the netG calls of the steps behind its stop step did not move this slot's buffers
             step_calls = lambda k: 2 * (k + 1) + (k // int(self.cfg["entire_A_every"]) + 1 if self.plan_e is not None else 0)
@@ -448,10 +493,13 @@ class MultiScaleEngine:
         self.cfg = dict(DEFAULT_CFG, **cfg)
         if stop_rule(self.cfg)[0] > 0:
             raise NotImplementedError("stop_window > 0: the plateau stop rule lives in the fused step's own update; MultiScaleEngine updates outside the step")
+        self.ema_rule = ema_rule(self.cfg)
+        self.ema = None
         self.scales = tuple(scales)
         self.engines = []
         for k, sz in enumerate(self.scales):
-            e = SpliceEngine(dict(self.cfg, dino_global_patch_size=sz), vit_state if k == 0 else None, gen_state, crop_hw, entire_hw, device=device,
+            # (ema_decay=0: the handles are gradient-only, the average rides in this engine's own update below)
+            e = SpliceEngine(dict(self.cfg, dino_global_patch_size=sz, ema_decay=0.0), vit_state if k == 0 else None, gen_state, crop_hw, entire_hw, device=device,
                              vit_engine=vit_engine if k == 0 else self.engines[0].vit, n_crops=n_crops, fp8=fp8)
             _lib.check(_lib.lib().splice_step_set_mode(e.handle, 1, 0), "step_set_mode")
             if k > 0:   # one parameter set: every scale sees the arenas of the first engine; netG bookkeeping once
@@ -461,6 +509,8 @@ class MultiScaleEngine:
             self.engines.append(e)
         self.vit, self.gen = self.engines[0].vit, self.engines[0].gen
         self.params, self.grads = self.engines[0].params, self.engines[0].grads
+        if self.ema_rule[0] > 0:
+            self.ema = self.engines[0].ema = self.params.clone()   # (the leader serves pair_ema / generate / state_dict with it)
         self.step_idx = -1
         self.opt_kind, *self.opt_hp = fused_optimizer(self.cfg)
         self.schedule = LrSchedule(self.cfg)
@@ -477,15 +527,19 @@ class MultiScaleEngine:
         _lib.check(L.splice_step_set_phases(e0.handle, 4, None), "step_set_phases")
         e0.step(A_crop, B_crop, A_entire, _repeat=True)      # G backward of the summed image gradient
         self.lr = self.schedule.lr(self.step_idx)
-        optim_step(self.opt_kind, e0.params, e0.grads, e0.m, e0.v, self.lr, *self.opt_hp, self.step_idx + 1)
+        optim_step(self.opt_kind, e0.params, e0.grads, e0.m, e0.v, self.lr, *self.opt_hp, self.step_idx + 1, ema=self.ema,
+                   ema_decay=self.ema_rule[0], ema_start=self.ema_rule[1])
 
     def losses(self):
         """Per-scale loss dicts and their sum: ``{"loss": total, "scales": {224: {...}, ...}}``."""
         per = {sz: e.losses() for sz, e in zip(self.scales, self.engines)}
         return {"loss": sum(d["loss"] for d in per.values()), "scales": per}
 
-    def generate(self, img, pair=0, track_running_stats=False):
-        return self.engines[0].generate(img, pair, track_running_stats)
+    def generate(self, img, pair=0, track_running_stats=False, ema=False):
+        return self.engines[0].generate(img, pair, track_running_stats, ema=ema)
+
+    def pair_ema(self, pair=0):
+        return self.engines[0].pair_ema(pair)
 
     def book_logged_forward(self):
         self.engines[0].book_logged_forward()
@@ -495,8 +549,8 @@ class MultiScaleEngine:
     def window_closes(self, step_idx):
         return False
 
-    def state_dict(self, pair=0):
-        return self.engines[0].state_dict(pair)
+    def state_dict(self, pair=0, ema=False):
+        return self.engines[0].state_dict(pair, ema=ema)
 
 
 def synthetic_engine(cfg, pair_id=0, hw=(224, 224), seed=1234, device="cuda", vit_engine=None, entire=True, pairs=1, fp8=False, top_cls_only=True, crop_hw=None):

@@ -171,22 +171,30 @@ def adam_step(params, grads, m, v, lr, beta1, beta2, eps, step, zero_grad=False)
 OPTIMIZER_KINDS = {"adam": 0, "rmsprop": 1, "sgd": 2}   # the `kind` of splice_optim_step
 
 
-def optim_step(kind, params, grads, m, v, lr, hp0, hp1, eps, step, zero_grad=False, g2=None, lr_dev=None):
+def optim_step(kind, params, grads, m, v, lr, hp0, hp1, eps, step, zero_grad=False, g2=None, lr_dev=None, ema=None, ema_decay=0.0, ema_start=0):
     """One fused optimiser step over a flat arena (``splice_optim_step_ex``): kind 0 Adam (hp0 / hp1 = betas, step >= 1),
     1 RMSprop (hp0 = alpha, ``v`` = square_avg, ``m`` unused), 2 SGD (``m`` / ``v`` unused).  ``g2``: second gradient arena
-    added to ``grads`` first; ``lr_dev``: one-element device tensor read as the learning rate when the kernel runs."""
+    added to ``grads`` first; ``lr_dev``: one-element device tensor read as the learning rate when the kernel runs.
+    ``ema``: the weight-average arena, written in the same walk (``splice_optim_step_ema``): ``step <= ema_start``: a copy of the
+    parameters just written, later ``ema_decay * ema + (1 - ema_decay) * params``; every kind then needs ``step >= 1``."""
     if kind not in OPTIMIZER_KINDS.values():
         raise ValueError(f"optim_step: unknown optimiser kind {kind}")
     m = m if kind == 0 else None            # arenas the kind does not touch are not passed
     v = v if kind in (0, 1) else None
     n = params.numel()
-    for name, t, needed in (("params", params, True), ("grads", grads, True), ("g2", g2, False), ("m", m, kind == 0), ("v", v, kind in (0, 1))):
+    for name, t, needed in (("params", params, True), ("grads", grads, True), ("g2", g2, False), ("m", m, kind == 0), ("v", v, kind in (0, 1)),
+                            ("ema", ema, False)):
         if t is None and not needed:
             continue
         if t is None or not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n):
             raise ValueError(f"optim_step: {name} must be a contiguous fp32 CUDA tensor of {n} elements")
     if lr_dev is not None and not (lr_dev.is_cuda and lr_dev.dtype == torch.float32 and lr_dev.numel() >= 1):
         raise ValueError("optim_step: lr_dev must be a fp32 CUDA tensor")
+    if ema is not None:
+        _lib.check(_lib.lib().splice_optim_step_ema(int(kind), _lib.ptr(params), _lib.ptr(grads), _lib.ptr(g2), _lib.ptr(m), _lib.ptr(v), _lib.ptr(ema), n,
+                                                    float(lr), _lib.ptr(lr_dev), float(hp0), float(hp1), float(eps), int(step), int(zero_grad),
+                                                    float(ema_decay), int(ema_start), _lib.current_stream()), "optim_step_ema")
+        return
     _lib.check(_lib.lib().splice_optim_step_ex(int(kind), _lib.ptr(params), _lib.ptr(grads), _lib.ptr(g2), _lib.ptr(m), _lib.ptr(v), n,
                                                float(lr), _lib.ptr(lr_dev), float(hp0), float(hp1), float(eps), int(step), int(zero_grad),
                                                _lib.current_stream()), "optim_step")

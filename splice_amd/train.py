@@ -4,7 +4,8 @@ Same contract as the reference (``train.py:15-80``): reads ``conf/default/config
 working directory (falling back to the packaged copy), seeds python / numpy / torch, opens the first
 image of ``<dataroot>/A`` and ``<dataroot>/B``, runs ``n_epochs`` optimisation steps and every
 ``log_images_freq`` steps writes ``<dataroot>/out/output.png`` (asynchronously: ``util.AsyncResultWriter``) and calls
-``callback(output[0])`` with the ``[3,H,W]`` float image.  The step itself is the fused HIP engine (``SpliceEngine``), one host
+``callback(output[0])`` with the ``[3,H,W]`` float image.  With ``ema_decay > 0`` (an extension) the run ends by writing one more image,
+``<dataroot>/out/output_ema.png``, from the averaged weights.  The step itself is the fused HIP engine (``SpliceEngine``), one host
 call per step, losses read back only when a progress line is printed.
 
 Data feed: the reference augments PIL images on the CPU every step (``data/Dataset.py:62-70``).
@@ -208,6 +209,7 @@ def train_model(dataroot, callback=None, cfg_overrides=None, vit_state=None, pro
                 if progress:
                     print(f"Epoch {epoch}: the loss has plateaued, stopping")
                 break
+        _ema_images(engine, [writer], [feed.get_A()])
     finally:
         writer.close()
     return engine
@@ -252,6 +254,16 @@ def _final_images(engine, writers, As, callback):
         writers[p].submit(out[0], force=True)
         if callback is not None:
             callback(p, out[0])
+
+
+def _ema_images(engine, writers, As):
+    """The end of a run that keeps a weight average (``ema_decay > 0``), however it ended: one more image per slot,
+    ``output_ema.png`` beside ``output.png``, from the averaged weights.  No callback and no bookkeeping: the logged images stay
+    those of the live weights."""
+    if engine.ema is None or engine.step_idx < 0:
+        return
+    for p, A in enumerate(As):
+        writers[p].submit(engine.generate(A, pair=p, ema=True)[0], force=True, name="output_ema.png")
 
 
 def train_pairs(dataroots, callback=None, cfg_overrides=None, vit_state=None, progress=True):
@@ -326,6 +338,7 @@ def train_pairs(dataroots, callback=None, cfg_overrides=None, vit_state=None, pr
             if engine.window_closes(engine.step_idx) and engine.all_stopped():   # every pair has plateaued (see train_model)
                 _final_images(engine, writers, [feed.get_A(p) for p in range(len(dataroots))], callback)
                 break
+        _ema_images(engine, writers, [feed.get_A(p) for p in range(len(dataroots))])
     finally:
         for w in writers:
             w.close()
@@ -421,6 +434,7 @@ def train_sweep(dataroot, variants, cfg_overrides=None, vit_state=None, callback
             if engine.window_closes(engine.step_idx) and engine.all_stopped():   # every variant has plateaued (see train_model)
                 _final_images(engine, writers, [feed.get_A()] * K, callback)
                 break
+        _ema_images(engine, writers, [feed.get_A()] * K)
     finally:
         for w in writers:
             w.close()

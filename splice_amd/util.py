@@ -173,9 +173,10 @@ class AsyncResultWriter:
         self._t = threading.Thread(target=self._run, name="splice-result-writer", daemon=True)
         self._t.start()
 
-    def submit(self, image_t, force=True):
+    def submit(self, image_t, force=True, name="output.png"):
         """force=False: the image may be skipped when the previous one was submitted less than ``min_interval`` seconds ago (the file is
-        overwritten every time anyway; the encoder thread shares the interpreter lock with the loop that launches the steps)."""
+        overwritten every time anyway; the encoder thread shares the interpreter lock with the loop that launches the steps).
+        ``name``: the file in the writer's directory (``output_ema.png``: the image of the averaged weights at the end of a run)."""
         import time
         now = time.monotonic()
         if not force and now - self._last < max(self.min_interval, self._gap):
@@ -191,7 +192,7 @@ class AsyncResultWriter:
         if img.is_cuda:
             ev = torch.cuda.Event()
             ev.record()
-        self._q.put((buf, ev))
+        self._q.put((buf, ev, name))
 
     def _run(self):
         from PIL import Image
@@ -199,16 +200,16 @@ class AsyncResultWriter:
             item = self._q.get()
             if item is None:
                 return
-            buf, ev = item
+            buf, ev, name = item
             try:
                 if ev is not None:
                     ev.synchronize()
                 import time
                 t0 = time.monotonic()
                 arr = (buf.clamp(0.0, 1.0).numpy().transpose(1, 2, 0) * 255.0).astype(np.uint8)
-                tmp = self.dir / "output.png.tmp"
+                tmp = self.dir / (name + ".tmp")
                 Image.fromarray(arr).save(tmp, format="PNG")
-                tmp.replace(self.dir / "output.png")      # readers never see a half-written file
+                tmp.replace(self.dir / name)              # readers never see a half-written file
                 if self.min_interval > 0:
                     self._gap = 10.0 * (time.monotonic() - t0)
             except Exception as e:                         # surfaced by close()
