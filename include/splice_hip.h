@@ -488,6 +488,54 @@ int splice_optim_step_pairs_ema(int kind, float* params, float* grads, const flo
                                 long long stride, long long n, const float* lr_dev, float hp0, float hp1, float eps, const int* step_dev,
                                 const splice_stop_state* stop, int zero_grad, float ema_decay, int ema_start, splice_stream_t stream);
 
+/* ------------------------------------------------------------------ gradient clipping by the global norm (an extension: the reference does
+ * not clip).  torch.nn.utils.clip_grad_norm_(params, max_norm) per pair, plus a guard: a pair whose norm is not finite is not updated at
+ * that step.  Per pair, over the n gradient floats of its arena (s = fl(g + g2) where a second gradient arena is folded in), fp32 with one
+ * rounding per operation unless noted:
+ *   stage 1, one partial per chunk of SPLICE_CLIP_CHUNK floats counted from the start of the pair's arena: element e of a chunk belongs to
+ *     thread t = (e / 4) % 256, round j = e / 1024, component c = e % 4; thread t adds fl(s * s) to acc = 0 in the order j = 0..3, c = 0..3
+ *     (elements at or beyond n add nothing); the 256 values are combined by the halving tree a[t] += a[t + off], off = 128, 64, ..., 1.
+ *   stage 2, per pair: thread t of 256 adds partials[t], partials[t + 256], ... in fp64, the same tree in fp64 combines the threads;
+ *     sumsq = (float)total, norm = sqrtf(sumsq); norm finite: coef = fminf(1, max_norm / (norm + 1e-6f)), skip = 0, clipped += coef < 1;
+ *     otherwise coef = 0, skip = 1, skipped += 1.
+ * The update then uses fl(s * coef) as its gradient -- multiplied even when coef is 1, as torch does, which changes no bit -- and with
+ * skip set writes nothing of the pair but the zeros of zero_grad.  The bits of a pair do not depend on the other pairs of the call. */
+#define SPLICE_CLIP_CHUNK 4096
+typedef struct splice_clip_state {
+    float sumsq;      /* of the pair's gradient at the last step */
+    float norm;       /* sqrtf(sumsq) */
+    float coef;       /* the factor the update multiplied the gradient by (0 with skip) */
+    int skip;         /* the last step's norm was not finite: the pair was not updated */
+    int clipped;      /* steps so far with coef < 1 */
+    int skipped;      /* steps so far with skip */
+} splice_clip_state;
+/* The two norm stages for n_pairs arenas of n floats, pair p at grads + p * stride (g2 alike; may be NULL).  partials: device,
+ * n_pairs * ceil(n / SPLICE_CLIP_CHUNK) floats, the caller's scratch; state: device, [n_pairs] records (the caller starts the two counts
+ * at zero).  n_pairs == 1: the stride is not used and n is arbitrary; otherwise stride % 4 == 0 and stride >= n.  An arena that is not
+ * 16-byte aligned is read element by element, with the same result.  stop (may be NULL; device, [n_pairs] records) with step_dev (device,
+ * one int, step index + 1): a pair frozen at that step is left out, its record stays.  0 < max_norm < inf. */
+int splice_grad_norm_pairs(const float* grads, const float* g2, int n_pairs, long long stride, long long n, float max_norm, float* partials,
+                           splice_clip_state* state, const splice_stop_state* stop, const int* step_dev, splice_stream_t stream);
+/* as splice_optim_step_pairs_ema with the records splice_grad_norm_pairs has just written for the same gradient (clip: device, [n_pairs]):
+ * pair p's gradient is fl(fl(g + g2) * clip[p].coef), and a pair with clip[p].skip set is not written (its grads are zeroed when zero_grad
+ * is set).  Where grads is written back (g2 or zero_grad) it holds the clipped sum.  ema may be NULL (no average) and stop may be NULL;
+ * n_pairs == 1: the stride is not used and n is arbitrary, lr_dev[0] is the learning rate. */
+int splice_optim_step_pairs_clip(int kind, float* params, float* grads, const float* g2, float* m, float* v, float* ema, int n_pairs,
+                                 long long stride, long long n, const float* lr_dev, float hp0, float hp1, float eps, const int* step_dev,
+                                 const splice_stop_state* stop, int zero_grad, float ema_decay, int ema_start, const splice_clip_state* clip,
+                                 splice_stream_t stream);
+/* the host-step form for one arena of n floats (as splice_optim_step_ema, ema optional): lr / lr_dev and step as in splice_optim_step_ex,
+ * clip: the one record splice_grad_norm_pairs wrote for this gradient with n_pairs == 1 */
+int splice_optim_step_clip(int kind, float* params, float* grads, const float* g2, float* m, float* v, float* ema, long long n, float lr,
+                           const float* lr_dev, float hp0, float hp1, float eps, int step, int zero_grad, float ema_decay, int ema_start,
+                           const splice_clip_state* clip, splice_stream_t stream);
+/* Clip every pair's gradient inside the step: the two norm launches go out on the main stream directly before the optimiser launch, which
+ * then reads the records.  state: device, [pairs] records, the caller's (zeros).  The handle owns the partials.  With max_norm so large
+ * that no step is clipped, params / m / v / ema / losses are, bit for bit, what they are without the rule.  A slot frozen by the stop rule
+ * keeps the record of its stop step.  Before the first splice_step_run only; refused on a handle in gradient-only (splice_step_set_mode)
+ * or phase mode (splice_step_set_phases), which the rule in turn bars.  0 < max_norm < inf. */
+int splice_step_set_grad_clip(void* step, float max_norm, splice_clip_state* state);
+
 #ifdef __cplusplus
 }
 #endif

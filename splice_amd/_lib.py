@@ -52,6 +52,10 @@ class StopState(C.Structure):   # splice_stop_state
     _fields_ = [("sum", C.c_float), ("count", C.c_int), ("windows", C.c_int), ("best", C.c_float), ("bad", C.c_int), ("stop_step", C.c_int)]
 
 
+class ClipState(C.Structure):   # splice_clip_state
+    _fields_ = [("sumsq", C.c_float), ("norm", C.c_float), ("coef", C.c_float), ("skip", C.c_int), ("clipped", C.c_int), ("skipped", C.c_int)]
+
+
 EPI_BIAS, EPI_RESID, EPI_OUT_F32, EPI_OUT_BF, EPI_OUT_T = 1, 2, 4, 8, 16
 EPI_GELU, EPI_GELU_GRAD, EPI_COLS_F32, EPI_ALPHA, EPI_ROWDOT, EPI_SCALE_RC, EPI_OUT_F8, EPI_OUT_F8T = 32, 64, 128, 256, 512, 1024, 2048, 4096
 
@@ -125,6 +129,11 @@ _SIGNATURES = {
     "splice_optim_step_ema": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, _f, _vp, _f, _f, _f, _i, _i, _f, _i, _vp], _i),
     "splice_optim_step_pairs_ema": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_longlong, C.c_longlong, _vp, _f, _f, _f, _vp, _vp, _i, _f, _i, _vp], _i),
     "splice_step_set_ema": ([_vp, _vp, _f, _i], _i),
+    # gradient clipping by the pair's global norm
+    "splice_grad_norm_pairs": ([_vp, _vp, _i, C.c_longlong, C.c_longlong, _f, _vp, _vp, _vp, _vp, _vp], _i),
+    "splice_optim_step_pairs_clip": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_longlong, C.c_longlong, _vp, _f, _f, _f, _vp, _vp, _i, _f, _i, _vp, _vp], _i),
+    "splice_optim_step_clip": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, _f, _vp, _f, _f, _f, _i, _i, _f, _i, _vp, _vp], _i),
+    "splice_step_set_grad_clip": ([_vp, _f, _vp], _i),
     "splice_prof_begin": ([_i], _i),
     "splice_prof_end": ([C.POINTER(_f), C.POINTER(_i)], _i),
     "splice_prof_end_ex": ([C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)], _i),

@@ -26,6 +26,10 @@ updated it.  A group or a sweep ends when all of its slots have stopped; a loss 
 ``--set ema_decay=0.999`` (with ``ema_start``) keeps an exponential moving average of every pair's generator weights inside the fused
 update; the run then also writes ``out/output_ema.png`` from the averaged weights, and ``result.json`` carries ``ema_decay``.
 
+``--set grad_clip_norm=1.0`` clips every pair's gradient to that global norm inside the fused step (``torch.nn.utils.clip_grad_norm_``
+per pair; a step whose norm is not finite does not update the pair); ``result.json`` carries ``grad_clip_norm``, ``clipped_steps`` and
+``skipped_steps`` per pair (per variant in a sweep).
+
     python -m splice_amd.batch --root pairs/ --gpus 8 [--pairs-per-gpu P] [--n_epochs 2000] [--set key=value ...]
 
 ``--pairs-per-gpu P`` works with ``--set global_A_crops_n_crops=n`` (and ``global_B_crops_n_crops``): each pair's n crops are one
@@ -85,6 +89,11 @@ def _ema_fields(eng):
     return {"ema_decay": eng.ema_rule[0]}
 
 
+def _clip_fields(eng, slot=None):
+    from .train import clip_fields
+    return clip_fields(eng, slot)
+
+
 def train_runner(pair_dir, overrides):
     """Default runner: the drop-in ``train_model`` on the pair's directory."""
     from .train import train_model
@@ -92,7 +101,8 @@ def train_runner(pair_dir, overrides):
     eng = train_model(pair_dir, cfg_overrides=overrides, progress=False)
     import torch
     torch.cuda.synchronize()
-    return {"steps": eng.step_idx + 1, "loss": eng.losses()["loss"], "seconds": round(time.perf_counter() - t0, 3), **_stop_fields(eng), **_ema_fields(eng)}
+    return {"steps": eng.step_idx + 1, "loss": eng.losses()["loss"], "seconds": round(time.perf_counter() - t0, 3), **_stop_fields(eng), **_ema_fields(eng),
+            **_clip_fields(eng)}
 
 
 def train_group_runner(pair_dirs, overrides):
@@ -103,7 +113,8 @@ def train_group_runner(pair_dirs, overrides):
     import torch
     torch.cuda.synchronize()
     dt = round(time.perf_counter() - t0, 3)
-    return [{"steps": eng.step_idx + 1, "loss": d["loss"], "seconds": dt, "pairs_in_step": len(pair_dirs), **_stop_fields(eng, p), **_ema_fields(eng)} for p, d in enumerate(eng.losses())]
+    return [{"steps": eng.step_idx + 1, "loss": d["loss"], "seconds": dt, "pairs_in_step": len(pair_dirs), **_stop_fields(eng, p), **_ema_fields(eng),
+             **_clip_fields(eng, p)} for p, d in enumerate(eng.losses())]
 
 
 def train_sweep_runner(pair_dir, overrides, variants):
@@ -115,7 +126,7 @@ def train_sweep_runner(pair_dir, overrides, variants):
     torch.cuda.synchronize()
     losses = eng.losses()
     return {"steps": eng.step_idx + 1, "seconds": round(time.perf_counter() - t0, 3), **_ema_fields(eng),
-            "variants": [{"index": k, "overrides": v, "loss": d["loss"], "losses": d, **_stop_fields(eng, k)} for k, (v, d) in enumerate(zip(variants, losses))]}
+            "variants": [{"index": k, "overrides": v, "loss": d["loss"], "losses": d, **_stop_fields(eng, k), **_clip_fields(eng, k)} for k, (v, d) in enumerate(zip(variants, losses))]}
 
 
 def sweep_variants(specs):

@@ -26,5 +26,14 @@ struct OptimArgs {
     float* ema = nullptr;
     float ema_decay = 0.f;
     int ema_start = 0;
+    // optional (gradient clipping): [slots] records written by grad_norm_launch for this gradient.  Element i uses clip[i / clip_stride]
+    // (a multiple of 4; 0: the one arena is slot 0): its gradient is fl(fl(g + g2) * coef), and with skip set the slot is not written
+    // (its g is zeroed under zero_grad)
+    const splice_clip_state* clip = nullptr;
+    size_t clip_stride = 0;
 };
 int optim_launch(const OptimArgs& a, hipStream_t s);
+// The per-pair gradient norm and clip coefficient (include/splice_hip.h has the rule): two launches, partials[pairs][ceil(n / 4096)] then
+// state[pairs].  stop (optional) with step_dev: a frozen pair is left out of both.
+int grad_norm_launch(const float* g, const float* g2, int pairs, size_t stride, size_t n, float max_norm, float* partials, splice_clip_state* state,
+                     const splice_stop_state* stop, const int* step_dev, hipStream_t s);

@@ -58,6 +58,13 @@ __device__ __forceinline__ float ema_update(float ei, float pi, float d, bool tr
     return track ? pi : d * ei + (1.f - d) * pi;
 }
 
+// Gradient clipping (OptimArgs::clip): the element's gradient is the sum of the two arenas times the pair's coefficient, two roundings.
+__device__ __forceinline__ float clip_scale(float gi, float g2i, bool has_g2, float coef) {
+#pragma clang fp contract(off)
+    if (has_g2) gi += g2i;
+    return gi * coef;
+}
+
 // ---- the walk.  One float4 per thread and (at the generator's size) ONE pass: the operand vectors of an element group are a single
 // memory round trip; the kernel is the last node of the step's critical chain.
 // PAIR_LR: every pair of the arena has its own learning rate, lr_ptr[element / lr_stride] (lr_stride = the arena stride, a multiple
@@ -77,12 +84,18 @@ __device__ __forceinline__ float ema_update(float ei, float pi, float d, bool tr
 // The step count is *ema_step_ptr where set (the fused step's device count), else the host's ema_step; every rule reads it here, RMSprop
 // and SGD too.  An unaligned e sends the call down the scalar path like any other arena; a frozen slot's e is skipped with the rest of
 // it.  The five arguments lie behind the masked ones, and the instances without EMA do not read them.
-template <class Rule, bool PAIR_LR, bool MASKED, bool EMA>
+// CLIP (gradient clipping by the pair's global norm): element i uses the record clip[i / clip_stride] (clip_stride 0: slot 0, read once
+// at the kernel's head) that grad_norm_launch wrote for this gradient.  The rule sees gi = fl(fl(g + g2) * coef) -- multiplied when coef is 1 too, which changes no
+// bit -- and where g is written back it holds that value.  A slot whose record has skip set (its norm was not finite) is left as it is:
+// no write to p, m, v or e; its g is written only as the zeros of zero_grad.  A frozen slot is skipped before its record is read.  The
+// two arguments lie behind the EMA ones, and the instances without CLIP do not read them.
+template <class Rule, bool PAIR_LR, bool MASKED, bool EMA, bool CLIP>
 __global__ void optim_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, size_t n, float lr,
                              float hp0, float hp1, float eps, float bc1, float bc2_sqrt, int zero_grad, const int* __restrict__ step_ptr,
                              const float* __restrict__ g2, const float* __restrict__ lr_ptr, unsigned lr_stride,
                              const splice_stop_state* __restrict__ mask, const int* __restrict__ mask_step, unsigned mask_stride,
-                             float* __restrict__ e, float ema_decay, int ema_start, const int* __restrict__ ema_step_ptr, int ema_step) {
+                             float* __restrict__ e, float ema_decay, int ema_start, const int* __restrict__ ema_step_ptr, int ema_step,
+                             const splice_clip_state* __restrict__ clip, unsigned clip_stride) {
     int step_idx = 0;
     if (MASKED) {
         step_idx = *mask_step - 1;
@@ -97,8 +110,19 @@ __global__ void optim_kernel(float* __restrict__ p, float* __restrict__ g, float
     bool ema_track = false;
     if (EMA) ema_track = (ema_step_ptr ? *ema_step_ptr : ema_step) <= ema_start;
     const Rule rule(hp0, hp1, eps, bc1, bc2_sqrt);
-    auto upd = [&](float& pi, float& gi, float& mi, float& vi, float g2i) { rule.update(pi, gi, mi, vi, g2i, g2 != nullptr, lr, zero_grad); };
-    const unsigned lr_stride4 = lr_stride / 4, mask_stride4 = mask_stride / 4;
+    // one arena: its record is read once, at the head, with the step count; several: per element group, behind the group's own loads
+    float coef = 1.f;
+    int skip = 0;
+    if (CLIP && !clip_stride) { coef = clip->coef; skip = clip->skip; }
+    auto upd = [&](float& pi, float& gi, float& mi, float& vi, float g2i) {
+        if (CLIP) {
+            gi = clip_scale(gi, g2i, g2 != nullptr, coef);
+            rule.update(pi, gi, mi, vi, 0.f, false, lr, zero_grad);
+        } else {
+            rule.update(pi, gi, mi, vi, g2i, g2 != nullptr, lr, zero_grad);
+        }
+    };
+    const unsigned lr_stride4 = lr_stride / 4, mask_stride4 = mask_stride / 4, clip_stride4 = clip_stride / 4;
     const size_t align = reinterpret_cast<size_t>(p) | reinterpret_cast<size_t>(g) | (Rule::USES_M ? reinterpret_cast<size_t>(m) : 0) |
                          (Rule::USES_V ? reinterpret_cast<size_t>(v) : 0) | reinterpret_cast<size_t>(g2) | (EMA ? reinterpret_cast<size_t>(e) : 0);
     const size_t n4 = (align & 15) ? 0 : n / 4;
@@ -109,6 +133,17 @@ __global__ void optim_kernel(float* __restrict__ p, float* __restrict__ g, float
         if (Rule::USES_V) vv = reinterpret_cast<float4*>(v)[i];
         const float4 g2v = g2 ? reinterpret_cast<const float4*>(g2)[i] : float4{0.f, 0.f, 0.f, 0.f};
         if (PAIR_LR) lr = lr_ptr[(unsigned)i / lr_stride4];
+        if (CLIP) {
+            if (clip_stride4) {
+                const splice_clip_state* cs = clip + (unsigned)i / clip_stride4;
+                coef = cs->coef;
+                skip = cs->skip;
+            }
+            if (skip) {
+                if (zero_grad) reinterpret_cast<float4*>(g)[i] = float4{0.f, 0.f, 0.f, 0.f};
+                continue;
+            }
+        }
         upd(pv.x, gv.x, mv.x, vv.x, g2v.x); upd(pv.y, gv.y, mv.y, vv.y, g2v.y); upd(pv.z, gv.z, mv.z, vv.z, g2v.z); upd(pv.w, gv.w, mv.w, vv.w, g2v.w);
         reinterpret_cast<float4*>(p)[i] = pv;
         if (EMA) {
@@ -124,6 +159,17 @@ __global__ void optim_kernel(float* __restrict__ p, float* __restrict__ g, float
     }
     for (size_t i = n4 * 4 + (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
         if (MASKED && mask_stride && stop_frozen(mask + (unsigned)i / mask_stride, step_idx)) continue;
+        if (CLIP) {
+            if (clip_stride) {
+                const splice_clip_state* cs = clip + (unsigned)i / clip_stride;
+                coef = cs->coef;
+                skip = cs->skip;
+            }
+            if (skip) {
+                if (zero_grad) g[i] = 0.f;
+                continue;
+            }
+        }
         float pi = p[i], gi = g[i], mi = 0.f, vi = 0.f;
         if (Rule::USES_M) mi = m[i];
         if (Rule::USES_V) vi = v[i];
@@ -142,12 +188,14 @@ static unsigned optim_grid(size_t n) {
 }
 
 int optim_launch(const OptimArgs& a, hipStream_t s) {
-#define OPTIM_EMA(Rule, PAIR_LR, MASKED) {optim_kernel<Rule, PAIR_LR, MASKED, false>, optim_kernel<Rule, PAIR_LR, MASKED, true>}
+#define OPTIM_CLIP(Rule, PAIR_LR, MASKED, EMA) {optim_kernel<Rule, PAIR_LR, MASKED, EMA, false>, optim_kernel<Rule, PAIR_LR, MASKED, EMA, true>}
+#define OPTIM_EMA(Rule, PAIR_LR, MASKED) {OPTIM_CLIP(Rule, PAIR_LR, MASKED, false), OPTIM_CLIP(Rule, PAIR_LR, MASKED, true)}
 #define OPTIM_INSTANCES(Rule) {{OPTIM_EMA(Rule, false, false), OPTIM_EMA(Rule, false, true)}, {OPTIM_EMA(Rule, true, false), OPTIM_EMA(Rule, true, true)}}
-    static constexpr decltype(&optim_kernel<AdamRule, false, false, false>) kernels[3][2][2][2] = {
-        OPTIM_INSTANCES(AdamRule), OPTIM_INSTANCES(RmspropRule), OPTIM_INSTANCES(SgdRule)};   // [kind][PAIR_LR][MASKED][EMA]
+    static constexpr decltype(&optim_kernel<AdamRule, false, false, false, false>) kernels[3][2][2][2][2] = {
+        OPTIM_INSTANCES(AdamRule), OPTIM_INSTANCES(RmspropRule), OPTIM_INSTANCES(SgdRule)};   // [kind][PAIR_LR][MASKED][EMA][CLIP]
 #undef OPTIM_INSTANCES
 #undef OPTIM_EMA
+#undef OPTIM_CLIP
     if (a.kind < SPLICE_OPT_ADAM || a.kind > SPLICE_OPT_SGD) {
         splice_set_error("optimiser: unknown optimiser kind %d", a.kind);
         return SPLICE_ERR_ARG;
@@ -170,14 +218,131 @@ int optim_launch(const OptimArgs& a, hipStream_t s) {
         splice_set_error("optimiser: a weight average needs 0 < ema_decay < 1, ema_start >= 0 and a step count (on the device, or step >= 1)");
         return SPLICE_ERR_ARG;
     }
+    // the clip records are indexed like the stop records
+    if (a.clip && (a.clip_stride % 4 || a.n > 0xFFFFFFFFull || a.clip_stride > 0xFFFFFFFFull || (a.lr_stride && a.clip_stride != a.lr_stride) ||
+                   (a.mask && a.clip_stride != a.mask_stride))) {
+        splice_set_error("optimiser: a clipped update needs a slot stride that is a multiple of 4 (that of the per-pair lr and of the mask where they are set) and < 2^32 elements");
+        return SPLICE_ERR_ARG;
+    }
     // a host step count: the bias corrections come from the HOST's powf (host and device powf need not agree to the bit, so a caller
     // stays with the form it has)
     const float bc1 = host_step ? 1.0f - powf(a.hp0, (float)a.step) : 1.f;
     const float bc2_sqrt = host_step ? sqrtf(1.0f - powf(a.hp1, (float)a.step)) : 1.f;
-    const auto kernel = kernels[a.kind][a.lr_stride != 0][a.mask != nullptr][a.ema != nullptr];
+    const auto kernel = kernels[a.kind][a.lr_stride != 0][a.mask != nullptr][a.ema != nullptr][a.clip != nullptr];
     SPLICE_LAUNCH(kernel, dim3(optim_grid(a.n)), dim3(256), 0, s, a.p, a.g, a.m, a.v, a.n, a.lr, a.hp0, a.hp1, a.eps, bc1, bc2_sqrt, a.zero_grad,
                   adam ? a.step_dev : nullptr, a.g2, a.lr_dev, (unsigned)a.lr_stride, a.mask, a.mask_step, (unsigned)a.mask_stride,
-                  a.ema, a.ema_decay, a.ema_start, ema_step_dev, a.step);
+                  a.ema, a.ema_decay, a.ema_start, ema_step_dev, a.step, a.clip, (unsigned)a.clip_stride);
+    return SPLICE_OK;
+}
+
+// ---- the gradient norm of every pair (include/splice_hip.h states the rule).  No float atomics and a fixed
+// assignment of elements to threads and of chunks to partials, counted from the start of the pair's arena: a pair's sum does not depend
+// on the other pairs of the launch.
+// Stage 1: workgroup (chunk, pair) sums the squares of SPLICE_CLIP_CHUNK floats.  An arena that is not 16-byte aligned (and the float4
+// that straddles n) is read element by element into the same thread and component, so the bits are the same.
+static_assert(SPLICE_CLIP_CHUNK == 4 * 4 * 256, "a chunk is four float4 rounds of 256 threads");
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, const float* __restrict__ g2, size_t stride, size_t n,
+                                                         float* __restrict__ partials, const splice_stop_state* __restrict__ stop,
+                                                         const int* __restrict__ step_dev) {
+#pragma clang fp contract(off)
+    __shared__ float sm[256];
+    const unsigned pair = blockIdx.y, t = threadIdx.x;
+    if (stop && stop_frozen(stop + pair, *step_dev - 1)) return;
+    const float* a = g + (size_t)pair * stride;
+    const float* b = g2 ? g2 + (size_t)pair * stride : nullptr;
+    const bool vec = ((reinterpret_cast<size_t>(a) | reinterpret_cast<size_t>(b)) & 15) == 0;
+    float acc = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const size_t e = (size_t)blockIdx.x * SPLICE_CLIP_CHUNK + (size_t)j * 1024 + t * 4;
+        float s[4] = {0.f, 0.f, 0.f, 0.f};   // (an element at or beyond n adds +0)
+        if (vec && e + 4 <= n) {
+            const float4 x = *reinterpret_cast<const float4*>(a + e);
+            s[0] = x.x; s[1] = x.y; s[2] = x.z; s[3] = x.w;
+            if (b) {
+                const float4 y = *reinterpret_cast<const float4*>(b + e);
+                s[0] += y.x; s[1] += y.y; s[2] += y.z; s[3] += y.w;
+            }
+        } else {
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                if (e + c < n) {
+                    s[c] = a[e + c];
+                    if (b) s[c] += b[e + c];
+                }
+        }
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc += s[c] * s[c];
+    }
+    // the halving tree a[t] += a[t + off]: off = 128 and 64 across the waves through LDS, 32 .. 1 inside wave 0 (lane t < off reads t + off)
+    sm[t] = acc;
+    __syncthreads();
+    if (t < 64) {
+        float v = (sm[t] + sm[t + 128]) + (sm[t + 64] + sm[t + 192]);
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+        if (t == 0) partials[(size_t)pair * gridDim.x + blockIdx.x] = v;
+    }
+}
+// Stage 2: workgroup = pair.  The partials in fp64 (their order is fixed, the rounding of 254 of them no longer shows in the fp32 result),
+// then the record.  Thread 0 alone writes it.
+__global__ __launch_bounds__(256) void grad_clip_coef_kernel(const float* __restrict__ partials, unsigned chunks, float max_norm,
+                                                             splice_clip_state* __restrict__ state, const splice_stop_state* __restrict__ stop,
+                                                             const int* __restrict__ step_dev) {
+#pragma clang fp contract(off)
+    __shared__ double sd[256];
+    const unsigned pair = blockIdx.x, t = threadIdx.x;
+    if (stop && stop_frozen(stop + pair, *step_dev - 1)) return;
+    const float* part = partials + (size_t)pair * chunks;
+    double acc = 0.0;
+    for (unsigned i = t; i < chunks; i += 256) acc += (double)part[i];
+    sd[t] = acc;
+    __syncthreads();
+    if (t < 64) {
+        double v = (sd[t] + sd[t + 128]) + (sd[t + 64] + sd[t + 192]);
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+        if (t == 0) {
+            splice_clip_state r = state[pair];
+            r.sumsq = (float)v;
+            r.norm = sqrtf(r.sumsq);
+            if (r.norm <= 3.402823466e+38f) {   // finite (a NaN compares false)
+                r.coef = fminf(1.f, max_norm / (r.norm + 1e-6f));
+                r.skip = 0;
+                r.clipped += r.coef < 1.f ? 1 : 0;
+            } else {
+                r.coef = 0.f;
+                r.skip = 1;
+                r.skipped += 1;
+            }
+            state[pair] = r;
+        }
+    }
+}
+
+int grad_norm_launch(const float* g, const float* g2, int pairs, size_t stride, size_t n, float max_norm, float* partials, splice_clip_state* state,
+                     const splice_stop_state* stop, const int* step_dev, hipStream_t s) {
+    if (!(max_norm > 0.f) || !(max_norm <= 3.402823466e+38f)) {
+        splice_set_error("gradient clipping: max_norm must be a finite number > 0, got %g", (double)max_norm);
+        return SPLICE_ERR_ARG;
+    }
+    if (!g || !partials || !state || pairs < 1 || n < 1 || (stop && !step_dev)) {
+        splice_set_error("gradient clipping (max_norm %g): needs the gradient arena, the partials and the state records, n_pairs >= 1, n >= 1 and the device step count with stop records",
+                         (double)max_norm);
+        return SPLICE_ERR_ARG;
+    }
+    if (pairs > 1 && (stride % 4 || stride < n)) {
+        splice_set_error("gradient clipping (max_norm %g): more than one pair needs n <= stride with stride a multiple of 4", (double)max_norm);
+        return SPLICE_ERR_ARG;
+    }
+    const size_t chunks = (n + SPLICE_CLIP_CHUNK - 1) / SPLICE_CLIP_CHUNK;
+    if (chunks > 0x7FFFFFFFull || pairs > 65535) {
+        splice_set_error("gradient clipping (max_norm %g): at most 65535 pairs of < 2^43 floats", (double)max_norm);
+        return SPLICE_ERR_ARG;
+    }
+    if (pairs == 1) stride = 0;
+    SPLICE_LAUNCH(grad_sumsq_kernel, dim3((unsigned)chunks, (unsigned)pairs), dim3(256), 0, s, g, g2, stride, n, partials, stop, step_dev);
+    SPLICE_LAUNCH(grad_clip_coef_kernel, dim3((unsigned)pairs), dim3(256), 0, s, (const float*)partials, (unsigned)chunks, max_norm, state, stop, step_dev);
     return SPLICE_OK;
 }
 
@@ -232,6 +397,37 @@ int splice_optim_step_pairs_ema(int kind, float* params, float* grads, const flo
     a.step_dev = step_dev;
     if (stop) { a.mask = stop; a.mask_step = step_dev; a.mask_stride = (size_t)stride; }
     a.ema = ema; a.ema_decay = ema_decay; a.ema_start = ema_start;
+    return optim_launch(a, (hipStream_t)stream);
+}
+// as splice_optim_step_ema (ema optional) with the one clip record of this gradient: the host-step form of the clipped update
+int splice_optim_step_clip(int kind, float* params, float* grads, const float* g2, float* m, float* v, float* ema, long long n, float lr,
+                           const float* lr_dev, float hp0, float hp1, float eps, int step, int zero_grad, float ema_decay, int ema_start,
+                           const splice_clip_state* clip, splice_stream_t stream) {
+    if (!clip) { splice_set_error("splice_optim_step_clip: needs the clip record"); return SPLICE_ERR_ARG; }
+    OptimArgs a = optim_args(kind, params, grads, g2, m, v, n, lr, lr_dev, 0, hp0, hp1, eps, step, zero_grad);
+    if (ema) { a.ema = ema; a.ema_decay = ema_decay; a.ema_start = ema_start; }
+    a.clip = clip;
+    return optim_launch(a, (hipStream_t)stream);
+}
+int splice_grad_norm_pairs(const float* grads, const float* g2, int n_pairs, long long stride, long long n, float max_norm, float* partials,
+                           splice_clip_state* state, const splice_stop_state* stop, const int* step_dev, splice_stream_t stream) {
+    return grad_norm_launch(grads, g2, n_pairs, stride < 0 ? 1 : (size_t)stride, n < 1 ? 0 : (size_t)n, max_norm, partials, state, stop, step_dev,
+                            (hipStream_t)stream);
+}
+// as splice_optim_step_pairs_ema (ema optional) with the clip records of splice_grad_norm_pairs; one pair: a single arena of n floats
+int splice_optim_step_pairs_clip(int kind, float* params, float* grads, const float* g2, float* m, float* v, float* ema, int n_pairs, long long stride,
+                                 long long n, const float* lr_dev, float hp0, float hp1, float eps, const int* step_dev, const splice_stop_state* stop,
+                                 int zero_grad, float ema_decay, int ema_start, const splice_clip_state* clip, splice_stream_t stream) {
+    if (!params || !grads || !clip || !lr_dev || !step_dev || n_pairs < 1 || n < 1 || (n_pairs > 1 && (stride < n || stride % 4))) {
+        splice_set_error("splice_optim_step_pairs_clip: needs the clip records, a device lr table and step count, n_pairs >= 1, n >= 1 and, for more than one pair, n <= stride with stride a multiple of 4");
+        return SPLICE_ERR_ARG;
+    }
+    const size_t slot = n_pairs > 1 ? (size_t)stride : 0;   // one pair: a single arena, slot 0 of every table
+    OptimArgs a = optim_args(kind, params, grads, g2, m, v, n_pairs > 1 ? (long long)n_pairs * stride : n, 0.f, lr_dev, slot, hp0, hp1, eps, 0, zero_grad);
+    a.step_dev = step_dev;
+    if (stop) { a.mask = stop; a.mask_step = step_dev; a.mask_stride = slot; }
+    if (ema) { a.ema = ema; a.ema_decay = ema_decay; a.ema_start = ema_start; }
+    a.clip = clip; a.clip_stride = slot;
     return optim_launch(a, (hipStream_t)stream);
 }
 }

@@ -120,6 +120,11 @@ struct SpliceStep {
     float* ema = nullptr;
     float ema_decay = 0.f;
     int ema_start = 0;
+    // gradient clipping (splice_step_set_grad_clip): the caller's [pairs] records and the handle's chunk partials; null: off -- the step
+    // launches what it always did
+    splice_clip_state* clip = nullptr;
+    float* clip_partials = nullptr;
+    float clip_norm = 0.f;
 };
 
 static size_t arena_floats(const SpliceStep* st) { return st->astride ? st->pairs * st->astride : (size_t)st->nparams; }   // of all pairs' arenas
@@ -486,6 +491,7 @@ int splice_step_set_mode(void* h, int skip_adam, int accumulate) {
     if (!st || (accumulate && !skip_adam)) return SPLICE_ERR_ARG;
     if (skip_adam && st->stop_rule.window > 0) { splice_set_error("splice_step_set_mode: a handle with a stop rule runs whole steps (no gradient-only mode)"); return SPLICE_ERR_STATE; }
     if (skip_adam && st->ema) { splice_set_error("splice_step_set_mode: a handle with a weight average runs whole steps (no gradient-only mode)"); return SPLICE_ERR_STATE; }
+    if (skip_adam && st->clip) { splice_set_error("splice_step_set_mode: a handle with gradient clipping runs whole steps (no gradient-only mode)"); return SPLICE_ERR_STATE; }
     if (st->skip_adam != (skip_adam ? 1 : 0) || st->accumulate != (accumulate ? 1 : 0)) st->graphs.retire();
     st->skip_adam = skip_adam ? 1 : 0; st->accumulate = accumulate ? 1 : 0;
     return SPLICE_OK;
@@ -571,6 +577,7 @@ int splice_step_set_phases(void* h, int phases, void* leader) {
     if (!st || phases <= 0 || phases > 7 || leader == h || (leader && phases != 2) || (leader && ((SpliceStep*)leader)->leader)) return SPLICE_ERR_ARG;
     if ((phases != 7 || leader) && st->stop_rule.window > 0) { splice_set_error("splice_step_set_phases: a handle with a stop rule runs whole steps (no phase mode)"); return SPLICE_ERR_STATE; }
     if ((phases != 7 || leader) && st->ema) { splice_set_error("splice_step_set_phases: a handle with a weight average runs whole steps (no phase mode)"); return SPLICE_ERR_STATE; }
+    if ((phases != 7 || leader) && st->clip) { splice_set_error("splice_step_set_phases: a handle with gradient clipping runs whole steps (no phase mode)"); return SPLICE_ERR_STATE; }
     if (st->leader != (SpliceStep*)leader) st->graphs.retire();
     st->phases = phases;
     st->leader = (SpliceStep*)leader;
@@ -609,6 +616,26 @@ int splice_step_set_ema(void* h, float* ema, float decay, int start) {
     }
     st->graphs.retire();
     st->ema = ema; st->ema_decay = decay; st->ema_start = start;
+    return SPLICE_OK;
+}
+// Gradient clipping of every pair of the handle (include/splice_hip.h has the rule): the step's two norm launches write `state`, its optimiser
+// launch reads it.  Before the first step only, and not on a gradient-only or phase-mode handle, as the weight average.
+int splice_step_set_grad_clip(void* h, float max_norm, splice_clip_state* state) {
+    SpliceStep* st = (SpliceStep*)h;
+    if (!st) return SPLICE_ERR_ARG;
+    if (!state || !(max_norm > 0.f) || !(max_norm <= 3.402823466e+38f)) {
+        splice_set_error("splice_step_set_grad_clip: needs the state records and a finite max_norm > 0, got %g", (double)max_norm);
+        return SPLICE_ERR_ARG;
+    }
+    if (st->runs > 0) { splice_set_error("splice_step_set_grad_clip: the rule is set before the first step"); return SPLICE_ERR_STATE; }
+    if (st->skip_adam || st->phases != 7 || st->leader) {
+        splice_set_error("splice_step_set_grad_clip: not on a handle in gradient-only (splice_step_set_mode) or phase mode (splice_step_set_phases)");
+        return SPLICE_ERR_STATE;
+    }
+    if (st->astride % 4) { splice_set_error("splice_step_set_grad_clip: the arena stride must be a multiple of 4"); return SPLICE_ERR_ARG; }
+    if (!st->clip_partials) RC(salloc(st, &st->clip_partials, (size_t)st->pairs * (((size_t)st->nparams + SPLICE_CLIP_CHUNK - 1) / SPLICE_CLIP_CHUNK)));
+    st->graphs.retire();
+    st->clip = state; st->clip_norm = max_norm;
     return SPLICE_OK;
 }
 int splice_step_stop_state(void* h, splice_stop_state* out, splice_stream_t stream) {
@@ -821,6 +848,11 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
         a.lr_stride = st->pair_lr ? st->astride : 0;
         if (stop_on) { a.mask = st->stop; a.mask_step = st->dev_t; a.mask_stride = st->astride; }
         if (st->ema) { a.ema = st->ema; a.ema_decay = st->ema_decay; a.ema_start = st->ema_start; }   // (another kernel: the graph pool keys on it)
+        if (st->clip) {   // two launches more: the norm of the gradient the update is about to read, frozen slots left out
+            RC(grad_norm_launch(grads, adam_g2, st->pairs, st->astride, (size_t)st->nparams, st->clip_norm, st->clip_partials, st->clip,
+                                stop_on ? st->stop : nullptr, st->dev_t, s));
+            a.clip = st->clip; a.clip_stride = st->astride;
+        }
         RC(optim_launch(a, s));
     }
     return SPLICE_OK;

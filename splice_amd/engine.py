@@ -28,7 +28,9 @@ DEFAULT_CFG = dict(  # conf/default/config.yaml of the reference
     # extensions (absent from the reference's config): the plateau stop rule, off by default
     stop_window=0, stop_rel=0.01, stop_patience=2, stop_min_steps=0,
     # ... and the weight average kept by the fused update, off by default
-    ema_decay=0.0, ema_start=0)
+    ema_decay=0.0, ema_start=0,
+    # ... and clipping of every pair's gradient by its global norm inside the fused step, off by default
+    grad_clip_norm=0.0)
 
 
 # Per-slot keys of a sweep (MultiPairEngine(pair_cfgs=...), train.train_sweep): the five loss weights in the order of
@@ -78,6 +80,72 @@ def np_ema(e, p, step, decay, start):
         return np.array(p, dtype=f)
     d = f(decay)
     return (d * np.asarray(e, dtype=f) + (f(1) - d) * np.asarray(p, dtype=f)).astype(f)
+
+
+CLIP_CHUNK = 4096   # SPLICE_CLIP_CHUNK
+
+
+def grad_clip_rule(c):
+    """``max_norm`` of the gradient clipping in config ``c``, checked on the host: a finite number
+    ``grad_clip_norm >= 0`` (0: the gradient is not clipped).  Raises ValueError naming the key."""
+    v = c.get("grad_clip_norm", DEFAULT_CFG["grad_clip_norm"])
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or not 0 <= v < float("inf"):
+        raise ValueError(f"'grad_clip_norm' must be a finite number >= 0, got {v!r}")
+    with np.errstate(over="ignore"):
+        if not np.isfinite(np.float32(v)):   # (the kernels take it as a float)
+            raise ValueError(f"'grad_clip_norm' must be a finite float32 number, got {v!r}")
+    return float(v)
+
+
+def _halving_tree(a):
+    """``a[..., t] += a[..., t + off]`` for off = 128, 64, ..., 1 over the last axis (256 wide); returns ``a[..., 0]``."""
+    a = a.copy()
+    off = 128
+    while off:
+        a[..., :off] = a[..., :off] + a[..., off:2 * off]
+        off //= 2
+    return a[..., 0]
+
+
+def np_grad_clip(g, g2, max_norm):
+    """The rule of the gradient clipping (``splice_grad_norm_pairs``; include/splice_hip.h) restated in NumPy, one float32 rounding
+    per operation where the kernels work in fp32: ``(sumsq, norm, coef, skip)`` of ONE pair's gradient ``g`` (+ ``g2`` unless None),
+    the first three float32 scalars."""
+    f = np.float32
+    with np.errstate(all="ignore"):
+        s = np.asarray(g, dtype=f).reshape(-1)
+        if g2 is not None:
+            s = (s + np.asarray(g2, dtype=f).reshape(-1)).astype(f)
+        n = s.size
+        chunks = (n + CLIP_CHUNK - 1) // CLIP_CHUNK
+        sq = np.zeros(chunks * CLIP_CHUNK, dtype=f)
+        sq[:n] = s * s
+        sq = sq.reshape(chunks, 4, 256, 4)   # [chunk][round j][thread t][component c]
+        acc = np.zeros((chunks, 256), dtype=f)
+        for j in range(4):
+            for c in range(4):
+                acc = (acc + sq[:, j, :, c]).astype(f)
+        partials = _halving_tree(acc).astype(np.float64)   # stage 2 in fp64
+        rows = (chunks + 255) // 256
+        pad = np.zeros(rows * 256, dtype=np.float64)
+        pad[:chunks] = partials
+        pad = pad.reshape(rows, 256)
+        acc2 = np.zeros(256, dtype=np.float64)
+        for r in range(rows):
+            acc2 = acc2 + pad[r]
+        sumsq = f(_halving_tree(acc2))
+        norm = np.sqrt(sumsq)
+        if np.isfinite(norm):
+            return sumsq, norm, np.minimum(f(1), f(max_norm) / (norm + f(1e-6))), 0
+        return sumsq, norm, f(0), 1
+
+
+def clip_records(clip_dev):
+    """Host dicts of device ``splice_clip_state`` records held as an int32 tensor ``[P, 6]`` (a synchronising copy)."""
+    raw = clip_dev.cpu().numpy()
+    fl = raw[:, :3].copy().view(np.float32)
+    return [dict(sumsq=fl[p, 0], norm=fl[p, 1], coef=fl[p, 2], skip=int(raw[p, 3]), clipped=int(raw[p, 4]), skipped=int(raw[p, 5]))
+            for p in range(raw.shape[0])]
 
 
 def counted_steps(step_idx, cls_warmup, entire_every=0):
@@ -173,6 +241,8 @@ class MultiPairEngine:
         self.stop_rule = stop_rule(self.cfg)   # (host checks first: nothing below this line has touched a GPU yet)
         self.ema_rule = ema_rule(self.cfg)
         self.ema = None
+        self.grad_clip = grad_clip_rule(self.cfg)
+        self.clip_dev = None
         P_in = len(gen_states)
         self.cfgs = [self.cfg] * P_in
         self._pair_lambdas = self._pair_lr = False
@@ -295,6 +365,10 @@ class MultiPairEngine:
         if self.ema_rule[0] > 0:
             self.ema = self.params.clone()
             _lib.check(_lib.lib().splice_step_set_ema(self.handle, _lib.ptr(self.ema), *self.ema_rule), "step_set_ema")
+        # gradient clipping (shared by the slots): one record per slot on the device, written by the step's norm launches; before the first step
+        if self.grad_clip > 0:
+            self.clip_dev = torch.zeros(P, 6, dtype=torch.int32, device=self.device)
+            _lib.check(_lib.lib().splice_step_set_grad_clip(self.handle, self.grad_clip, _lib.ptr(self.clip_dev)), "step_set_grad_clip")
         self._stopped = [None] * P   # the host's copy of every slot's stop step, refreshed by stop_state()
         self._stop_dirty = False     # a window has closed since the last stop_state(): the copy may be behind
         if self._pair_lambdas:
@@ -381,6 +455,16 @@ class MultiPairEngine:
     def _frozen(self, pair):
         k = self._stops()[pair] if self.stop_rule[0] > 0 else None
         return k is not None and self.step_idx > k
+
+    def clip_state(self, pair=None):
+        """The gradient-clipping record(s) of the last step (``grad_clip_norm > 0``), copied from the device (waits for the current
+        stream): ``sumsq`` / ``norm`` of the slot's gradient, the ``coef`` its update multiplied it by, ``skip`` (the norm was not
+        finite, the slot was not updated) and the counts ``clipped`` / ``skipped`` of such steps so far.  One dict for ``pair``, a list
+        over the slots for ``pair=None``."""
+        if self.clip_dev is None:
+            raise RuntimeError("clip_state: the gradient is not clipped (grad_clip_norm == 0)")
+        dicts = clip_records(self.clip_dev)
+        return dicts if pair is None else dicts[pair]
 
     def losses(self, pair=None):
         """Host dict(s) of the last step's losses with the reference's keys (inactive terms omitted): one dict for ``pair``,
@@ -473,6 +557,9 @@ class SpliceEngine(MultiPairEngine):
     def losses(self):
         return super().losses(0)
 
+    def clip_state(self, pair=None):
+        return super().clip_state(0)
+
     @property
     def stopped_at(self):
         """The step index the pair stopped at (the plateau stop rule), or None."""
@@ -495,11 +582,13 @@ class MultiScaleEngine:
             raise NotImplementedError("stop_window > 0: the plateau stop rule lives in the fused step's own update; MultiScaleEngine updates outside the step")
         self.ema_rule = ema_rule(self.cfg)
         self.ema = None
+        self.grad_clip = grad_clip_rule(self.cfg)
+        self.clip_dev = None
         self.scales = tuple(scales)
         self.engines = []
         for k, sz in enumerate(self.scales):
-            # (ema_decay=0: the handles are gradient-only, the average rides in this engine's own update below)
-            e = SpliceEngine(dict(self.cfg, dino_global_patch_size=sz, ema_decay=0.0), vit_state if k == 0 else None, gen_state, crop_hw, entire_hw, device=device,
+            # (ema_decay=0, grad_clip_norm=0: the handles are gradient-only, the average and the clipping ride in this engine's own update below)
+            e = SpliceEngine(dict(self.cfg, dino_global_patch_size=sz, ema_decay=0.0, grad_clip_norm=0.0), vit_state if k == 0 else None, gen_state, crop_hw, entire_hw, device=device,
                              vit_engine=vit_engine if k == 0 else self.engines[0].vit, n_crops=n_crops, fp8=fp8)
             _lib.check(_lib.lib().splice_step_set_mode(e.handle, 1, 0), "step_set_mode")
             if k > 0:   # one parameter set: every scale sees the arenas of the first engine; netG bookkeeping once
@@ -511,10 +600,18 @@ class MultiScaleEngine:
         self.params, self.grads = self.engines[0].params, self.engines[0].grads
         if self.ema_rule[0] > 0:
             self.ema = self.engines[0].ema = self.params.clone()   # (the leader serves pair_ema / generate / state_dict with it)
+        if self.grad_clip > 0:
+            self.clip_dev = torch.zeros(1, 6, dtype=torch.int32, device=self.params.device)
         self.step_idx = -1
         self.opt_kind, *self.opt_hp = fused_optimizer(self.cfg)
         self.schedule = LrSchedule(self.cfg)
         self.lr = None
+
+    def clip_state(self, pair=None):
+        """The gradient-clipping record of the last step, as ``SpliceEngine.clip_state``."""
+        if self.clip_dev is None:
+            raise RuntimeError("clip_state: the gradient is not clipped (grad_clip_norm == 0)")
+        return clip_records(self.clip_dev)[0]
 
     def step(self, A_crop, B_crop, A_entire=None):
         from .generator import optim_step
@@ -528,7 +625,7 @@ class MultiScaleEngine:
         e0.step(A_crop, B_crop, A_entire, _repeat=True)      # G backward of the summed image gradient
         self.lr = self.schedule.lr(self.step_idx)
         optim_step(self.opt_kind, e0.params, e0.grads, e0.m, e0.v, self.lr, *self.opt_hp, self.step_idx + 1, ema=self.ema,
-                   ema_decay=self.ema_rule[0], ema_start=self.ema_rule[1])
+                   ema_decay=self.ema_rule[0], ema_start=self.ema_rule[1], clip_norm=self.grad_clip, clip_state=self.clip_dev)
 
     def losses(self):
         """Per-scale loss dicts and their sum: ``{"loss": total, "scales": {224: {...}, ...}}``."""

@@ -171,12 +171,16 @@ def adam_step(params, grads, m, v, lr, beta1, beta2, eps, step, zero_grad=False)
 OPTIMIZER_KINDS = {"adam": 0, "rmsprop": 1, "sgd": 2}   # the `kind` of splice_optim_step
 
 
-def optim_step(kind, params, grads, m, v, lr, hp0, hp1, eps, step, zero_grad=False, g2=None, lr_dev=None, ema=None, ema_decay=0.0, ema_start=0):
+def optim_step(kind, params, grads, m, v, lr, hp0, hp1, eps, step, zero_grad=False, g2=None, lr_dev=None, ema=None, ema_decay=0.0, ema_start=0,
+               clip_norm=0.0, clip_state=None):
     """One fused optimiser step over a flat arena (``splice_optim_step_ex``): kind 0 Adam (hp0 / hp1 = betas, step >= 1),
     1 RMSprop (hp0 = alpha, ``v`` = square_avg, ``m`` unused), 2 SGD (``m`` / ``v`` unused).  ``g2``: second gradient arena
     added to ``grads`` first; ``lr_dev``: one-element device tensor read as the learning rate when the kernel runs.
     ``ema``: the weight-average arena, written in the same walk (``splice_optim_step_ema``): ``step <= ema_start``: a copy of the
-    parameters just written, later ``ema_decay * ema + (1 - ema_decay) * params``; every kind then needs ``step >= 1``."""
+    parameters just written, later ``ema_decay * ema + (1 - ema_decay) * params``; every kind then needs ``step >= 1``.
+    ``clip_norm > 0``: the gradient (``grads + g2``) is clipped to that global norm first, as ``torch.nn.utils.clip_grad_norm_``, and an
+    update whose norm is not finite is skipped (``splice_grad_norm_pairs`` then ``splice_optim_step_clip``); ``clip_state``: the int32
+    CUDA tensor of 6 elements that receives the ``splice_clip_state`` record (its two counts are the caller's to start at zero)."""
     if kind not in OPTIMIZER_KINDS.values():
         raise ValueError(f"optim_step: unknown optimiser kind {kind}")
     m = m if kind == 0 else None            # arenas the kind does not touch are not passed
@@ -190,6 +194,16 @@ def optim_step(kind, params, grads, m, v, lr, hp0, hp1, eps, step, zero_grad=Fal
             raise ValueError(f"optim_step: {name} must be a contiguous fp32 CUDA tensor of {n} elements")
     if lr_dev is not None and not (lr_dev.is_cuda and lr_dev.dtype == torch.float32 and lr_dev.numel() >= 1):
         raise ValueError("optim_step: lr_dev must be a fp32 CUDA tensor")
+    if clip_norm:
+        if clip_state is None or not (clip_state.is_cuda and clip_state.dtype == torch.int32 and clip_state.is_contiguous() and clip_state.numel() == 6):
+            raise ValueError("optim_step: clip_state must be a contiguous int32 CUDA tensor of 6 elements")
+        partials = torch.empty((n + 4095) // 4096, dtype=torch.float32, device=params.device)
+        _lib.check(_lib.lib().splice_grad_norm_pairs(_lib.ptr(grads), _lib.ptr(g2), 1, 0, n, float(clip_norm), _lib.ptr(partials), _lib.ptr(clip_state),
+                                                     None, None, _lib.current_stream()), "grad_norm_pairs")
+        _lib.check(_lib.lib().splice_optim_step_clip(int(kind), _lib.ptr(params), _lib.ptr(grads), _lib.ptr(g2), _lib.ptr(m), _lib.ptr(v), _lib.ptr(ema), n,
+                                                     float(lr), _lib.ptr(lr_dev), float(hp0), float(hp1), float(eps), int(step), int(zero_grad),
+                                                     float(ema_decay), int(ema_start), _lib.ptr(clip_state), _lib.current_stream()), "optim_step_clip")
+        return
     if ema is not None:
         _lib.check(_lib.lib().splice_optim_step_ema(int(kind), _lib.ptr(params), _lib.ptr(grads), _lib.ptr(g2), _lib.ptr(m), _lib.ptr(v), _lib.ptr(ema), n,
                                                     float(lr), _lib.ptr(lr_dev), float(hp0), float(hp1), float(eps), int(step), int(zero_grad),

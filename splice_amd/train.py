@@ -266,6 +266,16 @@ def _ema_images(engine, writers, As):
         writers[p].submit(engine.generate(A, pair=p, ema=True)[0], force=True, name="output_ema.png")
 
 
+def clip_fields(engine, slot=None):
+    """What ``result.json`` says about the gradient clipping of a run (``splice_amd.batch``): ``grad_clip_norm`` (0: the gradient was
+    not clipped), and for ``slot`` (None: the one pair of the engine) ``clipped_steps`` -- steps whose gradient norm exceeded it --
+    and ``skipped_steps`` -- steps whose norm was not finite and did not update the slot."""
+    if engine.clip_dev is None or engine.step_idx < 0:
+        return {"grad_clip_norm": engine.grad_clip, "clipped_steps": 0, "skipped_steps": 0}
+    rec = engine.clip_state(slot)
+    return {"grad_clip_norm": engine.grad_clip, "clipped_steps": rec["clipped"], "skipped_steps": rec["skipped"]}
+
+
 def train_pairs(dataroots, callback=None, cfg_overrides=None, vit_state=None, progress=True):
     """``train_model`` for P pairs on ONE GPU in the same kernel launches (``MultiPairEngine``): P independent optimisations that
     share only the frozen ViT -- the throughput form of the reference's one-pair-per-process loop (train.py:34-80).  ``dataroots``:
