@@ -67,7 +67,10 @@ typedef struct splice_gemm_epilogue {
     int ksplit;               /* > 1 with flags == SPLICE_EPI_OUT_F32 only: K is cut into ksplit slices, slice s writes */
     long long slab_stride;    /* out_f32 + s * slab_stride; the consumer adds the slabs in order (deterministic split-K).
                                * With splice_gemm_splitk_slabs(M, ksplit) == 1 (many rows) the slices are summed IN the kernel,
-                               * in the same order -- the same bits -- and only slab 0 is written */
+                               * in the same order -- the same bits -- and only slab 0 is written.
+                               * K % (ksplit * 64) != 0: the call runs UNSPLIT -- slab 0 holds the whole product and the other slabs
+                               * are not written -- while splice_gemm_splitk_slabs(M, ksplit) still answers ksplit: a caller that
+                               * sums the slabs must keep K a multiple of ksplit * 64 (the ViT engine's ks rules do) */
     /* SPLICE_EPI_ROWDOT (with OUT_BF): rowdot[(row / rd_rows) * (N/64) * rd_rows + (col/64) * rd_rows + row % rd_rows]
      * = sum over the 64 columns [col, col+64) of bf16(C[row][c]) * rd_other[row][c] -- the attention backward's
      * delta = rowsum(dO * O) per (pass, head, query), formed where dO is produced (proj dgrad).  N % 64 == 0. */

@@ -4,7 +4,8 @@
 Tolerances: bf16 operands (8 mantissa bits) with fp32 accumulation -> inputs are rounded
 to bf16 first so the comparison isolates the kernel's own arithmetic; remaining error is
 output rounding (bf16 outputs: rel 2^-8) and accumulation order (fp32 outputs: ~1e-5 rel
-of the operand magnitude sum).
+of the operand magnitude sum).  The GEMM epilogues are checked element by element, with padded pitches and sentinels, in
+tests/test_gemm_epilogues_gpu.py; the casts, the transpose and LayerNorm at its edges at the end of this file.
 """
 import ctypes as C
 import os
@@ -509,3 +510,199 @@ def test_resize_kernels_against_independent_numpy_restatement(case, tol):
     torch.cuda.synchronize()
     lhs, rhs = (y.double() * dy.double()).sum().item(), (x.double() * dx.double()).sum().item()
     assert abs(lhs - rhs) < 1e-5 * max(1.0, abs(lhs)), (lhs, rhs)
+
+
+# ---- the small ops beside the GEMM: casts, transpose, LayerNorm at its edges ----------------------------------------------------
+
+def _f32_from_bits(vals):
+    return torch.tensor([v - (1 << 32) if v >= (1 << 31) else v for v in vals], dtype=torch.int32).view(torch.float32)
+
+
+# fp32 bit patterns where a cast to bf16 goes wrong first: exact ties in both directions (round to even), one below / above a tie, the ends
+# of a binade (the carry into the next one), +-0, subnormals (ties among them, the largest rounds up to the smallest normal), +-inf, the
+# largest finite bf16, and values that round to inf (the tie at the top and the largest finite fp32)
+_CAST_SPECIALS = [0x3F808000, 0x3F818000, 0xBF808000, 0xBF818000, 0x3F807FFF, 0x3F808001, 0x3F817FFF, 0x3F818001,
+                  0x3F800000, 0x3FFFFFFF, 0x3FFF8000, 0x3FFF7FFF, 0x40000000, 0xBFFFFFFF,
+                  0x00000000, 0x80000000, 0x00000001, 0x00008000, 0x00008001, 0x00018000, 0x007FFFFF, 0x807FFFFF, 0x00800000,
+                  0x7F800000, 0xFF800000, 0x7F7F0000, 0x7F7F7FFF, 0x7F7F8000, 0x7F7FFFFF, 0xFF7FFFFF]
+
+
+def _cast_input(n):
+    g = torch.Generator().manual_seed(50)
+    x = torch.randn(n, generator=g) * torch.exp2(torch.randint(-40, 40, (n,), generator=g).float())
+    sp = _f32_from_bits(_CAST_SPECIALS)
+    k = min(n, sp.numel())
+    x[:k] = sp[:k]
+    return x
+
+
+@pytest.mark.parametrize("n", [1, 255, 257, 4096 * 256 + 3])   # the last: the grid-stride loop takes a second trip
+def test_cast_f32_bf16_bit_exact(n):
+    """splice_cast_f32_bf16 (packs every frozen weight at load) against torch's round-to-nearest-even conversion on the CPU, bit for bit;
+    NaN stays NaN; element n of the output keeps its sentinel."""
+    L = _lib.lib()
+    x = _cast_input(n)
+    want = x.to(torch.bfloat16)
+    y = torch.full((n + 8,), -7.0, device=DEV, dtype=torch.bfloat16)
+    xd = x.to(DEV)
+    _lib.check(L.splice_cast_f32_bf16(_lib.ptr(xd), _lib.ptr(y), n, _st()))
+    torch.cuda.synchronize()
+    got = y.cpu()
+    bad = (got[:n].view(torch.int16) != want.view(torch.int16)).nonzero().flatten()
+    assert bad.numel() == 0, (n, bad[:8].tolist(), x[bad[:8]].view(torch.int32).tolist(), got[bad[:8]].view(torch.int16).tolist())
+    assert (got[n:] == -7.0).all(), "written past element n - 1"
+    # NaNs, among them payloads in the low 16 bits only (a truncating cast would turn those into inf)
+    nan = _f32_from_bits([0x7FC00000, 0x7F800001, 0x7F80FFFF, 0xFFFFFFFF, 0x7FFFFFFF, 0xFF800100]).to(DEV)
+    yn = torch.full((nan.numel() + 1,), -7.0, device=DEV, dtype=torch.bfloat16)
+    _lib.check(L.splice_cast_f32_bf16(_lib.ptr(nan), _lib.ptr(yn), nan.numel(), _st()))
+    torch.cuda.synchronize()
+    assert torch.isnan(yn[:-1].float()).all() and yn[-1].item() == -7.0, yn.view(torch.int16).tolist()
+
+
+@pytest.mark.parametrize("n", [1, 255, 257, 4096 * 256 + 3])
+def test_cast_bf16_f32_exact(n):
+    """splice_cast_bf16_f32 is exact: every bf16 bit pattern (n >= 65536) widened bit for bit; NaN stays NaN; element n keeps its sentinel."""
+    bits = ((torch.arange(n, dtype=torch.int64) * 40503 + 0x3F80) % 65536)   # n = 1: 1.0; an odd multiplier walks all 65536 patterns
+    x = (bits - (bits >= 32768) * 65536).to(torch.int16).view(torch.bfloat16)
+    want = bits << 16
+    want = (want - (want >= 2 ** 31) * 2 ** 32).to(torch.int32)
+    y = torch.full((n + 8,), -12345.0, device=DEV)
+    xd = x.to(DEV)
+    _lib.check(_lib.lib().splice_cast_bf16_f32(_lib.ptr(xd), _lib.ptr(y), n, _st()))
+    torch.cuda.synchronize()
+    got = y.cpu()
+    isnan = torch.isnan(x.float())
+    assert torch.equal(got[:n].view(torch.int32)[~isnan], want[~isnan])
+    assert torch.isnan(got[:n][isnan]).all()
+    assert (got[n:] == -12345.0).all(), "written past element n - 1"
+
+
+@pytest.mark.parametrize("rows,cols,ldy", [(1, 1, 4), (33, 31, 40), (70, 100, 72)])
+def test_transpose_f32_bf16_bit_exact(rows, cols, ldy):
+    """splice_transpose_f32_bf16: y [cols][ldy] = bf16(x^T) bit for bit; columns [rows, ldy) and the rows behind stay untouched."""
+    x = _rand(rows, cols, seed=51)
+    y = torch.full((cols + 2, ldy), -7.0, device=DEV, dtype=torch.bfloat16)
+    _lib.check(_lib.lib().splice_transpose_f32_bf16(_lib.ptr(x), _lib.ptr(y), rows, cols, ldy, _st()))
+    torch.cuda.synchronize()
+    want = x.cpu().T.contiguous().to(torch.bfloat16)
+    assert torch.equal(y[:cols, :rows].cpu().view(torch.int16), want.view(torch.int16))
+    assert (y[:cols, rows:] == -7.0).all() and (y[cols:] == -7.0).all()
+
+
+def _ln_refs(x, gamma, beta, eps, dtype):
+    x, gamma, beta = x.to(dtype), gamma.to(dtype), beta.to(dtype)
+    mean = x.mean(1, keepdim=True)
+    var = ((x - mean) ** 2).mean(1, keepdim=True)
+    rstd = (var + eps).rsqrt()
+    return (x - mean) * rstd * gamma + beta, mean[:, 0], rstd[:, 0]
+
+
+def _ln_bwd_ref(dy, x, gamma, mean, rstd, g_in, dtype):
+    dy, x, gamma, mean, rstd, g_in = (t.to(dtype) for t in (dy, x, gamma, mean[:, None], rstd[:, None], g_in))
+    xh, dh = (x - mean) * rstd, dy * gamma
+    return rstd * (dh - dh.mean(1, keepdim=True) - xh * (dh * xh).mean(1, keepdim=True)) + g_in
+
+
+_LN_WORST = {}
+
+
+def _ln_check(x, gamma, beta, tag):
+    """Forward and backward of one LayerNorm problem, element-wise.  Bars: bf16 outputs 2^-8 |ref| + e32, where e32 = 4 x the element-wise
+    error of a plain fp32 torch evaluation against the fp64 reference on the same input (the factor allows another summation order); fp32 g_out:
+    e32 with a floor of 2^-22 x max |ref| of the row.  The backward takes the fp64 reference's mean / rstd rounded to fp32, so it is checked
+    independently of the forward kernel.  Returns the kernel outputs."""
+    L = _lib.lib()
+    rows, D = x.shape
+    eps = 1e-6
+    y = torch.full((rows + 1, D), -7.0, device=DEV, dtype=torch.bfloat16)
+    mean, rstd = torch.full((rows + 1,), -12345.0, device=DEV), torch.full((rows + 1,), -12345.0, device=DEV)
+    _lib.check(L.splice_layernorm_fwd(_lib.ptr(x), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(y), _lib.ptr(mean), _lib.ptr(rstd), rows, D, eps, _st()))
+    y64, m64, r64 = _ln_refs(x, gamma, beta, eps, torch.float64)
+    y32, _, _ = _ln_refs(x, gamma, beta, eps, torch.float32)
+    e32 = 4 * (y32.double() - y64).abs()
+    ratio = ((y[:rows].double() - y64).abs() / (2.0 ** -8 * y64.abs() + e32 + 1e-300)).max().item()
+    margin = (e32 / (2.0 ** -8 * y64.abs() + 1e-300)).max().item()
+    print(f"[layernorm-parity] {tag} fwd: worst err / bound = {ratio:.3f}; worst e32 / (2^-8 |ref|) = {margin:.2e}")
+    assert torch.isfinite(y[:rows].float()).all() and ratio <= 1.0, (tag, "y", ratio)
+    # mean: a D-term fp32 sum; rstd: a D-term sum of non-negative terms and one rsqrtf
+    assert ((mean[:rows].double() - m64).abs() <= (D + 4) * 2.0 ** -24 * x.double().abs().mean(1) + 1e-300).all(), (tag, "mean")
+    # (an error d of the mean adds exactly d^2 to the two-pass variance: 0.5 rstd^3 d^2 on rstd, d bounded as above)
+    d_mean = (D + 4) * 2.0 ** -24 * x.double().abs().mean(1)
+    assert ((rstd[:rows].double() - r64).abs() <= (D + 16) * 2.0 ** -24 * r64 + 0.5 * r64 ** 3 * d_mean ** 2).all(), \
+        (tag, "rstd", ((rstd[:rows].double() - r64).abs() / r64).max().item())
+    assert (y[rows:] == -7.0).all() and mean[rows].item() == -12345.0 and rstd[rows].item() == -12345.0, (tag, "written behind the rows")
+    y_nostat = torch.full_like(y, -7.0)
+    _lib.check(L.splice_layernorm_fwd(_lib.ptr(x), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(y_nostat), None, None, rows, D, eps, _st()))
+    assert torch.equal(y_nostat, y), (tag, "y depends on mean / rstd being requested")
+
+    dy, g_in = _rand(rows, D, seed=61), _rand(rows, D, seed=62)
+    m_in, r_in = m64.float(), r64.float()
+    ref = _ln_bwd_ref(dy, x, gamma, m_in, r_in, g_in, torch.float64)
+    r32 = _ln_bwd_ref(dy, x, gamma, m_in, r_in, g_in, torch.float32)
+    e32 = 4 * (r32.double() - ref).abs()
+
+    def bwd(gi, want_bf):
+        go = torch.full((rows + 1, D), -12345.0, device=DEV)
+        gb = torch.full((rows + 1, D), -7.0, device=DEV, dtype=torch.bfloat16)
+        _lib.check(L.splice_layernorm_bwd(_lib.ptr(dy), _lib.ptr(x), _lib.ptr(gamma), _lib.ptr(m_in), _lib.ptr(r_in), _lib.ptr(gi), _lib.ptr(go),
+                                          _lib.ptr(gb) if want_bf else None, rows, D, _st()))
+        torch.cuda.synchronize()
+        return go, gb
+    go, gb = bwd(g_in, True)
+    b32 = torch.maximum(e32, 2.0 ** -22 * ref.abs().amax(1, keepdim=True))
+    r_f32 = ((go[:rows].double() - ref).abs() / (b32 + 1e-300)).max().item()
+    r_bf = ((gb[:rows].double() - ref).abs() / (2.0 ** -8 * ref.abs() + e32 + 1e-300)).max().item()
+    print(f"[layernorm-parity] {tag} bwd: worst err / bound fp32 = {r_f32:.3f}, bf16 = {r_bf:.3f}")
+    assert torch.isfinite(go[:rows]).all() and r_f32 <= 1.0, (tag, "g_out", r_f32)
+    assert torch.isfinite(gb[:rows].float()).all() and r_bf <= 1.0, (tag, "g_out_bf", r_bf)
+    assert (go[rows:] == -12345.0).all() and (gb[rows:] == -7.0).all(), (tag, "written behind the rows")
+    go2, gb2 = bwd(g_in, False)
+    assert torch.equal(go2, go) and (gb2 == -7.0).all(), (tag, "g_out depends on g_out_bf being requested")
+    go_z, gb_z = bwd(torch.zeros_like(g_in), True)
+    go_n, gb_n = bwd(None, True)
+    assert torch.equal(go_n, go_z) and torch.equal(gb_n, gb_z), (tag, "g_in = NULL differs from g_in = 0")
+    return y, rstd
+
+
+@pytest.mark.parametrize("rows", [1, 7])
+@pytest.mark.parametrize("D", [4, 384, 768, 1024])   # 1024 = the size limit (64 lanes x 4 float4)
+def test_layernorm_elementwise(rows, D):
+    """splice_layernorm_fwd / _bwd element-wise against fp64 at one float4 per row, ViT-S, ViT-B and the size limit; NULL mean / rstd, NULL g_in and
+    NULL g_out_bf leave the other outputs unchanged bit for bit.  Measured on MI355X, worst err / bound: forward 0.445 ... 0.993, backward fp32
+    0.134 ... 0.276, backward bf16 0.701 ... 0.994; the e32 share of the bf16 bar, worst e32 / (2^-8 |ref|): 1e-3 ... 6e-2 (the bar is the bf16
+    rounding; e32 matters only where |ref| is near zero)."""
+    x = _rand(rows, D, seed=60, std=3.0) + 0.5
+    gamma, beta = 1 + 0.1 * _rand(D, seed=9), 0.1 * _rand(D, seed=10)
+    _ln_check(x, gamma, beta, f"rows={rows} D={D}")
+
+
+@pytest.mark.parametrize("D", [1028, 6])
+def test_layernorm_refuses_unsupported_width(D):
+    L = _lib.lib()
+    rows = 3
+    x, gamma, beta = _rand(rows, D, seed=63), torch.ones(D, device=DEV), torch.zeros(D, device=DEV)
+    y = torch.full((rows, D), -7.0, device=DEV, dtype=torch.bfloat16)
+    stat = torch.full((2, rows), -12345.0, device=DEV)
+    assert L.splice_layernorm_fwd(_lib.ptr(x), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(y), _lib.ptr(stat[0]), _lib.ptr(stat[1]), rows, D, 1e-6, _st()) != 0
+    go = torch.full((rows, D), -12345.0, device=DEV)
+    gb = torch.full((rows, D), -7.0, device=DEV, dtype=torch.bfloat16)
+    mean, rstd = torch.zeros(rows, device=DEV), torch.ones(rows, device=DEV)
+    assert L.splice_layernorm_bwd(_lib.ptr(x), _lib.ptr(x), _lib.ptr(gamma), _lib.ptr(mean), _lib.ptr(rstd), None, _lib.ptr(go), _lib.ptr(gb), rows, D, _st()) != 0
+    torch.cuda.synchronize()
+    assert (y == -7.0).all() and (stat == -12345.0).all() and (go == -12345.0).all() and (gb == -7.0).all()
+
+
+@pytest.mark.parametrize("D", [4, 768])
+def test_layernorm_zero_variance_and_large_mean_rows(D):
+    """Row 0 holds one repeated value (1.5: every partial sum of it is exact in fp32, so the mean is exact in any summation order): y == bf16(beta),
+    rstd finite (eps^-1/2), backward finite.  Row 1 has mean 100 and standard deviation 0.1 and meets the same bars as any row: the kernel's two-pass
+    variance survives this, a one-pass E[x^2] - E[x]^2 would not.  Row 2 is an ordinary row.
+    Measured on MI355X, worst err / bound: forward 0.666 (D = 4) / 0.968 (D = 768), backward fp32 0.374 / 0.346, bf16 0.766 / 0.988; worst
+    e32 / (2^-8 |ref|) 0.42 / 7e2 (elements of the large-mean row whose reference is almost zero)."""
+    x = _rand(3, D, seed=64, std=3.0)
+    x[0] = 1.5
+    x[1] = 100.0 + 0.1 * _rand(D, seed=65)
+    gamma, beta = 1 + 0.1 * _rand(D, seed=9), 0.1 * _rand(D, seed=10)
+    y, rstd = _ln_check(x, gamma, beta, f"edge rows D={D}")
+    assert torch.equal(y[0], beta.to(torch.bfloat16)), (y[0].float() - beta).abs().max().item()
+    assert torch.isfinite(rstd[:3]).all() and abs(rstd[0].item() - 1000.0) < 1e-3
