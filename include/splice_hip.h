@@ -539,6 +539,43 @@ int splice_optim_step_clip(int kind, float* params, float* grads, const float* g
  * or phase mode (splice_step_set_phases), which the rule in turn bars.  0 < max_norm < inf. */
 int splice_step_set_grad_clip(void* step, float max_norm, splice_clip_state* state);
 
+/* ------------------------------------------------------------------ keep the best window's weights (an extension of the stop rule).  A slot
+ * stops `patience` windows behind the window the rule judged best, so the weights it is frozen with are not those the rule liked.  While
+ * a slot is LIVE at a counted step -- its stop_step < 0 on entry to the rule -- the rule also writes, at the close of a window:
+ *   best_step = that step's index and best_window = the window's index (`windows` before its increment), where it sets best = mean
+ *     (the first window, or mean < best * (1 - rel));
+ *   means[windows before the increment] = mean, for the first SPLICE_STOP_HISTORY windows.
+ * After its stop the slot's splice_stop_state goes on evolving as it always did; the record and the history no longer move.  The update
+ * of the step whose index equals best_step then copies the parameter it has just written (and the average, where one is kept) into the
+ * caller's best arena: no float is computed again, the snapshot holds the bits of params / ema after that step.  best_mean is
+ * means[best_window], and stop_state.best while the slot is live. */
+#define SPLICE_STOP_HISTORY 64
+typedef struct splice_best_state {
+    int best_step;    /* index of the step that closed the best window so far; -1 until a window has closed */
+    int best_window;  /* index of that window; -1 alike */
+} splice_best_state;
+/* splice_plateau_update with the record and the history: best: device [pairs] records (the caller starts them as -1 / -1), means: device
+ * [pairs][SPLICE_STOP_HISTORY] floats (zeros).  The state is, bit for bit, that of splice_plateau_update. */
+int splice_plateau_update_best(splice_stop_state* state, splice_best_state* best, float* means, const float* losses8, int pairs, int window,
+                               float rel, int patience, int min_steps, int step_idx, int counted, splice_stream_t stream);
+/* as splice_optim_step_pairs_clip -- stop is required here, clip and ema may be NULL -- with the snapshot: a pair that is not frozen and
+ * whose best[p].best_step equals the step index *step_dev - 1 has the params just written copied to best_params, and its ema to best_ema
+ * (both laid out like params; best_ema is given exactly when ema is).  A pair whose clip record has skip set still takes the snapshot, of
+ * its unchanged params / ema.  Nothing else of best_params / best_ema is written; params, grads, m, v and ema are those of
+ * splice_optim_step_pairs_clip. */
+int splice_optim_step_pairs_best(int kind, float* params, float* grads, const float* g2, float* m, float* v, float* ema, int n_pairs,
+                                 long long stride, long long n, const float* lr_dev, float hp0, float hp1, float eps, const int* step_dev,
+                                 const splice_stop_state* stop, int zero_grad, float ema_decay, int ema_start, const splice_clip_state* clip,
+                                 const splice_best_state* best, float* best_params, float* best_ema, splice_stream_t stream);
+/* Keep every pair's best-window weights inside the step: the loss kernel's rule writes `state` and `means` (device, the caller's: [pairs]
+ * records at -1 / -1 and [pairs][SPLICE_STOP_HISTORY] zeros), the optimiser launch of the same step reads the record and writes
+ * best_params (and best_ema; both [P][arena_stride] like params, the caller's, they start as copies of params / ema).  No launch more,
+ * and params / m / v / ema / losses are what they are without it.  Before the first splice_step_run only, on a handle that has a stop
+ * rule (splice_step_set_stop_rule with window > 0), with best_ema given exactly when the handle keeps an average (splice_step_set_ema
+ * comes first); refused on a handle in gradient-only (splice_step_set_mode) or phase mode (splice_step_set_phases), which it in turn
+ * bars. */
+int splice_step_set_keep_best(void* step, float* best_params, float* best_ema, splice_best_state* state, float* means);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,6 +56,12 @@ class ClipState(C.Structure):   # splice_clip_state
     _fields_ = [("sumsq", C.c_float), ("norm", C.c_float), ("coef", C.c_float), ("skip", C.c_int), ("clipped", C.c_int), ("skipped", C.c_int)]
 
 
+class BestState(C.Structure):   # splice_best_state
+    _fields_ = [("best_step", C.c_int), ("best_window", C.c_int)]
+
+
+STOP_HISTORY = 64   # SPLICE_STOP_HISTORY
+
 EPI_BIAS, EPI_RESID, EPI_OUT_F32, EPI_OUT_BF, EPI_OUT_T = 1, 2, 4, 8, 16
 EPI_GELU, EPI_GELU_GRAD, EPI_COLS_F32, EPI_ALPHA, EPI_ROWDOT, EPI_SCALE_RC, EPI_OUT_F8, EPI_OUT_F8T = 32, 64, 128, 256, 512, 1024, 2048, 4096
 
@@ -134,6 +140,10 @@ _SIGNATURES = {
     "splice_optim_step_pairs_clip": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_longlong, C.c_longlong, _vp, _f, _f, _f, _vp, _vp, _i, _f, _i, _vp, _vp], _i),
     "splice_optim_step_clip": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, _f, _vp, _f, _f, _f, _i, _i, _f, _i, _vp, _vp], _i),
     "splice_step_set_grad_clip": ([_vp, _f, _vp], _i),
+    # keep the best window's weights under the stop rule
+    "splice_plateau_update_best": ([_vp, _vp, _vp, _vp, _i, _i, _f, _i, _i, _i, _i, _vp], _i),
+    "splice_optim_step_pairs_best": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_longlong, C.c_longlong, _vp, _f, _f, _f, _vp, _vp, _i, _f, _i, _vp, _vp, _vp, _vp, _vp], _i),
+    "splice_step_set_keep_best": ([_vp, _vp, _vp, _vp, _vp], _i),
     "splice_prof_begin": ([_i], _i),
     "splice_prof_end": ([C.POINTER(_f), C.POINTER(_i)], _i),
     "splice_prof_end_ex": ([C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)], _i),

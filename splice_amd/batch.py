@@ -30,6 +30,10 @@ update; the run then also writes ``out/output_ema.png`` from the averaged weight
 per pair; a step whose norm is not finite does not update the pair); ``result.json`` carries ``grad_clip_norm``, ``clipped_steps`` and
 ``skipped_steps`` per pair (per variant in a sweep).
 
+``--set stop_keep_best=true`` (with the stop rule on; shared by the variants of a sweep) keeps, on the device, every pair's weights of the
+step that closed the best window the rule has seen: the run also writes ``out/output_best.png`` (``output_best_ema.png`` with an average),
+and ``result.json`` carries ``best_step``, ``best_window_mean`` and ``window_means``.
+
     python -m splice_amd.batch --root pairs/ --gpus 8 [--pairs-per-gpu P] [--n_epochs 2000] [--set key=value ...]
 
 ``--pairs-per-gpu P`` works with ``--set global_A_crops_n_crops=n`` (and ``global_B_crops_n_crops``): each pair's n crops are one
@@ -94,6 +98,11 @@ def _clip_fields(eng, slot=None):
     return clip_fields(eng, slot)
 
 
+def _best_fields(eng, slot=None):
+    from .train import best_fields
+    return best_fields(eng, slot)
+
+
 def train_runner(pair_dir, overrides):
     """Default runner: the drop-in ``train_model`` on the pair's directory."""
     from .train import train_model
@@ -102,7 +111,7 @@ def train_runner(pair_dir, overrides):
     import torch
     torch.cuda.synchronize()
     return {"steps": eng.step_idx + 1, "loss": eng.losses()["loss"], "seconds": round(time.perf_counter() - t0, 3), **_stop_fields(eng), **_ema_fields(eng),
-            **_clip_fields(eng)}
+            **_clip_fields(eng), **_best_fields(eng)}
 
 
 def train_group_runner(pair_dirs, overrides):
@@ -114,7 +123,7 @@ def train_group_runner(pair_dirs, overrides):
     torch.cuda.synchronize()
     dt = round(time.perf_counter() - t0, 3)
     return [{"steps": eng.step_idx + 1, "loss": d["loss"], "seconds": dt, "pairs_in_step": len(pair_dirs), **_stop_fields(eng, p), **_ema_fields(eng),
-             **_clip_fields(eng, p)} for p, d in enumerate(eng.losses())]
+             **_clip_fields(eng, p), **_best_fields(eng, p)} for p, d in enumerate(eng.losses())]
 
 
 def train_sweep_runner(pair_dir, overrides, variants):
@@ -126,7 +135,7 @@ def train_sweep_runner(pair_dir, overrides, variants):
     torch.cuda.synchronize()
     losses = eng.losses()
     return {"steps": eng.step_idx + 1, "seconds": round(time.perf_counter() - t0, 3), **_ema_fields(eng),
-            "variants": [{"index": k, "overrides": v, "loss": d["loss"], "losses": d, **_stop_fields(eng, k), **_clip_fields(eng, k)} for k, (v, d) in enumerate(zip(variants, losses))]}
+            "variants": [{"index": k, "overrides": v, "loss": d["loss"], "losses": d, **_stop_fields(eng, k), **_clip_fields(eng, k), **_best_fields(eng, k)} for k, (v, d) in enumerate(zip(variants, losses))]}
 
 
 def sweep_variants(specs):

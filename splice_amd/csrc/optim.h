@@ -31,6 +31,12 @@ struct OptimArgs {
     // (its g is zeroed under zero_grad)
     const splice_clip_state* clip = nullptr;
     size_t clip_stride = 0;
+    // optional (keep the best window's weights; needs mask): [slots] records indexed by mask_stride, written by this step's rule.  A slot
+    // that is not frozen and whose best_step is the step index *mask_step - 1 has the p just written copied to best_p, and with ema the
+    // average just written to best_ema (given exactly when ema is); both are laid out like p
+    const splice_best_state* best = nullptr;
+    float* best_p = nullptr;
+    float* best_ema = nullptr;
 };
 int optim_launch(const OptimArgs& a, hipStream_t s);
 // The per-pair gradient norm and clip coefficient (include/splice_hip.h has the rule): two launches, partials[pairs][ceil(n / 4096)] then

@@ -89,13 +89,21 @@ __device__ __forceinline__ float clip_scale(float gi, float g2i, bool has_g2, fl
 // bit -- and where g is written back it holds that value.  A slot whose record has skip set (its norm was not finite) is left as it is:
 // no write to p, m, v or e; its g is written only as the zeros of zero_grad.  A frozen slot is skipped before its record is read.  The
 // two arguments lie behind the EMA ones, and the instances without CLIP do not read them.
-template <class Rule, bool PAIR_LR, bool MASKED, bool EMA, bool CLIP>
+// BEST (keep the best window's weights; only with MASKED, whose records and step count it needs): the slot's record best[i / mask_stride]
+// (mask_stride 0: slot 0, read once at the kernel's head) was written by this step's loss kernel; where its best_step is this step's index
+// -- `take` -- the parameter just written goes to best_p[i] as well, and with EMA the average just written to best_e[i]: copies of the
+// registers the ordinary stores hold, no float is computed again.  A frozen slot is skipped before its record is read; a slot skipped by
+// the clip guard still takes, its unchanged p (and e).  best_p / best_e take part in the alignment test like every arena.  The three
+// arguments lie behind the CLIP ones, and the instances without BEST do not read them.
+template <class Rule, bool PAIR_LR, bool MASKED, bool EMA, bool CLIP, bool BEST = false>
 __global__ void optim_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, size_t n, float lr,
                              float hp0, float hp1, float eps, float bc1, float bc2_sqrt, int zero_grad, const int* __restrict__ step_ptr,
                              const float* __restrict__ g2, const float* __restrict__ lr_ptr, unsigned lr_stride,
                              const splice_stop_state* __restrict__ mask, const int* __restrict__ mask_step, unsigned mask_stride,
                              float* __restrict__ e, float ema_decay, int ema_start, const int* __restrict__ ema_step_ptr, int ema_step,
-                             const splice_clip_state* __restrict__ clip, unsigned clip_stride) {
+                             const splice_clip_state* __restrict__ clip, unsigned clip_stride,
+                             const splice_best_state* __restrict__ best, float* __restrict__ best_p, float* __restrict__ best_e) {
+    static_assert(MASKED || !BEST, "the snapshot needs the stop records and the device step count");
     int step_idx = 0;
     if (MASKED) {
         step_idx = *mask_step - 1;
@@ -114,6 +122,8 @@ __global__ void optim_kernel(float* __restrict__ p, float* __restrict__ g, float
     float coef = 1.f;
     int skip = 0;
     if (CLIP && !clip_stride) { coef = clip->coef; skip = clip->skip; }
+    bool take = false;
+    if (BEST && !mask_stride) take = best->best_step == step_idx;
     auto upd = [&](float& pi, float& gi, float& mi, float& vi, float g2i) {
         if (CLIP) {
             gi = clip_scale(gi, g2i, g2 != nullptr, coef);
@@ -124,7 +134,8 @@ __global__ void optim_kernel(float* __restrict__ p, float* __restrict__ g, float
     };
     const unsigned lr_stride4 = lr_stride / 4, mask_stride4 = mask_stride / 4, clip_stride4 = clip_stride / 4;
     const size_t align = reinterpret_cast<size_t>(p) | reinterpret_cast<size_t>(g) | (Rule::USES_M ? reinterpret_cast<size_t>(m) : 0) |
-                         (Rule::USES_V ? reinterpret_cast<size_t>(v) : 0) | reinterpret_cast<size_t>(g2) | (EMA ? reinterpret_cast<size_t>(e) : 0);
+                         (Rule::USES_V ? reinterpret_cast<size_t>(v) : 0) | reinterpret_cast<size_t>(g2) | (EMA ? reinterpret_cast<size_t>(e) : 0) |
+                         (BEST ? reinterpret_cast<size_t>(best_p) : 0) | (BEST && EMA ? reinterpret_cast<size_t>(best_e) : 0);
     const size_t n4 = (align & 15) ? 0 : n / 4;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
         if (MASKED && mask_stride && stop_frozen(mask + (unsigned)i / mask_stride4, step_idx)) continue;
@@ -133,6 +144,7 @@ __global__ void optim_kernel(float* __restrict__ p, float* __restrict__ g, float
         if (Rule::USES_V) vv = reinterpret_cast<float4*>(v)[i];
         const float4 g2v = g2 ? reinterpret_cast<const float4*>(g2)[i] : float4{0.f, 0.f, 0.f, 0.f};
         if (PAIR_LR) lr = lr_ptr[(unsigned)i / lr_stride4];
+        if (BEST && mask_stride4) take = best[(unsigned)i / mask_stride4].best_step == step_idx;
         if (CLIP) {
             if (clip_stride4) {
                 const splice_clip_state* cs = clip + (unsigned)i / clip_stride4;
@@ -141,17 +153,23 @@ __global__ void optim_kernel(float* __restrict__ p, float* __restrict__ g, float
             }
             if (skip) {
                 if (zero_grad) reinterpret_cast<float4*>(g)[i] = float4{0.f, 0.f, 0.f, 0.f};
+                if (BEST && take) {   // (the slot is left as it is: its snapshot is the p and e it has)
+                    reinterpret_cast<float4*>(best_p)[i] = pv;
+                    if (EMA) reinterpret_cast<float4*>(best_e)[i] = reinterpret_cast<float4*>(e)[i];
+                }
                 continue;
             }
         }
         upd(pv.x, gv.x, mv.x, vv.x, g2v.x); upd(pv.y, gv.y, mv.y, vv.y, g2v.y); upd(pv.z, gv.z, mv.z, vv.z, g2v.z); upd(pv.w, gv.w, mv.w, vv.w, g2v.w);
         reinterpret_cast<float4*>(p)[i] = pv;
+        if (BEST && take) reinterpret_cast<float4*>(best_p)[i] = pv;
         if (EMA) {
             float4 ev = pv;   // (a tracking average is the parameter: e is not read)
             if (!ema_track) ev = reinterpret_cast<float4*>(e)[i];
             ev.x = ema_update(ev.x, pv.x, ema_decay, ema_track); ev.y = ema_update(ev.y, pv.y, ema_decay, ema_track);
             ev.z = ema_update(ev.z, pv.z, ema_decay, ema_track); ev.w = ema_update(ev.w, pv.w, ema_decay, ema_track);
             reinterpret_cast<float4*>(e)[i] = ev;
+            if (BEST && take) reinterpret_cast<float4*>(best_e)[i] = ev;
         }
         if (Rule::USES_M) reinterpret_cast<float4*>(m)[i] = mv;
         if (Rule::USES_V) reinterpret_cast<float4*>(v)[i] = vv;
@@ -159,6 +177,7 @@ __global__ void optim_kernel(float* __restrict__ p, float* __restrict__ g, float
     }
     for (size_t i = n4 * 4 + (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
         if (MASKED && mask_stride && stop_frozen(mask + (unsigned)i / mask_stride, step_idx)) continue;
+        if (BEST && mask_stride) take = best[(unsigned)i / mask_stride].best_step == step_idx;
         if (CLIP) {
             if (clip_stride) {
                 const splice_clip_state* cs = clip + (unsigned)i / clip_stride;
@@ -167,6 +186,10 @@ __global__ void optim_kernel(float* __restrict__ p, float* __restrict__ g, float
             }
             if (skip) {
                 if (zero_grad) g[i] = 0.f;
+                if (BEST && take) {
+                    best_p[i] = p[i];
+                    if (EMA) best_e[i] = e[i];
+                }
                 continue;
             }
         }
@@ -176,7 +199,12 @@ __global__ void optim_kernel(float* __restrict__ p, float* __restrict__ g, float
         if (PAIR_LR) lr = lr_ptr[(unsigned)i / lr_stride];
         upd(pi, gi, mi, vi, g2 ? g2[i] : 0.f);
         p[i] = pi;
-        if (EMA) e[i] = ema_update(ema_track ? pi : e[i], pi, ema_decay, ema_track);
+        if (BEST && take) best_p[i] = pi;
+        if (EMA) {
+            const float ei = ema_update(ema_track ? pi : e[i], pi, ema_decay, ema_track);
+            e[i] = ei;
+            if (BEST && take) best_e[i] = ei;
+        }
         if (Rule::USES_M) m[i] = mi;
         if (Rule::USES_V) v[i] = vi;
         if (g2 || zero_grad) g[i] = gi;
@@ -196,6 +224,12 @@ int optim_launch(const OptimArgs& a, hipStream_t s) {
 #undef OPTIM_INSTANCES
 #undef OPTIM_EMA
 #undef OPTIM_CLIP
+    // the snapshot rides in masked updates only: [kind][PAIR_LR][EMA][CLIP], 24 instances beside the 48 above
+#define OPTIM_BEST_CLIP(Rule, PAIR_LR, EMA) {optim_kernel<Rule, PAIR_LR, true, EMA, false, true>, optim_kernel<Rule, PAIR_LR, true, EMA, true, true>}
+#define OPTIM_BEST(Rule) {{OPTIM_BEST_CLIP(Rule, false, false), OPTIM_BEST_CLIP(Rule, false, true)}, {OPTIM_BEST_CLIP(Rule, true, false), OPTIM_BEST_CLIP(Rule, true, true)}}
+    static constexpr decltype(&optim_kernel<AdamRule, false, false, false, false>) best_kernels[3][2][2][2] = {OPTIM_BEST(AdamRule), OPTIM_BEST(RmspropRule), OPTIM_BEST(SgdRule)};
+#undef OPTIM_BEST
+#undef OPTIM_BEST_CLIP
     if (a.kind < SPLICE_OPT_ADAM || a.kind > SPLICE_OPT_SGD) {
         splice_set_error("optimiser: unknown optimiser kind %d", a.kind);
         return SPLICE_ERR_ARG;
@@ -224,14 +258,20 @@ int optim_launch(const OptimArgs& a, hipStream_t s) {
         splice_set_error("optimiser: a clipped update needs a slot stride that is a multiple of 4 (that of the per-pair lr and of the mask where they are set) and < 2^32 elements");
         return SPLICE_ERR_ARG;
     }
+    // the snapshot reads the record of the slot the stop records name: it needs them, its arena and -- exactly with an average -- the best average
+    if (a.best && (!a.mask || !a.best_p || (a.best_ema != nullptr) != (a.ema != nullptr))) {
+        splice_set_error("optimiser: keeping the best weights needs the stop records, the best arena and a best average exactly when an average is kept");
+        return SPLICE_ERR_ARG;
+    }
     // a host step count: the bias corrections come from the HOST's powf (host and device powf need not agree to the bit, so a caller
     // stays with the form it has)
     const float bc1 = host_step ? 1.0f - powf(a.hp0, (float)a.step) : 1.f;
     const float bc2_sqrt = host_step ? sqrtf(1.0f - powf(a.hp1, (float)a.step)) : 1.f;
-    const auto kernel = kernels[a.kind][a.lr_stride != 0][a.mask != nullptr][a.ema != nullptr][a.clip != nullptr];
+    const auto kernel = a.best ? best_kernels[a.kind][a.lr_stride != 0][a.ema != nullptr][a.clip != nullptr]
+                               : kernels[a.kind][a.lr_stride != 0][a.mask != nullptr][a.ema != nullptr][a.clip != nullptr];
     SPLICE_LAUNCH(kernel, dim3(optim_grid(a.n)), dim3(256), 0, s, a.p, a.g, a.m, a.v, a.n, a.lr, a.hp0, a.hp1, a.eps, bc1, bc2_sqrt, a.zero_grad,
                   adam ? a.step_dev : nullptr, a.g2, a.lr_dev, (unsigned)a.lr_stride, a.mask, a.mask_step, (unsigned)a.mask_stride,
-                  a.ema, a.ema_decay, a.ema_start, ema_step_dev, a.step, a.clip, (unsigned)a.clip_stride);
+                  a.ema, a.ema_decay, a.ema_start, ema_step_dev, a.step, a.clip, (unsigned)a.clip_stride, a.best, a.best_p, a.best_ema);
     return SPLICE_OK;
 }
 
@@ -428,6 +468,24 @@ int splice_optim_step_pairs_clip(int kind, float* params, float* grads, const fl
     if (stop) { a.mask = stop; a.mask_step = step_dev; a.mask_stride = slot; }
     if (ema) { a.ema = ema; a.ema_decay = ema_decay; a.ema_start = ema_start; }
     a.clip = clip; a.clip_stride = slot;
+    return optim_launch(a, (hipStream_t)stream);
+}
+// as splice_optim_step_pairs_clip (stop required; clip and ema optional) with the snapshot of the best window's weights
+int splice_optim_step_pairs_best(int kind, float* params, float* grads, const float* g2, float* m, float* v, float* ema, int n_pairs, long long stride,
+                                 long long n, const float* lr_dev, float hp0, float hp1, float eps, const int* step_dev, const splice_stop_state* stop,
+                                 int zero_grad, float ema_decay, int ema_start, const splice_clip_state* clip, const splice_best_state* best,
+                                 float* best_params, float* best_ema, splice_stream_t stream) {
+    if (!params || !grads || !stop || !best || !best_params || !lr_dev || !step_dev || n_pairs < 1 || n < 1 || (n_pairs > 1 && (stride < n || stride % 4))) {
+        splice_set_error("splice_optim_step_pairs_best: needs the stop and best records, the best arena, a device lr table and step count, n_pairs >= 1, n >= 1 and, for more than one pair, n <= stride with stride a multiple of 4");
+        return SPLICE_ERR_ARG;
+    }
+    const size_t slot = n_pairs > 1 ? (size_t)stride : 0;   // one pair: a single arena, slot 0 of every table
+    OptimArgs a = optim_args(kind, params, grads, g2, m, v, n_pairs > 1 ? (long long)n_pairs * stride : n, 0.f, lr_dev, slot, hp0, hp1, eps, 0, zero_grad);
+    a.step_dev = step_dev;
+    a.mask = stop; a.mask_step = step_dev; a.mask_stride = slot;
+    if (ema) { a.ema = ema; a.ema_decay = ema_decay; a.ema_start = ema_start; }
+    if (clip) { a.clip = clip; a.clip_stride = slot; }
+    a.best = best; a.best_p = best_params; a.best_ema = best_ema;
     return optim_launch(a, (hipStream_t)stream);
 }
 }

@@ -125,6 +125,12 @@ struct SpliceStep {
     splice_clip_state* clip = nullptr;
     float* clip_partials = nullptr;
     float clip_norm = 0.f;
+    // keep-best (splice_step_set_keep_best): the caller's [pairs] records, window means and best arena(s); null: off -- the step launches what
+    // it always did
+    splice_best_state* best = nullptr;
+    float* best_means = nullptr;
+    float* best_p = nullptr;
+    float* best_ema = nullptr;
 };
 
 static size_t arena_floats(const SpliceStep* st) { return st->astride ? st->pairs * st->astride : (size_t)st->nparams; }   // of all pairs' arenas
@@ -178,11 +184,13 @@ static int view_init(SpliceStep* st, VitView& v, void* ctx, int want_B) {
 // scalar weights are (ssim_on: global structure and identity; entire: the two entire-image terms)
 // MONITOR (the plateau stop rule, plateau.h): thread 0 then runs the rule for its pair on the total it has just written, on counted steps
 // -- ssim_on && !entire, both baked per graph variant -- with the step index read from dev_t (step_idx + 1: a replayed graph sees its own
-// step).  The instance without MONITOR does not read the three trailing arguments: its code is what it was.
+// step).  kb / means (keep-best; null: off): the rule's record and window means of every pair.  The instance without MONITOR does not read
+// the five trailing arguments: its code is what it was.
 template <bool MONITOR>
 __global__ __launch_bounds__(320) void total_loss_kernel(float* lbase, size_t lstride, int lp, float w_ssim, float w_essim, float w_ecls, float w_cls,
                                                          float w_id, float* out8, int n_a, int n_b, int n_c, int n_e, const float* wtab, int ssim_on,
-                                                         int entire, splice_stop_state* stop, const int* dev_t, StopRule rule) {
+                                                         int entire, splice_stop_state* stop, const int* dev_t, StopRule rule, splice_best_state* kb,
+                                                         float* means) {
     __shared__ float raw[8];
     float* l = lbase + (size_t)blockIdx.x * lstride;
     const int k = 1 + (threadIdx.x >> 6), lane = threadIdx.x & 63;   // wave k-1 owns term k (5 waves)
@@ -215,13 +223,17 @@ __global__ __launch_bounds__(320) void total_loss_kernel(float* lbase, size_t ls
             for (int t = 1; t <= 5; ++t) o[t] = raw[t];
             o[6] = 0.f; o[7] = 0.f;
         }
-        if (MONITOR && ssim_on && !entire) plateau_update(stop + blockIdx.x, l[L_TOTAL], rule, *dev_t - 1);
+        if (MONITOR && ssim_on && !entire)
+            plateau_update(stop + blockIdx.x, l[L_TOTAL], rule, *dev_t - 1, kb ? kb + blockIdx.x : nullptr,
+                           means ? means + (size_t)blockIdx.x * SPLICE_STOP_HISTORY : nullptr);
     }
 }
 // the rule alone on a caller's [pairs][8] losses (splice_plateau_update): one thread per slot
-__global__ __launch_bounds__(64) void plateau_update_kernel(splice_stop_state* stop, const float* losses8, int pairs, StopRule rule, int step_idx) {
+__global__ __launch_bounds__(64) void plateau_update_kernel(splice_stop_state* stop, const float* losses8, int pairs, StopRule rule, int step_idx,
+                                                            splice_best_state* kb, float* means) {
     const int p = blockIdx.x * 64 + threadIdx.x;
-    if (p < pairs) plateau_update(stop + p, losses8[(size_t)p * 8], rule, step_idx);
+    if (p < pairs)
+        plateau_update(stop + p, losses8[(size_t)p * 8], rule, step_idx, kb ? kb + p : nullptr, means ? means + (size_t)p * SPLICE_STOP_HISTORY : nullptr);
 }
 static bool stop_rule_ok(int window, float rel, int patience, int min_steps, const char* who) {
     if (window >= 0 && rel > 0.f && rel < 1.f && patience >= 1 && min_steps >= 0) return true;
@@ -492,6 +504,7 @@ int splice_step_set_mode(void* h, int skip_adam, int accumulate) {
     if (skip_adam && st->stop_rule.window > 0) { splice_set_error("splice_step_set_mode: a handle with a stop rule runs whole steps (no gradient-only mode)"); return SPLICE_ERR_STATE; }
     if (skip_adam && st->ema) { splice_set_error("splice_step_set_mode: a handle with a weight average runs whole steps (no gradient-only mode)"); return SPLICE_ERR_STATE; }
     if (skip_adam && st->clip) { splice_set_error("splice_step_set_mode: a handle with gradient clipping runs whole steps (no gradient-only mode)"); return SPLICE_ERR_STATE; }
+    if (skip_adam && st->best) { splice_set_error("splice_step_set_mode: a handle that keeps the best weights runs whole steps (no gradient-only mode)"); return SPLICE_ERR_STATE; }
     if (st->skip_adam != (skip_adam ? 1 : 0) || st->accumulate != (accumulate ? 1 : 0)) st->graphs.retire();
     st->skip_adam = skip_adam ? 1 : 0; st->accumulate = accumulate ? 1 : 0;
     return SPLICE_OK;
@@ -578,6 +591,7 @@ int splice_step_set_phases(void* h, int phases, void* leader) {
     if ((phases != 7 || leader) && st->stop_rule.window > 0) { splice_set_error("splice_step_set_phases: a handle with a stop rule runs whole steps (no phase mode)"); return SPLICE_ERR_STATE; }
     if ((phases != 7 || leader) && st->ema) { splice_set_error("splice_step_set_phases: a handle with a weight average runs whole steps (no phase mode)"); return SPLICE_ERR_STATE; }
     if ((phases != 7 || leader) && st->clip) { splice_set_error("splice_step_set_phases: a handle with gradient clipping runs whole steps (no phase mode)"); return SPLICE_ERR_STATE; }
+    if ((phases != 7 || leader) && st->best) { splice_set_error("splice_step_set_phases: a handle that keeps the best weights runs whole steps (no phase mode)"); return SPLICE_ERR_STATE; }
     if (st->leader != (SpliceStep*)leader) st->graphs.retire();
     st->phases = phases;
     st->leader = (SpliceStep*)leader;
@@ -595,6 +609,7 @@ int splice_step_set_stop_rule(void* h, int window, float rel, int patience, int 
         splice_set_error("splice_step_set_stop_rule: not on a handle in gradient-only (splice_step_set_mode) or phase mode (splice_step_set_phases)");
         return SPLICE_ERR_STATE;
     }
+    if (window == 0 && st->best) { splice_set_error("splice_step_set_stop_rule: a handle that keeps the best weights needs its rule (window > 0)"); return SPLICE_ERR_STATE; }
     if ((window > 0) != (st->stop_rule.window > 0)) st->graphs.retire();
     st->stop_rule = StopRule{window, rel, patience, min_steps};
     return SPLICE_OK;
@@ -614,6 +629,7 @@ int splice_step_set_ema(void* h, float* ema, float decay, int start) {
         splice_set_error("splice_step_set_ema: not on a handle in gradient-only (splice_step_set_mode) or phase mode (splice_step_set_phases)");
         return SPLICE_ERR_STATE;
     }
+    if (st->best) { splice_set_error("splice_step_set_ema: the average is set before splice_step_set_keep_best (which takes its best arena)"); return SPLICE_ERR_STATE; }
     st->graphs.retire();
     st->ema = ema; st->ema_decay = decay; st->ema_start = start;
     return SPLICE_OK;
@@ -638,6 +654,31 @@ int splice_step_set_grad_clip(void* h, float max_norm, splice_clip_state* state)
     st->clip = state; st->clip_norm = max_norm;
     return SPLICE_OK;
 }
+// Keep every pair's best-window weights (include/splice_hip.h has the rule): the loss kernel's rule writes `state` and `means`, the optimiser
+// launch of the same step reads the record and writes the best arena(s).  Before the first step only, behind the stop rule (and the
+// average, which decides whether best_ema is due), and not on a gradient-only or phase-mode handle, as the weight average.
+int splice_step_set_keep_best(void* h, float* best_params, float* best_ema, splice_best_state* state, float* means) {
+    SpliceStep* st = (SpliceStep*)h;
+    if (!st) return SPLICE_ERR_ARG;
+    if (!best_params || !state || !means) {
+        splice_set_error("splice_step_set_keep_best: needs the best arena, the state records and the window means");
+        return SPLICE_ERR_ARG;
+    }
+    if (st->runs > 0) { splice_set_error("splice_step_set_keep_best: the best weights are kept from before the first step"); return SPLICE_ERR_STATE; }
+    if (st->skip_adam || st->phases != 7 || st->leader) {
+        splice_set_error("splice_step_set_keep_best: not on a handle in gradient-only (splice_step_set_mode) or phase mode (splice_step_set_phases)");
+        return SPLICE_ERR_STATE;
+    }
+    if (st->stop_rule.window <= 0) { splice_set_error("splice_step_set_keep_best: needs a handle with a stop rule (splice_step_set_stop_rule, window > 0)"); return SPLICE_ERR_STATE; }
+    if ((best_ema != nullptr) != (st->ema != nullptr)) {
+        splice_set_error("splice_step_set_keep_best: best_ema goes with a weight average (splice_step_set_ema): given exactly when the handle keeps one");
+        return SPLICE_ERR_ARG;
+    }
+    if (st->astride % 4) { splice_set_error("splice_step_set_keep_best: the arena stride must be a multiple of 4"); return SPLICE_ERR_ARG; }
+    st->graphs.retire();
+    st->best = state; st->best_means = means; st->best_p = best_params; st->best_ema = best_ema;
+    return SPLICE_OK;
+}
 int splice_step_stop_state(void* h, splice_stop_state* out, splice_stream_t stream) {
     SpliceStep* st = (SpliceStep*)h;
     if (!st || !out) return SPLICE_ERR_ARG;
@@ -650,7 +691,18 @@ int splice_plateau_update(splice_stop_state* state, const float* losses8, int pa
     if (!state || !losses8 || pairs < 1 || step_idx < 0) return SPLICE_ERR_ARG;
     if (!stop_rule_ok(window, rel, patience, min_steps, "splice_plateau_update")) return SPLICE_ERR_ARG;
     if (!counted || window == 0) return SPLICE_OK;
-    SPLICE_LAUNCH(plateau_update_kernel, dim3((pairs + 63) / 64), dim3(64), 0, (hipStream_t)stream, state, losses8, pairs, StopRule{window, rel, patience, min_steps}, step_idx);
+    SPLICE_LAUNCH(plateau_update_kernel, dim3((pairs + 63) / 64), dim3(64), 0, (hipStream_t)stream, state, losses8, pairs, StopRule{window, rel, patience, min_steps}, step_idx,
+                  (splice_best_state*)nullptr, (float*)nullptr);
+    return SPLICE_OK;
+}
+// the same kernel, the same device function, with the keep-best record and the window means
+int splice_plateau_update_best(splice_stop_state* state, splice_best_state* best, float* means, const float* losses8, int pairs, int window, float rel,
+                               int patience, int min_steps, int step_idx, int counted, splice_stream_t stream) {
+    if (!state || !best || !means || !losses8 || pairs < 1 || step_idx < 0) return SPLICE_ERR_ARG;
+    if (!stop_rule_ok(window, rel, patience, min_steps, "splice_plateau_update_best")) return SPLICE_ERR_ARG;
+    if (!counted || window == 0) return SPLICE_OK;
+    SPLICE_LAUNCH(plateau_update_kernel, dim3((pairs + 63) / 64), dim3(64), 0, (hipStream_t)stream, state, losses8, pairs, StopRule{window, rel, patience, min_steps}, step_idx,
+                  best, means);
     return SPLICE_OK;
 }
 
@@ -800,7 +852,7 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
             const auto kernel = stop_on ? total_loss_kernel<true> : total_loss_kernel<false>;   // (the rule rides in the launch: no node more)
             SPLICE_LAUNCH(kernel, dim3(pairs), dim3(320), 0, q, st->losses, st->lstride, (int)st->lp, t[L_GLOBAL_SSIM].lambda, t[L_ENTIRE_SSIM].lambda,
                           t[L_ENTIRE_CLS].lambda, t[L_GLOBAL_CLS].lambda, t[L_GLOBAL_ID].lambda, st->losses_out, grouped ? st->na : n1, grouped ? st->nb : n1, grouped ? nc : n1,
-                          grouped ? 1 : n1, st->pw ? st->pw + (size_t)PW_LAMBDAS * P : nullptr, (int)ssim_on, (int)entire, st->stop, st->dev_t, st->stop_rule);
+                          grouped ? 1 : n1, st->pw ? st->pw + (size_t)PW_LAMBDAS * P : nullptr, (int)ssim_on, (int)entire, st->stop, st->dev_t, st->stop_rule, st->best, st->best_means);
         }
         if (!st->running || !gen_fwd) return SPLICE_OK;
         void* plans[3] = {st->plan_a, st->plan_b, nullptr};
@@ -853,6 +905,9 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
                                 stop_on ? st->stop : nullptr, st->dev_t, s));
             a.clip = st->clip; a.clip_stride = st->astride;
         }
+        // keep-best: the record this launch reads was written by THIS step's loss kernel -- on the side stream's tail, in front of the
+        // EV_JOIN2 wait above, or on the main stream in front of this launch -- so the update of the step that closes a best window sees it
+        if (st->best) { a.best = st->best; a.best_p = st->best_p; a.best_ema = st->best_ema; }   // (another kernel, as with the average)
         RC(optim_launch(a, s));
     }
     return SPLICE_OK;

@@ -30,7 +30,9 @@ DEFAULT_CFG = dict(  # conf/default/config.yaml of the reference
     # ... and the weight average kept by the fused update, off by default
     ema_decay=0.0, ema_start=0,
     # ... and clipping of every pair's gradient by its global norm inside the fused step, off by default
-    grad_clip_norm=0.0)
+    grad_clip_norm=0.0,
+    # ... and the weights of the window the stop rule judged best, kept on the device beside the live ones, off by default
+    stop_keep_best=False)
 
 
 # Per-slot keys of a sweep (MultiPairEngine(pair_cfgs=...), train.train_sweep): the five loss weights in the order of
@@ -80,6 +82,61 @@ def np_ema(e, p, step, decay, start):
         return np.array(p, dtype=f)
     d = f(decay)
     return (d * np.asarray(e, dtype=f) + (f(1) - d) * np.asarray(p, dtype=f)).astype(f)
+
+
+STOP_HISTORY = _lib.STOP_HISTORY   # SPLICE_STOP_HISTORY: window means kept per slot
+
+
+def best_rule(c):
+    """``stop_keep_best`` of config ``c``, checked on the host: a bool, and ``True`` only with the plateau stop
+    rule on (``stop_window > 0``) -- the snapshot is taken where that rule moves its ``best``.  Raises ValueError naming the key."""
+    v = c.get("stop_keep_best", DEFAULT_CFG["stop_keep_best"])
+    if not isinstance(v, (bool, np.bool_)):
+        raise ValueError(f"'stop_keep_best' must be true or false, got {v!r}")
+    if v and stop_rule(c)[0] == 0:
+        raise ValueError("'stop_keep_best' needs the plateau stop rule: 'stop_window' > 0")
+    return bool(v)
+
+
+def np_plateau(losses, counted, window, rel, patience, min_steps, margins=None):
+    """The plateau stop rule with its keep-best record and window history (include/splice_hip.h) restated in NumPy float32, one
+    rounding per operation: the slot's state after the steps ``losses`` (``counted[t]``: step t is counted).  Returns a dict of the
+    ``splice_stop_state`` fields (``sum count windows best bad stop_step``), the record ``best_step`` / ``best_window`` (-1 until a
+    window has closed), ``means`` -- float32, the means of the windows closed while the slot was live, at most STOP_HISTORY of them --
+    and ``moves``, how often the record moved.  ``margins`` collects |mean - threshold| / |threshold| of every comparison made."""
+    f = np.float32
+    s = dict(sum=f(0), count=0, windows=0, best=f(0), bad=0, stop_step=-1, best_step=-1, best_window=-1, moves=0)
+    means = []
+    for t, (loss, c) in enumerate(zip(losses, counted)):
+        if not c:
+            continue
+        s["sum"] = f(s["sum"] + f(loss))
+        s["count"] += 1
+        if s["count"] < window:
+            continue
+        mean = f(s["sum"] / f(window))
+        live = s["stop_step"] < 0            # on entry: the stopping step itself is still live
+        better = s["windows"] == 0
+        if not better:
+            thr = f(s["best"] * f(f(1.0) - f(rel)))
+            if margins is not None:
+                margins.append(abs(float(mean) - float(thr)) / abs(float(thr)))
+            better = bool(mean < thr)
+        if better:
+            s["best"], s["bad"] = mean, 0
+            if live:
+                s["best_step"], s["best_window"] = t, s["windows"]
+                s["moves"] += 1
+        else:
+            s["bad"] += 1
+        if live and s["windows"] < STOP_HISTORY:
+            means.append(mean)
+        s["windows"] += 1
+        s["sum"], s["count"] = f(0), 0
+        if s["bad"] >= patience and t >= min_steps and s["stop_step"] < 0:
+            s["stop_step"] = t
+    s["means"] = np.array(means, dtype=f)
+    return s
 
 
 CLIP_CHUNK = 4096   # SPLICE_CLIP_CHUNK
@@ -243,6 +300,8 @@ class MultiPairEngine:
         self.ema = None
         self.grad_clip = grad_clip_rule(self.cfg)
         self.clip_dev = None
+        self.keep_best = best_rule(self.cfg)
+        self.best = self.best_ema = self.best_dev = self.means_dev = None
         P_in = len(gen_states)
         self.cfgs = [self.cfg] * P_in
         self._pair_lambdas = self._pair_lr = False
@@ -369,6 +428,16 @@ class MultiPairEngine:
         if self.grad_clip > 0:
             self.clip_dev = torch.zeros(P, 6, dtype=torch.int32, device=self.device)
             _lib.check(_lib.lib().splice_step_set_grad_clip(self.handle, self.grad_clip, _lib.ptr(self.clip_dev)), "step_set_grad_clip")
+        # the best window's weights (shared by the slots): arenas like params / ema -- until a window closes, "best" is the initial weights --
+        # written by the step's own optimiser launch where the rule's record, written by the same step's loss kernel, says so; behind the
+        # rule and the average, before the first step
+        if self.keep_best:
+            self.best = self.params.clone()
+            self.best_ema = self.ema.clone() if self.ema is not None else None
+            self.best_dev = torch.full((P, 2), -1, dtype=torch.int32, device=self.device)
+            self.means_dev = torch.zeros(P, STOP_HISTORY, device=self.device)
+            _lib.check(_lib.lib().splice_step_set_keep_best(self.handle, _lib.ptr(self.best), _lib.ptr(self.best_ema), _lib.ptr(self.best_dev),
+                                                            _lib.ptr(self.means_dev)), "step_set_keep_best")
         self._stopped = [None] * P   # the host's copy of every slot's stop step, refreshed by stop_state()
         self._stop_dirty = False     # a window has closed since the last stop_state(): the copy may be behind
         if self._pair_lambdas:
@@ -456,6 +525,48 @@ class MultiPairEngine:
         k = self._stops()[pair] if self.stop_rule[0] > 0 else None
         return k is not None and self.step_idx > k
 
+    # ---- the best window's weights
+    def _need_best(self, who):
+        if self.best is None:
+            raise RuntimeError(f"{who}: the best weights are not kept (stop_keep_best is off)")
+
+    def pair_best(self, pair=0, ema=False):
+        """View of one pair's weights after the step that closed its best window so far (``stop_keep_best``; the initial weights
+        until a window has closed), laid out like ``pair_params``.  ``ema=True``: the weight average of that step."""
+        self._need_best("pair_best")
+        if ema and self.best_ema is None:
+            raise RuntimeError("pair_best: no weight average is kept (ema_decay == 0)")
+        arena = self.best_ema if ema else self.best
+        return arena[pair * self.stride: pair * self.stride + self.gen.numel]
+
+    def _best_records(self):
+        # one device-to-host copy of the records and the histories (the ints ride as float bit patterns); waits for the current stream
+        raw = torch.cat([self.best_dev.view(torch.float32), self.means_dev], dim=1).cpu().numpy()
+        return raw[:, :2].copy().view(np.int32), raw[:, 2:]
+
+    def best_state(self, pair=None):
+        """Per slot ``best_step`` (the index of the step that closed the best window so far; None until a window has closed),
+        ``best_window`` (that window's index, -1 alike) and ``best_mean`` (its mean; None until then, and for a window beyond the
+        STOP_HISTORY the device keeps), copied from the device (waits for the current stream): call it at the end of a run or after a
+        step that closes a window.  One dict for ``pair``, a list over the slots for ``pair=None``."""
+        self._need_best("best_state")
+        rec, means = self._best_records()
+        dicts = [dict(best_step=int(r[0]) if r[0] >= 0 else None, best_window=int(r[1]),
+                      best_mean=float(mu[r[1]]) if 0 <= r[1] < STOP_HISTORY else None) for r, mu in zip(rec, means)]
+        return dicts if pair is None else dicts[pair]
+
+    def window_means(self, pair=None):
+        """The means of the windows every slot closed while it was live (float32 arrays, at most STOP_HISTORY each), copied from the
+        device as ``best_state``.  One array for ``pair``, a list over the slots for ``pair=None``."""
+        self._need_best("window_means")
+        _, means = self._best_records()
+        ent = self.cfg["entire_A_every"] if self.plan_e is not None else 0
+        out = []
+        for p, k in enumerate(self._stops()):   # (how many windows a slot closed is host arithmetic on its last live step)
+            last = self.step_idx if k is None else k
+            out.append(means[p, :min(counted_steps(last, self.cfg["cls_warmup"], ent) // self.stop_rule[0], STOP_HISTORY)].copy())
+        return out if pair is None else out[pair]
+
     def clip_state(self, pair=None):
         """The gradient-clipping record(s) of the last step (``grad_clip_norm > 0``), copied from the device (waits for the current
         stream): ``sumsq`` / ``norm`` of the slot's gradient, the ``coef`` its update multiplied it by, ``skip`` (the norm was not
@@ -495,13 +606,19 @@ class MultiPairEngine:
             raise RuntimeError("pair_ema: no weight average is kept (ema_decay == 0)")
         return self.ema[pair * self.stride: pair * self.stride + self.gen.numel]
 
-    def generate(self, img, pair=0, track_running_stats=False, ema=False):
+    def generate(self, img, pair=0, track_running_stats=False, ema=False, best=False):
         """netG_pair(img) under no_grad (the logging forward of train.py:70-73); img ``[n,3,H,W]``.  The reference's net
         is in train mode there too, so the call also moves the BatchNorm running statistics: pass
         ``track_running_stats=True`` to book that (train_model does, after the step whose forwards precede it).
         ``ema=True``: the forward with the averaged weights (a plan of its own); the reference has no such call, so it never
-        books BatchNorm statistics and is not among the logged forwards."""
+        books BatchNorm statistics and is not among the logged forwards.  ``best=True`` (``stop_keep_best``): alike with the best
+        window's weights, or with ``ema=True`` too that step's average."""
         n, _, h, w = img.shape
+        if best:
+            key = ("best", bool(ema), pair, n, h, w)
+            if key not in self._log_plans:
+                self._log_plans[key] = GeneratorPlan(self.gen, n, h, w, False, batch_stats=n > 1)
+            return self._log_plans[key].forward(self.pair_best(pair, ema=ema), img.contiguous())
         if ema:
             key = ("ema", pair, n, h, w)
             if key not in self._log_plans:
@@ -533,10 +650,12 @@ class MultiPairEngine:
         _lib.check(_lib.lib().splice_gen_running_stats_update(plans, 1, _lib.ptr(self.running[pair]), 0, 0.1, _lib.current_stream()), "running_stats_update")
         self.generator_calls[pair] += 1
 
-    def state_dict(self, pair=0, ema=False):
+    def state_dict(self, pair=0, ema=False, best=False):
         """``netG.state_dict()`` of one pair: parameters, BatchNorm running statistics and ``num_batches_tracked``.
-        ``ema=True``: the averaged parameters with the live buffers."""
-        out = {k: v.clone() for k, v in self.gen.unflatten(self.pair_ema(pair) if ema else self.pair_params(pair)).items()}
+        ``ema=True``: the averaged parameters with the live buffers; ``best=True`` (``stop_keep_best``): the best window's weights
+        (its average with ``ema=True`` too) with the live buffers -- buffers are not snapshotted, the generator runs on batch statistics."""
+        flat = self.pair_best(pair, ema=ema) if best else self.pair_ema(pair) if ema else self.pair_params(pair)
+        out = {k: v.clone() for k, v in self.gen.unflatten(flat).items()}
         calls = self.generator_calls[pair]
         if self._frozen(pair):   # the netG calls of the steps behind its stop step did not move this slot's buffers
             step_calls = lambda k: 2 * (k + 1) + (k // int(self.cfg["entire_A_every"]) + 1 if self.plan_e is not None else 0)
@@ -560,6 +679,12 @@ class SpliceEngine(MultiPairEngine):
     def clip_state(self, pair=None):
         return super().clip_state(0)
 
+    def best_state(self, pair=None):
+        return super().best_state(0)
+
+    def window_means(self, pair=None):
+        return super().window_means(0)
+
     @property
     def stopped_at(self):
         """The step index the pair stopped at (the plateau stop rule), or None."""
@@ -578,6 +703,9 @@ class MultiScaleEngine:
     def __init__(self, cfg, vit_state, gen_state, crop_hw, entire_hw=None, scales=(224, 320, 448), device="cuda", vit_engine=None, n_crops=1,
                  fp8=False):
         self.cfg = dict(DEFAULT_CFG, **cfg)
+        if best_rule(self.cfg):
+            raise NotImplementedError("stop_keep_best: the snapshot rides in the fused step's own update under its stop rule; MultiScaleEngine updates outside the step")
+        self.best = None
         if stop_rule(self.cfg)[0] > 0:
             raise NotImplementedError("stop_window > 0: the plateau stop rule lives in the fused step's own update; MultiScaleEngine updates outside the step")
         self.ema_rule = ema_rule(self.cfg)
@@ -632,8 +760,8 @@ class MultiScaleEngine:
         per = {sz: e.losses() for sz, e in zip(self.scales, self.engines)}
         return {"loss": sum(d["loss"] for d in per.values()), "scales": per}
 
-    def generate(self, img, pair=0, track_running_stats=False, ema=False):
-        return self.engines[0].generate(img, pair, track_running_stats, ema=ema)
+    def generate(self, img, pair=0, track_running_stats=False, ema=False, best=False):
+        return self.engines[0].generate(img, pair, track_running_stats, ema=ema, best=best)
 
     def pair_ema(self, pair=0):
         return self.engines[0].pair_ema(pair)
@@ -646,8 +774,8 @@ class MultiScaleEngine:
     def window_closes(self, step_idx):
         return False
 
-    def state_dict(self, pair=0, ema=False):
-        return self.engines[0].state_dict(pair, ema=ema)
+    def state_dict(self, pair=0, ema=False, best=False):
+        return self.engines[0].state_dict(pair, ema=ema, best=best)
 
 
 def synthetic_engine(cfg, pair_id=0, hw=(224, 224), seed=1234, device="cuda", vit_engine=None, entire=True, pairs=1, fp8=False, top_cls_only=True, crop_hw=None):

@@ -5,7 +5,8 @@ working directory (falling back to the packaged copy), seeds python / numpy / to
 image of ``<dataroot>/A`` and ``<dataroot>/B``, runs ``n_epochs`` optimisation steps and every
 ``log_images_freq`` steps writes ``<dataroot>/out/output.png`` (asynchronously: ``util.AsyncResultWriter``) and calls
 ``callback(output[0])`` with the ``[3,H,W]`` float image.  With ``ema_decay > 0`` (an extension) the run ends by writing one more image,
-``<dataroot>/out/output_ema.png``, from the averaged weights.  The step itself is the fused HIP engine (``SpliceEngine``), one host
+``<dataroot>/out/output_ema.png``, from the averaged weights; with ``stop_keep_best`` (an extension of the stop rule) ``output_best.png``,
+from the weights of the step that closed the best window.  The step itself is the fused HIP engine (``SpliceEngine``), one host
 call per step, losses read back only when a progress line is printed.
 
 Data feed: the reference augments PIL images on the CPU every step (``data/Dataset.py:62-70``).
@@ -210,6 +211,7 @@ def train_model(dataroot, callback=None, cfg_overrides=None, vit_state=None, pro
                     print(f"Epoch {epoch}: the loss has plateaued, stopping")
                 break
         _ema_images(engine, [writer], [feed.get_A()])
+        _best_images(engine, [writer], [feed.get_A()])
     finally:
         writer.close()
     return engine
@@ -264,6 +266,29 @@ def _ema_images(engine, writers, As):
         return
     for p, A in enumerate(As):
         writers[p].submit(engine.generate(A, pair=p, ema=True)[0], force=True, name="output_ema.png")
+
+
+def _best_images(engine, writers, As):
+    """The end of a run that keeps the best window's weights (``stop_keep_best``), however it ended: one more image per slot,
+    ``output_best.png`` beside ``output.png``, from the weights of the step that closed the best window -- and with a weight average
+    ``output_best_ema.png`` from that step's average.  No callback and no bookkeeping, as ``_ema_images``."""
+    if getattr(engine, "best", None) is None or engine.step_idx < 0:
+        return
+    for p, A in enumerate(As):
+        writers[p].submit(engine.generate(A, pair=p, best=True)[0], force=True, name="output_best.png")
+        if engine.best_ema is not None:
+            writers[p].submit(engine.generate(A, pair=p, best=True, ema=True)[0], force=True, name="output_best_ema.png")
+
+
+def best_fields(engine, slot=None):
+    """What ``result.json`` says about the stop rule's windows (``splice_amd.batch``) of a run with ``stop_keep_best``: ``best_step`` (the
+    step whose weights ``output_best.png`` shows; None: no window closed, they are the initial weights), ``best_window_mean`` and
+    ``window_means``, the means of the windows the slot closed while it ran.  Without the option: nothing."""
+    if getattr(engine, "best", None) is None or engine.step_idx < 0:
+        return {}
+    rec = engine.best_state(0 if slot is None else slot)
+    means = engine.window_means(0 if slot is None else slot)
+    return {"best_step": rec["best_step"], "best_window_mean": rec["best_mean"], "window_means": [float(x) for x in means]}
 
 
 def clip_fields(engine, slot=None):
@@ -349,6 +374,7 @@ def train_pairs(dataroots, callback=None, cfg_overrides=None, vit_state=None, pr
                 _final_images(engine, writers, [feed.get_A(p) for p in range(len(dataroots))], callback)
                 break
         _ema_images(engine, writers, [feed.get_A(p) for p in range(len(dataroots))])
+        _best_images(engine, writers, [feed.get_A(p) for p in range(len(dataroots))])
     finally:
         for w in writers:
             w.close()
@@ -445,6 +471,7 @@ def train_sweep(dataroot, variants, cfg_overrides=None, vit_state=None, callback
                 _final_images(engine, writers, [feed.get_A()] * K, callback)
                 break
         _ema_images(engine, writers, [feed.get_A()] * K)
+        _best_images(engine, writers, [feed.get_A()] * K)
     finally:
         for w in writers:
             w.close()
