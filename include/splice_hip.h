@@ -576,6 +576,54 @@ int splice_optim_step_pairs_best(int kind, float* params, float* grads, const fl
  * bars. */
 int splice_step_set_keep_best(void* step, float* best_params, float* best_ema, splice_best_state* state, float* means);
 
+/* ------------------------------------------------------------------ test hooks: the loss stage as the fused step launches it.  The three
+ * entry points below call the step's own launchers (structure term, batched MSE, total) on the caller's buffers with the step's operand
+ * layout; they add no kernel and no code path (tests/test_loss_stage_gpu.py against oracle/loss_stage.py).
+ *
+ * Structure term of `pairs` problems (util/losses.py:74-83): pair p's partials and key gradient of
+ *     lambda * mean((cos-sim(k_x[p]) - cos-sim(k_tgt[p]))^2)         (attn_cosine_sim, models/extractor.py:4-9; both [T][D] keys)
+ *   k_tgt, k_x   bf16 [T][ldk] (D columns used), pair p at + p * k_pstride elements.  Rows >= T are never read.
+ *   kT_x         the transpose of k_x: bf16 [D][ldt], pair p at + p * kT_pstride elements (column t of pair p = token t).  The kernels read
+ *                it Tp = roundup(T, 64) columns wide per pair -- in the step's layout the columns past a pair's own are its padding, the
+ *                next pair's tokens or, for the last pair, the start of the next row -- and multiply what lies at columns >= T by exact
+ *                zeros: that memory must be READABLE and FINITE (an Inf or NaN there reaches every element of the pair's gradient).
+ *   lambda, e_scale_tab   loss_scale = 1 / ((float)T * (float)T) and e_scale = 4.0f * lambda * loss_scale, fp32, as the step forms them.
+ *                e_scale_tab (may be NULL; device, [pairs]) replaces e_scale per pair; a pair whose entry is 0 writes nothing at all.
+ *   fp8          != 0: both Gram matrices on the fp8 MFMA from per-row quantised keys; needs D % 128 == 0.  W and r use the true norms.
+ *   loss_part    pair p's per-tile partials at + p * part_pstride: slot t of the nt (nt + 1) / 2 upper-triangular 64 x 64 tiles, nt = Tp / 64
+ *                (row-major over tm <= tn), holds that tile's share of mean((S - S*)^2) -- an off-diagonal tile counted twice -- WITHOUT
+ *                lambda; the caller adds the slots.  Slots beyond the tile count are not written.
+ *   dk           fp32, pair p at + p * dk_pstride, [T][lddk]: rows < T and columns < D are overwritten (not accumulated) with
+ *                dK = W K - diag(r) K,  W_ij = e_ij / max(n_i n_j, eps),  r_i = sum_j [n_i n_j > eps] e_ij S_ij / max(n_i^2, 1e-30),
+ *                e = e_scale (S - S*), W rounded to bf16.  An all-zero key row i has S_ij = 0, is gated out of r by eps (r_i = 0) and gets what
+ *                autograd gives it, dK_i = sum_j e_ij K_j / eps; its own terms in the other rows' gradients vanish with K_i.
+ *   ws           splice_selfsim_loss_pairs_ws_bytes(T, D, pairs) bytes, 256-byte aligned.
+ * Refused with SPLICE_ERR_ARG before anything is launched: a NULL operand, T / pairs < 1, D % 64, fp8 with D % 128, ldk % 8, ldt % 8,
+ * k_pstride % 8 or kT_pstride % 8 (16-byte loads), part_pstride < nt (nt + 1) / 2, lddk < D. */
+size_t splice_selfsim_loss_pairs_ws_bytes(int T, int D, int pairs);
+int splice_selfsim_loss_pairs(const splice_bf16* k_tgt, const splice_bf16* k_x, int ldk, size_t k_pstride, const splice_bf16* kT_x, int ldt,
+                              size_t kT_pstride, int T, int D, int pairs, float lambda, const float* e_scale_tab, int fp8, float eps,
+                              float* loss_part, size_t part_pstride, float* dk, int lddk, size_t dk_pstride, void* ws, splice_stream_t stream);
+/* The batched strided MSE of the step ([CLS] and key-identity terms): for pair p, on a + p * a_ps ([rows][lda], cols used) and b + p * b_ps,
+ *   part[p * part_ps + w] = loss_weight / (rows * cols) * (sum of (a - b)^2 over workgroup w's elements), w < min(ceil(rows * cols / 256), 1024)
+ *   (workgroup w owns the flat elements i with (i / 256) % workgroups == w); other slots are not written;
+ *   grad (may be NULL; pair p at + p * g_ps, [rows][ldg]) = 2 * gmean * (a - b) with gmean = grad_weight / (rows * cols) or, with grad_tab
+ *   (may be NULL; device, [pairs]), gmean = grad_tab[p]; a pair whose entry is 0 writes neither partials nor gradient. */
+int splice_mse_pairs(const float* a, int lda, size_t a_ps, const float* b, int ldb, size_t b_ps, int rows, int cols, float loss_weight,
+                     float grad_weight, float* part, size_t part_ps, float* grad, int ldg, size_t g_ps, int pairs, const float* grad_tab,
+                     splice_stream_t stream);
+/* The step's total-loss launch (without the stop rule) on a caller's partials buffer.  lbase holds slots of lstride floats each; a slot
+ * is [8 values][term 0..5: lp partials each], i.e. term k's partials of a slot start at 8 + k * lp (k: 1 global structure, 2 entire
+ * structure, 3 entire [CLS], 4 global [CLS], 5 global identity; lstride >= 8 + 6 * lp).  Pair p's slots of a term are the n consecutive
+ * slots from p * n, with n = n_a (term 1), n_b (term 5), n_c (term 4), n_e (terms 2 and 3); raw_k = the slots' fixed-order sums added in
+ * slot order.  Written: slot p's values [0..5] = {total, raw_1..raw_5} and, when out8 is given, out8[p][0..7] = {total, raw_1..raw_5, 0, 0};
+ * total = w_ssim raw_1 + w_essim raw_2 + w_ecls raw_3 + w_cls raw_4 + w_id raw_5, added left to right.  wtab (may be NULL; device,
+ * [pairs][5] = {cls, ssim, id, ecls, essim}) replaces the five weights per pair: ssim and id are taken as 0 unless ssim_on, ecls and
+ * essim as 0 unless entire. */
+int splice_total_loss_pairs(float* lbase, size_t lstride, int lp, float w_ssim, float w_essim, float w_ecls, float w_cls, float w_id,
+                            float* out8, int pairs, int n_a, int n_b, int n_c, int n_e, const float* wtab, int ssim_on, int entire,
+                            splice_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

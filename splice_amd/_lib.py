@@ -90,6 +90,11 @@ _SIGNATURES = {
     "splice_keys_selfsim_fwd": ([_vp, _i, _i, _i, _f, _vp, _vp, _vp], _i),
     "splice_keys_selfsim_bwd": ([_vp, _vp, _i, _i, _f, _vp, _i, _i, _vp, _vp], _i),
     "splice_mse": ([_vp, _i, _vp, _i, _i, _i, _f, _vp, _vp, _i, _vp], _i),
+    # test hooks: the fused step's loss-stage launchers
+    "splice_selfsim_loss_pairs_ws_bytes": ([_i, _i, _i], _sz),
+    "splice_selfsim_loss_pairs": ([_vp, _vp, _i, _sz, _vp, _i, _sz, _i, _i, _i, _f, _vp, _i, _f, _vp, _sz, _vp, _i, _sz, _vp, _vp], _i),
+    "splice_mse_pairs": ([_vp, _i, _sz, _vp, _i, _sz, _i, _i, _f, _f, _vp, _sz, _vp, _i, _sz, _i, _vp, _vp], _i),
+    "splice_total_loss_pairs": ([_vp, _sz, _i, _f, _f, _f, _f, _f, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp], _i),
     "splice_patchify": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
     "splice_unpatchify": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
     "splice_cast_f32_bf16": ([_vp, _vp, _sz, _vp], _i),

@@ -126,6 +126,42 @@ int splice_mse(const float* a, int lda, const float* b, int ldb, int rows, int c
     return finish(mse_launch(a, lda, b, ldb, rows, cols, weight, loss_accum, grad, ldg, ST(stream)), "splice_mse");
 }
 
+/* test hooks: the loss-stage launchers of the fused step on caller-owned buffers */
+size_t splice_selfsim_loss_pairs_ws_bytes(int T, int D, int pairs) { return selfsim_batch_ws_bytes(T, D, pairs); }
+int splice_selfsim_loss_pairs(const splice_bf16* k_tgt, const splice_bf16* k_x, int ldk, size_t k_pstride, const splice_bf16* kT_x, int ldt,
+                              size_t kT_pstride, int T, int D, int pairs, float lambda, const float* e_scale_tab, int fp8, float eps,
+                              float* loss_part, size_t part_pstride, float* dk, int lddk, size_t dk_pstride, void* ws, splice_stream_t stream) {
+    const char* who = "splice_selfsim_loss_pairs";
+    if (!k_tgt || !k_x || !kT_x || !loss_part || !dk || !ws || T < 1 || pairs < 1 || D < 64 || D % 64 || ldk < D || ldk % 8 || ldt % 8 ||
+        k_pstride % 8 || kT_pstride % 8 || lddk < D)
+        return finish(SPLICE_ERR_ARG, who);
+    // the two launchers' own refusals, asked before the first of them launches (the second's would come behind the target's kernels)
+    const int nt = (T + 63) / 64;
+    if ((fp8 && D % 128) || (size_t)(nt * (nt + 1) / 2) > part_pstride) return finish(SPLICE_ERR_ARG, who);
+    SelfSimBatch b = {};
+    selfsim_batch_carve(ws, T, D, pairs, &b);
+    b.ldk = ldk; b.ldt = ldt; b.k_pstride = k_pstride; b.kT_pstride = kT_pstride;
+    b.k_tgt = k_tgt; b.k_x = k_x; b.kT_x = kT_x;
+    b.loss_part = loss_part; b.part_pstride = part_pstride;
+    b.dk = dk; b.dk_pstride = dk_pstride; b.lddk = lddk;
+    b.eps = eps;
+    b.fp8 = fp8 != 0;
+    b.loss_scale = 1.0f / ((float)T * (float)T);   // the fp32 expressions of the step's ssim_batch
+    b.e_scale = 4.0f * lambda * b.loss_scale;
+    b.e_scale_tab = e_scale_tab;
+    const int rc = selfsim_target_launch(b, ST(stream));
+    if (rc != SPLICE_OK) return finish(rc, who);
+    return finish(selfsim_loss_launch(b, ST(stream)), who);
+}
+int splice_mse_pairs(const float* a, int lda, size_t a_ps, const float* b, int ldb, size_t b_ps, int rows, int cols, float loss_weight,
+                     float grad_weight, float* part, size_t part_ps, float* grad, int ldg, size_t g_ps, int pairs, const float* grad_tab,
+                     splice_stream_t stream) {
+    if (!a || !b || rows < 1 || cols < 1) return finish(SPLICE_ERR_ARG, "splice_mse_pairs");
+    return finish(mse_batched_launch(a, lda, a_ps, b, ldb, b_ps, rows, cols, loss_weight, grad_weight, part, part_ps, grad, ldg, g_ps, pairs,
+                                     ST(stream), grad_tab),
+                  "splice_mse_pairs");
+}
+
 int splice_patchify(const float* img, splice_bf16* patches, int B, int H, int W, int p, int Tld, int normalize,
                     splice_stream_t stream) {
     return finish(patchify_launch(img, patches, B, H, W, p, Tld, normalize, ST(stream)), "splice_patchify");

@@ -705,6 +705,18 @@ int splice_plateau_update_best(splice_stop_state* state, splice_best_state* best
                   best, means);
     return SPLICE_OK;
 }
+// test hook: the step's total-loss launch (the instance without the stop rule) on a caller's partials buffer
+int splice_total_loss_pairs(float* lbase, size_t lstride, int lp, float w_ssim, float w_essim, float w_ecls, float w_cls, float w_id, float* out8,
+                            int pairs, int n_a, int n_b, int n_c, int n_e, const float* wtab, int ssim_on, int entire, splice_stream_t stream) {
+    if (!lbase || pairs < 1 || lp < 1 || lstride < 8 + (size_t)L_TERMS * lp || n_a < 1 || n_b < 1 || n_c < 1 || n_e < 1) {
+        splice_set_error("splice_total_loss_pairs: invalid argument");
+        return SPLICE_ERR_ARG;
+    }
+    SPLICE_LAUNCH(total_loss_kernel<false>, dim3(pairs), dim3(320), 0, (hipStream_t)stream, lbase, lstride, lp, w_ssim, w_essim, w_ecls, w_cls, w_id, out8,
+                  n_a, n_b, n_c, n_e, wtab, ssim_on, entire, (splice_stop_state*)nullptr, (const int*)nullptr, StopRule{}, (splice_best_state*)nullptr,
+                  (float*)nullptr);
+    return SPLICE_OK;
+}
 
 // BatchNorm running statistics (models/unet/common.py:95-96): when set, every step applies the momentum-0.1 update of its
 // netG calls in the reference's order (A_global, A on entire steps, B_global; models/model.py:15-23) to the caller's

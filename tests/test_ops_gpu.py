@@ -418,6 +418,54 @@ def test_mse():
     assert _relerr(grad, 10.0 * 2 * d / d.numel()) < 1e-6
 
 
+@pytest.mark.parametrize("T", [64, 65])
+def test_selfsim_fwd_bwd_elementwise_at_the_tile_edge(T):
+    """One tile exactly / one row into the second tile, a padded key pitch (ldk = D + 8, NaN in the gap) and an all-zero key row
+    (the eps gate): every S element within 2e-5 of fp64, every dK element inside the bound oracle/loss_stage.py derives for a given,
+    non-symmetric dS (bf16 storage of W = (dS + dS^T) / c, the S error inside r)."""
+    from oracle import loss_stage as ls
+    D = 128
+    g = torch.Generator().manual_seed(300 + T)
+    K = ls.bf16_round(torch.randn(T, D, generator=g) * (1 + torch.randn(T, 1, generator=g).abs()))
+    K[T // 3] = 0
+    dS = torch.randn(T, T, generator=g)
+    S_ref, dK_ref, bound = ls.selfsim_bwd_closed_form(K, dS)
+    Kd = torch.full((T, D + 8), float("nan"), device=DEV)
+    Kd[:, :D] = K.to(DEV)
+    S, ws = _selfsim(Kd, T, D)
+    assert (S.cpu().double() - S_ref).abs().max().item() < 2e-5
+    dK = torch.full((T, D + 8), 0x7FC0DEAD, dtype=torch.int32, device=DEV).view(torch.float32)
+    dSd = dS.to(DEV)
+    _lib.check(_lib.lib().splice_keys_selfsim_bwd(_lib.ptr(dSd), _lib.ptr(S), T, D, 1e-8, _lib.ptr(dK), D + 8, 0, _lib.ptr(ws), _st()))
+    torch.cuda.synchronize()
+    assert (dK[:, D:].contiguous().view(torch.int32) == 0x7FC0DEAD).all()
+    err = (dK[:, :D].cpu().double() - dK_ref).abs()
+    assert (err <= bound).all(), (err / bound.clamp(min=1e-300)).max().item()
+
+
+def test_mse_one_row_wrap_and_scratch_rezeroed():
+    """splice_mse at rows = 1, at 700 x 384 (268 800 elements: the smallest shape over the 1024 x 256 grid cap, the grid-stride loop
+    wraps) with lda != ldb, and two consecutive calls accumulating into one loss_accum -- the second (2 workgroups) would pick up the
+    first's 1024 partials if the scratch line were not re-zeroed.  Bounds: a gradient element has three fp32 roundings (4 * 2^-24
+    relative); the loss is a sum of non-negative terms with at most 16 roundings to a partial (oracle/loss_stage.py), 12 more along
+    the fixed-order sum of the 1024 partials (4 per thread, 6 in the wave, 2 across waves) and one for the accumulation."""
+    u = 2.0 ** -24
+    L = _lib.lib()
+    loss = torch.zeros(1, device=DEV)
+    expect = 0.0
+    for rows, cols, lda, ldb, w, seed in ((700, 384, 400, 384, 10.0, 42), (1, 384, 384, 392, 3.0, 43)):
+        a, b = _rand(rows, lda, seed=seed), _rand(rows, ldb, seed=seed + 10)
+        grad = torch.full((rows, cols + 8), float("nan"), device=DEV)
+        _lib.check(L.splice_mse(_lib.ptr(a), lda, _lib.ptr(b), ldb, rows, cols, w, _lib.ptr(loss), _lib.ptr(grad), cols + 8, _st()))
+        d = a[:, :cols].double() - b[:, :cols].double()
+        expect += w * (d * d).mean().item()
+        gmean = float(np.float32(w) / np.float32(rows * cols))
+        ref = 2.0 * gmean * d
+        assert ((grad[:, :cols].double() - ref).abs() <= 4 * u * ref.abs()).all()
+        assert torch.isnan(grad[:, cols:]).all()
+        assert abs(loss.item() - expect) <= 32 * u * expect, (rows, loss.item(), expect)
+
+
 @pytest.mark.parametrize("p,H,W", [(8, 32, 48), (16, 64, 64), (8, 224, 224)])
 def test_patchify_roundtrip(p, H, W):
     B = 2
