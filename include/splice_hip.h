@@ -624,6 +624,60 @@ int splice_total_loss_pairs(float* lbase, size_t lstride, int lp, float w_ssim, 
                             float* out8, int pairs, int n_a, int n_b, int n_c, int n_e, const float* wtab, int ssim_on, int entire,
                             splice_stream_t stream);
 
+/* ------------------------------------------------------------------ test hooks: the [CLS] tail of the top ViT block as the engine launches it
+ * in top_cls_only mode (vit_cls.hip).  The five entry points below check their arguments and call the engine's own launchers on the caller's
+ * buffers; they add no kernel and no code path (tests/test_cls_tail_gpu.py against oracle/cls_tail.py).
+ *
+ * Single-query attention of the [CLS] token (row 0) of each of B passes, heads of 64 columns (H = D / 64):
+ *   qkv     bf16 [B * Tld][3D], pass b at rows b * Tld ..; columns [0, D) q, [D, 2D) k, [2D, 3D) v, head h at + 64 h.  Read: q of row 0 and k
+ *           of rows < T (forward), q of row 0 and v of rows < T (backward).  Rows T..Tld-1 are never read.
+ *   qkvT    its transpose, bf16 [3D][ldt], pass b at column b * Tld.  The forward reads the v rows, the backward the k rows, Tld columns wide
+ *           per pass; what lies at columns T..Tld-1 is multiplied by exact zeros: it must be READABLE and FINITE (an Inf or NaN there reaches
+ *           every element of out / dq of that head).
+ *   scale   multiplies q . k (0.125 for plain q; ln 2 for the engine's stored q, which carries d^-1/2 log2 e).
+ *   out     bf16 [B][D], one compact row per pass: sum_j p_j v_j with p rounded to bf16, fp32 accumulation.  All of it is written.
+ *   probs   fp32 [B][H][Tld]: softmax over the T keys, fp32; columns T..Tld-1 are written as +0.  The backward reads columns < T only.
+ *   dout_slabs  the gradient of `out` as n_slabs (1..16) fp32 split-K slabs: slab s holds [B][D] at + s * slab_stride floats.  The kernel
+ *           forms dO = bf16(((0 + s_0) + s_1) + ...), in slab order.
+ *   dqkv    bf16 [B * Tld][3D].  Written, for every pass and head: the whole [Tld] x (q | k | v head slices) block -- dq on row 0 (with
+ *           ds rounded to bf16) and zeros on rows 1..Tld-1; dk_j = bf16(ds_j q), ds_j = p_j (dO . v_j - delta) scale, delta = sum_j p_j dO . v_j;
+ *           dv_j = bf16(p_j dO); rows T..Tld-1 all-zero bits.  Nothing outside [B * Tld][3D] is written.
+ * Refused with SPLICE_ERR_ARG before anything is launched: a NULL operand, B < 1, T < 1, T > Tld, Tld % 32, ldt % 8 (16-byte loads),
+ * ldt < B * Tld, D % 64, H != D / 64, n_slabs outside 1..16, dynamic LDS (6 Tld + 1056 bytes forward, 6 Tld + 1696 backward) above the
+ * device's limit for a launch without a function attribute (64 KiB). */
+int splice_attn_cls_fwd(const splice_bf16* qkv, const splice_bf16* qkvT, int ldt, int B, int T, int Tld, int D, int H, float scale, splice_bf16* out,
+                        float* probs, splice_stream_t stream);
+int splice_attn_cls_bwd(const splice_bf16* qkv, const splice_bf16* qkvT, int ldt, int B, int T, int Tld, int D, int H, float scale, const float* probs,
+                        const float* dout_slabs, int n_slabs, size_t slab_stride, splice_bf16* dqkv, splice_stream_t stream);
+/* LayerNorm of `rows` strided rows of D <= 768 columns (one workgroup per row): row r at x + r * xs, its output at y + r * ys (bf16), its
+ * statistics at mean[r * ss] / rstd[r * ss] (two-pass variance, rstd = rsqrt(var + eps)).  Strides in elements; only the D columns of a row
+ * are read or written, the gaps between rows are left alone.
+ *   slabs == NULL: x is read and not written.
+ *   slabs != NULL: the row is first FORMED as ((bias[c] + resid[r * rs + c]) + s_0) + s_1 ..., slab s at slabs[s * slab_stride + r * D + c]
+ *           (compact rows), added in slab order, stored to x (x is not read) and then normalised.  n_slabs >= 1, any number.
+ * Backward: dy row r at dy + r * dys, slab s at + s * slab_stride; with n_slabs > 1 the slabs are summed in slab order and the sum is
+ * stored back into slab 0 (n_slabs <= 1: dy is not written).  x, mean, rstd as the forward left them.  g (fp32) and g_bf (bf16) are both
+ * strided like x (row r at + r * xs): g += rstd (dxhat - mean(dxhat) - xhat mean(dxhat xhat)), dxhat = dy gamma -- g is READ, it must be
+ * finite -- and g_bf = bf16(g).
+ * Refused with SPLICE_ERR_ARG before anything is launched: a NULL operand (slabs, bias and resid may be NULL together), D outside 1..768,
+ * rows < 1, slabs given with n_slabs < 1 or without bias / resid. */
+int splice_ln_rows_fwd(float* x, size_t xs, const float* gamma, const float* beta, splice_bf16* y, size_t ys, float* mean, float* rstd, size_t ss,
+                       int rows, int D, float eps, const float* slabs, int n_slabs, size_t slab_stride, const float* bias, const float* resid, size_t rs,
+                       splice_stream_t stream);
+int splice_ln_rows_bwd(float* dy, size_t dys, const float* x, size_t xs, const float* gamma, const float* mean, const float* rstd, size_t ss, float* g,
+                       splice_bf16* g_bf, int rows, int D, int n_slabs, size_t slab_stride, splice_stream_t stream);
+/* Finisher of a split-K GEMM with `rows` rows: v = (bias[n] + s_0) + s_1 + ..., slab s at slabs[s * slab_stride + row * N + n], in slab order
+ * (modes 0 and 1; bias may be NULL = 0; mode 2 takes no bias), then
+ *   mode 0: out_f32[row * os + n] = v + resid[row * rs + n]                                                  (fc2: the block output rows)
+ *   mode 1: out_bf[row * N + n] = bf16(gelu(v)); pre_bf[row * ps + n] = bf16(v) for rows >= pre_lo, pre_bf may be NULL        (fc1)
+ *   mode 2: out_bf[row * N + n] = bf16(v * gelu'(aux[row * ps + n])), aux bf16                                              (fc2^T)
+ * Only the N columns of a row are written; rows of pre_bf below pre_lo and everything a mode does not name are left alone.
+ * Refused with SPLICE_ERR_ARG before anything is launched: mode outside 0..2, rows or N < 1, slabs NULL or n_slabs < 1, out_f32 or resid
+ * NULL in mode 0, out_bf NULL in modes 1 and 2, aux NULL in mode 2. */
+int splice_rows_finish(int mode, const float* slabs, int n_slabs, size_t slab_stride, int rows, int N, const float* bias, const float* resid, size_t rs,
+                       float* out_f32, size_t os, splice_bf16* out_bf, splice_bf16* pre_bf, const splice_bf16* aux, size_t ps, int pre_lo,
+                       splice_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -95,6 +95,12 @@ _SIGNATURES = {
     "splice_selfsim_loss_pairs": ([_vp, _vp, _i, _sz, _vp, _i, _sz, _i, _i, _i, _f, _vp, _i, _f, _vp, _sz, _vp, _i, _sz, _vp, _vp], _i),
     "splice_mse_pairs": ([_vp, _i, _sz, _vp, _i, _sz, _i, _i, _f, _f, _vp, _sz, _vp, _i, _sz, _i, _vp, _vp], _i),
     "splice_total_loss_pairs": ([_vp, _sz, _i, _f, _f, _f, _f, _f, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp], _i),
+    # test hooks: the [CLS]-tail launchers of the top ViT block
+    "splice_attn_cls_fwd": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp], _i),
+    "splice_attn_cls_bwd": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _i, _sz, _vp, _vp], _i),
+    "splice_ln_rows_fwd": ([_vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _i, _i, _f, _vp, _i, _sz, _vp, _vp, _sz, _vp], _i),
+    "splice_ln_rows_bwd": ([_vp, _sz, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _i, _i, _i, _sz, _vp], _i),
+    "splice_rows_finish": ([_i, _vp, _i, _sz, _i, _i, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _sz, _i, _vp], _i),
     "splice_patchify": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
     "splice_unpatchify": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
     "splice_cast_f32_bf16": ([_vp, _vp, _sz, _vp], _i),

@@ -162,6 +162,51 @@ int splice_mse_pairs(const float* a, int lda, size_t a_ps, const float* b, int l
                   "splice_mse_pairs");
 }
 
+/* test hooks: the [CLS]-tail launchers of the top ViT block (vit_cls.hip) on caller-owned buffers.  They only validate and forward. */
+static bool attn_cls_args_ok(const void* qkv, const void* qkvT, int ldt, int B, int T, int Tld, int D, int H, size_t lds) {
+    if (!qkv || !qkvT || B < 1 || T < 1 || T > Tld || Tld % 32 || ldt % 8 || (long long)ldt < (long long)B * Tld || D < 64 || D % 64 || H != D / 64)
+        return false;
+    int dev = 0, lim = 0;   // the launchers set no function attribute: the default dynamic LDS ceiling holds, and the device's own where it is lower
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&lim, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess) return false;
+    return lds <= (size_t)(lim < 65536 ? lim : 65536);
+}
+int splice_attn_cls_fwd(const splice_bf16* qkv, const splice_bf16* qkvT, int ldt, int B, int T, int Tld, int D, int H, float scale, splice_bf16* out,
+                        float* probs, splice_stream_t stream) {
+    const char* who = "splice_attn_cls_fwd";
+    if (!out || !probs || !attn_cls_args_ok(qkv, qkvT, ldt, B, T, Tld, D, H, ((size_t)Tld + Tld / 2 + 256 + 8) * sizeof(float)))
+        return finish(SPLICE_ERR_ARG, who);
+    return finish(attn_cls_fwd_launch(qkv, qkvT, ldt, B, T, Tld, D, H, scale, out, probs, ST(stream)), who);
+}
+int splice_attn_cls_bwd(const splice_bf16* qkv, const splice_bf16* qkvT, int ldt, int B, int T, int Tld, int D, int H, float scale, const float* probs,
+                        const float* dout_slabs, int n_slabs, size_t slab_stride, splice_bf16* dqkv, splice_stream_t stream) {
+    const char* who = "splice_attn_cls_bwd";
+    if (!probs || !dout_slabs || !dqkv || n_slabs < 1 || n_slabs > 16 ||
+        !attn_cls_args_ok(qkv, qkvT, ldt, B, T, Tld, D, H, ((size_t)Tld + Tld / 2 + 64 + 64 + 32 + 256 + 8) * sizeof(float)))
+        return finish(SPLICE_ERR_ARG, who);
+    return finish(attn_cls_bwd_launch(qkv, qkvT, ldt, B, T, Tld, D, H, scale, probs, dout_slabs, n_slabs, slab_stride, dqkv, ST(stream)), who);
+}
+int splice_ln_rows_fwd(float* x, size_t xs, const float* gamma, const float* beta, splice_bf16* y, size_t ys, float* mean, float* rstd, size_t ss,
+                       int rows, int D, float eps, const float* slabs, int n_slabs, size_t slab_stride, const float* bias, const float* resid, size_t rs,
+                       splice_stream_t stream) {
+    const char* who = "splice_ln_rows_fwd";
+    if (!x || !gamma || !beta || !y || !mean || !rstd || (slabs && (n_slabs < 1 || !bias || !resid))) return finish(SPLICE_ERR_ARG, who);
+    return finish(ln_rows_fwd_launch(x, xs, gamma, beta, y, ys, mean, rstd, ss, rows, D, eps, slabs, n_slabs, slab_stride, bias, resid, rs, ST(stream)), who);
+}
+int splice_ln_rows_bwd(float* dy, size_t dys, const float* x, size_t xs, const float* gamma, const float* mean, const float* rstd, size_t ss, float* g,
+                       splice_bf16* g_bf, int rows, int D, int n_slabs, size_t slab_stride, splice_stream_t stream) {
+    const char* who = "splice_ln_rows_bwd";
+    if (!dy || !x || !gamma || !mean || !rstd || !g || !g_bf) return finish(SPLICE_ERR_ARG, who);
+    return finish(ln_rows_bwd_launch(dy, dys, x, xs, gamma, mean, rstd, ss, g, g_bf, rows, D, n_slabs, slab_stride, ST(stream)), who);
+}
+int splice_rows_finish(int mode, const float* slabs, int n_slabs, size_t slab_stride, int rows, int N, const float* bias, const float* resid, size_t rs,
+                       float* out_f32, size_t os, splice_bf16* out_bf, splice_bf16* pre_bf, const splice_bf16* aux, size_t ps, int pre_lo,
+                       splice_stream_t stream) {
+    const char* who = "splice_rows_finish";
+    if (mode < 0 || mode > 2 || !slabs || n_slabs < 1 || rows < 1 || N < 1 || (long long)rows * N > 0x7fffffffLL) return finish(SPLICE_ERR_ARG, who);
+    if ((mode == 0 && (!out_f32 || !resid)) || (mode != 0 && !out_bf) || (mode == 2 && !aux)) return finish(SPLICE_ERR_ARG, who);
+    return finish(rows_finish_launch(mode, slabs, n_slabs, slab_stride, rows, N, bias, resid, rs, out_f32, os, out_bf, pre_bf, aux, ps, pre_lo, ST(stream)), who);
+}
+
 int splice_patchify(const float* img, splice_bf16* patches, int B, int H, int W, int p, int Tld, int normalize,
                     splice_stream_t stream) {
     return finish(patchify_launch(img, patches, B, H, W, p, Tld, normalize, ST(stream)), "splice_patchify");

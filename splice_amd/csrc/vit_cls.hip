@@ -215,7 +215,12 @@ __global__ __launch_bounds__(256) void attn_cls_bwd_kernel(const bf16_t* __restr
 #pragma unroll 2
         for (int c = 0; c < 8; ++c) {   // 16-byte stores: 8 per 64-wide head slice
             if (j != 0) rq[c] = u32x4{0u, 0u, 0u, 0u};
-            rk[c] = u32x4{pack2bf(dsj * q[8 * c], dsj * q[8 * c + 1]), pack2bf(dsj * q[8 * c + 2], dsj * q[8 * c + 3]),
+            if (j >= T) {   // all-zero bits beyond T: 0 * (negative q / dO) would store -0
+                rk[c] = u32x4{0u, 0u, 0u, 0u};
+                rv[c] = u32x4{0u, 0u, 0u, 0u};
+                continue;
+            }
+            rk[c] =u32x4{pack2bf(dsj * q[8 * c], dsj * q[8 * c + 1]), pack2bf(dsj * q[8 * c + 2], dsj * q[8 * c + 3]),
                           pack2bf(dsj * q[8 * c + 4], dsj * q[8 * c + 5]), pack2bf(dsj * q[8 * c + 6], dsj * q[8 * c + 7])};
             rv[c] = u32x4{pack2bf(pj * dO[8 * c], pj * dO[8 * c + 1]), pack2bf(pj * dO[8 * c + 2], pj * dO[8 * c + 3]),
                           pack2bf(pj * dO[8 * c + 4], pj * dO[8 * c + 5]), pack2bf(pj * dO[8 * c + 6], pj * dO[8 * c + 7])};
