@@ -158,11 +158,20 @@ struct GemmTile {
     static __device__ __forceinline__ void dma16(uint32_t lds_byte, uint32_t voff, const void* sbase) {
         asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_byte), "v"(voff), "s"(sbase) : "memory");
     }
-    template <int NS>
+    //
+    // The drain (the last min(nsl, NS-1) slices: no DMA is issued any more) is peeled, and `ops(pre)` runs at its head: the caller's
+    // epilogue operand loads (plain vector loads into registers; they depend on nothing the K loop computes) go out while slices are
+    // still in flight, instead of as a cold burst once every workgroup of the launch has finished its MFMAs.  vmcnt retires in
+    // order, so every wait of the drain counts what was issued BEHIND the slice it awaits: d younger slices (d * NL DMAs) + the
+    // operand loads -- NRD of them always, NPRE more when `pre` (a runtime alignment condition of the caller).  NPRE / NRD are the
+    // caller's instruction counts (one global_load per 16- / 8-byte operand vector; gemm_nt_kernel derives them from the same
+    // loop bounds that issue the loads).
+    template <int NS, int NPRE = 0, int NRD = 0, class Ops>
     __device__ __forceinline__ void run_ring(const bf16_t* __restrict__ A, int lda, const bf16_t* __restrict__ B, int ldb,
-                                             int M, int N, int K, int m0, int n0, bf16_t* smem, int kbeg = 0) {
+                                             int M, int N, int K, int m0, int n0, bf16_t* smem, int kbeg, bool pre, Ops&& ops) {
         static_assert(NS >= 3, "use run_glds for the 2-stage form");
         constexpr int NL = A_LOADS + B_LOADS;
+        static_assert((NS - 2) * NL + NPRE + NRD <= 63, "vmcnt is a 6-bit counter");
         const int tid = threadIdx.x, lane = tid & 63;
         const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
         const int wm = wave >> 1, wn = wave & 1;
@@ -200,16 +209,46 @@ struct GemmTile {
             if (p < nsl) issue(p, p);
         const int frow = lane & 15, fchunk = lane >> 4;
         int stage = 0, nstage = NS - 1;   // stage of slice t, stage of slice t + NS - 1
-        for (int t = 0; t < nsl; ++t) {
-            if (t + NS - 2 < nsl) wait_dma<(NS - 2) * NL>(); else wait_dma<0>();
+        // steady state: slice t + NS - 1 is issued in iteration t, so NS - 2 younger slices are in flight behind slice t
+        for (int t = 0; t + NS - 1 < nsl; ++t) {
+            wait_dma<(NS - 2) * NL>();
             __builtin_amdgcn_s_barrier();   // slice t landed for every wave; the stage of slice t-1 is free again
-            if (t + NS - 1 < nsl) issue(t + NS - 1, nstage);
+            issue(t + NS - 1, nstage);
             const bf16_t* As = smem + stage * LDS_ELEMS;
             const bf16_t* Bs = As + BM * GEMM_BK;
             slice_mfma(As, Bs, wm, wn, frow, fchunk);
             stage = stage + 1 == NS ? 0 : stage + 1;
             nstage = nstage + 1 == NS ? 0 : nstage + 1;
         }
+        // drain: r = min(nsl, NS - 1) slices are left, all issued (by the steady state, or by the prologue alone when K / 64 < NS - 1);
+        // the one with d younger slices behind it is read in the unrolled step d (steps d >= r do not exist for this K)
+        const int r = nsl < NS - 1 ? nsl : NS - 1;
+        ops(pre);
+#pragma unroll
+        for (int d = NS - 2; d >= 0; --d) {
+            if (d < r) {
+                if (NPRE && pre) drain_wait<NS - 2, NL, NPRE + NRD>(d); else drain_wait<NS - 2, NL, NRD>(d);
+                __builtin_amdgcn_s_barrier();
+                const bf16_t* As = smem + stage * LDS_ELEMS;
+                const bf16_t* Bs = As + BM * GEMM_BK;
+                slice_mfma(As, Bs, wm, wn, frow, fchunk);
+                stage = stage + 1 == NS ? 0 : stage + 1;
+            }
+        }
+    }
+    // (no operands to fetch: the ring with its counted drain alone)
+    template <int NS>
+    __device__ __forceinline__ void run_ring(const bf16_t* __restrict__ A, int lda, const bf16_t* __restrict__ B, int ldb,
+                                             int M, int N, int K, int m0, int n0, bf16_t* smem, int kbeg = 0) {
+        run_ring<NS, 0, 0>(A, lda, B, ldb, M, N, K, m0, n0, smem, kbeg, false, [](bool) {});
+    }
+    // s_waitcnt vmcnt(d * NL + NOPS) for the (unrolled, compile-time) drain step d <= DMAX
+    template <int DMAX, int NL, int NOPS>
+    static __device__ __forceinline__ void drain_wait(int d) {
+        if constexpr (DMAX > 0) {
+            if (d < DMAX) { drain_wait<DMAX - 1, NL, NOPS>(d); return; }
+        }
+        wait_dma<DMAX * NL + NOPS>();
     }
 
     // run_ring + the squared norms of the operand rows, taken from the bf16 fragments on their way to the MFMAs (no extra memory
@@ -669,6 +708,43 @@ __device__ __forceinline__ void gemm_stage_store_f32(const f32x4 (&acc)[BM / 32]
     }
 }
 
+// The per-lane epilogue operands of the swapped fragment layout, one vector per fragment, from clamped (always valid) addresses:
+// bias / residual / GELU' input (load_pre: needs N and the leading dimensions multiples of 4) and the row-dot operand (load_rd).
+// NPRE / NRD = the vector-memory instructions load_pre / load_rd issue (one global_load_dwordx4 / dwordx2 each): the ring's drain
+// counts its waits with them (GemmTile::run_ring).
+template <int BM, int BN, unsigned FLAGS>
+struct GemmEpiOperands {
+    static constexpr int FMt = BM / 32, FNt = BN / 32;
+    static constexpr int NPRE = ((FLAGS & EPI_BIAS) ? FNt : 0) + ((FLAGS & EPI_RESID) ? FMt * FNt : 0) + ((FLAGS & EPI_GELU_GRAD) ? FMt * FNt : 0);
+    static constexpr int NRD = (FLAGS & EPI_ROWDOT) ? FMt * FNt : 0;
+    float4 pb[FNt], pr[FMt][FNt];
+    uint2 pa[FMt][FNt], ov[FMt][FNt];
+    __device__ __forceinline__ void load_pre(const GemmEpi& e, int M, int N, int m0, int n0) {
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wm = wave >> 1, wn = wave & 1;
+#pragma unroll
+        for (int j = 0; j < FNt; ++j) {
+            const int colc = min(n0 + wn * (BN / 2) + j * 16 + (lane >> 4) * 4, N - 4);
+            if (FLAGS & EPI_BIAS) pb[j] = *reinterpret_cast<const float4*>(e.bias + colc);
+#pragma unroll
+            for (int i = 0; i < FMt; ++i) {
+                const int rowc = min(m0 + wm * (BM / 2) + i * 16 + (lane & 15), M - 1);
+                const int rr = e.resid_mod ? rowc % e.resid_mod : rowc;
+                if (FLAGS & EPI_RESID) pr[i][j] = *reinterpret_cast<const float4*>(e.resid + (size_t)rr * e.ldr + colc);
+                if (FLAGS & EPI_GELU_GRAD) pa[i][j] = *reinterpret_cast<const uint2*>(e.aux + (size_t)rowc * e.ldaux + colc);
+            }
+        }
+    }
+    __device__ __forceinline__ void load_rd(const GemmEpi& e, int M, int m0, int n0) {
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wm = wave >> 1, wn = wave & 1;
+#pragma unroll
+        for (int i = 0; i < FMt; ++i)
+#pragma unroll
+            for (int j = 0; j < FNt; ++j)
+                ov[i][j] = *reinterpret_cast<const uint2*>(e.rd_other + (size_t)min(m0 + wm * (BM / 2) + i * 16 + (lane & 15), M - 1) * e.ld_rd + n0 +
+                                                           wn * (BN / 2) + j * 16 + (lane >> 4) * 4);
+    }
+};
+
 template <int BM, int BN, unsigned FLAGS, int NS, bool FP8 = false>
 __global__ __launch_bounds__(256) void gemm_nt_kernel(const bf16_t* __restrict__ A, int lda, const bf16_t* __restrict__ B,
                                                       int ldb, int M, int N, int K, int gm, int ksplit, GemmEpi e) {
@@ -714,15 +790,24 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const bf16_t* __restrict__
             walked = true;
         }
     }
-    if (walked) {
-    } else if (NS == 2) tile.run_glds(A, lda, B, ldb, M, N, K, m0, n0, gemm_smem, kbeg);
-    else tile.template run_ring<(NS < 3 ? 3 : NS)>(A, lda, B, ldb, M, N, K, m0, n0, gemm_smem, kbeg);
     // Epilogue operands: lane-guarded loads inside the per-fragment epilogue compile to load + s_waitcnt per fragment,
     // one memory round trip each (4 ... 16 per lane, the residual usually an L2 miss).  With N and the leading dimensions
-    // multiples of 4 every fragment's operands are loaded first, from clamped (always valid) addresses.
+    // multiples of 4 (pre_ok) every fragment's operands are loaded first, from clamped (always valid) addresses: by the bf16 ring
+    // forms (EARLY) at the head of the ring's drain, under the last slices still in flight; by the 2-stage and the fp8 forms behind the K loop.
     constexpr bool HAS_OPERANDS = (FLAGS & (EPI_BIAS | EPI_RESID | EPI_GELU_GRAD)) != 0;
     constexpr bool STAGE_F32_FITS = (size_t)NS * GemmTile<BM, BN>::LDS_ELEMS * 2 >= (size_t)BM * (BN + 4) * 4;
+    constexpr bool EARLY = NS >= 3 && !FP8;
     const bool pre_ok = HAS_OPERANDS && !(N & 3) && (!(FLAGS & EPI_RESID) || !(e.ldr & 3)) && (!(FLAGS & EPI_GELU_GRAD) || !(e.ldaux & 3));
+    typedef GemmEpiOperands<BM, BN, FLAGS> Operands;
+    Operands ops;
+    if (walked) {
+    } else if (NS == 2) tile.run_glds(A, lda, B, ldb, M, N, K, m0, n0, gemm_smem, kbeg);
+    else if constexpr (EARLY)
+        tile.template run_ring<(NS < 3 ? 3 : NS), Operands::NPRE, Operands::NRD>(A, lda, B, ldb, M, N, K, m0, n0, gemm_smem, kbeg, pre_ok, [&](bool pre) {
+            if (Operands::NPRE && pre) ops.load_pre(e, M, N, m0, n0);
+            if (Operands::NRD) ops.load_rd(e, M, m0, n0);
+        });
+    else tile.template run_ring<(NS < 3 ? 3 : NS)>(A, lda, B, ldb, M, N, K, m0, n0, gemm_smem, kbeg);
     // staged bf16 outputs (see gemm_stage_store): every vector access of gemm_frag_value must be aligned
     const bool stage_ok = (FLAGS & EPI_OUT_BF) && !(N & 3) && (!(FLAGS & EPI_RESID) || !(e.ldr & 3)) && (!(FLAGS & EPI_GELU_GRAD) || !(e.ldaux & 3)) &&
                           (!(FLAGS & EPI_OUT_F32) || !(e.ldo & 3)) && (!(FLAGS & EPI_OUT_T) || !(e.ldt & 7));
@@ -756,28 +841,13 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const bf16_t* __restrict__
         static_assert((size_t)NS * GemmTile<BM, BN>::LDS_ELEMS >= (size_t)BM * (BN + 8) && (size_t)NS * GemmTile<BM, BN>::LDS_ELEMS >= (size_t)BN * (BM + 8),
                       "the ring must hold one staged output tile");
         const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wm = wave >> 1, wn = wave & 1;
-        float4 pb[FNt], pr[FMt][FNt];
-        uint2 pa[FMt][FNt];
-        if (HAS_OPERANDS) {   // operands of every fragment before the first use (clamped addresses)
-#pragma unroll
-            for (int j = 0; j < FNt; ++j) {
-                const int colc = min(n0 + wn * (BN / 2) + j * 16 + (lane >> 4) * 4, N - 4);
-                if (FLAGS & EPI_BIAS) pb[j] = *reinterpret_cast<const float4*>(e.bias + colc);
-#pragma unroll
-                for (int i = 0; i < FMt; ++i) {
-                    const int rowc = min(m0 + wm * (BM / 2) + i * 16 + (lane & 15), M - 1);
-                    const int rr = e.resid_mod ? rowc % e.resid_mod : rowc;
-                    if (FLAGS & EPI_RESID) pr[i][j] = *reinterpret_cast<const float4*>(e.resid + (size_t)rr * e.ldr + colc);
-                    if (FLAGS & EPI_GELU_GRAD) pa[i][j] = *reinterpret_cast<const uint2*>(e.aux + (size_t)rowc * e.ldaux + colc);
-                }
-            }
-        }
+        if (HAS_OPERANDS && !EARLY) ops.load_pre(e, M, N, m0, n0);   // operands of every fragment before the first use (stage_ok implies pre_ok)
 #pragma unroll
         for (int i = 0; i < FMt; ++i)
 #pragma unroll
             for (int j = 0; j < FNt; ++j)
                 tile.acc[i][j] = gemm_frag_value<FLAGS, HAS_OPERANDS>(e, M, N, m0 + wm * (BM / 2) + i * 16 + (lane & 15), n0 + wn * (BN / 2) + j * 16 + (lane >> 4) * 4,
-                                                                      tile.acc[i][j], pb[j], pr[i][j], pa[i][j]);
+                                                                      tile.acc[i][j], ops.pb[j], ops.pr[i][j], ops.pa[i][j]);
         if (FLAGS & EPI_GELU) {
             if (e.out_pre) gemm_stage_store<BM, BN, false>(tile.acc, gemm_smem, e.out_pre, e.ldp, M, N, m0, n0, e.pre_row_lo);   // only gradient-carrying rows need it
 #pragma unroll
@@ -799,58 +869,29 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const bf16_t* __restrict__
 #pragma unroll
                     for (int r = 0; r < 4; ++r) tile.acc[i][j][r] = bf2f(f2bf(tile.acc[i][j][r]));
         }
-    } else if (STAGE_F32_FITS && (FLAGS & EPI_OUT_F32) && !(FLAGS & (EPI_OUT_BF | EPI_COLS_F32)) && !(N & 3) && !(e.ldo & 3) && (!(FLAGS & EPI_RESID) || !(e.ldr & 3))) {
+    } else if (STAGE_F32_FITS && (FLAGS & EPI_OUT_F32) && !(FLAGS & (EPI_OUT_BF | EPI_COLS_F32 | EPI_GELU_GRAD)) && !(N & 3) && !(e.ldo & 3) && (!(FLAGS & EPI_RESID) || !(e.ldr & 3))) {
         // fp32 output (proj / fc2 forward, the dgrads into LayerNorm backward): staged like the bf16 tiles (where the ring holds the tile)
+        // (without a GELU' operand these conditions imply pre_ok wherever there are operands)
         constexpr int FMt = GemmTile<BM, BN>::FM, FNt = GemmTile<BM, BN>::FN;
         const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wm = wave >> 1, wn = wave & 1;
-        float4 pb[FNt], pr[FMt][FNt];
-        if (HAS_OPERANDS) {
-#pragma unroll
-            for (int j = 0; j < FNt; ++j) {
-                const int colc = min(n0 + wn * (BN / 2) + j * 16 + (lane >> 4) * 4, N - 4);
-                if (FLAGS & EPI_BIAS) pb[j] = *reinterpret_cast<const float4*>(e.bias + colc);
-#pragma unroll
-                for (int i = 0; i < FMt; ++i) {
-                    const int rowc = min(m0 + wm * (BM / 2) + i * 16 + (lane & 15), M - 1);
-                    const int rr = e.resid_mod ? rowc % e.resid_mod : rowc;
-                    if (FLAGS & EPI_RESID) pr[i][j] = *reinterpret_cast<const float4*>(e.resid + (size_t)rr * e.ldr + colc);
-                }
-            }
-        }
+        if (HAS_OPERANDS && !EARLY) ops.load_pre(e, M, N, m0, n0);
 #pragma unroll
         for (int i = 0; i < FMt; ++i)
 #pragma unroll
             for (int j = 0; j < FNt; ++j)
                 tile.acc[i][j] = gemm_frag_value<FLAGS, HAS_OPERANDS, false>(e, M, N, m0 + wm * (BM / 2) + i * 16 + (lane & 15),
-                                                                             n0 + wn * (BN / 2) + j * 16 + (lane >> 4) * 4, tile.acc[i][j], pb[j], pr[i][j], uint2{});
+                                                                             n0 + wn * (BN / 2) + j * 16 + (lane >> 4) * 4, tile.acc[i][j], ops.pb[j], ops.pr[i][j], uint2{});
         if constexpr (STAGE_F32_FITS) gemm_stage_store_f32<BM, BN>(tile.acc, reinterpret_cast<float*>(gemm_smem), e.out_f32, e.ldo, M, N, m0, n0);
     } else if (pre_ok) {
         constexpr int FMt = GemmTile<BM, BN>::FM, FNt = GemmTile<BM, BN>::FN;
         const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wm = wave >> 1, wn = wave & 1;
-        float4 pb[FNt], pr[FMt][FNt];
-        uint2 pa[FMt][FNt];
-        int colc[FNt];
-#pragma unroll
-        for (int j = 0; j < FNt; ++j) {
-            colc[j] = min(n0 + wn * (BN / 2) + j * 16 + (lane >> 4) * 4, N - 4);
-            if (FLAGS & EPI_BIAS) pb[j] = *reinterpret_cast<const float4*>(e.bias + colc[j]);
-        }
-#pragma unroll
-        for (int i = 0; i < FMt; ++i) {
-            const int rowc = min(m0 + wm * (BM / 2) + i * 16 + (lane & 15), M - 1);
-            const int rr = e.resid_mod ? rowc % e.resid_mod : rowc;
-#pragma unroll
-            for (int j = 0; j < FNt; ++j) {
-                if (FLAGS & EPI_RESID) pr[i][j] = *reinterpret_cast<const float4*>(e.resid + (size_t)rr * e.ldr + colc[j]);
-                if (FLAGS & EPI_GELU_GRAD) pa[i][j] = *reinterpret_cast<const uint2*>(e.aux + (size_t)rowc * e.ldaux + colc[j]);
-            }
-        }
+        if (!EARLY) ops.load_pre(e, M, N, m0, n0);
 #pragma unroll
         for (int i = 0; i < FMt; ++i)
 #pragma unroll
             for (int j = 0; j < FNt; ++j)
                 gemm_epilogue_cols<FLAGS, true>(e, M, N, m0 + wm * (BM / 2) + i * 16 + (lane & 15), n0 + wn * (BN / 2) + j * 16 + (lane >> 4) * 4,
-                                                tile.acc[i][j], pb[j], pr[i][j], pa[i][j]);
+                                                tile.acc[i][j], ops.pb[j], ops.pr[i][j], ops.pa[i][j]);
     } else {
         tile.for_each_cols(m0, n0, [&](int row, int col0, f32x4 v) { gemm_epilogue_cols<FLAGS>(e, M, N, row, col0, v); });
     }
@@ -861,14 +902,9 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const bf16_t* __restrict__
         constexpr int FMt = GemmTile<BM, BN>::FM, FNt = GemmTile<BM, BN>::FN;
         const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wm = wave >> 1, wn = wave & 1;
         float* red = reinterpret_cast<float*>(gemm_smem);   // [2 wn][BM] (the K loop is over)
-        __syncthreads();
-        uint2 ov[FMt][FNt];   // every fragment's operand is loaded before the first use (clamped row: the loads are unconditional)
-#pragma unroll
-        for (int i = 0; i < FMt; ++i)
-#pragma unroll
-            for (int j = 0; j < FNt; ++j)
-                ov[i][j] = *reinterpret_cast<const uint2*>(e.rd_other + (size_t)min(m0 + wm * (BM / 2) + i * 16 + (lane & 15), M - 1) * e.ld_rd + n0 +
-                                                           wn * (BN / 2) + j * 16 + (lane >> 4) * 4);
+        __syncthreads();   // red[] lies in the ring / the staged output tile: every wave is done reading them
+        // every fragment's operand is loaded before the first use (clamped row: the loads are unconditional); the ring forms did it in their drain
+        if (!EARLY) ops.load_rd(e, M, m0, n0);
 #pragma unroll
         for (int i = 0; i < FMt; ++i) {
             const int lrow = wm * (BM / 2) + i * 16 + (lane & 15);
@@ -877,7 +913,7 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const bf16_t* __restrict__
             if (row < M) {
 #pragma unroll
                 for (int j = 0; j < FNt; ++j) {
-                    const uint2 o = ov[i][j];
+                    const uint2 o = ops.ov[i][j];
                     const f32x4 v = tile.acc[i][j];
                     part += bf2f(f2bf(v[0])) * bf2f((bf16_t)(o.x & 0xFFFF)) + bf2f(f2bf(v[1])) * bf2f((bf16_t)(o.x >> 16)) +
                             bf2f(f2bf(v[2])) * bf2f((bf16_t)(o.y & 0xFFFF)) + bf2f(f2bf(v[3])) * bf2f((bf16_t)(o.y >> 16));

@@ -3,7 +3,7 @@
 #include "kernels.h"
 #include "gemm8p.h"
 
-static int g_force_tile = 0;   // 0 auto; tile + 10 * ring: tile 1 = 128x128, 2 = 128x64, 3 = 64x64; ring 0 = 2 stages, 1 = 4 stages, 2 = 3 stages (64x64 only) (tools/gemm_bench.py); 5 = the persistent 256x256 8-phase tile where it exists (gemm8p.h), else automatic
+static int g_force_tile = 0;   // 0 auto; tile + 10 * ring: tile 1 = 128x128, 2 = 128x64, 3 = 64x64; ring 0 = 2 stages, 1 = 4 stages, 2 = 3 stages (64x64 and 128x64) (tools/gemm_bench.py); the row-dot forms take the ring code only (their tile is 64x64); 5 = the persistent 256x256 8-phase tile where it exists (gemm8p.h), else automatic
 void gemm_force_tile(int t) { g_force_tile = t; }
 
 template <unsigned FLAGS>
@@ -23,7 +23,8 @@ static int dispatch_tile(const bf16_t* A, int lda, const bf16_t* B, int ldb, int
         }
     }
     int tile, ring;
-    if (g_force_tile && g_force_tile != 5 && !(FLAGS & EPI_ROWDOT)) { tile = g_force_tile % 10; ring = g_force_tile / 10; }
+    // (the row-dot forms exist for the 64 x 64 tile only: the hook pins their ring depth)
+    if (g_force_tile && g_force_tile != 5) { tile = (FLAGS & EPI_ROWDOT) ? 3 : g_force_tile % 10; ring = g_force_tile / 10; }
     else {
         // measured on MI355X (tools/gemm_bench.py): with N <= 768 the 64x64 tile wins (more workgroups on the long-K shapes);
         // otherwise the biggest tile that still yields ~2 workgroups per CU (M = 1600: 128x64 beats 128x128 by 10 %, M = 800: 64x64)
