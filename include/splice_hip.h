@@ -678,6 +678,143 @@ int splice_rows_finish(int mode, const float* slabs, int n_slabs, size_t slab_st
                        float* out_f32, size_t os, splice_bf16* out_bf, splice_bf16* pre_bf, const splice_bf16* aux, size_t ps, int pre_lo,
                        splice_stream_t stream);
 
+/* ------------------------------------------------------------------ test hooks: generator launchers on caller-owned buffers
+ * (gen_conv.hip, gen_wgrad.hip, gen_bn.hip, gen_pointwise.hip).  Each entry point checks its arguments and calls the launcher the generator
+ * engine calls, on the caller's buffers; it adds no kernel, no policy and no code path (tests/test_gen_ops_gpu.py against oracle/gen_ops.py).
+ * Which kernel instantiation runs is the launchers' own decision from the shapes; the hooks report it.  Everything a launcher would index out
+ * of bounds with is refused with SPLICE_ERR_ARG before anything is launched: a NULL required pointer, a size < 1, a filter size outside
+ * {1, 3, 5, 7}, a stride outside {1, 2}, a channel stride smaller than its plane, an image stride smaller than its channels (N > 1), reflection
+ * with pad >= height or width, more than 128 output channels in a weight gradient, a batch above 8 or one that does not divide N, scratch
+ * smaller than the launcher needs, offsets beyond the 32-bit gathers (channels x channel stride and the weight block at most 2^29 - 1 floats).
+ *
+ * Convolution (fp32 NCHW, exact-fp32 MFMA): channel c of image n of `in` at in + n * in_nstride + c * in_cstride, [Hi][Wi]; output column j
+ * at out + n * out_nstride + j * out_cstride, [Ho][Wo]; weight element (column j, reduction channel c, tap) at w + j * w_jstride + c * w_cstride
+ * + tap.  Cin counts the REDUCTION channels and Cout the output columns in either direction:
+ *   forward      out[j][oy][ox] = bias[j] + sum_{c,ky,kx} in[c][oy * stride + ky - pad][ox * stride + kx - pad] w[j][c][ky][kx]  (zero padding;
+ *                reflect: nn.ReflectionPad2d(pad) in front instead), act = 1: sigmoid behind it.
+ *   transposed   the data gradient: out[j][iy][ix] = sum_{c,ky,kx} in[c][oy][ox] w(j, c, ky, kx) over oy * stride + ky - pad = iy (and x alike);
+ *                for a forward weight [Co][Ci][ks][ks] that is Cin = Co, Cout = Ci, w_jstride = ks * ks, w_cstride = Ci * ks * ks.
+ *   accumulate   out = out + result (one rounding more).  p_nstride > 0: image n reads w / bias at + (p_group > 1 ? n / p_group : n) * p_nstride.
+ *   ws           optional split-K scratch of ws_floats floats (NULL: no split-K); defer_reduce leaves the raw slices in ws, slice k of image n,
+ *                column j at ws + ((k * N + n) * Cout + j) * Ho * Wo, and does not touch out when form_out[4] > 1.
+ * form_out (SPLICE_GEN_CONV_FORM_INTS ints, may be NULL): {1 = LDS-halo tile kernel / 0 = implicit GEMM, channels per K tile, output-channel
+ * fragments per workgroup, wave groups, split-K slices}. */
+typedef struct splice_gen_conv_args {
+    const float* in;
+    const float* w;
+    const float* bias;        /* [Cout] or NULL */
+    float* out;
+    size_t in_nstride, in_cstride, out_nstride, out_cstride, w_jstride, w_cstride, p_nstride;
+    int N, Cin, Hi, Wi, Cout, Ho, Wo, ks, stride, pad;
+    int reflect, act, transposed, accumulate;
+    float* ws;
+    size_t ws_floats;
+    int p_group, defer_reduce;
+} splice_gen_conv_args;
+#define SPLICE_GEN_CONV_FORM_INTS 5
+int splice_gen_conv(const splice_gen_conv_args* args, int* form_out, splice_stream_t stream);
+/* conv_pair_launch: a (1x1, stride 1) and b in one launch where an instantiation exists, else two launches; the results of two
+ * splice_gen_conv calls bit for bit.  forms_out: 2 x SPLICE_GEN_CONV_FORM_INTS ints (a's, then b's), may be NULL. */
+int splice_gen_conv_pair(const splice_gen_conv_args* a, const splice_gen_conv_args* b, int* forms_out, splice_stream_t stream);
+/* Data gradient of a reflection-padded convolution.  args in data-gradient form as for the zero-padded layer (in = the output gradient, out =
+ * the input gradient [N][Cout][Ho][Wo], pad = the layer's padding); pad_scratch: at least N * Cout * (Ho + 2 pad) * (Wo + 2 pad) floats. */
+int splice_gen_conv_reflect_dgrad(const splice_gen_conv_args* args, float* pad_scratch, size_t scratch_floats, splice_stream_t stream);
+
+/* Weight gradient dw[j][c][tap] (+)= sum over images and pixels of dy[j][oy][ox] x[c][oy * stride + ky - pad][ox * stride + kx - pad] (reflect: of the
+ * reflection-padded x): conv_wgrad_add into an empty queue, conv_wgrad_batched_launch, wgrad_reduce_all_launch with one entry.
+ * ws: splice_gen_conv_wgrad_ws_floats(...) floats of chunk partials.  p_nstride == 0: n_img = 1, one sum over the N images; p_nstride > 0:
+ * n_img = N independent images, image i summed into dw + i * p_nstride.
+ * form_out (SPLICE_GEN_WGRAD_FORM_INTS ints, may be NULL): {0 small / 1 big / 2 tile class, kernel variant, pixels per chunk, chunks,
+ * 1 = the reduction runs four elements per thread, workgroups}. */
+typedef struct splice_gen_wgrad_args {
+    const float* x;
+    const float* dy;
+    float* ws;
+    size_t ws_floats;
+    size_t x_nstride, x_cstride, dy_nstride, dy_cstride;
+    int N, Cin, Hi, Wi, Cout, Ho, Wo, ks, stride, pad, reflect;
+} splice_gen_wgrad_args;
+#define SPLICE_GEN_WGRAD_FORM_INTS 6
+size_t splice_gen_conv_wgrad_ws_floats(int N, int Cin, int Cout, int ks, int Ho, int Wo);
+int splice_gen_conv_wgrad(const splice_gen_wgrad_args* args, float* dw, int accumulate, int n_img, size_t p_nstride, int* form_out,
+                          splice_stream_t stream);
+
+/* Train-mode BatchNorm (biased variance, rstd = 1 / sqrt(var + eps)) + LeakyReLU(slope) on [N][C][HW] planes, either direction, as
+ * bn_fwd_launch / bn_bwd_launch run it.  splice_gen_bn_form reports the form of a plane as SPLICE_GEN_BN_FORM_INTS ints: {kind (0 SMALL, 1 MID,
+ * 2 TWO_STAGE, 3 TWO_STAGE_VEC), hosts_pre, fwd_takes_slabs, bwd_takes_slabs, fwd_fuses_upsample, bwd_fuses_upsample, sign_from_y}.
+ *   y / out      the BatchNorm's input and its activated output, image n at + n * y_nstride / out_nstride.  The forward WRITES y where it forms
+ *                it (slabs, upsampled channels, the channels behind a pre BatchNorm); the backward reads both.
+ *   batch        0: per-image statistics; > 0: statistics over groups of `batch` images (batch <= 8, N % batch == 0, batch < N needs p_nstride).
+ *   p_nstride    > 0: image n (group n / batch) reads gamma / beta -- and writes dgamma / dbeta -- at + n * p_nstride.
+ *   part         splice_gen_bn_part_floats(N, C) floats of scratch, needed by the two-stage kinds.  mean / rstd: [N][C], written by the forward.
+ *   up_*         channels >= up_c0 are the x2 bilinear upsampling (align_corners = False, top-left up_Ho x up_Wo window, up_Ho * up_Wo = HW) of
+ *                up_src [N][C - up_c0][up_h][up_w]; the backward sends their gradient through the adjoint into up_d_src.
+ *   slabs        forward: y = bias + slab 0 + slab 1 + ... is formed and stored first; slabs [ksplit][N][C][HW], ksplit >= 2.
+ *   da_slabs     backward: the gradient of out is (da_accumulate ? da : 0) + (slab 0 + slab 1 + ...), slabs [da_ksplit][N][C][HW].
+ *   pre_*        a BatchNorm + LeakyReLU(pre_slope) of its own in front of the first pre_C channels: its input pre_y [N][pre_C][HW] (or formed from
+ *                pre_slabs + pre_bias and stored there), its activated output stored into y; backward into pre_dy / pre_dgamma / pre_dbeta.
+ * A pre or slabs on a form that cannot take them is refused (SPLICE_ERR_ARG, nothing written). */
+typedef struct splice_gen_bn_args {
+    float* y;
+    float* out;
+    size_t y_nstride, out_nstride;
+    int N, C, HW, batch;
+    const float* gamma;
+    const float* beta;
+    float eps, slope;
+    size_t p_nstride;
+    float* part;
+    size_t part_floats;
+    float* mean;
+    float* rstd;
+    const float* up_src;
+    float* up_d_src;
+    size_t up_src_ns, up_d_src_ns;
+    int up_c0, up_h, up_w, up_Ho, up_Wo;
+    const float* slabs;
+    const float* bias;
+    int ksplit;
+    const float* da;
+    float* dy;
+    size_t da_nstride, dy_nstride;
+    float* dgamma;
+    float* dbeta;
+    int accumulate;
+    const float* da_slabs;
+    int da_ksplit, da_accumulate;
+    float* pre_y;
+    size_t pre_y_ns;
+    const float* pre_slabs;
+    const float* pre_bias;
+    int pre_ksplit, pre_C;
+    const float* pre_gamma;
+    const float* pre_beta;
+    float* pre_mean;
+    float* pre_rstd;
+    float pre_slope;
+    float* pre_dy;
+    float* pre_dgamma;
+    float* pre_dbeta;
+} splice_gen_bn_args;
+#define SPLICE_GEN_BN_FORM_INTS 7
+int splice_gen_bn_form(int HW, int N, size_t p_nstride, int batch, int* out);
+size_t splice_gen_bn_part_floats(int N, int C);
+int splice_gen_bn_fwd(const splice_gen_bn_args* args, splice_stream_t stream);
+int splice_gen_bn_bwd(const splice_gen_bn_args* args, splice_stream_t stream);
+
+/* The three launchers of gen_pointwise.hip.  Upsampling: in [N][C][h][w] -> the top-left Ho x Wo window of its x2 bilinear upsampling
+ * (Ho <= 2h, Wo <= 2w), and the adjoint dout [N][C][Ho][Wo] -> din [N][C][h][w]; image strides in floats.  Sigmoid backward of the compact
+ * [N][C][HW] head: dpre = dout * s * (1 - s), and per-segment sums of dpre into part ([image or group][segment][channel],
+ * splice_gen_sigmoid_bias_part_floats(N, C) floats); *chunks_out = the partials per channel.  p_nstride > 0: one set of partials per group of
+ * `group` images (N % group == 0), else one over all N. */
+int splice_gen_upsample2x_fwd(const float* in, size_t in_nstride, float* out, size_t out_nstride, int N, int C, int h, int w, int Ho, int Wo,
+                              splice_stream_t stream);
+int splice_gen_upsample2x_bwd(const float* dout, size_t dout_nstride, float* din, size_t din_nstride, int N, int C, int h, int w, int Ho, int Wo,
+                              splice_stream_t stream);
+size_t splice_gen_sigmoid_bias_part_floats(int N, int C);
+int splice_gen_sigmoid_bwd_bias(const float* dout, const float* sout, float* dpre, int N, int C, int HW, float* part, size_t part_floats,
+                                size_t p_nstride, int group, int* chunks_out, splice_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -60,6 +60,38 @@ class BestState(C.Structure):   # splice_best_state
     _fields_ = [("best_step", C.c_int), ("best_window", C.c_int)]
 
 
+class GenConvArgs(C.Structure):   # splice_gen_conv_args (test hooks)
+    _fields_ = [("in", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("out", C.c_void_p)] + \
+               [(n, C.c_size_t) for n in ("in_nstride", "in_cstride", "out_nstride", "out_cstride", "w_jstride", "w_cstride", "p_nstride")] + \
+               [(n, C.c_int) for n in ("N", "Cin", "Hi", "Wi", "Cout", "Ho", "Wo", "ks", "stride", "pad", "reflect", "act", "transposed", "accumulate")] + \
+               [("ws", C.c_void_p), ("ws_floats", C.c_size_t), ("p_group", C.c_int), ("defer_reduce", C.c_int)]
+
+
+class GenWgradArgs(C.Structure):   # splice_gen_wgrad_args (test hooks)
+    _fields_ = [("x", C.c_void_p), ("dy", C.c_void_p), ("ws", C.c_void_p), ("ws_floats", C.c_size_t)] + \
+               [(n, C.c_size_t) for n in ("x_nstride", "x_cstride", "dy_nstride", "dy_cstride")] + \
+               [(n, C.c_int) for n in ("N", "Cin", "Hi", "Wi", "Cout", "Ho", "Wo", "ks", "stride", "pad", "reflect")]
+
+
+class GenBnArgs(C.Structure):   # splice_gen_bn_args (test hooks)
+    _fields_ = [("y", C.c_void_p), ("out", C.c_void_p), ("y_nstride", C.c_size_t), ("out_nstride", C.c_size_t),
+                ("N", C.c_int), ("C", C.c_int), ("HW", C.c_int), ("batch", C.c_int),
+                ("gamma", C.c_void_p), ("beta", C.c_void_p), ("eps", C.c_float), ("slope", C.c_float), ("p_nstride", C.c_size_t),
+                ("part", C.c_void_p), ("part_floats", C.c_size_t), ("mean", C.c_void_p), ("rstd", C.c_void_p),
+                ("up_src", C.c_void_p), ("up_d_src", C.c_void_p), ("up_src_ns", C.c_size_t), ("up_d_src_ns", C.c_size_t),
+                ("up_c0", C.c_int), ("up_h", C.c_int), ("up_w", C.c_int), ("up_Ho", C.c_int), ("up_Wo", C.c_int),
+                ("slabs", C.c_void_p), ("bias", C.c_void_p), ("ksplit", C.c_int),
+                ("da", C.c_void_p), ("dy", C.c_void_p), ("da_nstride", C.c_size_t), ("dy_nstride", C.c_size_t),
+                ("dgamma", C.c_void_p), ("dbeta", C.c_void_p), ("accumulate", C.c_int),
+                ("da_slabs", C.c_void_p), ("da_ksplit", C.c_int), ("da_accumulate", C.c_int),
+                ("pre_y", C.c_void_p), ("pre_y_ns", C.c_size_t), ("pre_slabs", C.c_void_p), ("pre_bias", C.c_void_p),
+                ("pre_ksplit", C.c_int), ("pre_C", C.c_int), ("pre_gamma", C.c_void_p), ("pre_beta", C.c_void_p),
+                ("pre_mean", C.c_void_p), ("pre_rstd", C.c_void_p), ("pre_slope", C.c_float),
+                ("pre_dy", C.c_void_p), ("pre_dgamma", C.c_void_p), ("pre_dbeta", C.c_void_p)]
+
+
+GEN_CONV_FORM_INTS, GEN_WGRAD_FORM_INTS, GEN_BN_FORM_INTS = 5, 6, 7   # SPLICE_GEN_*_FORM_INTS
+
 STOP_HISTORY = 64   # SPLICE_STOP_HISTORY
 
 EPI_BIAS, EPI_RESID, EPI_OUT_F32, EPI_OUT_BF, EPI_OUT_T = 1, 2, 4, 8, 16
@@ -101,6 +133,20 @@ _SIGNATURES = {
     "splice_ln_rows_fwd": ([_vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _i, _i, _f, _vp, _i, _sz, _vp, _vp, _sz, _vp], _i),
     "splice_ln_rows_bwd": ([_vp, _sz, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _i, _i, _i, _sz, _vp], _i),
     "splice_rows_finish": ([_i, _vp, _i, _sz, _i, _i, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _sz, _i, _vp], _i),
+    # test hooks: generator launchers on caller-owned buffers
+    "splice_gen_conv": ([C.POINTER(GenConvArgs), C.POINTER(_i), _vp], _i),
+    "splice_gen_conv_pair": ([C.POINTER(GenConvArgs), C.POINTER(GenConvArgs), C.POINTER(_i), _vp], _i),
+    "splice_gen_conv_reflect_dgrad": ([C.POINTER(GenConvArgs), _vp, _sz, _vp], _i),
+    "splice_gen_conv_wgrad_ws_floats": ([_i, _i, _i, _i, _i, _i], _sz),
+    "splice_gen_conv_wgrad": ([C.POINTER(GenWgradArgs), _vp, _i, _i, _sz, C.POINTER(_i), _vp], _i),
+    "splice_gen_bn_form": ([_i, _i, _sz, _i, C.POINTER(_i)], _i),
+    "splice_gen_bn_part_floats": ([_i, _i], _sz),
+    "splice_gen_bn_fwd": ([C.POINTER(GenBnArgs), _vp], _i),
+    "splice_gen_bn_bwd": ([C.POINTER(GenBnArgs), _vp], _i),
+    "splice_gen_upsample2x_fwd": ([_vp, _sz, _vp, _sz, _i, _i, _i, _i, _i, _i, _vp], _i),
+    "splice_gen_upsample2x_bwd": ([_vp, _sz, _vp, _sz, _i, _i, _i, _i, _i, _i, _vp], _i),
+    "splice_gen_sigmoid_bias_part_floats": ([_i, _i], _sz),
+    "splice_gen_sigmoid_bwd_bias": ([_vp, _vp, _vp, _i, _i, _i, _vp, _sz, _sz, _i, C.POINTER(_i), _vp], _i),
     "splice_patchify": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
     "splice_unpatchify": ([_vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
     "splice_cast_f32_bf16": ([_vp, _vp, _sz, _vp], _i),

@@ -2,6 +2,7 @@
 #include <stdarg.h>
 #include <stdio.h>
 
+#include "gen_kernels.h"
 #include "kernels.h"
 
 static thread_local char g_err[512] = "";
@@ -205,6 +206,208 @@ int splice_rows_finish(int mode, const float* slabs, int n_slabs, size_t slab_st
     if (mode < 0 || mode > 2 || !slabs || n_slabs < 1 || rows < 1 || N < 1 || (long long)rows * N > 0x7fffffffLL) return finish(SPLICE_ERR_ARG, who);
     if ((mode == 0 && (!out_f32 || !resid)) || (mode != 0 && !out_bf) || (mode == 2 && !aux)) return finish(SPLICE_ERR_ARG, who);
     return finish(rows_finish_launch(mode, slabs, n_slabs, slab_stride, rows, N, bias, resid, rs, out_f32, os, out_bf, pre_bf, aux, ps, pre_lo, ST(stream)), who);
+}
+
+/* test hooks: generator launchers on caller-owned buffers.  They only validate and forward: no launcher, policy or kernel is theirs. */
+static bool gen_conv_args_ok(const splice_gen_conv_args* g, bool reflect_dgrad) {
+    if (!g || !g->in || !g->w || !g->out) return false;
+    if (g->N < 1 || g->Cin < 1 || g->Hi < 1 || g->Wi < 1 || g->Cout < 1 || g->Ho < 1 || g->Wo < 1 || g->pad < 0) return false;
+    if (g->ks != 1 && g->ks != 3 && g->ks != 5 && g->ks != 7) return false;
+    if (g->stride != 1 && g->stride != 2) return false;
+    if ((g->act != 0 && g->act != 1) || (g->reflect && g->transposed && !reflect_dgrad)) return false;
+    const long long HWi = (long long)g->Hi * g->Wi, HWo = (long long)g->Ho * g->Wo;
+    if (HWi > 0x1fffffffLL || HWo > 0x1fffffffLL) return false;
+    if (g->in_cstride < (size_t)HWi || g->out_cstride < (size_t)HWo) return false;
+    if (g->N > 1 && (g->in_nstride < (size_t)g->Cin * g->in_cstride || g->out_nstride < (size_t)g->Cout * g->out_cstride)) return false;
+    // the 32-bit offsets of the gathers (bytes, bit 31 reserved as the out-of-range mark): reduction channels x channel stride, the weight block
+    if ((size_t)g->Cin * g->in_cstride > 0x1fffffffULL) return false;
+    if ((size_t)g->Cout * g->w_jstride + (size_t)g->Cin * g->w_cstride + (size_t)g->ks * g->ks > 0x1fffffffULL) return false;
+    if ((size_t)g->Cout * g->out_cstride > 0x7fffffffULL) return false;
+    if (g->w_jstride < 1 || g->w_cstride < 1) return false;
+    if (g->p_group < 0 || (g->p_group > 1 && (!g->p_nstride || g->N % g->p_group))) return false;
+    if (g->reflect && !reflect_dgrad && (g->pad >= g->Hi || g->pad >= g->Wi)) return false;   // a mirror needs pad < size
+    if (reflect_dgrad && (g->pad >= g->Ho || g->pad >= g->Wo || g->act)) return false;
+    if (g->ws && g->ws_floats < 1) return false;
+    if (g->defer_reduce && !g->ws) return false;
+    return true;
+}
+static ConvArgs gen_conv_fill(const splice_gen_conv_args* g) {
+    ConvArgs a = {};
+    a.in = g->in; a.w = g->w; a.bias = g->bias; a.out = g->out;
+    a.in_nstride = g->in_nstride; a.in_cstride = g->in_cstride; a.out_nstride = g->out_nstride; a.out_cstride = g->out_cstride;
+    a.w_jstride = g->w_jstride; a.w_cstride = g->w_cstride; a.p_nstride = g->p_nstride;
+    a.N = g->N; a.Cin = g->Cin; a.Hi = g->Hi; a.Wi = g->Wi; a.Cout = g->Cout; a.Ho = g->Ho; a.Wo = g->Wo;
+    a.ks = g->ks; a.stride = g->stride; a.pad = g->pad;
+    a.reflect = g->reflect; a.act = g->act; a.transposed = g->transposed; a.accumulate = g->accumulate;
+    a.ws = g->ws; a.ws_floats = g->ws_floats; a.p_group = g->p_group; a.defer_reduce = g->defer_reduce;
+    return a;
+}
+int splice_gen_conv(const splice_gen_conv_args* args, int* form_out, splice_stream_t stream) {
+    const char* who = "splice_gen_conv";
+    if (!gen_conv_args_ok(args, false)) return finish(SPLICE_ERR_ARG, who);
+    const ConvArgs a = gen_conv_fill(args);
+    if (form_out) conv_form_report(a, form_out);
+    return finish(conv_launch(a, ST(stream)), who);
+}
+int splice_gen_conv_pair(const splice_gen_conv_args* a_args, const splice_gen_conv_args* b_args, int* forms_out, splice_stream_t stream) {
+    const char* who = "splice_gen_conv_pair";
+    if (!gen_conv_args_ok(a_args, false) || !gen_conv_args_ok(b_args, false)) return finish(SPLICE_ERR_ARG, who);
+    const ConvArgs a = gen_conv_fill(a_args), b = gen_conv_fill(b_args);
+    if (forms_out) { conv_form_report(a, forms_out); conv_form_report(b, forms_out + SPLICE_GEN_CONV_FORM_INTS); }
+    return finish(conv_pair_launch(a, b, ST(stream)), who);
+}
+int splice_gen_conv_reflect_dgrad(const splice_gen_conv_args* args, float* pad_scratch, size_t scratch_floats, splice_stream_t stream) {
+    const char* who = "splice_gen_conv_reflect_dgrad";
+    if (!gen_conv_args_ok(args, true) || !pad_scratch) return finish(SPLICE_ERR_ARG, who);
+    const size_t Hp = (size_t)args->Ho + 2 * args->pad, Wp = (size_t)args->Wo + 2 * args->pad;
+    if (scratch_floats < (size_t)args->N * args->Cout * Hp * Wp || (size_t)args->Cout * Hp * Wp > 0x7fffffffULL) return finish(SPLICE_ERR_ARG, who);
+    return finish(conv_reflect_dgrad_launch(gen_conv_fill(args), pad_scratch, ST(stream)), who);
+}
+
+static bool gen_wgrad_args_ok(const splice_gen_wgrad_args* g) {
+    if (!g || !g->x || !g->dy) return false;
+    if (g->N < 1 || g->Cin < 1 || g->Hi < 1 || g->Wi < 1 || g->Cout < 1 || g->Ho < 1 || g->Wo < 1 || g->pad < 0 || g->pad > 255) return false;
+    if (g->ks != 1 && g->ks != 3 && g->ks != 5 && g->ks != 7) return false;
+    if ((g->stride != 1 && g->stride != 2) || g->Cout > 128) return false;
+    if (g->Hi > 65535 || g->Wi > 65535 || g->Ho > 65535 || g->Wo > 65535 || g->Cin > 65535) return false;
+    const long long HWi = (long long)g->Hi * g->Wi, HWo = (long long)g->Ho * g->Wo;
+    if (HWo > (1LL << 22)) return false;   // pix_per_chunk is a 16-bit field of the descriptor (128 chunks per image): planes far below 128 x 65535 pixels
+    if (g->x_cstride < (size_t)HWi || g->dy_cstride < (size_t)HWo) return false;
+    if (g->N > 1 && (g->x_nstride < (size_t)g->Cin * g->x_cstride || g->dy_nstride < (size_t)g->Cout * g->dy_cstride)) return false;
+    if ((size_t)g->Cin * g->x_cstride > 0x1fffffffULL || (size_t)g->Cout * g->dy_cstride > 0x1fffffffULL) return false;   // 32-bit byte offsets
+    if (g->x_nstride > 0xffffffffULL || g->dy_nstride > 0xffffffffULL) return false;
+    if (g->reflect && (g->pad >= g->Hi || g->pad >= g->Wi)) return false;
+    return true;
+}
+size_t splice_gen_conv_wgrad_ws_floats(int N, int Cin, int Cout, int ks, int Ho, int Wo) {
+    if (N < 1 || Cin < 1 || Cout < 1 || ks < 1 || Ho < 1 || Wo < 1) return 0;
+    int ppc = 0, cpi = 0;
+    return (size_t)wgrad_chunks(N, Ho, Wo, &ppc, &cpi) * Cout * Cin * ks * ks;
+}
+int splice_gen_conv_wgrad(const splice_gen_wgrad_args* args, float* dw, int accumulate, int n_img, size_t p_nstride, int* form_out, splice_stream_t stream) {
+    const char* who = "splice_gen_conv_wgrad";
+    if (!gen_wgrad_args_ok(args) || !dw || !args->ws) return finish(SPLICE_ERR_ARG, who);
+    const size_t n = (size_t)args->Cout * args->Cin * args->ks * args->ks;
+    if (n > 0x7fffffffULL || args->ws_floats < splice_gen_conv_wgrad_ws_floats(args->N, args->Cin, args->Cout, args->ks, args->Ho, args->Wo))
+        return finish(SPLICE_ERR_ARG, who);
+    // independent images (p_nstride > 0): image i's chunks are summed into dw + i * p_nstride; else one sum over every image
+    if (p_nstride ? (n_img != args->N || p_nstride < n) : n_img != 1) return finish(SPLICE_ERR_ARG, who);
+    WgradArgs a = {};
+    a.x = args->x; a.dy = args->dy; a.ws = args->ws;
+    a.x_nstride = args->x_nstride; a.x_cstride = args->x_cstride; a.dy_nstride = args->dy_nstride; a.dy_cstride = args->dy_cstride;
+    a.N = args->N; a.Cin = args->Cin; a.Hi = args->Hi; a.Wi = args->Wi; a.Cout = args->Cout; a.Ho = args->Ho; a.Wo = args->Wo;
+    a.ks = args->ks; a.stride = args->stride; a.pad = args->pad; a.reflect = args->reflect;
+    WgradBatchPair pair = {};
+    int chunks = 0;
+    int rc = conv_wgrad_add(&pair, a, &chunks);
+    if (rc != SPLICE_OK) return finish(rc, who);
+    WgradReduceAll r = {};
+    r.count = 1; r.n[0] = (int)n; r.chunks[0] = chunks; r.ws_off[0] = 0; r.dw_off[0] = 0;
+    if (form_out) {   // class and variant as the queue holds them; the reduce's 16-byte form by the launcher's own rule (SPLICE_WGRAD_REDUCE_VEC unset)
+        const WgradBatch& b = pair.tile.count ? pair.tile : pair.big.count ? pair.big : pair.small;
+        form_out[0] = pair.tile.count ? 2 : pair.big.count ? 1 : 0;
+        form_out[1] = b.d[0].variant;
+        form_out[2] = b.d[0].pix_per_chunk;
+        form_out[3] = chunks;
+        form_out[4] = !((reinterpret_cast<size_t>(args->ws) | reinterpret_cast<size_t>(dw)) & 15) && p_nstride % 4 == 0 && n % 4 == 0;
+        form_out[5] = b.total_wgs;
+    }
+    rc = conv_wgrad_batched_launch(pair, ST(stream));
+    if (rc != SPLICE_OK) return finish(rc, who);
+    return finish(wgrad_reduce_all_launch(r, args->ws, dw, accumulate, ST(stream), n_img, p_nstride), who);
+}
+
+int splice_gen_bn_form(int HW, int N, size_t p_nstride, int batch, int* out) {
+    if (HW < 1 || N < 1 || batch < 0 || !out) return finish(SPLICE_ERR_ARG, "splice_gen_bn_form");
+    const BnForm f = bn_form(HW, N, p_nstride, batch);
+    out[0] = (int)f.kind; out[1] = f.hosts_pre; out[2] = f.fwd_takes_slabs; out[3] = f.bwd_takes_slabs;
+    out[4] = f.fwd_fuses_upsample; out[5] = f.bwd_fuses_upsample; out[6] = f.sign_from_y;
+    return SPLICE_OK;
+}
+size_t splice_gen_bn_part_floats(int N, int C) { return N < 1 || C < 1 ? 0 : (size_t)bn_part_floats(N, C); }
+// what both directions need; fills the launcher's structs (up / pre / slabs point into the caller's frame)
+static bool gen_bn_fill(const splice_gen_bn_args* g, bool bwd, BnArgs* a, BnUpsample* up, BnPre* pre, BnSlabs* sl) {
+    if (!g || !g->y || !g->out || !g->gamma || !g->mean || !g->rstd) return false;
+    if (g->N < 1 || g->C < 1 || g->HW < 1 || g->N > 65535 || g->C > 65535 || g->batch < 0 || g->batch > 8) return false;
+    if (g->batch && (g->N % g->batch || (g->N != g->batch && !g->p_nstride))) return false;
+    if (g->N > 1 && (g->y_nstride < (size_t)g->C * g->HW || g->out_nstride < (size_t)g->C * g->HW)) return false;
+    const BnForm f = bn_form(g->HW, g->N, g->p_nstride, g->batch);
+    const bool two_stage = f.kind == BnForm::TWO_STAGE || f.kind == BnForm::TWO_STAGE_VEC;
+    if (two_stage && (!g->part || g->part_floats < (size_t)bn_part_floats(g->N, g->C))) return false;
+    if (!bwd && !g->beta) return false;
+    if (bwd && ((f.sign_from_y && !g->beta) || !g->da || !g->dy || !g->dgamma || !g->dbeta)) return false;
+    if (bwd && g->N > 1 && (g->da_nstride < (size_t)g->C * g->HW || g->dy_nstride < (size_t)g->C * g->HW)) return false;
+    a->y = g->y; a->y_nstride = g->y_nstride; a->out = g->out; a->out_nstride = g->out_nstride;
+    a->N = g->N; a->C = g->C; a->HW = g->HW; a->gamma = g->gamma; a->beta = g->beta; a->eps = g->eps; a->slope = g->slope;
+    a->p_nstride = g->p_nstride; a->batch = g->batch; a->part = g->part; a->mean = g->mean; a->rstd = g->rstd;
+    if (g->up_src || g->up_d_src) {
+        if (bwd ? !g->up_d_src : !g->up_src) return false;
+        if (g->up_c0 < 0 || g->up_c0 >= g->C || g->up_h < 1 || g->up_w < 1 || g->up_Ho < 1 || g->up_Wo < 1) return false;
+        if (g->up_Ho > 2 * g->up_h || g->up_Wo > 2 * g->up_w || (long long)g->up_Ho * g->up_Wo != g->HW) return false;
+        const size_t src = (size_t)(g->C - g->up_c0) * g->up_h * g->up_w;
+        if (g->N > 1 && (bwd ? g->up_d_src_ns : g->up_src_ns) < src) return false;
+        up->src = g->up_src; up->src_ns = g->up_src_ns; up->d_src = g->up_d_src; up->d_src_ns = g->up_d_src_ns;
+        up->c0 = g->up_c0; up->h = g->up_h; up->w = g->up_w; up->Ho = g->up_Ho; up->Wo = g->up_Wo;
+        a->up = up;
+    }
+    if (g->pre_y) {
+        if (!g->pre_gamma || !g->pre_beta || !g->pre_mean || !g->pre_rstd || g->pre_C < 1 || g->pre_C > (a->up ? g->up_c0 : g->C)) return false;
+        if (g->N > 1 && g->pre_y_ns < (size_t)g->pre_C * g->HW) return false;
+        if (g->pre_slabs && (bwd || !f.fwd_takes_slabs || g->pre_ksplit < 1 || g->pre_ksplit > 16)) return false;   // only the small-plane kernel forms the skip plane from slabs
+        if (bwd && (!g->pre_dy || !g->pre_dgamma || !g->pre_dbeta)) return false;
+        pre->y = g->pre_y; pre->y_ns = g->pre_y_ns; pre->slabs = g->pre_slabs; pre->ksplit = g->pre_ksplit; pre->bias = g->pre_bias;
+        pre->gamma = g->pre_gamma; pre->beta = g->pre_beta; pre->mean = g->pre_mean; pre->rstd = g->pre_rstd; pre->slope = g->pre_slope; pre->C = g->pre_C;
+        pre->dy = g->pre_dy; pre->dgamma = g->pre_dgamma; pre->dbeta = g->pre_dbeta;
+        a->pre = pre;
+    }
+    if (!bwd && g->slabs) {
+        if (g->ksplit < 2 || g->ksplit > 16) return false;
+        a->slabs = g->slabs; a->ksplit = g->ksplit; a->bias = g->bias;
+    }
+    if (bwd) {
+        a->da = g->da; a->da_nstride = g->da_nstride; a->dy = g->dy; a->dy_nstride = g->dy_nstride;
+        a->dgamma = g->dgamma; a->dbeta = g->dbeta; a->accumulate = g->accumulate;
+        if (g->da_slabs) {
+            if (g->da_ksplit < 1 || g->da_ksplit > 16) return false;
+            sl->slabs = g->da_slabs; sl->ksplit = g->da_ksplit; sl->accumulate = g->da_accumulate;
+            a->da_slabs = sl;
+        }
+    }
+    return true;
+}
+int splice_gen_bn_fwd(const splice_gen_bn_args* args, splice_stream_t stream) {
+    BnArgs a; BnUpsample up; BnPre pre; BnSlabs sl;
+    if (!gen_bn_fill(args, false, &a, &up, &pre, &sl)) return finish(SPLICE_ERR_ARG, "splice_gen_bn_fwd");
+    return finish(bn_fwd_launch(a, ST(stream)), "splice_gen_bn_fwd");
+}
+int splice_gen_bn_bwd(const splice_gen_bn_args* args, splice_stream_t stream) {
+    BnArgs a; BnUpsample up; BnPre pre; BnSlabs sl;
+    if (!gen_bn_fill(args, true, &a, &up, &pre, &sl)) return finish(SPLICE_ERR_ARG, "splice_gen_bn_bwd");
+    return finish(bn_bwd_launch(a, ST(stream)), "splice_gen_bn_bwd");
+}
+
+static bool gen_up_args_ok(const void* a, const void* b, size_t in_ns, size_t out_ns, int N, int C, int h, int w, int Ho, int Wo) {
+    if (!a || !b || N < 1 || C < 1 || h < 1 || w < 1 || Ho < 1 || Wo < 1 || N > 65535 || C > 65535) return false;
+    if (Ho > 2 * h || Wo > 2 * w || (long long)h * w > 0x7fffffffLL / 4 || (long long)Ho * Wo > 0x7fffffffLL) return false;
+    return N == 1 || (in_ns >= (size_t)C * h * w && out_ns >= (size_t)C * Ho * Wo);
+}
+int splice_gen_upsample2x_fwd(const float* in, size_t in_nstride, float* out, size_t out_nstride, int N, int C, int h, int w, int Ho, int Wo,
+                              splice_stream_t stream) {
+    if (!gen_up_args_ok(in, out, in_nstride, out_nstride, N, C, h, w, Ho, Wo)) return finish(SPLICE_ERR_ARG, "splice_gen_upsample2x_fwd");
+    return finish(upsample2x_fwd_launch(in, in_nstride, out, out_nstride, N, C, h, w, Ho, Wo, ST(stream)), "splice_gen_upsample2x_fwd");
+}
+int splice_gen_upsample2x_bwd(const float* dout, size_t dout_nstride, float* din, size_t din_nstride, int N, int C, int h, int w, int Ho, int Wo,
+                              splice_stream_t stream) {
+    if (!gen_up_args_ok(din, dout, din_nstride, dout_nstride, N, C, h, w, Ho, Wo)) return finish(SPLICE_ERR_ARG, "splice_gen_upsample2x_bwd");
+    return finish(upsample2x_bwd_launch(dout, dout_nstride, din, din_nstride, N, C, h, w, Ho, Wo, ST(stream)), "splice_gen_upsample2x_bwd");
+}
+size_t splice_gen_sigmoid_bias_part_floats(int N, int C) { return N < 1 || C < 1 ? 0 : (size_t)sigmoid_bias_part_floats(N, C); }
+int splice_gen_sigmoid_bwd_bias(const float* dout, const float* sout, float* dpre, int N, int C, int HW, float* part, size_t part_floats, size_t p_nstride,
+                                int group, int* chunks_out, splice_stream_t stream) {
+    const char* who = "splice_gen_sigmoid_bwd_bias";
+    if (!dout || !sout || !dpre || !part || N < 1 || C < 1 || HW < 1 || N > 65535 || C > 65535 || group < 1) return finish(SPLICE_ERR_ARG, who);
+    if (part_floats < splice_gen_sigmoid_bias_part_floats(N, C) || (group > 1 && !p_nstride) || N % group) return finish(SPLICE_ERR_ARG, who);
+    return finish(sigmoid_bwd_bias_launch(dout, sout, dpre, N, C, HW, part, ST(stream), p_nstride, chunks_out, group), who);
 }
 
 int splice_patchify(const float* img, splice_bf16* patches, int B, int H, int W, int p, int Tld, int normalize,

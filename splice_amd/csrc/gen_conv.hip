@@ -664,6 +664,19 @@ int conv_launch(const ConvArgs& a, hipStream_t s, int* ksplit_out) {
     return SPLICE_OK;
 }
 
+// The path conv_launch takes for `a`, as five ints {tile kernel, CK, fn_run, ng, ksplit}: read off conv_tile_ok / conv_ck / conv_policy, the
+// functions the dispatch itself asks (the op-level test hooks report it; nothing else calls this)
+void conv_form_report(const ConvArgs& a, int* form) {
+    const bool tile = a.ks == 3 && conv_tile_ok(a);
+    const int CK = a.ks >= 5 ? 4 : conv_ck(a);
+    const ConvPolicy pol = conv_policy(a, a.ks, CK);
+    form[0] = tile ? 1 : 0;
+    form[1] = CK;
+    form[2] = tile ? (a.Cout <= 16 ? 1 : 2) : pol.fn_run;
+    form[3] = tile ? 1 : pol.ng;
+    form[4] = tile ? 1 : pol.ksplit;
+}
+
 // Data gradient of a reflection-padded convolution: y = conv(pad_reflect(x)), so dL/dx = fold(dL/dx_pad) where dL/dx_pad is the
 // plain transposed convolution on the PADDED domain (Hi + 2p) x (Wi + 2p) -- conv_launch in data-gradient form with pad 0 --
 // and fold adds every padded position into the interior pixel it mirrors (separable: up to 3 source rows x 3 source

@@ -23,6 +23,7 @@ struct ConvArgs {
     int defer_reduce; // split-K: leave the raw slabs in ws (ksplit_out tells how many); the consumer adds bias + slabs in slice order
 };
 int conv_launch(const ConvArgs& a, hipStream_t s, int* ksplit_out = nullptr);
+void conv_form_report(const ConvArgs& a, int* form);   // {tile kernel, CK, fn_run, ng, ksplit} of the path conv_launch takes (test hooks)
 // two independent convolutions (a: 1x1, stride 1) in ONE launch where an instantiation exists, else two launches; same results
 // as two conv_launch calls up to the summation order of `a` (it adopts b's wave groups)
 int conv_pair_launch(ConvArgs a, ConvArgs b, hipStream_t s, int* ksplit_a = nullptr, int* ksplit_b = nullptr);

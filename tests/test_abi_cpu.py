@@ -57,7 +57,8 @@ def test_struct_layouts_match_header(tmp_path):
     offset for every field, and no field of the header missing from the binding (or vice versa)."""
     src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "splice_hip.h")).read(), flags=re.S)
     src = re.sub(r"\[[A-Za-z_0-9]+\]", "", src)   # array extents (int down[SPLICE_GEN_MAX_SCALES]) do not matter for the field list
-    for cname, mirror in (("splice_gemm_epilogue", _lib.GemmEpilogue), ("splice_step_config", _lib.StepConfig), ("splice_gen_arch", _lib.GenArch)):
+    for cname, mirror in (("splice_gemm_epilogue", _lib.GemmEpilogue), ("splice_step_config", _lib.StepConfig), ("splice_gen_arch", _lib.GenArch),
+                          ("splice_gen_conv_args", _lib.GenConvArgs), ("splice_gen_wgrad_args", _lib.GenWgradArgs), ("splice_gen_bn_args", _lib.GenBnArgs)):
         body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (cname, cname), src, flags=re.S).group(1)
         header_fields = []
         for decl in body.split(";"):
