@@ -82,60 +82,47 @@ def work_items(sizes, pairs_per_gpu=1):
     return sorted(items, key=lambda it: (-cost(it), it[0]))
 
 
-def _stop_fields(eng, slot=None):
-    """``steps_run`` (steps that updated the slot) and ``stopped_at`` (the step index the plateau stop rule stopped it at, or None)."""
+def _slot_fields(eng, slot=None):
+    """What ``result.json`` says about the optional rules of one slot (None: the one pair of the engine).  The stop rule: ``steps_run``
+    (steps that updated the slot) and ``stopped_at`` (the step index it stopped at, or None).  The weight average: ``ema_decay`` (0: none
+    was kept, there is no ``output_ema.png``).  Gradient clipping and the best window: ``train.clip_fields`` / ``train.best_fields``."""
+    from .train import best_fields, clip_fields
     at = eng.stopped_at if slot is None else eng.stopped_at[slot]
-    return {"steps_run": eng.step_idx + 1 if at is None else at + 1, "stopped_at": at}
+    return {"steps_run": eng.step_idx + 1 if at is None else at + 1, "stopped_at": at, "ema_decay": eng.ema_rule[0],
+            **clip_fields(eng, slot), **best_fields(eng, slot)}
 
 
-def _ema_fields(eng):
-    """``ema_decay`` of the run's weight average (0: none was kept, there is no ``output_ema.png``)."""
-    return {"ema_decay": eng.ema_rule[0]}
-
-
-def _clip_fields(eng, slot=None):
-    from .train import clip_fields
-    return clip_fields(eng, slot)
-
-
-def _best_fields(eng, slot=None):
-    from .train import best_fields
-    return best_fields(eng, slot)
+def _timed(train, *args, **kw):
+    """``(engine, seconds)`` of a finished run."""
+    import torch
+    t0 = time.perf_counter()
+    eng = train(*args, **kw, progress=False)
+    torch.cuda.synchronize()
+    return eng, round(time.perf_counter() - t0, 3)
 
 
 def train_runner(pair_dir, overrides):
     """Default runner: the drop-in ``train_model`` on the pair's directory."""
     from .train import train_model
-    t0 = time.perf_counter()
-    eng = train_model(pair_dir, cfg_overrides=overrides, progress=False)
-    import torch
-    torch.cuda.synchronize()
-    return {"steps": eng.step_idx + 1, "loss": eng.losses()["loss"], "seconds": round(time.perf_counter() - t0, 3), **_stop_fields(eng), **_ema_fields(eng),
-            **_clip_fields(eng), **_best_fields(eng)}
+    eng, dt = _timed(train_model, pair_dir, cfg_overrides=overrides)
+    return {"steps": eng.step_idx + 1, "loss": eng.losses()["loss"], "seconds": dt, **_slot_fields(eng)}
 
 
 def train_group_runner(pair_dirs, overrides):
     """Several pairs of one worker in the SAME launches (``train_pairs``): used when ``run_batch(pairs_per_gpu > 1)``."""
     from .train import train_pairs
-    t0 = time.perf_counter()
-    eng = train_pairs(pair_dirs, cfg_overrides=overrides, progress=False)
-    import torch
-    torch.cuda.synchronize()
-    dt = round(time.perf_counter() - t0, 3)
-    return [{"steps": eng.step_idx + 1, "loss": d["loss"], "seconds": dt, "pairs_in_step": len(pair_dirs), **_stop_fields(eng, p), **_ema_fields(eng),
-             **_clip_fields(eng, p), **_best_fields(eng, p)} for p, d in enumerate(eng.losses())]
+    eng, dt = _timed(train_pairs, pair_dirs, cfg_overrides=overrides)
+    return [{"steps": eng.step_idx + 1, "loss": d["loss"], "seconds": dt, "pairs_in_step": len(pair_dirs), **_slot_fields(eng, p)} for p, d in enumerate(eng.losses())]
 
 
 def train_sweep_runner(pair_dir, overrides, variants):
     """Sweep runner: all ``variants`` of one pair in one engine (``train_sweep``)."""
     from .train import train_sweep
-    t0 = time.perf_counter()
-    eng = train_sweep(pair_dir, variants, cfg_overrides=overrides, progress=False)
-    import torch
-    torch.cuda.synchronize()
-    losses = eng.losses()
-    return {"steps": eng.step_idx + 1, "seconds": round(time.perf_counter() - t0, 3), **_ema_fields(eng),
-            "variants": [{"index": k, "overrides": v, "loss": d["loss"], "losses": d, **_stop_fields(eng, k), **_clip_fields(eng, k), **_best_fields(eng, k)} for k, (v, d) in enumerate(zip(variants, losses))]}
+    eng, dt = _timed(train_sweep, pair_dir, variants, cfg_overrides=overrides)
+    slots = [_slot_fields(eng, k) for k in range(len(variants))]
+    ema = [s.pop("ema_decay") for s in slots][0]   # (shared by the variants: said once)
+    return {"steps": eng.step_idx + 1, "seconds": dt, "ema_decay": ema,
+            "variants": [{"index": k, "overrides": v, "loss": d["loss"], "losses": d, **slots[k]} for k, (v, d) in enumerate(zip(variants, eng.losses()))]}
 
 
 def sweep_variants(specs):

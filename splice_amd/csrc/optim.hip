@@ -413,16 +413,29 @@ int splice_optim_step(int kind, float* params, float* grads, float* m, float* v,
                       int zero_grad, splice_stream_t stream) {
     return splice_optim_step_ex(kind, params, grads, nullptr, m, v, n, lr, nullptr, hp0, hp1, eps, step, zero_grad, stream);
 }
-// The whole range n_pairs * stride is updated, the padding floats between two arenas included (they hold zero gradients, so they stay
-// as they are).
+// The OptimArgs of the pairs forms.  slot: floats between two pairs' arenas and the stride of every per-pair table; the whole range
+// n_pairs * slot is updated, the padding floats between two arenas included (they hold zero gradients, so they stay as they are).
+// slot 0: a single arena of n floats, slot 0 of every table.  step_dev / stop / ema / clip / best: optional.
+static OptimArgs pairs_args(int kind, float* params, float* grads, const float* g2, float* m, float* v, int n_pairs, size_t slot, long long n,
+                            const float* lr_dev, float hp0, float hp1, float eps, int step, const int* step_dev, const splice_stop_state* stop,
+                            int zero_grad, float* ema, float ema_decay, int ema_start, const splice_clip_state* clip, const splice_best_state* best,
+                            float* best_params, float* best_ema) {
+    OptimArgs a = optim_args(kind, params, grads, g2, m, v, slot ? (long long)n_pairs * (long long)slot : n, 0.f, lr_dev, slot, hp0, hp1, eps, step, zero_grad);
+    a.step_dev = step_dev;
+    if (stop) { a.mask = stop; a.mask_step = step_dev; a.mask_stride = slot; }
+    if (ema) { a.ema = ema; a.ema_decay = ema_decay; a.ema_start = ema_start; }
+    if (clip) { a.clip = clip; a.clip_stride = slot; }
+    a.best = best; a.best_p = best_params; a.best_ema = best_ema;
+    return a;
+}
 int splice_optim_step_pairs(int kind, float* params, float* grads, const float* g2, float* m, float* v, int n_pairs, long long stride, long long n,
                             const float* lr_dev, float hp0, float hp1, float eps, int step, int zero_grad, splice_stream_t stream) {
     if (!params || !grads || !lr_dev || n_pairs < 1 || n < 1 || stride < n || stride % 4) {
         splice_set_error("splice_optim_step_pairs: needs a device lr table, n_pairs >= 1 and 1 <= n <= stride with stride a multiple of 4");
         return SPLICE_ERR_ARG;
     }
-    return optim_launch(optim_args(kind, params, grads, g2, m, v, (long long)n_pairs * stride, 0.f, lr_dev, (size_t)stride, hp0, hp1, eps, step, zero_grad),
-                        (hipStream_t)stream);
+    return optim_launch(pairs_args(kind, params, grads, g2, m, v, n_pairs, (size_t)stride, n, lr_dev, hp0, hp1, eps, step, nullptr, nullptr, zero_grad, nullptr, 0.f, 0,
+                                   nullptr, nullptr, nullptr, nullptr), (hipStream_t)stream);
 }
 // as splice_optim_step_pairs with the weight average, the fused step's form of the launch: the step count is read from the device
 // (step_dev), and with `stop` ([n_pairs] records) a pair that is frozen at step *step_dev - 1 is skipped -- its ema with the rest of it
@@ -433,11 +446,8 @@ int splice_optim_step_pairs_ema(int kind, float* params, float* grads, const flo
         splice_set_error("splice_optim_step_pairs_ema: needs the ema arena, a device lr table and step count, n_pairs >= 1 and 1 <= n <= stride with stride a multiple of 4");
         return SPLICE_ERR_ARG;
     }
-    OptimArgs a = optim_args(kind, params, grads, g2, m, v, (long long)n_pairs * stride, 0.f, lr_dev, (size_t)stride, hp0, hp1, eps, 0, zero_grad);
-    a.step_dev = step_dev;
-    if (stop) { a.mask = stop; a.mask_step = step_dev; a.mask_stride = (size_t)stride; }
-    a.ema = ema; a.ema_decay = ema_decay; a.ema_start = ema_start;
-    return optim_launch(a, (hipStream_t)stream);
+    return optim_launch(pairs_args(kind, params, grads, g2, m, v, n_pairs, (size_t)stride, n, lr_dev, hp0, hp1, eps, 0, step_dev, stop, zero_grad, ema, ema_decay, ema_start,
+                                   nullptr, nullptr, nullptr, nullptr), (hipStream_t)stream);
 }
 // as splice_optim_step_ema (ema optional) with the one clip record of this gradient: the host-step form of the clipped update
 int splice_optim_step_clip(int kind, float* params, float* grads, const float* g2, float* m, float* v, float* ema, long long n, float lr,
@@ -462,13 +472,8 @@ int splice_optim_step_pairs_clip(int kind, float* params, float* grads, const fl
         splice_set_error("splice_optim_step_pairs_clip: needs the clip records, a device lr table and step count, n_pairs >= 1, n >= 1 and, for more than one pair, n <= stride with stride a multiple of 4");
         return SPLICE_ERR_ARG;
     }
-    const size_t slot = n_pairs > 1 ? (size_t)stride : 0;   // one pair: a single arena, slot 0 of every table
-    OptimArgs a = optim_args(kind, params, grads, g2, m, v, n_pairs > 1 ? (long long)n_pairs * stride : n, 0.f, lr_dev, slot, hp0, hp1, eps, 0, zero_grad);
-    a.step_dev = step_dev;
-    if (stop) { a.mask = stop; a.mask_step = step_dev; a.mask_stride = slot; }
-    if (ema) { a.ema = ema; a.ema_decay = ema_decay; a.ema_start = ema_start; }
-    a.clip = clip; a.clip_stride = slot;
-    return optim_launch(a, (hipStream_t)stream);
+    return optim_launch(pairs_args(kind, params, grads, g2, m, v, n_pairs, n_pairs > 1 ? (size_t)stride : 0, n, lr_dev, hp0, hp1, eps, 0, step_dev, stop, zero_grad, ema,
+                                   ema_decay, ema_start, clip, nullptr, nullptr, nullptr), (hipStream_t)stream);
 }
 // as splice_optim_step_pairs_clip (stop required; clip and ema optional) with the snapshot of the best window's weights
 int splice_optim_step_pairs_best(int kind, float* params, float* grads, const float* g2, float* m, float* v, float* ema, int n_pairs, long long stride,
@@ -479,13 +484,7 @@ int splice_optim_step_pairs_best(int kind, float* params, float* grads, const fl
         splice_set_error("splice_optim_step_pairs_best: needs the stop and best records, the best arena, a device lr table and step count, n_pairs >= 1, n >= 1 and, for more than one pair, n <= stride with stride a multiple of 4");
         return SPLICE_ERR_ARG;
     }
-    const size_t slot = n_pairs > 1 ? (size_t)stride : 0;   // one pair: a single arena, slot 0 of every table
-    OptimArgs a = optim_args(kind, params, grads, g2, m, v, n_pairs > 1 ? (long long)n_pairs * stride : n, 0.f, lr_dev, slot, hp0, hp1, eps, 0, zero_grad);
-    a.step_dev = step_dev;
-    a.mask = stop; a.mask_step = step_dev; a.mask_stride = slot;
-    if (ema) { a.ema = ema; a.ema_decay = ema_decay; a.ema_start = ema_start; }
-    if (clip) { a.clip = clip; a.clip_stride = slot; }
-    a.best = best; a.best_p = best_params; a.best_ema = best_ema;
-    return optim_launch(a, (hipStream_t)stream);
+    return optim_launch(pairs_args(kind, params, grads, g2, m, v, n_pairs, n_pairs > 1 ? (size_t)stride : 0, n, lr_dev, hp0, hp1, eps, 0, step_dev, stop, zero_grad, ema,
+                                   ema_decay, ema_start, clip, best, best_params, best_ema), (hipStream_t)stream);
 }
 }

@@ -495,16 +495,31 @@ int splice_step_set_crops(void* h, int a_h, int a_w, int b_h, int b_w) {
     return SPLICE_OK;
 }
 
+// The first rule the handle carries that rides in its own update, so that it runs whole steps only (neither gradient-only nor phase
+// mode), named for an error text; null: none.
+static const char* whole_step_rule(const SpliceStep* st) {
+    return st->stop_rule.window > 0 ? "with a stop rule" : st->ema ? "with a weight average" : st->clip ? "with gradient clipping"
+           : st->best ? "that keeps the best weights" : nullptr;
+}
+// The shared opening of the rule setters below: before the first step only (`what` of the rule, for the error text), and not on a
+// gradient-only or phase-mode handle.  Callers return its code plainly, not through RC(): the message stays the last error.
+static int rule_setter_ok(const SpliceStep* st, const char* who, const char* what) {
+    if (st->runs > 0) { splice_set_error("%s: %s before the first step", who, what); return SPLICE_ERR_STATE; }
+    if (st->skip_adam || st->phases != 7 || st->leader) {
+        splice_set_error("%s: not on a handle in gradient-only (splice_step_set_mode) or phase mode (splice_step_set_phases)", who);
+        return SPLICE_ERR_STATE;
+    }
+    return SPLICE_OK;
+}
+
 // skip_adam != 0: the step stops after backward -- `grads` holds the gradient of this step's loss (+= its previous content
 // when accumulate != 0) and the parameters are untouched; the caller sums several losses that way (e.g. the same crops seen
 // at several ViT input scales) and applies splice_adam_step once.
 int splice_step_set_mode(void* h, int skip_adam, int accumulate) {
     SpliceStep* st = (SpliceStep*)h;
     if (!st || (accumulate && !skip_adam)) return SPLICE_ERR_ARG;
-    if (skip_adam && st->stop_rule.window > 0) { splice_set_error("splice_step_set_mode: a handle with a stop rule runs whole steps (no gradient-only mode)"); return SPLICE_ERR_STATE; }
-    if (skip_adam && st->ema) { splice_set_error("splice_step_set_mode: a handle with a weight average runs whole steps (no gradient-only mode)"); return SPLICE_ERR_STATE; }
-    if (skip_adam && st->clip) { splice_set_error("splice_step_set_mode: a handle with gradient clipping runs whole steps (no gradient-only mode)"); return SPLICE_ERR_STATE; }
-    if (skip_adam && st->best) { splice_set_error("splice_step_set_mode: a handle that keeps the best weights runs whole steps (no gradient-only mode)"); return SPLICE_ERR_STATE; }
+    const char* rule = skip_adam ? whole_step_rule(st) : nullptr;
+    if (rule) { splice_set_error("splice_step_set_mode: a handle %s runs whole steps (no gradient-only mode)", rule); return SPLICE_ERR_STATE; }
     if (st->skip_adam != (skip_adam ? 1 : 0) || st->accumulate != (accumulate ? 1 : 0)) st->graphs.retire();
     st->skip_adam = skip_adam ? 1 : 0; st->accumulate = accumulate ? 1 : 0;
     return SPLICE_OK;
@@ -588,10 +603,8 @@ int splice_step_set_pair_lr(void* h, const float* lr) {
 int splice_step_set_phases(void* h, int phases, void* leader) {
     SpliceStep* st = (SpliceStep*)h;
     if (!st || phases <= 0 || phases > 7 || leader == h || (leader && phases != 2) || (leader && ((SpliceStep*)leader)->leader)) return SPLICE_ERR_ARG;
-    if ((phases != 7 || leader) && st->stop_rule.window > 0) { splice_set_error("splice_step_set_phases: a handle with a stop rule runs whole steps (no phase mode)"); return SPLICE_ERR_STATE; }
-    if ((phases != 7 || leader) && st->ema) { splice_set_error("splice_step_set_phases: a handle with a weight average runs whole steps (no phase mode)"); return SPLICE_ERR_STATE; }
-    if ((phases != 7 || leader) && st->clip) { splice_set_error("splice_step_set_phases: a handle with gradient clipping runs whole steps (no phase mode)"); return SPLICE_ERR_STATE; }
-    if ((phases != 7 || leader) && st->best) { splice_set_error("splice_step_set_phases: a handle that keeps the best weights runs whole steps (no phase mode)"); return SPLICE_ERR_STATE; }
+    const char* rule = phases != 7 || leader ? whole_step_rule(st) : nullptr;
+    if (rule) { splice_set_error("splice_step_set_phases: a handle %s runs whole steps (no phase mode)", rule); return SPLICE_ERR_STATE; }
     if (st->leader != (SpliceStep*)leader) st->graphs.retire();
     st->phases = phases;
     st->leader = (SpliceStep*)leader;
@@ -604,11 +617,7 @@ int splice_step_set_stop_rule(void* h, int window, float rel, int patience, int 
     SpliceStep* st = (SpliceStep*)h;
     if (!st) return SPLICE_ERR_ARG;
     if (!stop_rule_ok(window, rel, patience, min_steps, "splice_step_set_stop_rule")) return SPLICE_ERR_ARG;
-    if (st->runs > 0) { splice_set_error("splice_step_set_stop_rule: the rule is set before the first step"); return SPLICE_ERR_STATE; }
-    if (st->skip_adam || st->phases != 7 || st->leader) {
-        splice_set_error("splice_step_set_stop_rule: not on a handle in gradient-only (splice_step_set_mode) or phase mode (splice_step_set_phases)");
-        return SPLICE_ERR_STATE;
-    }
+    if (int rc = rule_setter_ok(st, "splice_step_set_stop_rule", "the rule is set")) return rc;
     if (window == 0 && st->best) { splice_set_error("splice_step_set_stop_rule: a handle that keeps the best weights needs its rule (window > 0)"); return SPLICE_ERR_STATE; }
     if ((window > 0) != (st->stop_rule.window > 0)) st->graphs.retire();
     st->stop_rule = StopRule{window, rel, patience, min_steps};
@@ -624,11 +633,7 @@ int splice_step_set_ema(void* h, float* ema, float decay, int start) {
         splice_set_error("splice_step_set_ema: needs the ema arena, 0 < decay < 1 and start >= 0");
         return SPLICE_ERR_ARG;
     }
-    if (st->runs > 0) { splice_set_error("splice_step_set_ema: the average is set before the first step"); return SPLICE_ERR_STATE; }
-    if (st->skip_adam || st->phases != 7 || st->leader) {
-        splice_set_error("splice_step_set_ema: not on a handle in gradient-only (splice_step_set_mode) or phase mode (splice_step_set_phases)");
-        return SPLICE_ERR_STATE;
-    }
+    if (int rc = rule_setter_ok(st, "splice_step_set_ema", "the average is set")) return rc;
     if (st->best) { splice_set_error("splice_step_set_ema: the average is set before splice_step_set_keep_best (which takes its best arena)"); return SPLICE_ERR_STATE; }
     st->graphs.retire();
     st->ema = ema; st->ema_decay = decay; st->ema_start = start;
@@ -643,11 +648,7 @@ int splice_step_set_grad_clip(void* h, float max_norm, splice_clip_state* state)
         splice_set_error("splice_step_set_grad_clip: needs the state records and a finite max_norm > 0, got %g", (double)max_norm);
         return SPLICE_ERR_ARG;
     }
-    if (st->runs > 0) { splice_set_error("splice_step_set_grad_clip: the rule is set before the first step"); return SPLICE_ERR_STATE; }
-    if (st->skip_adam || st->phases != 7 || st->leader) {
-        splice_set_error("splice_step_set_grad_clip: not on a handle in gradient-only (splice_step_set_mode) or phase mode (splice_step_set_phases)");
-        return SPLICE_ERR_STATE;
-    }
+    if (int rc = rule_setter_ok(st, "splice_step_set_grad_clip", "the rule is set")) return rc;
     if (st->astride % 4) { splice_set_error("splice_step_set_grad_clip: the arena stride must be a multiple of 4"); return SPLICE_ERR_ARG; }
     if (!st->clip_partials) RC(salloc(st, &st->clip_partials, (size_t)st->pairs * (((size_t)st->nparams + SPLICE_CLIP_CHUNK - 1) / SPLICE_CLIP_CHUNK)));
     st->graphs.retire();
@@ -664,11 +665,7 @@ int splice_step_set_keep_best(void* h, float* best_params, float* best_ema, spli
         splice_set_error("splice_step_set_keep_best: needs the best arena, the state records and the window means");
         return SPLICE_ERR_ARG;
     }
-    if (st->runs > 0) { splice_set_error("splice_step_set_keep_best: the best weights are kept from before the first step"); return SPLICE_ERR_STATE; }
-    if (st->skip_adam || st->phases != 7 || st->leader) {
-        splice_set_error("splice_step_set_keep_best: not on a handle in gradient-only (splice_step_set_mode) or phase mode (splice_step_set_phases)");
-        return SPLICE_ERR_STATE;
-    }
+    if (int rc = rule_setter_ok(st, "splice_step_set_keep_best", "the best weights are kept from")) return rc;
     if (st->stop_rule.window <= 0) { splice_set_error("splice_step_set_keep_best: needs a handle with a stop rule (splice_step_set_stop_rule, window > 0)"); return SPLICE_ERR_STATE; }
     if ((best_ema != nullptr) != (st->ema != nullptr)) {
         splice_set_error("splice_step_set_keep_best: best_ema goes with a weight average (splice_step_set_ema): given exactly when the handle keeps one");

@@ -46,32 +46,34 @@ MAX_PAIR_CFGS = 32   # SPLICE_STEP_MAX_PAIR_CFGS
 MAX_GROUP_IMAGES = 32   # SPLICE_STEP_MAX_GROUP_IMAGES: images per side (pairs x n_crops) of several pairs with n_crops > 1
 
 
+def _number(c, key, kinds, ok, what):
+    """``c[key]`` (absent: the default) when it is one of ``kinds``, no bool, and ``ok(value)``; else ValueError naming the key."""
+    v = c.get(key, DEFAULT_CFG[key])
+    if isinstance(v, bool) or not isinstance(v, kinds) or not ok(v):
+        raise ValueError(f"'{key}' must be {what}, got {v!r}")
+    return v
+
+
+_INT, _REAL = (int, np.integer), (int, float, np.integer, np.floating)
+
+
+def _integer(c, key, lo):
+    return int(_number(c, key, _INT, lambda v: v >= lo, f"an integer >= {lo}"))
+
+
 def stop_rule(c):
     """``(window, rel, patience, min_steps)`` of the plateau stop rule in config ``c``, checked on the host:
     ``stop_window >= 0`` (0: the rule is off), ``0 < stop_rel < 1``, ``stop_patience >= 1``, ``stop_min_steps >= 0``.  Raises
     ValueError naming the key."""
-    def integer(key, lo):
-        v = c.get(key, DEFAULT_CFG[key])
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo:
-            raise ValueError(f"'{key}' must be an integer >= {lo}, got {v!r}")
-        return int(v)
-    rel = c.get("stop_rel", DEFAULT_CFG["stop_rel"])
-    if isinstance(rel, bool) or not isinstance(rel, (int, float, np.floating)) or not 0 < rel < 1:
-        raise ValueError(f"'stop_rel' must be a number in (0, 1), got {rel!r}")
-    return integer("stop_window", 0), float(rel), integer("stop_patience", 1), integer("stop_min_steps", 0)
+    rel = float(_number(c, "stop_rel", _REAL, lambda v: 0 < v < 1, "a number in (0, 1)"))
+    return _integer(c, "stop_window", 0), rel, _integer(c, "stop_patience", 1), _integer(c, "stop_min_steps", 0)
 
 
 def ema_rule(c):
     """``(decay, start)`` of the weight average in config ``c``, checked on the host: ``0 <= ema_decay < 1``
     (0: no average is kept) and an integer ``ema_start >= 0``, the number of updates the average merely copies the weights for.
     Raises ValueError naming the key."""
-    d = c.get("ema_decay", DEFAULT_CFG["ema_decay"])
-    if isinstance(d, bool) or not isinstance(d, (int, float, np.floating, np.integer)) or not 0 <= d < 1:
-        raise ValueError(f"'ema_decay' must be a number in [0, 1), got {d!r}")
-    s = c.get("ema_start", DEFAULT_CFG["ema_start"])
-    if isinstance(s, bool) or not isinstance(s, (int, np.integer)) or s < 0:
-        raise ValueError(f"'ema_start' must be an integer >= 0, got {s!r}")
-    return float(d), int(s)
+    return float(_number(c, "ema_decay", _REAL, lambda v: 0 <= v < 1, "a number in [0, 1)")), _integer(c, "ema_start", 0)
 
 
 def np_ema(e, p, step, decay, start):
@@ -145,9 +147,7 @@ CLIP_CHUNK = 4096   # SPLICE_CLIP_CHUNK
 def grad_clip_rule(c):
     """``max_norm`` of the gradient clipping in config ``c``, checked on the host: a finite number
     ``grad_clip_norm >= 0`` (0: the gradient is not clipped).  Raises ValueError naming the key."""
-    v = c.get("grad_clip_norm", DEFAULT_CFG["grad_clip_norm"])
-    if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or not 0 <= v < float("inf"):
-        raise ValueError(f"'grad_clip_norm' must be a finite number >= 0, got {v!r}")
+    v = _number(c, "grad_clip_norm", _REAL, lambda v: 0 <= v < float("inf"), "a finite number >= 0")
     with np.errstate(over="ignore"):
         if not np.isfinite(np.float32(v)):   # (the kernels take it as a float)
             raise ValueError(f"'grad_clip_norm' must be a finite float32 number, got {v!r}")
@@ -614,20 +614,13 @@ class MultiPairEngine:
         books BatchNorm statistics and is not among the logged forwards.  ``best=True`` (``stop_keep_best``): alike with the best
         window's weights, or with ``ema=True`` too that step's average."""
         n, _, h, w = img.shape
-        if best:
-            key = ("best", bool(ema), pair, n, h, w)
-            if key not in self._log_plans:
-                self._log_plans[key] = GeneratorPlan(self.gen, n, h, w, False, batch_stats=n > 1)
-            return self._log_plans[key].forward(self.pair_best(pair, ema=ema), img.contiguous())
-        if ema:
-            key = ("ema", pair, n, h, w)
-            if key not in self._log_plans:
-                self._log_plans[key] = GeneratorPlan(self.gen, n, h, w, False, batch_stats=n > 1)
-            return self._log_plans[key].forward(self.pair_ema(pair), img.contiguous())
-        key = (pair, n, h, w)   # one plan per pair: a plan holds the BatchNorm statistics of its last forward until they are booked
+        # one plan per pair and weight set: a plan holds the BatchNorm statistics of its last forward until they are booked
+        key = (("best", bool(ema)) if best else ("ema",) if ema else ()) + (pair, n, h, w)
         if key not in self._log_plans:
             self._log_plans[key] = GeneratorPlan(self.gen, n, h, w, False, batch_stats=n > 1)   # ONE netG call on n images: batch statistics, as nn.BatchNorm2d
         plan = self._log_plans[key]
+        if best or ema:
+            return plan.forward(self.pair_best(pair, ema=ema) if best else self.pair_ema(pair), img.contiguous())
         out = plan.forward(self.pair_params(pair), img.contiguous())
         if track_running_stats:
             self.book_running_stats(plan, pair)
@@ -784,27 +777,19 @@ def synthetic_engine(cfg, pair_id=0, hw=(224, 224), seed=1234, device="cuda", vi
     (inputs ``[P,3,h,w]``); ``pairs == 1``: the single-pair ``SpliceEngine`` with ``[3,h,w]`` inputs.
     ``crop_hw``: the global crops are the top-left ``crop_hw`` window of the ``hw`` images (the reference's default shape: 900 x 900 crops of
     900 x 1200 images, every crop resized to ``dino_global_patch_size``); the return value then carries the entire image as a fourth entry."""
-    if crop_hw is not None:
-        if pairs != 1:
-            raise ValueError("crop_hw: one pair per engine")
-        c = dict(DEFAULT_CFG, **cfg)
-        vit_state = None if vit_engine is not None else synth.vit_params(seed, c["dino_model_name"], img_size=c["dino_global_patch_size"])
-        a, b = synth.image_pair(seed, pair_id, hw[0], hw[1])
-        eng = SpliceEngine(c, vit_state, synth.generator_params(seed + 1 + pair_id, c["init_gain"]), crop_hw, hw if entire else None, device=device, vit_engine=vit_engine, fp8=fp8)
-        A, B = torch.from_numpy(a).to(device), torch.from_numpy(b).to(device)
-        return eng, A[:, :crop_hw[0], :crop_hw[1]].contiguous(), B[:, :crop_hw[0], :crop_hw[1]].contiguous(), A
+    if crop_hw is not None and pairs != 1:
+        raise ValueError("crop_hw: one pair per engine")
     c = dict(DEFAULT_CFG, **cfg)
-    P = c["dino_global_patch_size"]
-    vit_state = None
-    if vit_engine is None:
-        vit_state = synth.vit_params(seed, c["dino_model_name"], img_size=P)
+    vit_state = None if vit_engine is not None else synth.vit_params(seed, c["dino_model_name"], img_size=c["dino_global_patch_size"])
     ids = [pair_id + k for k in range(pairs)]
     gen_states = [synth.generator_params(seed + 1 + i, c["init_gain"]) for i in ids]
     imgs = [synth.image_pair(seed, i, hw[0], hw[1]) for i in ids]
-    if pairs == 1:
-        eng = SpliceEngine(c, vit_state, gen_states[0], hw, hw if entire else None, device=device, vit_engine=vit_engine, fp8=fp8)
-        return eng, torch.from_numpy(imgs[0][0]).to(device), torch.from_numpy(imgs[0][1]).to(device)
-    eng = MultiPairEngine(c, vit_state, gen_states, hw, hw if entire else None, device=device, vit_engine=vit_engine, fp8=fp8, top_cls_only=top_cls_only)
-    A = torch.from_numpy(np.stack([a for a, _ in imgs])).to(device)
-    B = torch.from_numpy(np.stack([b for _, b in imgs])).to(device)
-    return eng, A, B
+    ent = hw if entire else None
+    if pairs > 1:
+        eng = MultiPairEngine(c, vit_state, gen_states, hw, ent, device=device, vit_engine=vit_engine, fp8=fp8, top_cls_only=top_cls_only)
+        return eng, torch.from_numpy(np.stack([a for a, _ in imgs])).to(device), torch.from_numpy(np.stack([b for _, b in imgs])).to(device)
+    eng = SpliceEngine(c, vit_state, gen_states[0], crop_hw or hw, ent, device=device, vit_engine=vit_engine, fp8=fp8)
+    A, B = torch.from_numpy(imgs[0][0]).to(device), torch.from_numpy(imgs[0][1]).to(device)
+    if crop_hw is None:
+        return eng, A, B
+    return eng, A[:, :crop_hw[0], :crop_hw[1]].contiguous(), B[:, :crop_hw[0], :crop_hw[1]].contiguous(), A

@@ -131,13 +131,92 @@ class DeviceDataFeed:
         return sample
 
 
-def train_model(dataroot, callback=None, cfg_overrides=None, vit_state=None, progress=True):
+def _load_cfg(dataroot, cfg_overrides):
     cfg_path = "conf/default/config.yaml" if os.path.exists("conf/default/config.yaml") else _PKG_CFG
     with open(cfg_path, "r") as f:
         cfg = yaml.safe_load(f)
     if dataroot is not None:
         cfg['dataroot'] = dataroot
     cfg.update(cfg_overrides or {})
+    return cfg
+
+
+def _seed_host(seed):
+    """Seeds python and numpy (``-1``: with a drawn seed) and returns the seed; torch is the caller's business."""
+    if seed == -1:
+        seed = np.random.randint(2 ** 32 - 1, dtype=np.int64)
+    random.seed(int(seed))
+    np.random.seed(int(seed) % (2 ** 32))
+    return seed
+
+
+def _load_pair(root, cfg):
+    A = _load_image(_first_file(os.path.join(root, 'A')), cfg['A_resize'])
+    B = _load_image(_first_file(os.path.join(root, 'B')), cfg['B_resize'])
+    return (B, A) if cfg['direction'] == 'BtoA' else (A, B)
+
+
+def _crop_max(A, B):
+    return max(min(A.shape[1], A.shape[2]), min(B.shape[1], B.shape[2]))   # crops are squares of side <= min(h, w)
+
+
+def _one_scale(cfg):
+    """``dino_global_scales`` with one entry is the ViT input size, the reference's ``dino_global_patch_size``."""
+    if cfg.get('dino_global_scales'):
+        cfg['dino_global_patch_size'] = int(cfg['dino_global_scales'][0])
+
+
+def _init_generator(cfg):
+    """The parameters of ``define_G(init_type, init_gain)``, drawn from the torch RNG as it stands."""
+    from .networks import define_G
+    netG = define_G(cfg['init_type'], cfg['init_gain'], device=device)
+    return {k: v.detach().clone() for k, v in netG.state_dict().items() if k in netG.engine.table}
+
+
+def _optimise(cfg, engine, next_inputs, As, writers, callback, progress, single=False):
+    """The optimisation loop of every entry point, and the end of a run: ``cfg['n_epochs']`` steps of ``engine`` on the crops
+    ``next_inputs()`` returns (the arguments of ``engine.step``); every ``log_images_freq`` steps one image per slot from ``As`` goes to
+    the slot's writer and to ``callback(slot, image)``.  ``single``: the engine is a one-pair engine (one loss in the progress line, and
+    the stop is announced).  Closes the writers."""
+    n_epochs, freq = cfg['n_epochs'], cfg['log_images_freq']
+    try:
+        for epoch in range(1, n_epochs + 1):
+            inputs = next_inputs()
+            log = epoch % freq == 0
+            # train.py:70-76 generates the logged image between the loss and backward(): with the weights of epoch - 1
+            # updates.  The fused step updates in place, so the images are generated BEFORE it (same weights) ...
+            outputs = [engine.generate(A, pair=p) for p, A in enumerate(As)] if log else None
+            engine.step(*inputs)
+            if log:
+                engine.book_logged_forward()   # ... and their BatchNorm bookkeeping lands AFTER the step's, as in the reference
+                for p, out in enumerate(outputs):
+                    # (out/output.png is overwritten every time: intermediate images may be skipped when they come faster than the writer's interval, the last one never)
+                    writers[p].submit(out[0], force=epoch + freq > n_epochs)
+                    if callback is not None:
+                        callback(p, out[0])
+            if progress and (epoch % 50 == 0 or epoch == 1):
+                losses = f"{engine.losses()['loss']:.4f}" if single else ", ".join(f"{d['loss']:.4f}" for d in engine.losses())
+                print(f"Epoch {epoch}: loss={losses} lr={engine.lr}")
+            # the plateau stop rule (stop_window > 0; decided on the device): the host asks only after a step that closes a window -- no
+            # other step can stop a slot -- and ends the run, once every slot has stopped, with an image of each slot's final parameters
+            if engine.window_closes(engine.step_idx) and engine.all_stopped():
+                for p, A in enumerate(As):
+                    out = engine.generate(A, pair=p)
+                    writers[p].submit(out[0], force=True)
+                    if callback is not None:
+                        callback(p, out[0])
+                if single and progress:
+                    print(f"Epoch {epoch}: the loss has plateaued, stopping")
+                break
+        _ema_images(engine, writers, As)
+        _best_images(engine, writers, As)
+    finally:
+        for w in writers:   # PNG encode + disk write happen on a worker thread
+            w.close()
+
+
+def train_model(dataroot, callback=None, cfg_overrides=None, vit_state=None, progress=True):
+    cfg = _load_cfg(dataroot, cfg_overrides)
     n_crops = (int(cfg['global_A_crops_n_crops']), int(cfg['global_B_crops_n_crops']))
     if not all(1 <= n <= 8 for n in n_crops):
         raise NotImplementedError("the fused engine takes 1..8 global crops per image (global_{A,B}_crops_n_crops)")
@@ -146,74 +225,32 @@ def train_model(dataroot, callback=None, cfg_overrides=None, vit_state=None, pro
     if device.type != 'cuda':
         raise RuntimeError("train_model needs an MI355X: the product path has no CPU fallback")
 
-    seed = cfg['seed']
-    if seed == -1:
-        seed = np.random.randint(2 ** 32 - 1, dtype=np.int64)
-    random.seed(int(seed))
-    np.random.seed(int(seed) % (2 ** 32))
+    seed = _seed_host(cfg['seed'])
     torch.manual_seed(int(seed))
     print(f'running with seed: {seed}.')
 
-    A = _load_image(_first_file(os.path.join(cfg['dataroot'], 'A')), cfg['A_resize'])
-    B = _load_image(_first_file(os.path.join(cfg['dataroot'], 'B')), cfg['B_resize'])
-    if cfg['direction'] == 'BtoA':
-        A, B = B, A
+    A, B = _load_pair(cfg['dataroot'], cfg)
     print("Image sizes %s and %s" % (str((A.shape[2], A.shape[1])), str((B.shape[2], B.shape[1]))))
     feed = DeviceDataFeed(cfg, A, B)
 
     vit_engine = None if vit_state is not None else _shared_vit_engine(cfg['dino_model_name'], "train_model")
-    # generator initialised exactly as define_G(init_type, init_gain): xavier-normal from the torch RNG seeded above
-    from .networks import define_G
-    netG = define_G(cfg['init_type'], cfg['init_gain'], device=device)
-    gen_state = {k: v.detach() for k, v in netG.state_dict().items() if k in netG.engine.table}
-    crop_max = max(min(A.shape[1], A.shape[2]), min(B.shape[1], B.shape[2]))   # crops are squares of side <= min(h, w)
+    gen_state = _init_generator(cfg)   # exactly as define_G(init_type, init_gain): xavier-normal from the torch RNG seeded above
     # Extensions beyond the reference's config (BASELINE configs[4]): `dino_global_scales` = list of ViT input sizes at which every
     # loss term is evaluated each step (the reference has the single `dino_global_patch_size`), `fp8` = e4m3 operands for the
     # QKV / fc1 / fc2 projections and the self-similarity Gram matrices.  Absent keys = the reference's behaviour.
     scales = [int(x) for x in (cfg.get('dino_global_scales') or [])]
-    fp8 = fp8_mode(cfg)
-    crops, entire = (crop_max, crop_max), tuple(A.shape[1:])
+    crops, entire = (_crop_max(A, B),) * 2, tuple(A.shape[1:])
     if len(scales) > 1:
         from .engine import MultiScaleEngine
-        engine = MultiScaleEngine(cfg, vit_state, gen_state, crops, entire, scales=scales, device=device, n_crops=n_crops, vit_engine=vit_engine, fp8=fp8)
+        engine = MultiScaleEngine(cfg, vit_state, gen_state, crops, entire, scales=scales, device=device, n_crops=n_crops, vit_engine=vit_engine, fp8=fp8_mode(cfg))
     else:
-        if scales:
-            cfg['dino_global_patch_size'] = scales[0]
-        engine = SpliceEngine(cfg, vit_state, gen_state, crops, entire, device=device, n_crops=n_crops, vit_engine=vit_engine, fp8=fp8)
-    del netG
+        _one_scale(cfg)
+        engine = SpliceEngine(cfg, vit_state, gen_state, crops, entire, device=device, n_crops=n_crops, vit_engine=vit_engine, fp8=fp8_mode(cfg))
 
-    writer = AsyncResultWriter(cfg['dataroot'])   # PNG encode + disk write happen on a worker thread
-    try:
-        for epoch in range(1, cfg['n_epochs'] + 1):
-            inputs = feed.next()
-            log = epoch % cfg['log_images_freq'] == 0
-            if log:
-                # train.py:70-76 generates the logged image between the loss and backward(): with the weights of epoch - 1
-                # updates.  The fused step updates in place, so the image is generated BEFORE it (same weights) ...
-                output = engine.generate(feed.get_A())
-            engine.step(inputs['A_global'], inputs['B_global'], inputs['A'][0] if 'A' in inputs else None)
-            if log:
-                engine.book_logged_forward()   # ... and its BatchNorm bookkeeping lands AFTER the step's, as in the reference
-                # (out/output.png is overwritten every time: intermediate images may be skipped when they come faster than the writer's interval, the last one never)
-                writer.submit(output[0], force=epoch + cfg['log_images_freq'] > cfg['n_epochs'])
-                if callback is not None:
-                    callback(output[0])
-            if progress and (epoch % 50 == 0 or epoch == 1):
-                print(f"Epoch {epoch}: loss={engine.losses()['loss']:.4f} lr={engine.lr}")
-            # the plateau stop rule (stop_window > 0; decided on the device): the host asks only after a step that closes a window -- no
-            # other step can stop the pair -- and ends the run with an image of the final parameters
-            if engine.window_closes(engine.step_idx) and engine.all_stopped():
-                output = engine.generate(feed.get_A())
-                writer.submit(output[0], force=True)
-                if callback is not None:
-                    callback(output[0])
-                if progress:
-                    print(f"Epoch {epoch}: the loss has plateaued, stopping")
-                break
-        _ema_images(engine, [writer], [feed.get_A()])
-        _best_images(engine, [writer], [feed.get_A()])
-    finally:
-        writer.close()
+    def next_inputs():
+        inputs = feed.next()
+        return inputs['A_global'], inputs['B_global'], inputs['A'][0] if 'A' in inputs else None
+    _optimise(cfg, engine, next_inputs, [feed.get_A()], [AsyncResultWriter(cfg['dataroot'])], callback and (lambda p, image: callback(image)), progress, single=True)
     return engine
 
 
@@ -247,15 +284,6 @@ class PairBatchFeed:
         sample['A_global'] = self._crops([augment.structure_transforms(a) if aug else a for a in self.A], self.cfg['global_A_crops_min_cover'], self.n_crops[0])
         sample['B_global'] = self._crops([augment.texture_transforms(b) if aug else b for b in self.B], self.cfg['global_B_crops_min_cover'], self.n_crops[1])
         return sample
-
-
-def _final_images(engine, writers, As, callback):
-    """Every slot has stopped (the plateau stop rule): one image per slot from its final parameters, always written."""
-    for p, A in enumerate(As):
-        out = engine.generate(A, pair=p)
-        writers[p].submit(out[0], force=True)
-        if callback is not None:
-            callback(p, out[0])
 
 
 def _ema_images(engine, writers, As):
@@ -311,10 +339,7 @@ def train_pairs(dataroots, callback=None, cfg_overrides=None, vit_state=None, pr
     With deterministic full crops (``use_augmentations: False``, ``min_cover: 1``) the result of every pair is bit-identical to
     its single ``train_model`` run."""
     from .engine import MAX_GROUP_IMAGES, MultiPairEngine
-    cfg_path = "conf/default/config.yaml" if os.path.exists("conf/default/config.yaml") else _PKG_CFG
-    with open(cfg_path, "r") as f:
-        cfg = yaml.safe_load(f)
-    cfg.update(cfg_overrides or {})
+    cfg = _load_cfg(None, cfg_overrides)
     n_crops = (int(cfg['global_A_crops_n_crops']), int(cfg['global_B_crops_n_crops']))
     if not all(1 <= n <= 8 for n in n_crops):
         raise NotImplementedError("train_pairs: the fused engine takes 1..8 global crops per image (global_{A,B}_crops_n_crops)")
@@ -326,58 +351,24 @@ def train_pairs(dataroots, callback=None, cfg_overrides=None, vit_state=None, pr
                                   "grouped pairs would silently train single-scale")
     if device.type != 'cuda':
         raise RuntimeError("train_pairs needs an MI355X: the product path has no CPU fallback")
-    seed = cfg['seed']
-    if seed == -1:
-        seed = np.random.randint(2 ** 32 - 1, dtype=np.int64)
-    random.seed(int(seed))
-    np.random.seed(int(seed) % (2 ** 32))
+    seed = _seed_host(cfg['seed'])
     print(f'running {len(dataroots)} pairs with seed: {seed}.')
-    As, Bs = [], []
-    for root in dataroots:
-        A = _load_image(_first_file(os.path.join(root, 'A')), cfg['A_resize'])
-        B = _load_image(_first_file(os.path.join(root, 'B')), cfg['B_resize'])
-        if cfg['direction'] == 'BtoA':
-            A, B = B, A
-        As.append(A); Bs.append(B)
+    As, Bs = zip(*[_load_pair(root, cfg) for root in dataroots])
     feed = PairBatchFeed(cfg, As, Bs)
     vit_engine = None if vit_state is not None else _shared_vit_engine(cfg['dino_model_name'], "train_pairs")
-    from .networks import define_G
     gen_states = []
     for _ in dataroots:
         torch.manual_seed(int(seed))     # every pair starts as its own train_model run would
-        netG = define_G(cfg['init_type'], cfg['init_gain'], device=device)
-        gen_states.append({k: v.detach().clone() for k, v in netG.state_dict().items() if k in netG.engine.table})
-        del netG
+        gen_states.append(_init_generator(cfg))
     torch.manual_seed(int(seed))
-    if cfg.get('dino_global_scales'):
-        cfg['dino_global_patch_size'] = int(cfg['dino_global_scales'][0])   # one entry: the ViT input size, as in train_model
-    A0, B0 = As[0], Bs[0]
-    crop_max = max(min(A0.shape[1], A0.shape[2]), min(B0.shape[1], B0.shape[2]))
-    engine = MultiPairEngine(cfg, vit_state, gen_states, (crop_max, crop_max), tuple(A0.shape[1:]), device=device, vit_engine=vit_engine, fp8=fp8_mode(cfg),
+    _one_scale(cfg)
+    engine = MultiPairEngine(cfg, vit_state, gen_states, (_crop_max(As[0], Bs[0]),) * 2, tuple(As[0].shape[1:]), device=device, vit_engine=vit_engine, fp8=fp8_mode(cfg),
                              n_crops=n_crops[0] if n_crops[0] == n_crops[1] else n_crops)
-    writers = [AsyncResultWriter(root) for root in dataroots]
-    try:
-        for epoch in range(1, cfg['n_epochs'] + 1):
-            inputs = feed.next()
-            log = epoch % cfg['log_images_freq'] == 0
-            outputs = [engine.generate(feed.get_A(p), pair=p) for p in range(len(dataroots))] if log else None
-            engine.step(inputs['A_global'], inputs['B_global'], inputs.get('A'))
-            if log:
-                engine.book_logged_forward()   # BatchNorm bookkeeping of the P logging forwards, after the step's (train.py:70-79)
-                for p, out in enumerate(outputs):
-                    writers[p].submit(out[0], force=epoch + cfg['log_images_freq'] > cfg['n_epochs'])
-                    if callback is not None:
-                        callback(p, out[0])
-            if progress and (epoch % 50 == 0 or epoch == 1):
-                print(f"Epoch {epoch}: loss=" + ", ".join(f"{d['loss']:.4f}" for d in engine.losses()) + f" lr={engine.lr}")
-            if engine.window_closes(engine.step_idx) and engine.all_stopped():   # every pair has plateaued (see train_model)
-                _final_images(engine, writers, [feed.get_A(p) for p in range(len(dataroots))], callback)
-                break
-        _ema_images(engine, writers, [feed.get_A(p) for p in range(len(dataroots))])
-        _best_images(engine, writers, [feed.get_A(p) for p in range(len(dataroots))])
-    finally:
-        for w in writers:
-            w.close()
+
+    def next_inputs():
+        inputs = feed.next()
+        return inputs['A_global'], inputs['B_global'], inputs.get('A')
+    _optimise(cfg, engine, next_inputs, [feed.get_A(p) for p in range(len(dataroots))], [AsyncResultWriter(root) for root in dataroots], callback, progress)
     return engine
 
 
@@ -400,12 +391,7 @@ def train_sweep(dataroot, variants, cfg_overrides=None, vit_state=None, callback
     every variant that has it).  Writes ``<dataroot>/out/sweep/<k>/output.png`` and ``variant.json`` (overrides, seed, final
     losses); ``callback(k, image)``.  Returns the engine."""
     from .engine import MultiPairEngine
-    cfg_path = "conf/default/config.yaml" if os.path.exists("conf/default/config.yaml") else _PKG_CFG
-    with open(cfg_path, "r") as f:
-        cfg = yaml.safe_load(f)
-    if dataroot is not None:
-        cfg['dataroot'] = dataroot
-    cfg.update(cfg_overrides or {})
+    cfg = _load_cfg(dataroot, cfg_overrides)
     variants = [dict(v) for v in variants]
     cfgs = _sweep_checks(cfg, variants)
     if device.type != 'cuda':
@@ -420,61 +406,33 @@ def train_sweep(dataroot, variants, cfg_overrides=None, vit_state=None, callback
                 drawn = np.random.randint(2 ** 32 - 1, dtype=np.int64)
             seed = drawn
         seeds.append(int(seed))
-    random.seed(seeds[0])
-    np.random.seed(seeds[0] % (2 ** 32))
+    _seed_host(seeds[0])
     torch.manual_seed(seeds[0])
     print(f'running a sweep of {K} variants with seeds: {seeds}.')
 
-    A = _load_image(_first_file(os.path.join(cfg['dataroot'], 'A')), cfg['A_resize'])
-    B = _load_image(_first_file(os.path.join(cfg['dataroot'], 'B')), cfg['B_resize'])
-    if cfg['direction'] == 'BtoA':
-        A, B = B, A
+    A, B = _load_pair(cfg['dataroot'], cfg)
     feed = DeviceDataFeed(cfg, A, B)
     vit_engine = None if vit_state is not None else _shared_vit_engine(cfg['dino_model_name'], "train_sweep")
-    from .networks import define_G
     gen_states, rng = [], None
     for k, c in enumerate(cfgs):
         if k > 0:
             torch.manual_seed(seeds[k])
-        netG = define_G(c['init_type'], c['init_gain'], device=device)
-        gen_states.append({n: t.detach().clone() for n, t in netG.state_dict().items() if n in netG.engine.table})
-        del netG
+        gen_states.append(_init_generator(c))
         if k == 0:   # the state train_model's loop starts from (variant 0's)
             rng = (random.getstate(), np.random.get_state(), torch.get_rng_state(), torch.cuda.get_rng_state_all())
     random.setstate(rng[0])
     np.random.set_state(rng[1])
     torch.set_rng_state(rng[2])
     torch.cuda.set_rng_state_all(rng[3])
-    if cfg.get('dino_global_scales'):
-        cfg['dino_global_patch_size'] = int(cfg['dino_global_scales'][0])   # one entry: the ViT input size, as in train_model
-    crop_max = max(min(A.shape[1], A.shape[2]), min(B.shape[1], B.shape[2]))
-    engine = MultiPairEngine(cfg, vit_state, gen_states, (crop_max, crop_max), tuple(A.shape[1:]), device=device, vit_engine=vit_engine,
+    _one_scale(cfg)
+    engine = MultiPairEngine(cfg, vit_state, gen_states, (_crop_max(A, B),) * 2, tuple(A.shape[1:]), device=device, vit_engine=vit_engine,
                              fp8=fp8_mode(cfg), pair_cfgs=variants)
     out_dirs = [os.path.join(cfg['dataroot'], 'out', 'sweep', str(k)) for k in range(K)]
-    writers = [AsyncResultWriter(cfg['dataroot'], out_dir=d) for d in out_dirs]
-    try:
-        for epoch in range(1, cfg['n_epochs'] + 1):
-            inputs = feed.next()
-            log = epoch % cfg['log_images_freq'] == 0
-            outputs = [engine.generate(feed.get_A(), pair=k) for k in range(K)] if log else None
-            A_entire = inputs['A'].expand(K, -1, -1, -1).contiguous() if 'A' in inputs else None
-            engine.step(inputs['A_global'].expand(K, -1, -1, -1).contiguous(), inputs['B_global'].expand(K, -1, -1, -1).contiguous(), A_entire)
-            if log:
-                engine.book_logged_forward()
-                for k, out in enumerate(outputs):
-                    writers[k].submit(out[0], force=epoch + cfg['log_images_freq'] > cfg['n_epochs'])
-                    if callback is not None:
-                        callback(k, out[0])
-            if progress and (epoch % 50 == 0 or epoch == 1):
-                print(f"Epoch {epoch}: loss=" + ", ".join(f"{d['loss']:.4f}" for d in engine.losses()) + f" lr={engine.lr}")
-            if engine.window_closes(engine.step_idx) and engine.all_stopped():   # every variant has plateaued (see train_model)
-                _final_images(engine, writers, [feed.get_A()] * K, callback)
-                break
-        _ema_images(engine, writers, [feed.get_A()] * K)
-        _best_images(engine, writers, [feed.get_A()] * K)
-    finally:
-        for w in writers:
-            w.close()
+
+    def next_inputs():   # every slot sees the one feed's crops
+        inputs = feed.next()
+        return tuple(t.expand(K, -1, -1, -1).contiguous() if t is not None else None for t in (inputs['A_global'], inputs['B_global'], inputs.get('A')))
+    _optimise(cfg, engine, next_inputs, [feed.get_A()] * K, [AsyncResultWriter(cfg['dataroot'], out_dir=d) for d in out_dirs], callback, progress)
     losses = engine.losses() if engine.step_idx >= 0 else [{} for _ in range(K)]
     for k in range(K):
         with open(os.path.join(out_dirs[k], 'variant.json'), 'w') as f:

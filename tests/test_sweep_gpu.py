@@ -206,6 +206,33 @@ def test_train_sweep_equals_train_model_per_variant(tmp_path):
     assert not torch.equal(eng0.pair_params(0), want)
 
 
+def test_train_sweep_end_of_run_equals_train_model(tmp_path, capsys):
+    """The end of a sweep under every optional rule at once -- the stop rule (counted steps 1 2 3 | 4 6 7: a window mean must halve to
+    count as better, so a slot stops at step 7 of 12), its best window's weights and the weight average: each slot's three weight sets and
+    its three images are, bit for bit, those of the ``train_model`` run of its merged config."""
+    from splice_amd.train import train_model, train_sweep
+    vit_state = synth.vit_params(7, "dino_vits8", img_size=64, w_std=0.05)
+    over = dict(OVER, stop_window=3, stop_patience=1, stop_rel=0.5, stop_keep_best=True, ema_decay=0.9)
+    variants = [dict(lr=0.002), dict(lr=0.004)]
+    _write_pair(tmp_path / "sweep")
+    eng = train_sweep(str(tmp_path / "sweep"), variants, cfg_overrides=over, vit_state=vit_state, progress=False)
+    with capsys.disabled():
+        print(f"\nsweep: stopped_at {eng.stopped_at}, step_idx {eng.step_idx}")
+    assert any(at is not None and at + 1 < over["n_epochs"] for at in eng.stopped_at), eng.stopped_at
+    for k, v in enumerate(variants):
+        shutil.copytree(tmp_path / "sweep" / "A", tmp_path / f"single{k}" / "A")
+        shutil.copytree(tmp_path / "sweep" / "B", tmp_path / f"single{k}" / "B")
+        single = train_model(str(tmp_path / f"single{k}"), cfg_overrides=dict(over, **v), vit_state=vit_state, progress=False)
+        assert single.stopped_at == eng.stopped_at[k]
+        for which in ({}, dict(ema=True), dict(best=True)):
+            want, got = single.state_dict(**which), eng.state_dict(k, **which)
+            assert want.keys() == got.keys()
+            for name in want:
+                assert torch.equal(want[name], got[name]), (k, which, name)
+        for name in ("output.png", "output_ema.png", "output_best.png"):
+            assert (tmp_path / f"single{k}" / "out" / name).read_bytes() == (tmp_path / "sweep" / "out" / "sweep" / str(k) / name).read_bytes(), (k, name)
+
+
 def test_run_batch_sweep_equals_train_sweep(tmp_path, monkeypatch):
     from splice_amd import batch
     from splice_amd.train import train_sweep
