@@ -576,6 +576,20 @@ int splice_optim_step_pairs_best(int kind, float* params, float* grads, const fl
  * bars. */
 int splice_step_set_keep_best(void* step, float* best_params, float* best_ema, splice_best_state* state, float* means);
 
+/* ------------------------------------------------------------------ the per-step loss trace: a loss curve of every pair
+ * without a device-to-host copy per step.  trace: device, the caller's, [capacity][pairs][8] floats (the caller fills it, e.g. with NaN,
+ * to tell written rows from others).  The step with index s < capacity writes row s of pair p, at trace + (s * pairs + p) * 8:
+ *   words 0-5   the six values the step's loss kernel writes into losses_out[p][0..5] (splice_step_run), with the same bits, stored
+ *               by that kernel;
+ *   words 6-7   the pair's gradient norm and clip coefficient of the step (splice_clip_state norm / coef), stored by the norm launch
+ *               of a handle with gradient clipping (splice_step_set_grad_clip); without it they are not written.
+ * A step with s >= capacity writes nothing and is no error.  A pair frozen by the stop rule is not written behind its stop step: row
+ * stop_step is its last.  The row index is read from the step count on the device, so a replayed graph writes its own step's row.  No
+ * launch, event or graph node more, and params / m / v / ema / best arenas / rule records / losses are what they are without it.
+ * Before the first splice_step_run only; refused on a handle in gradient-only (splice_step_set_mode) or phase mode
+ * (splice_step_set_phases), which it in turn bars. */
+int splice_step_set_loss_trace(void* step, float* trace, int capacity);
+
 /* ------------------------------------------------------------------ test hooks: the loss stage as the fused step launches it.  The three
  * entry points below call the step's own launchers (structure term, batched MSE, total) on the caller's buffers with the step's operand
  * layout; they add no kernel and no code path (tests/test_loss_stage_gpu.py against oracle/loss_stage.py).
@@ -623,6 +637,15 @@ int splice_mse_pairs(const float* a, int lda, size_t a_ps, const float* b, int l
 int splice_total_loss_pairs(float* lbase, size_t lstride, int lp, float w_ssim, float w_essim, float w_ecls, float w_cls, float w_id,
                             float* out8, int pairs, int n_a, int n_b, int n_c, int n_e, const float* wtab, int ssim_on, int entire,
                             splice_stream_t stream);
+/* splice_total_loss_pairs as a handle with a loss trace launches it (splice_step_set_loss_trace): dev_t (device) holds step index + 1,
+ * and words 0-5 of row step index of trace ([capacity][pairs][8], device) receive pair p's out8 values, a row at or beyond capacity
+ * left out.  stop (may be NULL; device, [pairs] records) runs the instance of a handle with the stop rule, whose rule is window (>= 1),
+ * rel, patience and min_steps as splice_plateau_update takes them: a pair whose stop_step lies before the step index is not traced,
+ * and with ssim_on && !entire the records take the step as splice_plateau_update would. */
+int splice_total_loss_pairs_trace(float* lbase, size_t lstride, int lp, float w_ssim, float w_essim, float w_ecls, float w_cls, float w_id,
+                                  float* out8, int pairs, int n_a, int n_b, int n_c, int n_e, const float* wtab, int ssim_on, int entire,
+                                  splice_stop_state* stop, int window, float rel, int patience, int min_steps, const int* dev_t,
+                                  float* trace, int capacity, splice_stream_t stream);
 
 /* ------------------------------------------------------------------ test hooks: the [CLS] tail of the top ViT block as the engine launches it
  * in top_cls_only mode (vit_cls.hip).  The five entry points below check their arguments and call the engine's own launchers on the caller's

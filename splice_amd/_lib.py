@@ -201,6 +201,9 @@ _SIGNATURES = {
     "splice_plateau_update_best": ([_vp, _vp, _vp, _vp, _i, _i, _f, _i, _i, _i, _i, _vp], _i),
     "splice_optim_step_pairs_best": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_longlong, C.c_longlong, _vp, _f, _f, _f, _vp, _vp, _i, _f, _i, _vp, _vp, _vp, _vp, _vp], _i),
     "splice_step_set_keep_best": ([_vp, _vp, _vp, _vp, _vp], _i),
+    # per-step loss trace
+    "splice_step_set_loss_trace": ([_vp, _vp, _i], _i),
+    "splice_total_loss_pairs_trace": ([_vp, _sz, _i, _f, _f, _f, _f, _f, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _i, _f, _i, _i, _vp, _vp, _i, _vp], _i),
     "splice_prof_begin": ([_i], _i),
     "splice_prof_end": ([C.POINTER(_f), C.POINTER(_i)], _i),
     "splice_prof_end_ex": ([C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)], _i),

@@ -34,6 +34,10 @@ per pair; a step whose norm is not finite does not update the pair); ``result.js
 step that closed the best window the rule has seen: the run also writes ``out/output_best.png`` (``output_best_ema.png`` with an average),
 and ``result.json`` carries ``best_step``, ``best_window_mean`` and ``window_means``.
 
+``--set loss_trace=true`` (shared by the variants of a sweep) keeps one row per step and pair on the device -- the six loss values, and the
+gradient norm and clip coefficient with ``grad_clip_norm`` -- written by the step's own kernels: no copy per step.  The run ends by writing
+``out/losses.csv`` (``out/sweep/<k>/losses.csv`` per variant), and ``result.json`` names the file under ``loss_trace``.
+
     python -m splice_amd.batch --root pairs/ --gpus 8 [--pairs-per-gpu P] [--n_epochs 2000] [--set key=value ...]
 
 ``--pairs-per-gpu P`` works with ``--set global_A_crops_n_crops=n`` (and ``global_B_crops_n_crops``): each pair's n crops are one
@@ -85,11 +89,12 @@ def work_items(sizes, pairs_per_gpu=1):
 def _slot_fields(eng, slot=None):
     """What ``result.json`` says about the optional rules of one slot (None: the one pair of the engine).  The stop rule: ``steps_run``
     (steps that updated the slot) and ``stopped_at`` (the step index it stopped at, or None).  The weight average: ``ema_decay`` (0: none
-    was kept, there is no ``output_ema.png``).  Gradient clipping and the best window: ``train.clip_fields`` / ``train.best_fields``."""
-    from .train import best_fields, clip_fields
+    was kept, there is no ``output_ema.png``).  Gradient clipping, the best window and the loss trace: ``train.clip_fields`` /
+    ``train.best_fields`` / ``train.trace_fields``."""
+    from .train import best_fields, clip_fields, trace_fields
     at = eng.stopped_at if slot is None else eng.stopped_at[slot]
     return {"steps_run": eng.step_idx + 1 if at is None else at + 1, "stopped_at": at, "ema_decay": eng.ema_rule[0],
-            **clip_fields(eng, slot), **best_fields(eng, slot)}
+            **clip_fields(eng, slot), **best_fields(eng, slot), **trace_fields(eng)}
 
 
 def _timed(train, *args, **kw):
@@ -117,12 +122,12 @@ def train_group_runner(pair_dirs, overrides):
 
 def train_sweep_runner(pair_dir, overrides, variants):
     """Sweep runner: all ``variants`` of one pair in one engine (``train_sweep``)."""
-    from .train import train_sweep
+    from .train import trace_fields, train_sweep
     eng, dt = _timed(train_sweep, pair_dir, variants, cfg_overrides=overrides)
     slots = [_slot_fields(eng, k) for k in range(len(variants))]
     ema = [s.pop("ema_decay") for s in slots][0]   # (shared by the variants: said once)
     return {"steps": eng.step_idx + 1, "seconds": dt, "ema_decay": ema,
-            "variants": [{"index": k, "overrides": v, "loss": d["loss"], "losses": d, **slots[k]} for k, (v, d) in enumerate(zip(variants, eng.losses()))]}
+            "variants": [{"index": k, "overrides": v, "loss": d["loss"], "losses": d, **slots[k], **trace_fields(eng, os.path.join("sweep", str(k)))} for k, (v, d) in enumerate(zip(variants, eng.losses()))]}
 
 
 def sweep_variants(specs):

@@ -40,6 +40,7 @@ struct OptimArgs {
 };
 int optim_launch(const OptimArgs& a, hipStream_t s);
 // The per-pair gradient norm and clip coefficient (include/splice_hip.h has the rule): two launches, partials[pairs][ceil(n / 4096)] then
-// state[pairs].  stop (optional) with step_dev: a frozen pair is left out of both.
+// state[pairs].  stop (optional) with step_dev: a frozen pair is left out of both.  trace (optional, with step_dev; the loss trace,
+// [capacity][pairs][8]): the second launch also stores norm and coef into words 6 and 7 of row *step_dev - 1 of every pair it writes.
 int grad_norm_launch(const float* g, const float* g2, int pairs, size_t stride, size_t n, float max_norm, float* partials, splice_clip_state* state,
-                     const splice_stop_state* stop, const int* step_dev, hipStream_t s);
+                     const splice_stop_state* stop, const int* step_dev, hipStream_t s, float* trace = nullptr, int capacity = 0);

@@ -325,10 +325,13 @@ __global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict
     }
 }
 // Stage 2: workgroup = pair.  The partials in fp64 (their order is fixed, the rounding of 254 of them no longer shows in the fp32 result),
-// then the record.  Thread 0 alone writes it.
+// then the record.  Thread 0 alone writes it.  TRACE (the loss trace): it also stores the norm and the coefficient into
+// words 6 and 7 of row *step_dev - 1 of the pair's trace ([capacity][pairs][8]; words 0-5 belong to total_loss_kernel), a row beyond
+// capacity left out.  The instance without TRACE does not read the two trailing arguments.
+template <bool TRACE>
 __global__ __launch_bounds__(256) void grad_clip_coef_kernel(const float* __restrict__ partials, unsigned chunks, float max_norm,
                                                              splice_clip_state* __restrict__ state, const splice_stop_state* __restrict__ stop,
-                                                             const int* __restrict__ step_dev) {
+                                                             const int* __restrict__ step_dev, float* __restrict__ trace, int capacity) {
 #pragma clang fp contract(off)
     __shared__ double sd[256];
     const unsigned pair = blockIdx.x, t = threadIdx.x;
@@ -356,12 +359,20 @@ __global__ __launch_bounds__(256) void grad_clip_coef_kernel(const float* __rest
                 r.skipped += 1;
             }
             state[pair] = r;
+            if (TRACE) {
+                const int row = *step_dev - 1;
+                if (row >= 0 && row < capacity) {
+                    float* tr = trace + ((size_t)row * gridDim.x + pair) * 8;
+                    tr[6] = r.norm;
+                    tr[7] = r.coef;
+                }
+            }
         }
     }
 }
 
 int grad_norm_launch(const float* g, const float* g2, int pairs, size_t stride, size_t n, float max_norm, float* partials, splice_clip_state* state,
-                     const splice_stop_state* stop, const int* step_dev, hipStream_t s) {
+                     const splice_stop_state* stop, const int* step_dev, hipStream_t s, float* trace, int capacity) {
     if (!(max_norm > 0.f) || !(max_norm <= 3.402823466e+38f)) {
         splice_set_error("gradient clipping: max_norm must be a finite number > 0, got %g", (double)max_norm);
         return SPLICE_ERR_ARG;
@@ -380,9 +391,16 @@ int grad_norm_launch(const float* g, const float* g2, int pairs, size_t stride, 
         splice_set_error("gradient clipping (max_norm %g): at most 65535 pairs of < 2^43 floats", (double)max_norm);
         return SPLICE_ERR_ARG;
     }
+    if (trace && (!step_dev || capacity < 1)) {
+        splice_set_error("gradient clipping (max_norm %g): a loss trace needs the device step count and a capacity >= 1", (double)max_norm);
+        return SPLICE_ERR_ARG;
+    }
     if (pairs == 1) stride = 0;
     SPLICE_LAUNCH(grad_sumsq_kernel, dim3((unsigned)chunks, (unsigned)pairs), dim3(256), 0, s, g, g2, stride, n, partials, stop, step_dev);
-    SPLICE_LAUNCH(grad_clip_coef_kernel, dim3((unsigned)pairs), dim3(256), 0, s, (const float*)partials, (unsigned)chunks, max_norm, state, stop, step_dev);
+    if (trace)   // (the trace rides in the launch)
+        SPLICE_LAUNCH(grad_clip_coef_kernel<true>, dim3((unsigned)pairs), dim3(256), 0, s, (const float*)partials, (unsigned)chunks, max_norm, state, stop, step_dev, trace, capacity);
+    else
+        SPLICE_LAUNCH(grad_clip_coef_kernel<false>, dim3((unsigned)pairs), dim3(256), 0, s, (const float*)partials, (unsigned)chunks, max_norm, state, stop, step_dev, (float*)nullptr, 0);
     return SPLICE_OK;
 }
 

@@ -131,6 +131,10 @@ struct SpliceStep {
     float* best_means = nullptr;
     float* best_p = nullptr;
     float* best_ema = nullptr;
+    // the per-step loss trace (splice_step_set_loss_trace): the caller's [trace_cap][pairs][8] rows; null: off -- the step launches what it
+    // always did
+    float* trace = nullptr;
+    int trace_cap = 0;
 };
 
 static size_t arena_floats(const SpliceStep* st) { return st->astride ? st->pairs * st->astride : (size_t)st->nparams; }   // of all pairs' arenas
@@ -186,11 +190,15 @@ static int view_init(SpliceStep* st, VitView& v, void* ctx, int want_B) {
 // -- ssim_on && !entire, both baked per graph variant -- with the step index read from dev_t (step_idx + 1: a replayed graph sees its own
 // step).  kb / means (keep-best; null: off): the rule's record and window means of every pair.  The instance without MONITOR does not read
 // the five trailing arguments: its code is what it was.
-template <bool MONITOR>
+// TRACE (the loss trace): thread 0 also stores the six values of the out8 row, with their bits, into words 0-5 of row
+// *dev_t - 1 of the pair's trace ([capacity][pairs][8]; words 6-7 belong to grad_clip_coef_kernel) -- unless the row lies beyond
+// capacity or, with MONITOR, the slot stopped at an earlier step (read before this step's rule runs: the stop step's own row is
+// written).  The instances without TRACE do not read the two trailing arguments.
+template <bool MONITOR, bool TRACE>
 __global__ __launch_bounds__(320) void total_loss_kernel(float* lbase, size_t lstride, int lp, float w_ssim, float w_essim, float w_ecls, float w_cls,
                                                          float w_id, float* out8, int n_a, int n_b, int n_c, int n_e, const float* wtab, int ssim_on,
                                                          int entire, splice_stop_state* stop, const int* dev_t, StopRule rule, splice_best_state* kb,
-                                                         float* means) {
+                                                         float* means, float* trace, int capacity) {
     __shared__ float raw[8];
     float* l = lbase + (size_t)blockIdx.x * lstride;
     const int k = 1 + (threadIdx.x >> 6), lane = threadIdx.x & 63;   // wave k-1 owns term k (5 waves)
@@ -222,6 +230,14 @@ __global__ __launch_bounds__(320) void total_loss_kernel(float* lbase, size_t ls
             o[0] = l[L_TOTAL];
             for (int t = 1; t <= 5; ++t) o[t] = raw[t];
             o[6] = 0.f; o[7] = 0.f;
+        }
+        if (TRACE) {
+            const int row = *dev_t - 1;
+            if (row >= 0 && row < capacity && !(MONITOR && stop_frozen(stop + blockIdx.x, row))) {
+                float* tr = trace + ((size_t)row * gridDim.x + blockIdx.x) * 8;
+                tr[0] = l[L_TOTAL];
+                for (int t = 1; t <= 5; ++t) tr[t] = raw[t];
+            }
         }
         if (MONITOR && ssim_on && !entire)
             plateau_update(stop + blockIdx.x, l[L_TOTAL], rule, *dev_t - 1, kb ? kb + blockIdx.x : nullptr,
@@ -499,7 +515,7 @@ int splice_step_set_crops(void* h, int a_h, int a_w, int b_h, int b_w) {
 // mode), named for an error text; null: none.
 static const char* whole_step_rule(const SpliceStep* st) {
     return st->stop_rule.window > 0 ? "with a stop rule" : st->ema ? "with a weight average" : st->clip ? "with gradient clipping"
-           : st->best ? "that keeps the best weights" : nullptr;
+           : st->best ? "that keeps the best weights" : st->trace ? "with a loss trace" : nullptr;
 }
 // The shared opening of the rule setters below: before the first step only (`what` of the rule, for the error text), and not on a
 // gradient-only or phase-mode handle.  Callers return its code plainly, not through RC(): the message stays the last error.
@@ -676,6 +692,21 @@ int splice_step_set_keep_best(void* h, float* best_params, float* best_ema, spli
     st->best = state; st->best_means = means; st->best_p = best_params; st->best_ema = best_ema;
     return SPLICE_OK;
 }
+// The per-step loss trace of every pair of the handle (include/splice_hip.h has the row): the step's loss kernel writes words 0-5 of row
+// step_idx, with gradient clipping its norm launch words 6-7.  Before the first step only: the rows belong to a run from step 0.  Not on a
+// gradient-only or phase-mode handle: such a handle's step is one of several that share a step index.
+int splice_step_set_loss_trace(void* h, float* trace, int capacity) {
+    SpliceStep* st = (SpliceStep*)h;
+    if (!st) return SPLICE_ERR_ARG;
+    if (!trace || capacity < 1) {
+        splice_set_error("splice_step_set_loss_trace: needs the trace rows and a capacity >= 1, got %d", capacity);
+        return SPLICE_ERR_ARG;
+    }
+    if (int rc = rule_setter_ok(st, "splice_step_set_loss_trace", "the trace is set")) return rc;
+    st->graphs.retire();
+    st->trace = trace; st->trace_cap = capacity;
+    return SPLICE_OK;
+}
 int splice_step_stop_state(void* h, splice_stop_state* out, splice_stream_t stream) {
     SpliceStep* st = (SpliceStep*)h;
     if (!st || !out) return SPLICE_ERR_ARG;
@@ -709,9 +740,30 @@ int splice_total_loss_pairs(float* lbase, size_t lstride, int lp, float w_ssim, 
         splice_set_error("splice_total_loss_pairs: invalid argument");
         return SPLICE_ERR_ARG;
     }
-    SPLICE_LAUNCH(total_loss_kernel<false>, dim3(pairs), dim3(320), 0, (hipStream_t)stream, lbase, lstride, lp, w_ssim, w_essim, w_ecls, w_cls, w_id, out8,
+    const auto kernel = total_loss_kernel<false, false>;
+    SPLICE_LAUNCH(kernel, dim3(pairs), dim3(320), 0, (hipStream_t)stream, lbase, lstride, lp, w_ssim, w_essim, w_ecls, w_cls, w_id, out8,
                   n_a, n_b, n_c, n_e, wtab, ssim_on, entire, (splice_stop_state*)nullptr, (const int*)nullptr, StopRule{}, (splice_best_state*)nullptr,
-                  (float*)nullptr);
+                  (float*)nullptr, (float*)nullptr, 0);
+    return SPLICE_OK;
+}
+// test hook: the same launch with the loss trace (the TRACE instances): dev_t holds step index + 1 on the device; stop (optional, with its
+// rule: the MONITOR instance, as a handle with the stop rule launches it) the [pairs] records
+int splice_total_loss_pairs_trace(float* lbase, size_t lstride, int lp, float w_ssim, float w_essim, float w_ecls, float w_cls, float w_id, float* out8,
+                                  int pairs, int n_a, int n_b, int n_c, int n_e, const float* wtab, int ssim_on, int entire, splice_stop_state* stop,
+                                  int window, float rel, int patience, int min_steps, const int* dev_t, float* trace, int capacity,
+                                  splice_stream_t stream) {
+    if (!lbase || pairs < 1 || lp < 1 || lstride < 8 + (size_t)L_TERMS * lp || n_a < 1 || n_b < 1 || n_c < 1 || n_e < 1 || !dev_t || !trace || capacity < 1) {
+        splice_set_error("splice_total_loss_pairs_trace: invalid argument");
+        return SPLICE_ERR_ARG;
+    }
+    if (stop && (window < 1 || !stop_rule_ok(window, rel, patience, min_steps, "splice_total_loss_pairs_trace"))) {
+        if (window < 1) splice_set_error("splice_total_loss_pairs_trace: stop records go with their rule (window >= 1)");
+        return SPLICE_ERR_ARG;
+    }
+    const auto kernel = stop ? total_loss_kernel<true, true> : total_loss_kernel<false, true>;
+    SPLICE_LAUNCH(kernel, dim3(pairs), dim3(320), 0, (hipStream_t)stream, lbase, lstride, lp, w_ssim, w_essim, w_ecls, w_cls, w_id, out8, n_a, n_b, n_c, n_e, wtab,
+                  ssim_on, entire, stop, dev_t, stop ? StopRule{window, rel, patience, min_steps} : StopRule{}, (splice_best_state*)nullptr, (float*)nullptr, trace,
+                  capacity);
     return SPLICE_OK;
 }
 
@@ -858,10 +910,13 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
             // term's crops per pair (several pairs with n_crops)
             const bool grouped = st->crops_mode && pairs > 1;
             const int n1 = st->crops_mode ? P : 1;
-            const auto kernel = stop_on ? total_loss_kernel<true> : total_loss_kernel<false>;   // (the rule rides in the launch: no node more)
+            // (the rule and the trace ride in the launch: no node more)
+            const auto kernel = st->trace ? (stop_on ? total_loss_kernel<true, true> : total_loss_kernel<false, true>)
+                                          : (stop_on ? total_loss_kernel<true, false> : total_loss_kernel<false, false>);
             SPLICE_LAUNCH(kernel, dim3(pairs), dim3(320), 0, q, st->losses, st->lstride, (int)st->lp, t[L_GLOBAL_SSIM].lambda, t[L_ENTIRE_SSIM].lambda,
                           t[L_ENTIRE_CLS].lambda, t[L_GLOBAL_CLS].lambda, t[L_GLOBAL_ID].lambda, st->losses_out, grouped ? st->na : n1, grouped ? st->nb : n1, grouped ? nc : n1,
-                          grouped ? 1 : n1, st->pw ? st->pw + (size_t)PW_LAMBDAS * P : nullptr, (int)ssim_on, (int)entire, st->stop, st->dev_t, st->stop_rule, st->best, st->best_means);
+                          grouped ? 1 : n1, st->pw ? st->pw + (size_t)PW_LAMBDAS * P : nullptr, (int)ssim_on, (int)entire, st->stop, st->dev_t, st->stop_rule, st->best, st->best_means,
+                          st->trace, st->trace_cap);
         }
         if (!st->running || !gen_fwd) return SPLICE_OK;
         void* plans[3] = {st->plan_a, st->plan_b, nullptr};
@@ -911,7 +966,7 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
         if (st->ema) { a.ema = st->ema; a.ema_decay = st->ema_decay; a.ema_start = st->ema_start; }   // (another kernel: the graph pool keys on it)
         if (st->clip) {   // two launches more: the norm of the gradient the update is about to read, frozen slots left out
             RC(grad_norm_launch(grads, adam_g2, st->pairs, st->astride, (size_t)st->nparams, st->clip_norm, st->clip_partials, st->clip,
-                                stop_on ? st->stop : nullptr, st->dev_t, s));
+                                stop_on ? st->stop : nullptr, st->dev_t, s, st->trace, st->trace_cap));
             a.clip = st->clip; a.clip_stride = st->astride;
         }
         // keep-best: the record this launch reads was written by THIS step's loss kernel -- on the side stream's tail, in front of the

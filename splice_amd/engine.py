@@ -32,7 +32,9 @@ DEFAULT_CFG = dict(  # conf/default/config.yaml of the reference
     # ... and clipping of every pair's gradient by its global norm inside the fused step, off by default
     grad_clip_norm=0.0,
     # ... and the weights of the window the stop rule judged best, kept on the device beside the live ones, off by default
-    stop_keep_best=False)
+    stop_keep_best=False,
+    # ... and one row per step and slot of the loss values (and the gradient norm under clipping), kept on the device, off by default
+    loss_trace=False)
 
 
 # Per-slot keys of a sweep (MultiPairEngine(pair_cfgs=...), train.train_sweep): the five loss weights in the order of
@@ -139,6 +141,25 @@ def np_plateau(losses, counted, window, rel, patience, min_steps, margins=None):
             s["stop_step"] = t
     s["means"] = np.array(means, dtype=f)
     return s
+
+
+def trace_rule(c):
+    """``loss_trace`` of config ``c``, checked on the host: a bool.  Raises ValueError naming the key."""
+    v = c.get("loss_trace", DEFAULT_CFG["loss_trace"])
+    if not isinstance(v, (bool, np.bool_)):
+        raise ValueError(f"'loss_trace' must be true or false, got {v!r}")
+    return bool(v)
+
+
+def active_terms(c, step_idx, entire_branch):
+    """Which of LOSS_KEYS the step ``step_idx`` of a slot with config ``c`` computes (host arithmetic only): the global structure
+    and identity terms from ``cls_warmup`` on, the entire-image terms on every ``entire_A_every``-th step of an engine that has the
+    branch (``entire_branch``), each only with its lambda > 0."""
+    on = step_idx >= c["cls_warmup"]
+    ent = bool(entire_branch) and step_idx % c["entire_A_every"] == 0
+    return {"loss": True, "loss_global_ssim": on and c["lambda_global_ssim"] > 0, "loss_entire_ssim": ent and c["lambda_entire_ssim"] > 0,
+            "loss_entire_cls": ent and c["lambda_entire_cls"] > 0, "loss_global_cls": c["lambda_global_cls"] > 0,
+            "loss_global_id_B": on and c["lambda_global_identity"] > 0}
 
 
 CLIP_CHUNK = 4096   # SPLICE_CLIP_CHUNK
@@ -302,6 +323,8 @@ class MultiPairEngine:
         self.clip_dev = None
         self.keep_best = best_rule(self.cfg)
         self.best = self.best_ema = self.best_dev = self.means_dev = None
+        self.trace_on = trace_rule(self.cfg)
+        self.trace_dev = None
         P_in = len(gen_states)
         self.cfgs = [self.cfg] * P_in
         self._pair_lambdas = self._pair_lr = False
@@ -438,6 +461,11 @@ class MultiPairEngine:
             self.means_dev = torch.zeros(P, STOP_HISTORY, device=self.device)
             _lib.check(_lib.lib().splice_step_set_keep_best(self.handle, _lib.ptr(self.best), _lib.ptr(self.best_ema), _lib.ptr(self.best_dev),
                                                             _lib.ptr(self.means_dev)), "step_set_keep_best")
+        # the loss trace (shared by the slots): one row of 8 floats per step and slot, NaN until the step's own launches write it; before
+        # the first step
+        if self.trace_on:
+            self.trace_dev = torch.full((max(int(c["n_epochs"]), 1), P, 8), float("nan"), device=self.device)
+            _lib.check(_lib.lib().splice_step_set_loss_trace(self.handle, _lib.ptr(self.trace_dev), self.trace_dev.shape[0]), "step_set_loss_trace")
         self._stopped = [None] * P   # the host's copy of every slot's stop step, refreshed by stop_state()
         self._stop_dirty = False     # a window has closed since the last stop_state(): the copy may be behind
         if self._pair_lambdas:
@@ -581,17 +609,40 @@ class MultiPairEngine:
         """Host dict(s) of the last step's losses with the reference's keys (inactive terms omitted): one dict for ``pair``,
         a list over the pairs for ``pair=None``."""
         rows = self.losses_dev.cpu().tolist()
-        s = self.step_idx
-        on = s >= self.cfg["cls_warmup"]
-        ent = self.plan_e is not None and s % self.cfg["entire_A_every"] == 0
-
-        def active(c):   # (a slot's terms follow that slot's own lambdas)
-            return {"loss": True, "loss_global_ssim": on and c["lambda_global_ssim"] > 0, "loss_entire_ssim": ent and c["lambda_entire_ssim"] > 0,
-                    "loss_entire_cls": ent and c["lambda_entire_cls"] > 0, "loss_global_cls": c["lambda_global_cls"] > 0,
-                    "loss_global_id_B": on and c["lambda_global_identity"] > 0}
-        acts = [active(c) for c in (self.cfgs if len(self.cfgs) == len(rows) else [self.cfg] * len(rows))]
+        acts = self.active_terms(self.step_idx)
         dicts = [{k: vals[i] for i, k in enumerate(LOSS_KEYS) if act[k]} for vals, act in zip(rows, acts)]
         return dicts if pair is None else dicts[pair]
+
+    def active_terms(self, step_idx):
+        """Per slot: which of LOSS_KEYS step ``step_idx`` computes (``engine.active_terms``; a slot's terms follow that slot's own
+        lambdas).  Host arithmetic only."""
+        return [active_terms(c, step_idx, self.plan_e is not None) for c in (self.cfgs if len(self.cfgs) == self.P else [self.cfg] * self.P)]
+
+    # ---- the loss trace (DESIGN.md section 9e)
+    def loss_trace(self, pair=None):
+        """The rows the steps so far wrote (``loss_trace``): per slot a float32 array ``[rows, 8]`` -- the six LOSS_KEYS values of every
+        step (inactive terms are 0, as in ``losses_dev``), then the gradient norm and the clip coefficient (NaN without
+        ``grad_clip_norm``) -- with ``rows = min(step_idx + 1, n_epochs)``, cut behind a stopped slot's stop step.  One device-to-host
+        copy (waits for the current stream): call it at the end of a run.  One array for ``pair``, a list over the slots for
+        ``pair=None``."""
+        if self.trace_dev is None:
+            raise RuntimeError("loss_trace: no trace is kept (loss_trace is off)")
+        rows = min(self.step_idx + 1, self.trace_dev.shape[0])
+        host = self.trace_dev[:rows].cpu().numpy()
+        stops = self._stops() if self.stop_rule[0] > 0 else [None] * self.P
+        out = [host[:rows if k is None else min(rows, k + 1), p].copy() for p, k in enumerate(stops)]
+        return out if pair is None else out[pair]
+
+    def loss_trace_columns(self):
+        """What ``losses.csv`` holds (``util.write_loss_trace``), per slot ``(rows, lrs, active)``: the slot's trace, the learning rate
+        of every row from the host's schedule (the slot's own in a sweep) and the terms every row's step computed."""
+        traces = MultiPairEngine.loss_trace(self)
+        acts = [self.active_terms(s) for s in range(max(len(r) for r in traces))]
+        out = []
+        for p, rows in enumerate(traces):
+            sch = LrSchedule(self.cfgs[p] if self._pair_lr else self.cfg)   # (a fresh recurrence: the engine's own stays where it is)
+            out.append((rows, [sch.lr(s) for s in range(len(rows))], [acts[s][p] for s in range(len(rows))]))
+        return out
 
     def pair_params(self, pair=0):
         """View of one pair's parameter arena (``numel`` floats)."""
@@ -672,6 +723,9 @@ class SpliceEngine(MultiPairEngine):
     def clip_state(self, pair=None):
         return super().clip_state(0)
 
+    def loss_trace(self, pair=None):
+        return super().loss_trace(0)
+
     def best_state(self, pair=None):
         return super().best_state(0)
 
@@ -699,6 +753,9 @@ class MultiScaleEngine:
         if best_rule(self.cfg):
             raise NotImplementedError("stop_keep_best: the snapshot rides in the fused step's own update under its stop rule; MultiScaleEngine updates outside the step")
         self.best = None
+        if trace_rule(self.cfg):
+            raise NotImplementedError("loss_trace: the rows are written by a whole fused step under its own step count; MultiScaleEngine runs each scale as a phase-mode handle")
+        self.trace_dev = None
         if stop_rule(self.cfg)[0] > 0:
             raise NotImplementedError("stop_window > 0: the plateau stop rule lives in the fused step's own update; MultiScaleEngine updates outside the step")
         self.ema_rule = ema_rule(self.cfg)

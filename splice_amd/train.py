@@ -4,7 +4,8 @@ Same contract as the reference (``train.py:15-80``): reads ``conf/default/config
 working directory (falling back to the packaged copy), seeds python / numpy / torch, opens the first
 image of ``<dataroot>/A`` and ``<dataroot>/B``, runs ``n_epochs`` optimisation steps and every
 ``log_images_freq`` steps writes ``<dataroot>/out/output.png`` (asynchronously: ``util.AsyncResultWriter``) and calls
-``callback(output[0])`` with the ``[3,H,W]`` float image.  With ``ema_decay > 0`` (an extension) the run ends by writing one more image,
+``callback(output[0])`` with the ``[3,H,W]`` float image.  With ``loss_trace`` (an extension) the run ends by writing
+``<dataroot>/out/losses.csv``, one line per step, from rows its own kernels kept on the device.  With ``ema_decay > 0`` (an extension) the run ends by writing one more image,
 ``<dataroot>/out/output_ema.png``, from the averaged weights; with ``stop_keep_best`` (an extension of the stop rule) ``output_best.png``,
 from the weights of the step that closed the best window.  The step itself is the fused HIP engine (``SpliceEngine``), one host
 call per step, losses read back only when a progress line is printed.
@@ -25,7 +26,7 @@ import yaml
 
 from . import augment
 from .engine import SpliceEngine
-from .util import AsyncResultWriter
+from .util import AsyncResultWriter, write_loss_trace
 
 device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
 _PKG_CFG = os.path.join(os.path.dirname(os.path.abspath(__file__)), "conf", "default", "config.yaml")
@@ -210,6 +211,7 @@ def _optimise(cfg, engine, next_inputs, As, writers, callback, progress, single=
                 break
         _ema_images(engine, writers, As)
         _best_images(engine, writers, As)
+        _loss_traces(cfg, engine, writers)
     finally:
         for w in writers:   # PNG encode + disk write happen on a worker thread
             w.close()
@@ -308,6 +310,23 @@ def _best_images(engine, writers, As):
             writers[p].submit(engine.generate(A, pair=p, best=True, ema=True)[0], force=True, name="output_best_ema.png")
 
 
+def _loss_traces(cfg, engine, writers):
+    """The end of a run that keeps a loss trace (``loss_trace``), however it ended: ``losses.csv`` beside every slot's ``output.png``,
+    one line per step the slot ran (``util.write_loss_trace``).  The one device-to-host copy of the curve."""
+    if not cfg.get('loss_trace', False) or engine.step_idx < 0:
+        return
+    for w, (rows, lrs, active) in zip(writers, engine.loss_trace_columns()):
+        write_loss_trace(os.path.join(w.dir, "losses.csv"), rows, lrs, active, engine.grad_clip > 0)
+
+
+def trace_fields(engine, out_dir=""):
+    """What ``result.json`` / ``variant.json`` say about the loss trace of a run: ``loss_trace``, the file's name below ``out/``
+    (``out_dir``: the variant's directory there).  Without the option: nothing."""
+    if getattr(engine, "trace_dev", None) is None or engine.step_idx < 0:
+        return {}
+    return {"loss_trace": os.path.join(out_dir, "losses.csv")}
+
+
 def best_fields(engine, slot=None):
     """What ``result.json`` says about the stop rule's windows (``splice_amd.batch``) of a run with ``stop_keep_best``: ``best_step`` (the
     step whose weights ``output_best.png`` shows; None: no window closed, they are the initial weights), ``best_window_mean`` and
@@ -389,7 +408,7 @@ def train_sweep(dataroot, variants, cfg_overrides=None, vit_state=None, callback
     seed.  The random state right after variant 0's ``define_G`` drives the loop, so when the variants share the seed every
     slot is, bit for bit, the ``train_model`` run of its merged config, random crops included (``seed: -1`` draws one seed for
     every variant that has it).  Writes ``<dataroot>/out/sweep/<k>/output.png`` and ``variant.json`` (overrides, seed, final
-    losses); ``callback(k, image)``.  Returns the engine."""
+    losses; with ``loss_trace`` the name of the variant's ``losses.csv`` beside it); ``callback(k, image)``.  Returns the engine."""
     from .engine import MultiPairEngine
     cfg = _load_cfg(dataroot, cfg_overrides)
     variants = [dict(v) for v in variants]
@@ -436,7 +455,7 @@ def train_sweep(dataroot, variants, cfg_overrides=None, vit_state=None, callback
     losses = engine.losses() if engine.step_idx >= 0 else [{} for _ in range(K)]
     for k in range(K):
         with open(os.path.join(out_dirs[k], 'variant.json'), 'w') as f:
-            json.dump({"index": k, "overrides": variants[k], "seed": seeds[k], "losses": losses[k], "stopped_at": engine.stopped_at[k]}, f)
+            json.dump({"index": k, "overrides": variants[k], "seed": seeds[k], "losses": losses[k], "stopped_at": engine.stopped_at[k], **trace_fields(engine)}, f)
     return engine
 
 

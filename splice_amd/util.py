@@ -115,6 +115,26 @@ def fused_optimizer(cfg):
     raise NotImplementedError(f"optimizer [{name}] is not implemented")
 
 
+def write_loss_trace(path, rows, lrs, active, clip):
+    """``losses.csv`` of one slot's loss trace (``engine.loss_trace``): ``rows`` float32 ``[n, 8]``, ``lrs`` the n learning rates,
+    ``active`` per row the dict of ``engine.active_terms`` (an inactive term is an empty field), ``clip``: the run clipped its gradient
+    (the columns ``grad_norm,clip_coef`` exist).  Floats are written with ``%.9g``: every float32, denormals included, parses back to
+    its bits.  The file appears whole (written beside, then renamed)."""
+    from .engine import LOSS_KEYS
+    rows = np.asarray(rows, dtype=np.float32).reshape(-1, 8)
+    lines = ["step,lr," + ",".join(LOSS_KEYS) + (",grad_norm,clip_coef" if clip else "")]
+    for s, (row, lr, act) in enumerate(zip(rows, lrs, active)):
+        fields = [str(s), "%.9g" % lr] + ["%.9g" % row[i] if act[k] else "" for i, k in enumerate(LOSS_KEYS)]
+        if clip:
+            fields += ["%.9g" % row[6], "%.9g" % row[7]]
+        lines.append(",".join(fields))
+    path = Path(path)
+    path.parent.mkdir(exist_ok=True, parents=True)
+    tmp = path.with_name(path.name + ".tmp")
+    tmp.write_text("\n".join(lines) + "\n")
+    tmp.replace(path)
+
+
 def _to_uint8_hwc(chw):
     """[3,H,W] float tensor in (roughly) [0,1] -> HxWx3 array scaled to 0..255 (still float)."""
     return chw.detach().clamp(0.0, 1.0).cpu().float().numpy().transpose(1, 2, 0) * 255.0
