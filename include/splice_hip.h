@@ -590,6 +590,45 @@ int splice_step_set_keep_best(void* step, float* best_params, float* best_ema, s
  * (splice_step_set_phases), which it in turn bars. */
 int splice_step_set_loss_trace(void* step, float* trace, int capacity);
 
+/* ------------------------------------------------------------------ the plateau lr rule (an extension of the stop rule):
+ * cut a slot's learning rate where the stop rule's windows stop getting better.  It uses that rule's windows, its `rel` and its verdict
+ * on every window (the first window counts as better), and leaves its state as it is without the lr rule: a cut does not reset the stop
+ * rule's `bad`, and min_steps does not gate cuts.  Per slot a record and a row cut_steps[SPLICE_STOP_HISTORY] of step indices.  Every
+ * step, counted or not, thread 0 of the slot's loss-kernel workgroup does, in this order (fp32, one rounding per operation):
+ *   lr_eff[slot] = lr_in[slot] * scale       with the scale as it stands before this step's rule: a cut made at step t first acts on
+ *                                            the update of step t + 1, as a host loop that calls its scheduler behind optimizer.step();
+ *   on a counted step that closes a window, and only if the slot is live on entry (stop_step < 0):
+ *     better:  bad = 0
+ *     else:    bad += 1; then if bad >= patience && scale > min_scale && cuts < SPLICE_STOP_HISTORY:
+ *              scale = max(fl(scale * factor), min_scale); cut_steps[cuts] = step index; cuts += 1; last_cut_step = step index; bad = 0.
+ * The record of a slot that stopped is never written again.  This is torch.optim.lr_scheduler.ReduceLROnPlateau(mode='min', factor,
+ * patience = patience - 1, threshold = rel, threshold_mode='rel', cooldown=0) fed the window means, but for the cap of
+ * SPLICE_STOP_HISTORY cuts and the floor, which is a scale (min_scale) and no learning rate. */
+typedef struct splice_lr_state {
+    float scale;        /* what the next update's learning rate is multiplied by; starts as 1 */
+    int bad;            /* consecutive closed windows that were not better since the last cut; starts as 0 */
+    int cuts;           /* cuts so far (at most SPLICE_STOP_HISTORY); starts as 0 */
+    int last_cut_step;  /* step index of the last cut; -1 until the first */
+} splice_lr_state;
+/* Switch the rule on for every pair of the handle: 0 < factor < 1, patience >= 1 (windows), 0 <= min_scale < 1.  state: device, [pairs]
+ * records, the caller's ({1, 0, 0, -1} each); cut_steps: device, [pairs][SPLICE_STOP_HISTORY] ints, the caller's (-1).  The step's loss
+ * kernel writes both and lr_eff, a [pairs] table the handle owns; the optimiser launch of the same step -- always behind the loss
+ * kernel -- reads its learning rate(s) there through the device-lr paths it has (one arena: lr_dev; several: lr_dev[element /
+ * arena_stride], so the stride must be a multiple of 4).  lr_in is what the step stages anyway: the table of splice_step_set_pair_lr,
+ * else the one value of splice_step_set_lr, else -- neither called -- the config's lr, which the handle then stages itself.  No launch,
+ * event or graph node more; while no cut has happened params / m / v / ema / best arenas / rule records / losses / trace are, bit for
+ * bit, what they are without the rule.  Before the first splice_step_run only, on a handle that has a stop rule
+ * (splice_step_set_stop_rule with window > 0); refused on a handle in gradient-only (splice_step_set_mode) or phase mode
+ * (splice_step_set_phases), which the stop rule in turn bars. */
+int splice_step_set_lr_plateau(void* step, float factor, int patience, float min_scale, splice_lr_state* state, int* cut_steps);
+/* The stop rule with the lr rule, as the step's loss kernel runs them (the same device function): one step of `pairs` slots.  state,
+ * losses8, window .. min_steps, step_idx, counted: as splice_plateau_update, and the state records are, bit for bit, what that call
+ * leaves.  lr_state / cut_steps: device, as splice_step_set_lr_plateau takes them.  lr_in: device, one float (per_pair == 0) or [pairs]
+ * floats; lr_eff: device, [pairs], written at every call, counted or not. */
+int splice_plateau_update_lr(splice_stop_state* state, splice_lr_state* lr_state, int* cut_steps, const float* losses8, const float* lr_in,
+                             int per_pair, float* lr_eff, int pairs, int window, float rel, int patience, int min_steps, float factor,
+                             int lr_patience, float min_scale, int step_idx, int counted, splice_stream_t stream);
+
 /* ------------------------------------------------------------------ test hooks: the loss stage as the fused step launches it.  The three
  * entry points below call the step's own launchers (structure term, batched MSE, total) on the caller's buffers with the step's operand
  * layout; they add no kernel and no code path (tests/test_loss_stage_gpu.py against oracle/loss_stage.py).
@@ -631,7 +670,8 @@ int splice_mse_pairs(const float* a, int lda, size_t a_ps, const float* b, int l
  * structure, 3 entire [CLS], 4 global [CLS], 5 global identity; lstride >= 8 + 6 * lp).  Pair p's slots of a term are the n consecutive
  * slots from p * n, with n = n_a (term 1), n_b (term 5), n_c (term 4), n_e (terms 2 and 3); raw_k = the slots' fixed-order sums added in
  * slot order.  Written: slot p's values [0..5] = {total, raw_1..raw_5} and, when out8 is given, out8[p][0..7] = {total, raw_1..raw_5, 0, 0};
- * total = w_ssim raw_1 + w_essim raw_2 + w_ecls raw_3 + w_cls raw_4 + w_id raw_5, added left to right.  wtab (may be NULL; device,
+ * total = w_ssim raw_1 + w_essim raw_2 + w_ecls raw_3 + w_cls raw_4 + w_id raw_5, added left to right -- as one product and four fused
+ * multiply-adds, fma(w_id, raw_5, fma(w_cls, raw_4, fma(w_ecls, raw_3, fma(w_ssim, raw_1, w_essim raw_2)))), in every instance.  wtab (may be NULL; device,
  * [pairs][5] = {cls, ssim, id, ecls, essim}) replaces the five weights per pair: ssim and id are taken as 0 unless ssim_on, ecls and
  * essim as 0 unless entire. */
 int splice_total_loss_pairs(float* lbase, size_t lstride, int lp, float w_ssim, float w_essim, float w_ecls, float w_cls, float w_id,

@@ -60,6 +60,10 @@ class BestState(C.Structure):   # splice_best_state
     _fields_ = [("best_step", C.c_int), ("best_window", C.c_int)]
 
 
+class LrState(C.Structure):   # splice_lr_state
+    _fields_ = [("scale", C.c_float), ("bad", C.c_int), ("cuts", C.c_int), ("last_cut_step", C.c_int)]
+
+
 class GenConvArgs(C.Structure):   # splice_gen_conv_args (test hooks)
     _fields_ = [("in", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("out", C.c_void_p)] + \
                [(n, C.c_size_t) for n in ("in_nstride", "in_cstride", "out_nstride", "out_cstride", "w_jstride", "w_cstride", "p_nstride")] + \
@@ -204,6 +208,9 @@ _SIGNATURES = {
     # per-step loss trace
     "splice_step_set_loss_trace": ([_vp, _vp, _i], _i),
     "splice_total_loss_pairs_trace": ([_vp, _sz, _i, _f, _f, _f, _f, _f, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _i, _f, _i, _i, _vp, _vp, _i, _vp], _i),
+    # plateau lr rule
+    "splice_step_set_lr_plateau": ([_vp, _f, _i, _f, _vp, _vp], _i),
+    "splice_plateau_update_lr": ([_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _f, _i, _i, _f, _i, _f, _i, _i, _vp], _i),
     "splice_prof_begin": ([_i], _i),
     "splice_prof_end": ([C.POINTER(_f), C.POINTER(_i)], _i),
     "splice_prof_end_ex": ([C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)], _i),

@@ -34,6 +34,11 @@ per pair; a step whose norm is not finite does not update the pair); ``result.js
 step that closed the best window the rule has seen: the run also writes ``out/output_best.png`` (``output_best_ema.png`` with an average),
 and ``result.json`` carries ``best_step``, ``best_window_mean`` and ``window_means``.
 
+``--set lr_plateau_factor=0.5`` (with the stop rule on; ``lr_plateau_patience`` / ``lr_plateau_min_scale``; shared by the variants of a sweep)
+multiplies a pair's learning rate by that factor where the stop rule's windows stop getting better, decided in the step's loss kernel;
+``result.json`` carries ``lr_plateau_factor``, ``lr_cuts``, ``lr_cut_steps`` and ``lr_scale`` per pair (per variant in a sweep), and
+``losses.csv`` holds the effective learning rate of every step.
+
 ``--set loss_trace=true`` (shared by the variants of a sweep) keeps one row per step and pair on the device -- the six loss values, and the
 gradient norm and clip coefficient with ``grad_clip_norm`` -- written by the step's own kernels: no copy per step.  The run ends by writing
 ``out/losses.csv`` (``out/sweep/<k>/losses.csv`` per variant), and ``result.json`` names the file under ``loss_trace``.
@@ -89,12 +94,12 @@ def work_items(sizes, pairs_per_gpu=1):
 def _slot_fields(eng, slot=None):
     """What ``result.json`` says about the optional rules of one slot (None: the one pair of the engine).  The stop rule: ``steps_run``
     (steps that updated the slot) and ``stopped_at`` (the step index it stopped at, or None).  The weight average: ``ema_decay`` (0: none
-    was kept, there is no ``output_ema.png``).  Gradient clipping, the best window and the loss trace: ``train.clip_fields`` /
-    ``train.best_fields`` / ``train.trace_fields``."""
-    from .train import best_fields, clip_fields, trace_fields
+    was kept, there is no ``output_ema.png``).  Gradient clipping, the best window, the loss trace and the plateau lr rule:
+    ``train.clip_fields`` / ``train.best_fields`` / ``train.trace_fields`` / ``train.lr_fields``."""
+    from .train import best_fields, clip_fields, lr_fields, trace_fields
     at = eng.stopped_at if slot is None else eng.stopped_at[slot]
     return {"steps_run": eng.step_idx + 1 if at is None else at + 1, "stopped_at": at, "ema_decay": eng.ema_rule[0],
-            **clip_fields(eng, slot), **best_fields(eng, slot), **trace_fields(eng)}
+            **clip_fields(eng, slot), **best_fields(eng, slot), **trace_fields(eng), **lr_fields(eng, slot)}
 
 
 def _timed(train, *args, **kw):

@@ -135,6 +135,13 @@ struct SpliceStep {
     // always did
     float* trace = nullptr;
     int trace_cap = 0;
+    // the plateau lr rule (splice_step_set_lr_plateau): the caller's [pairs] records and cut-step rows, and the handle's [pairs] table of
+    // effective learning rates -- written by the loss kernel, read by the optimiser launch of the same step; null: off -- the step launches
+    // what it always did
+    LrRule lr_rule = {0.f, 1, 0.f};
+    splice_lr_state* lr_state = nullptr;
+    int* lr_cuts = nullptr;
+    float* lr_eff = nullptr;
 };
 
 static size_t arena_floats(const SpliceStep* st) { return st->astride ? st->pairs * st->astride : (size_t)st->nparams; }   // of all pairs' arenas
@@ -194,11 +201,17 @@ static int view_init(SpliceStep* st, VitView& v, void* ctx, int want_B) {
 // *dev_t - 1 of the pair's trace ([capacity][pairs][8]; words 6-7 belong to grad_clip_coef_kernel) -- unless the row lies beyond
 // capacity or, with MONITOR, the slot stopped at an earlier step (read before this step's rule runs: the stop step's own row is
 // written).  The instances without TRACE do not read the two trailing arguments.
-template <bool MONITOR, bool TRACE>
+// LRP (the plateau lr rule; only with MONITOR): thread 0 runs lr_plateau_step in place of the bare stop rule -- at
+// EVERY step it writes lr_eff[pair] = lr_in[pair * lr_in_stride] * scale (lr_in: the staged per-pair table, stride 1, or the one staged
+// lr, stride 0), on counted steps the stop rule follows and the pair's lr record takes its verdict.  The instances without LRP do not
+// read the six trailing arguments.
+template <bool MONITOR, bool TRACE, bool LRP = false>
 __global__ __launch_bounds__(320) void total_loss_kernel(float* lbase, size_t lstride, int lp, float w_ssim, float w_essim, float w_ecls, float w_cls,
                                                          float w_id, float* out8, int n_a, int n_b, int n_c, int n_e, const float* wtab, int ssim_on,
                                                          int entire, splice_stop_state* stop, const int* dev_t, StopRule rule, splice_best_state* kb,
-                                                         float* means, float* trace, int capacity) {
+                                                         float* means, float* trace, int capacity, LrRule lr_rule, splice_lr_state* lr_state, int* lr_cuts,
+                                                         const float* lr_in, int lr_in_stride, float* lr_eff) {
+    static_assert(MONITOR || !LRP, "the lr rule rides on the stop rule");
     __shared__ float raw[8];
     float* l = lbase + (size_t)blockIdx.x * lstride;
     const int k = 1 + (threadIdx.x >> 6), lane = threadIdx.x & 63;   // wave k-1 owns term k (5 waves)
@@ -224,7 +237,10 @@ __global__ __launch_bounds__(320) void total_loss_kernel(float* lbase, size_t ls
             w_essim = entire ? w[4] : 0.f;
         }
         for (int t = 1; t <= 5; ++t) l[t] = raw[t];
-        l[L_TOTAL] = w_ssim * raw[L_GLOBAL_SSIM] + w_essim * raw[L_ENTIRE_SSIM] + w_ecls * raw[L_ENTIRE_CLS] + w_cls * raw[L_GLOBAL_CLS] + w_id * raw[L_GLOBAL_ID];
+        // (the sum of five products with its contraction spelled out -- one product, then four fused multiply-adds: what the compiler made
+        // of `w_ssim * raw_1 + w_essim * raw_2 + ...` in every instance before the lr rule, and would not make of it in the LRP instances)
+        l[L_TOTAL] = __builtin_fmaf(w_id, raw[L_GLOBAL_ID], __builtin_fmaf(w_cls, raw[L_GLOBAL_CLS], __builtin_fmaf(w_ecls, raw[L_ENTIRE_CLS],
+                         __builtin_fmaf(w_ssim, raw[L_GLOBAL_SSIM], w_essim * raw[L_ENTIRE_SSIM]))));
         if (out8) {   // the caller's losses buffer, written here instead of by a copy behind the step
             float* o = out8 + (size_t)blockIdx.x * 8;
             o[0] = l[L_TOTAL];
@@ -239,7 +255,11 @@ __global__ __launch_bounds__(320) void total_loss_kernel(float* lbase, size_t ls
                 for (int t = 1; t <= 5; ++t) tr[t] = raw[t];
             }
         }
-        if (MONITOR && ssim_on && !entire)
+        if (LRP)
+            lr_plateau_step(stop + blockIdx.x, lr_state + blockIdx.x, lr_cuts + (size_t)blockIdx.x * SPLICE_STOP_HISTORY, l[L_TOTAL], ssim_on && !entire, rule,
+                            lr_rule, *dev_t - 1, lr_in[(size_t)blockIdx.x * lr_in_stride], lr_eff + blockIdx.x, kb ? kb + blockIdx.x : nullptr,
+                            means ? means + (size_t)blockIdx.x * SPLICE_STOP_HISTORY : nullptr);
+        else if (MONITOR && ssim_on && !entire)
             plateau_update(stop + blockIdx.x, l[L_TOTAL], rule, *dev_t - 1, kb ? kb + blockIdx.x : nullptr,
                            means ? means + (size_t)blockIdx.x * SPLICE_STOP_HISTORY : nullptr);
     }
@@ -250,6 +270,22 @@ __global__ __launch_bounds__(64) void plateau_update_kernel(splice_stop_state* s
     const int p = blockIdx.x * 64 + threadIdx.x;
     if (p < pairs)
         plateau_update(stop + p, losses8[(size_t)p * 8], rule, step_idx, kb ? kb + p : nullptr, means ? means + (size_t)p * SPLICE_STOP_HISTORY : nullptr);
+}
+// the six trailing arguments of a total_loss_kernel launch without the plateau lr rule
+#define NO_LR_RULE LrRule{}, (splice_lr_state*)nullptr, (int*)nullptr, (const float*)nullptr, 0, (float*)nullptr
+// the two rules alone on a caller's [pairs][8] losses (splice_plateau_update_lr): one thread per slot, the loss kernel's device function
+__global__ __launch_bounds__(64) void plateau_update_lr_kernel(splice_stop_state* stop, splice_lr_state* lr_state, int* lr_cuts, const float* losses8, int pairs,
+                                                               StopRule rule, LrRule lr_rule, int step_idx, int counted, const float* lr_in, int lr_in_stride,
+                                                               float* lr_eff) {
+    const int p = blockIdx.x * 64 + threadIdx.x;
+    if (p < pairs)
+        lr_plateau_step(stop + p, lr_state + p, lr_cuts + (size_t)p * SPLICE_STOP_HISTORY, losses8[(size_t)p * 8], counted != 0, rule, lr_rule, step_idx,
+                        lr_in[(size_t)p * lr_in_stride], lr_eff + p);
+}
+static bool lr_rule_ok(float factor, int patience, float min_scale, const char* who) {
+    if (factor > 0.f && factor < 1.f && patience >= 1 && min_scale >= 0.f && min_scale < 1.f) return true;
+    splice_set_error("%s: needs 0 < factor < 1, patience >= 1 and 0 <= min_scale < 1, got %g, %d, %g", who, (double)factor, patience, (double)min_scale);
+    return false;
 }
 static bool stop_rule_ok(int window, float rel, int patience, int min_steps, const char* who) {
     if (window >= 0 && rel > 0.f && rel < 1.f && patience >= 1 && min_steps >= 0) return true;
@@ -635,6 +671,7 @@ int splice_step_set_stop_rule(void* h, int window, float rel, int patience, int 
     if (!stop_rule_ok(window, rel, patience, min_steps, "splice_step_set_stop_rule")) return SPLICE_ERR_ARG;
     if (int rc = rule_setter_ok(st, "splice_step_set_stop_rule", "the rule is set")) return rc;
     if (window == 0 && st->best) { splice_set_error("splice_step_set_stop_rule: a handle that keeps the best weights needs its rule (window > 0)"); return SPLICE_ERR_STATE; }
+    if (window == 0 && st->lr_state) { splice_set_error("splice_step_set_stop_rule: a handle with the plateau lr rule needs its windows (window > 0)"); return SPLICE_ERR_STATE; }
     if ((window > 0) != (st->stop_rule.window > 0)) st->graphs.retire();
     st->stop_rule = StopRule{window, rel, patience, min_steps};
     return SPLICE_OK;
@@ -707,6 +744,22 @@ int splice_step_set_loss_trace(void* h, float* trace, int capacity) {
     st->trace = trace; st->trace_cap = capacity;
     return SPLICE_OK;
 }
+// The plateau lr rule of every pair of the handle (include/splice_hip.h has the rule): the step's loss kernel writes `state`, `cut_steps` and
+// the handle's lr_eff table, the optimiser launch of the same step reads the table.  Before the first step only, behind the stop rule,
+// and not on a gradient-only or phase-mode handle, as that rule.
+int splice_step_set_lr_plateau(void* h, float factor, int patience, float min_scale, splice_lr_state* state, int* cut_steps) {
+    SpliceStep* st = (SpliceStep*)h;
+    if (!st) return SPLICE_ERR_ARG;
+    if (!state || !cut_steps) { splice_set_error("splice_step_set_lr_plateau: needs the state records and the cut-step rows"); return SPLICE_ERR_ARG; }
+    if (!lr_rule_ok(factor, patience, min_scale, "splice_step_set_lr_plateau")) return SPLICE_ERR_ARG;
+    if (int rc = rule_setter_ok(st, "splice_step_set_lr_plateau", "the rule is set")) return rc;
+    if (st->stop_rule.window <= 0) { splice_set_error("splice_step_set_lr_plateau: needs a handle with a stop rule (splice_step_set_stop_rule, window > 0)"); return SPLICE_ERR_STATE; }
+    if (st->astride % 4) { splice_set_error("splice_step_set_lr_plateau: the arena stride must be a multiple of 4"); return SPLICE_ERR_ARG; }
+    if (!st->lr_eff) RC(salloc(st, &st->lr_eff, (size_t)st->pairs));
+    st->graphs.retire();
+    st->lr_rule = LrRule{factor, patience, min_scale}; st->lr_state = state; st->lr_cuts = cut_steps;
+    return SPLICE_OK;
+}
 int splice_step_stop_state(void* h, splice_stop_state* out, splice_stream_t stream) {
     SpliceStep* st = (SpliceStep*)h;
     if (!st || !out) return SPLICE_ERR_ARG;
@@ -733,6 +786,18 @@ int splice_plateau_update_best(splice_stop_state* state, splice_best_state* best
                   best, means);
     return SPLICE_OK;
 }
+// the loss kernel's device function for both rules; launched at uncounted steps too (lr_eff is written at every step)
+int splice_plateau_update_lr(splice_stop_state* state, splice_lr_state* lr_state, int* cut_steps, const float* losses8, const float* lr_in, int per_pair,
+                             float* lr_eff, int pairs, int window, float rel, int patience, int min_steps, float factor, int lr_patience, float min_scale,
+                             int step_idx, int counted, splice_stream_t stream) {
+    if (!state || !lr_state || !cut_steps || !losses8 || !lr_in || !lr_eff || pairs < 1 || step_idx < 0) return SPLICE_ERR_ARG;
+    if (!stop_rule_ok(window, rel, patience, min_steps, "splice_plateau_update_lr")) return SPLICE_ERR_ARG;
+    if (window < 1) { splice_set_error("splice_plateau_update_lr: the lr rule needs the stop rule's windows (window >= 1)"); return SPLICE_ERR_ARG; }
+    if (!lr_rule_ok(factor, lr_patience, min_scale, "splice_plateau_update_lr")) return SPLICE_ERR_ARG;
+    SPLICE_LAUNCH(plateau_update_lr_kernel, dim3((pairs + 63) / 64), dim3(64), 0, (hipStream_t)stream, state, lr_state, cut_steps, losses8, pairs,
+                  StopRule{window, rel, patience, min_steps}, LrRule{factor, lr_patience, min_scale}, step_idx, counted, lr_in, per_pair ? 1 : 0, lr_eff);
+    return SPLICE_OK;
+}
 // test hook: the step's total-loss launch (the instance without the stop rule) on a caller's partials buffer
 int splice_total_loss_pairs(float* lbase, size_t lstride, int lp, float w_ssim, float w_essim, float w_ecls, float w_cls, float w_id, float* out8,
                             int pairs, int n_a, int n_b, int n_c, int n_e, const float* wtab, int ssim_on, int entire, splice_stream_t stream) {
@@ -743,7 +808,7 @@ int splice_total_loss_pairs(float* lbase, size_t lstride, int lp, float w_ssim, 
     const auto kernel = total_loss_kernel<false, false>;
     SPLICE_LAUNCH(kernel, dim3(pairs), dim3(320), 0, (hipStream_t)stream, lbase, lstride, lp, w_ssim, w_essim, w_ecls, w_cls, w_id, out8,
                   n_a, n_b, n_c, n_e, wtab, ssim_on, entire, (splice_stop_state*)nullptr, (const int*)nullptr, StopRule{}, (splice_best_state*)nullptr,
-                  (float*)nullptr, (float*)nullptr, 0);
+                  (float*)nullptr, (float*)nullptr, 0, NO_LR_RULE);
     return SPLICE_OK;
 }
 // test hook: the same launch with the loss trace (the TRACE instances): dev_t holds step index + 1 on the device; stop (optional, with its
@@ -763,7 +828,7 @@ int splice_total_loss_pairs_trace(float* lbase, size_t lstride, int lp, float w_
     const auto kernel = stop ? total_loss_kernel<true, true> : total_loss_kernel<false, true>;
     SPLICE_LAUNCH(kernel, dim3(pairs), dim3(320), 0, (hipStream_t)stream, lbase, lstride, lp, w_ssim, w_essim, w_ecls, w_cls, w_id, out8, n_a, n_b, n_c, n_e, wtab,
                   ssim_on, entire, stop, dev_t, stop ? StopRule{window, rel, patience, min_steps} : StopRule{}, (splice_best_state*)nullptr, (float*)nullptr, trace,
-                  capacity);
+                  capacity, NO_LR_RULE);
     return SPLICE_OK;
 }
 
@@ -911,12 +976,14 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
             const bool grouped = st->crops_mode && pairs > 1;
             const int n1 = st->crops_mode ? P : 1;
             // (the rule and the trace ride in the launch: no node more)
-            const auto kernel = st->trace ? (stop_on ? total_loss_kernel<true, true> : total_loss_kernel<false, true>)
-                                          : (stop_on ? total_loss_kernel<true, false> : total_loss_kernel<false, false>);
+            const auto kernel = st->lr_state ? (st->trace ? total_loss_kernel<true, true, true> : total_loss_kernel<true, false, true>)
+                                : st->trace  ? (stop_on ? total_loss_kernel<true, true> : total_loss_kernel<false, true>)
+                                             : (stop_on ? total_loss_kernel<true, false> : total_loss_kernel<false, false>);
             SPLICE_LAUNCH(kernel, dim3(pairs), dim3(320), 0, q, st->losses, st->lstride, (int)st->lp, t[L_GLOBAL_SSIM].lambda, t[L_ENTIRE_SSIM].lambda,
                           t[L_ENTIRE_CLS].lambda, t[L_GLOBAL_CLS].lambda, t[L_GLOBAL_ID].lambda, st->losses_out, grouped ? st->na : n1, grouped ? st->nb : n1, grouped ? nc : n1,
                           grouped ? 1 : n1, st->pw ? st->pw + (size_t)PW_LAMBDAS * P : nullptr, (int)ssim_on, (int)entire, st->stop, st->dev_t, st->stop_rule, st->best, st->best_means,
-                          st->trace, st->trace_cap);
+                          st->trace, st->trace_cap, st->lr_rule, st->lr_state, st->lr_cuts, (const float*)(st->pair_lr ? st->dev_lrs : st->dev_lr), st->pair_lr ? 1 : 0,
+                          st->lr_eff);
         }
         if (!st->running || !gen_fwd) return SPLICE_OK;
         void* plans[3] = {st->plan_a, st->plan_b, nullptr};
@@ -962,6 +1029,10 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
         // per-pair lrs (splice_step_set_pair_lr): pair p's arena reads dev_lrs[p]
         a.lr_dev = st->pair_lr ? st->dev_lrs : st->lr_set ? st->dev_lr : nullptr;
         a.lr_stride = st->pair_lr ? st->astride : 0;
+        // the plateau lr rule: the learning rate(s) THIS step's loss kernel wrote, lr_in * scale -- that kernel always precedes this launch
+        // (the order keep-best relies on, below): on the side stream's tail, in front of the EV_JOIN2 wait above, or on the main stream in
+        // front of this launch.  One arena reads lr_eff[0] as a scheduled lr, several the per-pair instances (no other kernel than a sweep's)
+        if (st->lr_state) { a.lr_dev = st->lr_eff; a.lr_stride = st->pairs > 1 ? st->astride : 0; }
         if (stop_on) { a.mask = st->stop; a.mask_step = st->dev_t; a.mask_stride = st->astride; }
         if (st->ema) { a.ema = st->ema; a.ema_decay = st->ema_decay; a.ema_start = st->ema_start; }   // (another kernel: the graph pool keys on it)
         if (st->clip) {   // two launches more: the norm of the gradient the update is about to read, frozen slots left out
@@ -1050,8 +1121,8 @@ int splice_step_run(void* h, float* params, float* grads, float* m, float* v, co
         if (st->pair_lr) {
             sa.fp = st->dev_lrs; sa.nf = P;
             for (int p = 0; p < P; ++p) sa.fv[p] = st->lrs[p];
-        } else if (st->lr_set) {
-            sa.fp = st->dev_lr; sa.nf = 1; sa.fv[0] = st->lr;
+        } else if (st->lr_set || st->lr_state) {   // (the plateau lr rule reads its lr_in on the device: without a setter the handle stages cfg.lr itself)
+            sa.fp = st->dev_lr; sa.nf = 1; sa.fv[0] = st->lr_set ? st->lr : c.lr;
         }
         SPLICE_LAUNCH(stage_inputs_kernel, dim3(128 * (P > 4 ? 4 : P)), dim3(256), 0, s, sa);
     }
@@ -1075,9 +1146,10 @@ int splice_step_run(void* h, float* params, float* grads, float* m, float* v, co
             }
             // several pairs with n_crops: the layout is part of the pool key (other keys unchanged)
             const bool grouped = st->crops_mode && st->pairs > 1;
-            // ... and so is the stop rule: its loss-kernel and update nodes are other kernels than those of a handle without it
+            // ... and so is the stop rule: its loss-kernel and update nodes are other kernels than those of a handle without it; and the
+            // plateau lr rule, whose loss-kernel node is another kernel again
             const unsigned long long salt = (grouped ? ((unsigned long long)st->pairs << 32) | ((unsigned long long)st->na << 16) | (unsigned long long)st->nb : 0) |
-                                            (st->stop_rule.window > 0 ? 1ull << 63 : 0);
+                                            (st->stop_rule.window > 0 ? 1ull << 63 : 0) | (st->lr_state ? 1ull << 62 : 0);
             ex = st->graphs.adopt(variant, g, salt);
             if (!ex) return SPLICE_ERR_HIP;
         }

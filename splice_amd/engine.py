@@ -34,7 +34,9 @@ DEFAULT_CFG = dict(  # conf/default/config.yaml of the reference
     # ... and the weights of the window the stop rule judged best, kept on the device beside the live ones, off by default
     stop_keep_best=False,
     # ... and one row per step and slot of the loss values (and the gradient norm under clipping), kept on the device, off by default
-    loss_trace=False)
+    loss_trace=False,
+    # ... and a cut of a slot's learning rate where the stop rule's windows stop getting better, decided in the loss kernel, off by default
+    lr_plateau_factor=0.0, lr_plateau_patience=1, lr_plateau_min_scale=0.0)
 
 
 # Per-slot keys of a sweep (MultiPairEngine(pair_cfgs=...), train.train_sweep): the five loss weights in the order of
@@ -141,6 +143,98 @@ def np_plateau(losses, counted, window, rel, patience, min_steps, margins=None):
             s["stop_step"] = t
     s["means"] = np.array(means, dtype=f)
     return s
+
+
+def lr_plateau_rule(c):
+    """``(factor, patience, min_scale)`` of the plateau lr rule in config ``c``, checked on the host:
+    ``lr_plateau_factor`` 0 (the rule is off) or in (0, 1), an integer ``lr_plateau_patience >= 1`` (windows) and
+    ``0 <= lr_plateau_min_scale < 1``; a factor > 0 needs the plateau stop rule (``stop_window > 0``), whose windows and ``stop_rel``
+    it uses.  Raises ValueError naming the key."""
+    factor = float(_number(c, "lr_plateau_factor", _REAL, lambda v: 0 <= v < 1, "0 (off) or a number in (0, 1)"))
+    patience = _integer(c, "lr_plateau_patience", 1)
+    min_scale = float(_number(c, "lr_plateau_min_scale", _REAL, lambda v: 0 <= v < 1, "a number in [0, 1)"))
+    if factor > 0:
+        if not 0 < float(np.float32(factor)) < 1:   # (the kernels take it as a float)
+            raise ValueError(f"'lr_plateau_factor' must be in (0, 1) as a float32 number, got {factor!r}")
+        if stop_rule(c)[0] == 0:
+            raise ValueError("'lr_plateau_factor' > 0 needs the windows of the plateau stop rule: 'stop_window' > 0 "
+                             "(cuts without a stop: a large 'stop_patience')")
+    return factor, patience, min_scale
+
+
+def np_lr_plateau(losses, counted, window, rel, patience, min_steps, factor, lr_patience, min_scale, margins=None):
+    """The plateau lr rule on top of the stop rule (include/splice_hip.h) restated in NumPy float32, one rounding per operation: the
+    slot's state after the steps ``losses`` (``counted[t]``: step t is counted).  Returns the ``splice_stop_state`` fields of
+    ``np_plateau`` (``sum count windows best bad stop_step``), ``lr`` -- the ``splice_lr_state`` record as ``lr_state()`` gives it:
+    ``scale bad cuts last_cut_step`` and ``cut_steps``, the step indices of the cuts -- and ``scales``, float32, the scale in force at
+    each step (what the step's update multiplied its lr by: a cut made at step t first shows at t + 1; for a stopped slot the scale
+    its record holds).  ``margins`` as in ``np_plateau``."""
+    f = np.float32
+    s = dict(sum=f(0), count=0, windows=0, best=f(0), bad=0, stop_step=-1)
+    lr = dict(scale=f(1), bad=0, cuts=0, last_cut_step=-1, cut_steps=[])
+    scales = []
+    for t, (loss, c) in enumerate(zip(losses, counted)):
+        scales.append(lr["scale"])           # read before this step's rule runs
+        if not c:
+            continue
+        s["sum"] = f(s["sum"] + f(loss))
+        s["count"] += 1
+        if s["count"] < window:
+            continue
+        mean = f(s["sum"] / f(window))
+        live = s["stop_step"] < 0            # on entry: the stopping step itself is still live
+        better = s["windows"] == 0
+        if not better:
+            thr = f(s["best"] * f(f(1.0) - f(rel)))
+            if margins is not None:
+                margins.append(abs(float(mean) - float(thr)) / abs(float(thr)))
+            better = bool(mean < thr)
+        if better:
+            s["best"], s["bad"] = mean, 0
+        else:
+            s["bad"] += 1
+        s["windows"] += 1
+        s["sum"], s["count"] = f(0), 0
+        if s["bad"] >= patience and t >= min_steps and s["stop_step"] < 0:
+            s["stop_step"] = t
+        if not live:                         # a frozen slot's record is never written again
+            continue
+        if better:
+            lr["bad"] = 0
+            continue
+        lr["bad"] += 1
+        if lr["bad"] >= lr_patience and lr["scale"] > f(min_scale) and lr["cuts"] < STOP_HISTORY:
+            lr["scale"] = max(f(lr["scale"] * f(factor)), f(min_scale))
+            lr["cut_steps"].append(t)
+            lr["cuts"] += 1
+            lr["last_cut_step"] = t
+            lr["bad"] = 0
+    s["lr"] = lr
+    s["scales"] = np.array(scales, dtype=f)
+    return s
+
+
+def replay_lr_scales(cut_steps, steps, factor, min_scale):
+    """The scale in force at each of ``steps`` steps, float32, replayed on the host from a slot's ``cut_steps``: the cut made at step
+    t first acts on step t + 1, each cut is ``scale = max(fl(scale * factor), min_scale)``."""
+    f = np.float32
+    out, scale, cuts = [], f(1), sorted(int(t) for t in cut_steps)
+    k = 0
+    for t in range(steps):
+        while k < len(cuts) and cuts[k] < t:
+            scale = max(f(scale * f(factor)), f(min_scale))
+            k += 1
+        out.append(scale)
+    return np.array(out, dtype=f)
+
+
+def lr_records(state_dev, cuts_dev):
+    """Host dicts of device ``splice_lr_state`` records (int32 ``[P, 4]``) and their ``cut_steps`` rows (int32 ``[P, STOP_HISTORY]``):
+    one synchronising copy."""
+    raw = torch.cat([state_dev, cuts_dev], dim=1).cpu().numpy()
+    scale = raw[:, :1].copy().view(np.float32)
+    return [dict(scale=scale[p, 0], bad=int(raw[p, 1]), cuts=int(raw[p, 2]), last_cut_step=int(raw[p, 3]),
+                 cut_steps=[int(t) for t in raw[p, 4:4 + max(0, min(int(raw[p, 2]), STOP_HISTORY))]]) for p in range(raw.shape[0])]
 
 
 def trace_rule(c):
@@ -325,6 +419,8 @@ class MultiPairEngine:
         self.best = self.best_ema = self.best_dev = self.means_dev = None
         self.trace_on = trace_rule(self.cfg)
         self.trace_dev = None
+        self.lr_rule = lr_plateau_rule(self.cfg)
+        self.lr_state_dev = self.lr_cuts_dev = None
         P_in = len(gen_states)
         self.cfgs = [self.cfg] * P_in
         self._pair_lambdas = self._pair_lr = False
@@ -466,6 +562,14 @@ class MultiPairEngine:
         if self.trace_on:
             self.trace_dev = torch.full((max(int(c["n_epochs"]), 1), P, 8), float("nan"), device=self.device)
             _lib.check(_lib.lib().splice_step_set_loss_trace(self.handle, _lib.ptr(self.trace_dev), self.trace_dev.shape[0]), "step_set_loss_trace")
+        # the plateau lr rule (shared by the slots; decided per slot in the loss kernel): one record and one row of cut steps per slot, the
+        # caller's; behind the stop rule, before the first step
+        if self.lr_rule[0] > 0:
+            self.lr_state_dev = torch.tensor([[np.float32(1).view(np.int32).item(), 0, 0, -1]] * P, dtype=torch.int32, device=self.device)
+            self.lr_cuts_dev = torch.full((P, STOP_HISTORY), -1, dtype=torch.int32, device=self.device)
+            _lib.check(_lib.lib().splice_step_set_lr_plateau(self.handle, *self.lr_rule, _lib.ptr(self.lr_state_dev), _lib.ptr(self.lr_cuts_dev)),
+                       "step_set_lr_plateau")
+        self._lr_scale = [1.0] * P   # the host's copy of every slot's lr scale, refreshed with the stop steps
         self._stopped = [None] * P   # the host's copy of every slot's stop step, refreshed by stop_state()
         self._stop_dirty = False     # a window has closed since the last stop_state(): the copy may be behind
         if self._pair_lambdas:
@@ -532,6 +636,8 @@ class MultiPairEngine:
         rec = (_lib.StopState * self.P)()
         _lib.check(_lib.lib().splice_step_stop_state(self.handle, rec, _lib.current_stream()), "step_stop_state")
         self._stopped = [r.stop_step if r.stop_step >= 0 else None for r in rec]
+        if self.lr_state_dev is not None:   # (a window closed: the only steps at which a scale can move)
+            self._lr_scale = [float(d["scale"]) for d in lr_records(self.lr_state_dev, self.lr_cuts_dev)]
         self._stop_dirty = False
         return [dict(stopped_at=k, windows=r.windows, best=r.best, bad=r.bad) for k, r in zip(self._stopped, rec)]
 
@@ -552,6 +658,24 @@ class MultiPairEngine:
     def _frozen(self, pair):
         k = self._stops()[pair] if self.stop_rule[0] > 0 else None
         return k is not None and self.step_idx > k
+
+    # ---- the plateau lr rule
+    @property
+    def lr_scale(self):
+        """Per slot: the factor the loss kernel multiplies the slot's scheduled lr (``engine.lr``) by, 1.0 with the rule off.  The
+        host's copy: refreshed, like the stop steps, only after a step that closed a window -- no other step can change it."""
+        self._stops()
+        return list(self._lr_scale)
+
+    def lr_state(self, pair=None):
+        """Per slot the plateau lr rule's record (``lr_plateau_factor > 0``): ``scale`` (float32, what the next update multiplies its lr
+        by), ``bad`` (consecutive windows that were not better since the last cut), ``cuts``, ``last_cut_step`` (-1: none) and
+        ``cut_steps``, the step index of every cut.  One device-to-host copy (waits for the current stream).  One dict for ``pair``, a
+        list over the slots for ``pair=None``."""
+        if self.lr_state_dev is None:
+            raise RuntimeError("lr_state: the lr is not cut on a plateau (lr_plateau_factor == 0)")
+        dicts = lr_records(self.lr_state_dev, self.lr_cuts_dev)
+        return dicts if pair is None else dicts[pair]
 
     # ---- the best window's weights (DESIGN.md section 9d)
     def _need_best(self, who):
@@ -635,13 +759,20 @@ class MultiPairEngine:
 
     def loss_trace_columns(self):
         """What ``losses.csv`` holds (``util.write_loss_trace``), per slot ``(rows, lrs, active)``: the slot's trace, the learning rate
-        of every row from the host's schedule (the slot's own in a sweep) and the terms every row's step computed."""
+        of every row from the host's schedule (the slot's own in a sweep) and the terms every row's step computed.  With the plateau
+        lr rule the learning rate is the effective one, ``float32(lr) * float32(scale)`` as the loss kernel forms it, the scale of
+        every step replayed on the host from the slot's ``cut_steps``."""
         traces = MultiPairEngine.loss_trace(self)
         acts = [self.active_terms(s) for s in range(max(len(r) for r in traces))]
+        cuts = MultiPairEngine.lr_state(self) if self.lr_state_dev is not None else None
         out = []
         for p, rows in enumerate(traces):
             sch = LrSchedule(self.cfgs[p] if self._pair_lr else self.cfg)   # (a fresh recurrence: the engine's own stays where it is)
-            out.append((rows, [sch.lr(s) for s in range(len(rows))], [acts[s][p] for s in range(len(rows))]))
+            lrs = [sch.lr(s) for s in range(len(rows))]
+            if cuts is not None:
+                scales = replay_lr_scales(cuts[p]["cut_steps"], len(rows), self.lr_rule[0], self.lr_rule[2])
+                lrs = [float(np.float32(lr) * k) for lr, k in zip(lrs, scales)]
+            out.append((rows, lrs, [acts[s][p] for s in range(len(rows))]))
         return out
 
     def pair_params(self, pair=0):
@@ -729,6 +860,15 @@ class SpliceEngine(MultiPairEngine):
     def best_state(self, pair=None):
         return super().best_state(0)
 
+    def lr_state(self, pair=None):
+        return super().lr_state(0)
+
+    @property
+    def lr_scale(self):
+        """The factor the loss kernel multiplies the scheduled lr by (the plateau lr rule; 1.0 with the rule off)."""
+        self._stops()
+        return self._lr_scale[0]
+
     def window_means(self, pair=None):
         return super().window_means(0)
 
@@ -756,6 +896,8 @@ class MultiScaleEngine:
         if trace_rule(self.cfg):
             raise NotImplementedError("loss_trace: the rows are written by a whole fused step under its own step count; MultiScaleEngine runs each scale as a phase-mode handle")
         self.trace_dev = None
+        if lr_plateau_rule(self.cfg)[0] > 0:
+            raise NotImplementedError("lr_plateau_factor > 0: the plateau lr rule lives in the fused step's loss kernel and its own update; MultiScaleEngine updates outside the step")
         if stop_rule(self.cfg)[0] > 0:
             raise NotImplementedError("stop_window > 0: the plateau stop rule lives in the fused step's own update; MultiScaleEngine updates outside the step")
         self.ema_rule = ema_rule(self.cfg)
@@ -820,6 +962,8 @@ class MultiScaleEngine:
         self.engines[0].book_logged_forward()
 
     stopped_at = None   # (no stop rule here)
+    lr_rule = (0.0, 1, 0.0)   # (nor the plateau lr rule)
+    lr_scale = 1.0
 
     def window_closes(self, step_idx):
         return False

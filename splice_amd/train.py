@@ -197,7 +197,9 @@ def _optimise(cfg, engine, next_inputs, As, writers, callback, progress, single=
                         callback(p, out[0])
             if progress and (epoch % 50 == 0 or epoch == 1):
                 losses = f"{engine.losses()['loss']:.4f}" if single else ", ".join(f"{d['loss']:.4f}" for d in engine.losses())
-                print(f"Epoch {epoch}: loss={losses} lr={engine.lr}")
+                # (the plateau lr rule: the factor the loss kernel multiplies that lr by, the host's copy of the last closed window)
+                scale = f" lr_scale={engine.lr_scale}" if getattr(engine, "lr_rule", (0,))[0] > 0 else ""
+                print(f"Epoch {epoch}: loss={losses} lr={engine.lr}{scale}")
             # the plateau stop rule (stop_window > 0; decided on the device): the host asks only after a step that closes a window -- no
             # other step can stop a slot -- and ends the run, once every slot has stopped, with an image of each slot's final parameters
             if engine.window_closes(engine.step_idx) and engine.all_stopped():
@@ -325,6 +327,17 @@ def trace_fields(engine, out_dir=""):
     if getattr(engine, "trace_dev", None) is None or engine.step_idx < 0:
         return {}
     return {"loss_trace": os.path.join(out_dir, "losses.csv")}
+
+
+def lr_fields(engine, slot=None):
+    """What ``result.json`` / ``variant.json`` say about the plateau lr rule of a run: ``lr_plateau_factor`` (0: the rule was off), and
+    for ``slot`` (None: the one pair of the engine) ``lr_cuts``, ``lr_cut_steps`` -- the step index of every cut -- and ``lr_scale``,
+    the factor the slot's lr ended at."""
+    factor = getattr(engine, "lr_rule", (0.0,))[0]
+    if getattr(engine, "lr_state_dev", None) is None or engine.step_idx < 0:
+        return {"lr_plateau_factor": factor, "lr_cuts": 0, "lr_cut_steps": [], "lr_scale": 1.0}
+    rec = engine.lr_state(0 if slot is None else slot)
+    return {"lr_plateau_factor": factor, "lr_cuts": rec["cuts"], "lr_cut_steps": list(rec["cut_steps"]), "lr_scale": float(rec["scale"])}
 
 
 def best_fields(engine, slot=None):
@@ -455,7 +468,7 @@ def train_sweep(dataroot, variants, cfg_overrides=None, vit_state=None, callback
     losses = engine.losses() if engine.step_idx >= 0 else [{} for _ in range(K)]
     for k in range(K):
         with open(os.path.join(out_dirs[k], 'variant.json'), 'w') as f:
-            json.dump({"index": k, "overrides": variants[k], "seed": seeds[k], "losses": losses[k], "stopped_at": engine.stopped_at[k], **trace_fields(engine)}, f)
+            json.dump({"index": k, "overrides": variants[k], "seed": seeds[k], "losses": losses[k], "stopped_at": engine.stopped_at[k], **trace_fields(engine), **lr_fields(engine, k)}, f)
     return engine
 
 

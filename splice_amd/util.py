@@ -56,7 +56,8 @@ class LrSchedule:
     """``lr(k)``: learning rate of optimisation step ``k`` (0-based) under the config's ``scheduler_policy`` with ``lr``,
     ``n_epochs``, ``scheduler_n_epochs_decay`` and ``scheduler_lr_decay_iters`` (the arguments train.py passes to get_scheduler).
     Policies: none, linear, step, cosine.  ``plateau`` is refused: the reference calls ``scheduler.step()`` without a metric
-    (train.py:80), which ReduceLROnPlateau rejects, and a plateau rule would need the loss on the host every step."""
+    (train.py:80), which ReduceLROnPlateau rejects, and a plateau rule would need the loss on the host every step -- the rule that is
+    decided on the device instead is the config key ``lr_plateau_factor`` (``engine.lr_plateau_rule``)."""
 
     POLICIES = ("none", "linear", "step", "cosine")
 
@@ -64,7 +65,8 @@ class LrSchedule:
         self.policy = cfg.get("scheduler_policy", "none")
         if self.policy == "plateau":
             raise NotImplementedError("scheduler_policy 'plateau' is not supported: the reference's loop calls scheduler.step() with no metric "
-                                      "(train.py:80), which ReduceLROnPlateau rejects, and a plateau rule would need the loss on the host every step")
+                                      "(train.py:80), which ReduceLROnPlateau rejects, and a plateau rule would need the loss on the host every step; "
+                                      "the rule decided on the device is 'lr_plateau_factor' (with 'stop_window' > 0)")
         if self.policy not in self.POLICIES:
             raise NotImplementedError(f"learning rate policy [{self.policy}] is not implemented")
         self.base_lr = cfg["lr"]
