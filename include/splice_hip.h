@@ -801,6 +801,11 @@ typedef struct splice_gen_wgrad_args {
 size_t splice_gen_conv_wgrad_ws_floats(int N, int Cin, int Cout, int ks, int Ho, int Wo);
 int splice_gen_conv_wgrad(const splice_gen_wgrad_args* args, float* dw, int accumulate, int n_img, size_t p_nstride, int* form_out,
                           splice_stream_t stream);
+/* Test hook: the reduction alone, for one layer on caller buffers.  partials = [chunks][n] floats; dw[i] (+)= the sum over the chunks of
+ * partials[c][i] in the reduction's fixed order: four chains, each in increasing c from +0 -- chunk c of a full group of four joins chain c mod 4,
+ * the chunks of the last, partial group all join chain 0 -- combined as (a0 + a1) + (a2 + a3), then the optional += into dw (accumulate).  p_nstride > 0: n_img independent images -- chunks must be a multiple of n_img, image i sums chunks
+ * [i * chunks / n_img, (i + 1) * chunks / n_img) into dw + i * p_nstride (p_nstride >= n); else n_img must be 1.  chunks >= 0 (0: exact zeros). */
+int splice_gen_wgrad_reduce(const float* partials, int n, int chunks, float* dw, int accumulate, int n_img, size_t p_nstride, splice_stream_t stream);
 
 /* Train-mode BatchNorm (biased variance, rstd = 1 / sqrt(var + eps)) + LeakyReLU(slope) on [N][C][HW] planes, either direction, as
  * bn_fwd_launch / bn_bwd_launch run it.  splice_gen_bn_form reports the form of a plane as SPLICE_GEN_BN_FORM_INTS ints: {kind (0 SMALL, 1 MID,
@@ -864,6 +869,12 @@ int splice_gen_bn_form(int HW, int N, size_t p_nstride, int batch, int* out);
 size_t splice_gen_bn_part_floats(int N, int C);
 int splice_gen_bn_fwd(const splice_gen_bn_args* args, splice_stream_t stream);
 int splice_gen_bn_bwd(const splice_gen_bn_args* args, splice_stream_t stream);
+/* Test hook.  The small-plane kernels (form SMALL) exist in instances that compile only the features a launch needs; `mask` is the OR of
+ * 1 batch statistics, 2 shared-parameter tail (backward, N > 1 without arenas), 4 slabs, 8 a pre BatchNorm, 16 a fused upsampling.  The launchers
+ * pick the first of {0, 4, 16, 24, 28, 1, 2, 31} that covers a call.  mask >= 0 (one of those) makes every later small-plane launch of the process
+ * take that instance -- 31 is the fully general one -- and splice_gen_bn_fwd / _bwd return SPLICE_ERR_ARG where the call needs a feature the instance
+ * lacks; -1 restores the automatic choice.  Every instance that covers a call gives the same bits. */
+int splice_gen_bn_small_instance(int mask);
 
 /* The three launchers of gen_pointwise.hip.  Upsampling: in [N][C][h][w] -> the top-left Ho x Wo window of its x2 bilinear upsampling
  * (Ho <= 2h, Wo <= 2w), and the adjoint dout [N][C][Ho][Wo] -> din [N][C][h][w]; image strides in floats.  Sigmoid backward of the compact

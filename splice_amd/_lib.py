@@ -143,6 +143,8 @@ _SIGNATURES = {
     "splice_gen_conv_reflect_dgrad": ([C.POINTER(GenConvArgs), _vp, _sz, _vp], _i),
     "splice_gen_conv_wgrad_ws_floats": ([_i, _i, _i, _i, _i, _i], _sz),
     "splice_gen_conv_wgrad": ([C.POINTER(GenWgradArgs), _vp, _i, _i, _sz, C.POINTER(_i), _vp], _i),
+    "splice_gen_wgrad_reduce": ([_vp, _i, _i, _vp, _i, _i, _sz, _vp], _i),
+    "splice_gen_bn_small_instance": ([_i], _i),
     "splice_gen_bn_form": ([_i, _i, _sz, _i, C.POINTER(_i)], _i),
     "splice_gen_bn_part_floats": ([_i, _i], _sz),
     "splice_gen_bn_fwd": ([C.POINTER(GenBnArgs), _vp], _i),

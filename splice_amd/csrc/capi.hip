@@ -317,6 +317,16 @@ int splice_gen_conv_wgrad(const splice_gen_wgrad_args* args, float* dw, int accu
     return finish(wgrad_reduce_all_launch(r, args->ws, dw, accumulate, ST(stream), n_img, p_nstride), who);
 }
 
+int splice_gen_wgrad_reduce(const float* partials, int n, int chunks, float* dw, int accumulate, int n_img, size_t p_nstride, splice_stream_t stream) {
+    const char* who = "splice_gen_wgrad_reduce";
+    if (!partials || !dw || n < 1 || chunks < 0 || n_img < 1 || n_img > 65535 || (long long)n * (chunks > 0 ? chunks : 1) > 0x7fffffffLL) return finish(SPLICE_ERR_ARG, who);
+    if (p_nstride ? (chunks % n_img || p_nstride < (size_t)n) : n_img != 1) return finish(SPLICE_ERR_ARG, who);
+    WgradReduceAll r = {};
+    r.count = 1; r.n[0] = n; r.chunks[0] = chunks; r.ws_off[0] = 0; r.dw_off[0] = 0;
+    return finish(wgrad_reduce_all_launch(r, partials, dw, accumulate, ST(stream), n_img, p_nstride), who);
+}
+
+int splice_gen_bn_small_instance(int mask) { return finish(bn_small_force_instance(mask), "splice_gen_bn_small_instance"); }
 int splice_gen_bn_form(int HW, int N, size_t p_nstride, int batch, int* out) {
     if (HW < 1 || N < 1 || batch < 0 || !out) return finish(SPLICE_ERR_ARG, "splice_gen_bn_form");
     const BnForm f = bn_form(HW, N, p_nstride, batch);

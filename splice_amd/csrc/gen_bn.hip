@@ -420,13 +420,28 @@ __device__ __forceinline__ float bn_dy(float gr, float dz, float k1, float xh, f
     rounded(g);
     return g;
 }
+// the plane size as a value the compiler has not seen: the 16 per-element bounds masks (an SGPR pair each) are formed again in the phase
+// that follows instead of being kept alive -- spilled -- from the first loads to the last stores
+__device__ __forceinline__ int bn_fresh(int hw) { asm volatile("" : "+s"(hw)); return hw; }
 constexpr int BN_SMALL_HW = 4096;
 constexpr int BN_MAX_BATCH = 8;               // images per batch-statistics call (n_crops)
 constexpr int BN_SMALL_PER = BN_SMALL_HW / 256;   // most plane elements a thread keeps in registers (kernels are instantiated for 1, 4 and 16:
                                                   // a 7x7 plane running the 16-element code fetched ten times the instructions it executed)
 constexpr int BN_UP_SRC = 34 * 34;            // low-resolution plane of a fused upsampling staged in LDS (else read from global)
+// What a small-plane launch can need beyond the plain plane.  The kernels take a mask F of these, fixed per launch, and an instance compiles
+// only the paths of its mask: the fully general <16> backward was 13.6 k instructions, 261 VGPRs and 293 spilled SGPRs, most of it code a
+// launch never ran, fetched cold at every launch (profiles/gen_bwd_slim_isa.txt).  The arithmetic of a path does not depend on the mask: every
+// instance that covers a launch's needs gives the same bits (tests/test_bn_small_instances_gpu.py).
+enum : unsigned {
+    BN_F_BATCH = 1,    // batch statistics (batch > 0)
+    BN_F_TAIL = 2,     // backward: one parameter set shared by N > 1 images -- image 0 walks the other images' sums
+    BN_F_SLABS = 4,    // split-K slabs summed while the plane is loaded (forward: the conv's or the BnPre's; backward: BnSlabs)
+    BN_F_PRE = 8,      // a BnPre rides in the launch
+    BN_F_UP = 16,      // a BnUpsample rides in the launch
+    BN_F_ALL = 31
+};
 // slabs != null: the plane is first formed as bias + sum of the feeding convolution's split-K slabs (slice order) and stored to y
-template <int PER>   // plane elements a thread keeps in registers: 1, 4 or 16 (planes of <= 256, <= 1024, <= 4096 pixels)
+template <int PER, unsigned F>   // PER: plane elements a thread keeps in registers: 1, 4 or 16 (planes of <= 256, <= 1024, <= 4096 pixels)
 __global__ __launch_bounds__(256) void bn_small_fwd_kernel(const float* y, size_t y_nstride, float* __restrict__ out,
                                                            size_t out_nstride, int C, int HW, const float* __restrict__ gamma,
                                                            const float* __restrict__ beta, float eps, float* __restrict__ mean_o,
@@ -434,8 +449,9 @@ __global__ __launch_bounds__(256) void bn_small_fwd_kernel(const float* y, size_
                                                            int ksplit, const float* __restrict__ bias, float* __restrict__ y_out, BnUpsample up,
                                                            size_t p_nstride, int batch, BnPre pre) {
     __shared__ float red[8];
-    __shared__ float up_src_s[BN_UP_SRC];
+    __shared__ float up_src_s[(F & BN_F_UP) ? BN_UP_SRC : 1];
     const int c = blockIdx.x, img = blockIdx.y;
+    if (!(F & BN_F_BATCH)) batch = 0;
     gamma += bn_arena(img, p_nstride, batch); beta += bn_arena(img, p_nstride, batch);
     if (bias) bias += bn_arena(img, p_nstride, batch);
     const float* p = y + (size_t)img * y_nstride + (size_t)c * HW;
@@ -444,12 +460,12 @@ __global__ __launch_bounds__(256) void bn_small_fwd_kernel(const float* y, size_
     // is masked afterwards): lane-guarded loads compile to load + s_waitcnt per element, i.e. one memory round trip each
     float v[PER];
     float s = 0.f, dummy = 0.f;
-    if (pre.y && c < pre.C) {
+    if ((F & BN_F_PRE) && pre.y && c < pre.C) {
         // ---- the skip branch's own BatchNorm + LeakyReLU on this plane (BnPre), in front of the concat's: the plane is formed
         // (from the skip convolution's output, or from its split-K slabs + bias), normalised with ITS statistics, activated and
         // stored into the concat buffer (the backward reads it there); v then holds the concat BatchNorm's input
         const float* py1 = pre.y + (size_t)img * pre.y_ns + (size_t)c * HW;
-        if (pre.slabs) {
+        if ((F & BN_F_SLABS) && pre.slabs) {
             const size_t per = (size_t)gridDim.y * pre.C * HW;
             const float* sp = pre.slabs + ((size_t)img * pre.C + c) * HW;
             float* yo = const_cast<float*>(py1);
@@ -519,7 +535,7 @@ __global__ __launch_bounds__(256) void bn_small_fwd_kernel(const float* y, size_
             if (i < HW) yo2[i] = v[k];
             s += v[k];
         }
-    } else if (slabs) {
+    } else if ((F & BN_F_SLABS) && slabs) {
         const size_t per = (size_t)gridDim.y * C * HW;
         const float* sp = slabs + ((size_t)img * C + c) * HW;
         float* yo = y_out + (size_t)img * y_nstride + (size_t)c * HW;
@@ -553,7 +569,7 @@ __global__ __launch_bounds__(256) void bn_small_fwd_kernel(const float* y, size_
             if (i < HW) yo[i] = v[k]; else v[k] = 0.f;
             s += v[k];
         }
-    } else if (up.src && c >= up.c0) {
+    } else if ((F & BN_F_UP) && up.src && c >= up.c0) {
         // upsampled channel of the concat: the values are produced here from the low-resolution plane (staged through LDS
         // when it fits) and stored into y for the backward -- the upsampling is not a launch of its own
         const float* sp = up.src + (size_t)img * up.src_ns + (size_t)(c - up.c0) * up.h * up.w;
@@ -659,25 +675,41 @@ __device__ __forceinline__ void bn_small_bwd_sums(const float* pd, const float* 
     s1 = 0.f; s2 = 0.f;
     // branch-free loads first (see bn_small_fwd_kernel), arithmetic after
     const bool act = slope != 1.0f;
+    // ... and free of wave-uniform value selects too: `act ? pa[j] : 1.f` put every load of the activated plane into a block of its own with
+    // the sign test behind it -- load, s_waitcnt vmcnt(0), compare, once per element: 16 dependent memory round trips in the 56x56
+    // kernel.  Without an activation nobody reads the activated plane: the loads then go to the y plane, whose lines the vy loads fetch anyway.
+    const float* pa_ld = act ? pa : py;
     float vd[PER], va[PER], vy[PER];
 #pragma unroll
     for (int k = 0; k < PER; ++k) {
         if (k * 256 >= HW) continue;
         const int i = threadIdx.x + k * 256;
         const int j = i < HW ? i : 0;
-        vd[k] = (!sp || sl_acc) ? pd[j] : 0.f;
         vy[k] = py[j];
-        va[k] = act ? pa[j] : 1.f;
+        va[k] = pa_ld[j];
+    }
+    if (!sp || sl_acc) {   // (plain slabs: the gradient is the slabs' sum alone)
+#pragma unroll
+        for (int k = 0; k < PER; ++k) {
+            if (k * 256 >= HW) continue;
+            const int i = threadIdx.x + k * 256;
+            vd[k] = pd[i < HW ? i : 0];
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < PER; ++k) vd[k] = 0.f;
     }
     if (sp) {
         float v[PER];
 #pragma unroll
         for (int k = 0; k < PER; ++k) v[k] = 0.f;
-        for (int ks = 0; ks < ksplit; ks += 4) {   // slice order, four slices of loads in flight
+        // slice order, four slices of loads in flight; the full groups run without a guard per slice (64 guarded loads kept half the
+        // register file busy), the last group of 1 to 3 slices with them
+        auto group = [&](int ks, int nu) {
             float t[4][PER];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                if (ks + u >= ksplit) continue;
+                if (u >= nu) continue;
                 const float* sk = sp + (size_t)(ks + u) * per;
 #pragma unroll
                 for (int k = 0; k < PER; ++k) {
@@ -688,21 +720,26 @@ __device__ __forceinline__ void bn_small_bwd_sums(const float* pd, const float* 
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                if (ks + u >= ksplit) continue;
+                if (u >= nu) continue;
 #pragma unroll
                 for (int k = 0; k < PER; ++k)
                     if (k * 256 < HW) v[k] += t[u][k];
             }
-        }
+        };
+        int ks = 0;
+        for (; ks + 3 < ksplit; ks += 4) group(ks, 4);
+        if (ks < ksplit) group(ks, ksplit - ks);
 #pragma unroll
         for (int k = 0; k < PER; ++k)
             if (k * 256 < HW) vd[k] = sl_acc ? vd[k] + v[k] : v[k];
     }
+    if (PER > 4) HW = bn_fresh(HW);
 #pragma unroll
     for (int k = 0; k < PER; ++k) {
         const int i = threadIdx.x + k * 256;
         float d = 0.f, x = 0.f;
         if (k * 256 < HW) {
+            rounded(va[k]);   // keeps the sign test here, behind every load (it was folded into the load's block: a wait per element)
             d = bn_dz(vd[k], va[k], slope, act);
             x = bn_xhat(vy[k], m, r);
             if (i >= HW) { d = 0.f; x = 0.f; }
@@ -713,7 +750,7 @@ __device__ __forceinline__ void bn_small_bwd_sums(const float* pd, const float* 
     }
     block_sum2(s1, s2, red);
 }
-template <int PER>
+template <int PER, unsigned F>
 __global__ __launch_bounds__(256) void bn_small_bwd_kernel(const float* __restrict__ da, size_t da_nstride, const float* __restrict__ aout,
                                                            size_t a_nstride, const float* __restrict__ y, size_t y_nstride,
                                                            float* __restrict__ dy, size_t dy_nstride, int C, int HW, int N,
@@ -722,17 +759,37 @@ __global__ __launch_bounds__(256) void bn_small_bwd_kernel(const float* __restri
                                                            float* __restrict__ dbeta, int accumulate, BnUpsample up, size_t p_nstride, int batch, BnPre pre,
                                                            BnSlabs sl) {
     __shared__ float red[8];
-    __shared__ float up_grad_s[BN_SMALL_HW];   // fused upsampling adjoint: this plane's input gradient
+    __shared__ float up_grad_s[(F & BN_F_UP) ? BN_SMALL_HW : 1];   // fused upsampling adjoint: this plane's input gradient
     const int c = blockIdx.x, img = blockIdx.y;
+    if (!(F & BN_F_BATCH)) batch = 0;
     gamma += bn_arena(img, p_nstride, batch);
     const int n0 = batch ? img / batch * batch : 0;   // first image of the batch / group
     float dz[PER], xh[PER];
     float s1, s2;
-    const bool chained = pre.y && c < pre.C;   // workgroup-uniform: a skip-branch BatchNorm sits in front of this channel (BnPre)
+    const bool chained = (F & BN_F_PRE) && pre.y && c < pre.C;   // workgroup-uniform: a skip-branch BatchNorm sits in front of this channel (BnPre)
+    // the chained adjoint's operands are fetched with the plane's own loads, not in a round trip of their own behind the first block sum
+    constexpr int CPER = (F & BN_F_PRE) ? PER : 1;
+    float cva[CPER], cvy[CPER];
+    float m1 = 0.f, r1 = 0.f, g1 = 0.f;
+    if constexpr ((F & BN_F_PRE) != 0) {
+        if (chained) {
+            m1 = pre.mean[img * pre.C + c]; r1 = pre.rstd[img * pre.C + c]; g1 = pre.gamma[(size_t)img * p_nstride + c];
+            const float* pa1 = y + (size_t)img * y_nstride + (size_t)c * HW;                   // a = act(bn1(y1)): sign selects the LeakyReLU branch
+            const float* py1 = pre.y + (size_t)img * pre.y_ns + (size_t)c * HW;
+#pragma unroll
+            for (int k = 0; k < PER; ++k) {
+                if (k * 256 >= HW) continue;
+                const int i = threadIdx.x + k * 256, j = i < HW ? i : 0;
+                cva[k] = pa1[j];
+                cvy[k] = py1[j];
+            }
+            asm volatile("" : : : "memory");   // the loads stay here (they were sunk behind the first block sum again)
+        }
+    }
     {
         const float m = mean[img * C + c], r = rstd[img * C + c];
         float b1 = 0.f, b2 = 0.f;   // batch statistics: sums over every image of the batch, in image order; the own plane last (dz / xh stay)
-        if (batch) {
+        if ((F & BN_F_BATCH) && batch) {
             float t1s[BN_MAX_BATCH], t2s[BN_MAX_BATCH];
 #pragma unroll
             for (int n = 0; n < BN_MAX_BATCH; ++n) {
@@ -750,14 +807,15 @@ __global__ __launch_bounds__(256) void bn_small_bwd_kernel(const float* __restri
         } else {
             bn_small_bwd_sums<PER>(da + (size_t)img * da_nstride + (size_t)c * HW, aout + (size_t)img * a_nstride + (size_t)c * HW,
                               y + (size_t)img * y_nstride + (size_t)c * HW, HW, m, r, slope, dz, xh, s1, s2, red,
-                              sl.slabs ? sl.slabs + ((size_t)img * C + c) * HW : nullptr, (size_t)gridDim.y * C * HW, sl.ksplit, sl.accumulate);
+                              (F & BN_F_SLABS) && sl.slabs ? sl.slabs + ((size_t)img * C + c) * HW : nullptr, (size_t)gridDim.y * C * HW, sl.ksplit, sl.accumulate);
         }
         const float cnt = batch ? (float)HW * (float)batch : (float)HW;
         const float k1 = (batch ? b1 : s1) / cnt, k2 = (batch ? b2 : s2) / cnt;
         if (batch) { s1 = b1; s2 = b2; }   // the parameter gradients are exactly these sums
         const float gr = gamma[c] * r;
         float* po = dy + (size_t)img * dy_nstride + (size_t)c * HW;
-        const bool through_adjoint = up.d_src && c >= up.c0;   // workgroup-uniform
+        const bool through_adjoint = (F & BN_F_UP) && up.d_src && c >= up.c0;   // workgroup-uniform
+        if (PER > 4) HW = bn_fresh(HW);
 #pragma unroll
         for (int k = 0; k < PER; ++k) {
             const int i = threadIdx.x + k * 256;
@@ -766,28 +824,19 @@ __global__ __launch_bounds__(256) void bn_small_bwd_kernel(const float* __restri
                 if (through_adjoint) up_grad_s[i] = gv; else if (chained) dz[k] = gv; else po[i] = gv;
             } else if (chained) dz[k] = 0.f;
         }
-        if (chained) {
+        if constexpr ((F & BN_F_PRE) != 0) if (chained) {
             // ---- the adjoint of the skip branch's BatchNorm + LeakyReLU behind the concat's, on the same plane: dz holds the
             // gradient w.r.t. the activated skip plane a (= this BatchNorm's input y, in the concat buffer)
-            const float m1 = pre.mean[img * pre.C + c], r1 = pre.rstd[img * pre.C + c];
-            const float* pa1 = y + (size_t)img * y_nstride + (size_t)c * HW;                   // a = act(bn1(y1)): sign selects the LeakyReLU branch
-            const float* py1 = pre.y + (size_t)img * pre.y_ns + (size_t)c * HW;
-            float va[PER], vy[PER];
-#pragma unroll
-            for (int k = 0; k < PER; ++k) {
-                if (k * 256 >= HW) continue;
-                const int i = threadIdx.x + k * 256, j = i < HW ? i : 0;
-                va[k] = pa1[j];
-                vy[k] = py1[j];
-            }
             float t1 = 0.f, t2 = 0.f;
+            if (PER > 4) HW = bn_fresh(HW);
 #pragma unroll
             for (int k = 0; k < PER; ++k) {
                 const int i = threadIdx.x + k * 256;
                 float d = 0.f, x = 0.f;
                 if (k * 256 < HW && i < HW) {
-                    d = bn_dz(dz[k], va[k], pre.slope, true);
-                    x = bn_xhat(vy[k], m1, r1);
+                    rounded(cva[k]);   // as in bn_small_bwd_sums: the sign test stays behind the loads
+                    d = bn_dz(dz[k], cva[k], pre.slope, true);
+                    x = bn_xhat(cvy[k], m1, r1);
                 }
                 dz[k] = d; xh[k] = x;
                 t1 += d;
@@ -795,8 +844,9 @@ __global__ __launch_bounds__(256) void bn_small_bwd_kernel(const float* __restri
             }
             block_sum2(t1, t2, red);
             const float j1 = t1 / (float)HW, j2 = t2 / (float)HW;
-            const float gr1 = pre.gamma[(size_t)img * p_nstride + c] * r1;
+            const float gr1 = g1 * r1;
             float* pd1 = pre.dy + (size_t)img * pre.y_ns + (size_t)c * HW;
+            if (PER > 4) HW = bn_fresh(HW);
 #pragma unroll
             for (int k = 0; k < PER; ++k) {
                 const int i = threadIdx.x + k * 256;
@@ -829,7 +879,7 @@ __global__ __launch_bounds__(256) void bn_small_bwd_kernel(const float* __restri
     }
     if (img != 0) return;
     float g = s2, be = s1;
-    for (int n = 1; n < (batch ? 0 : N); ++n) {
+    for (int n = 1; n < ((F & BN_F_TAIL) && !batch ? N : 0); ++n) {
         float t1, t2;
         bn_small_bwd_sums<PER>(da + (size_t)n * da_nstride + (size_t)c * HW, aout + (size_t)n * a_nstride + (size_t)c * HW,
                           y + (size_t)n * y_nstride + (size_t)c * HW, HW, mean[n * C + c], rstd[n * C + c], slope, dz, xh, t1, t2, red);
@@ -1060,12 +1110,42 @@ static void bn_mid_allow_lds() {   // > 48 KB of dynamic LDS has to be allowed o
 }
 // the instantiation whose register tile just covers the plane (same arithmetic in the same order: the surplus elements of a
 // bigger tile only ever added zeros)
-#define BN_SMALL_DISPATCH(HW_, KERNEL, GRID, STREAM, ...)                                                         \
+// ... and whose feature mask covers what the launch needs.  The instances that exist: what the engine issues (the plain plane; slabs; the
+// concat unit, which carries a BnPre and / or a BnUpsample, with or without slabs; batch statistics; the shared-parameter tail) and the fully
+// general one, which takes every other combination.  First entry of the list that covers the need.
+static const unsigned BN_SMALL_INSTANCES[] = {0, BN_F_SLABS, BN_F_UP, BN_F_PRE | BN_F_UP, BN_F_PRE | BN_F_UP | BN_F_SLABS, BN_F_BATCH, BN_F_TAIL, BN_F_ALL};
+static std::atomic<int> g_bn_small_forced{-1};   // test hook (splice_gen_bn_small_instance): >= 0 = the instance every small-plane launch takes
+int bn_small_force_instance(int mask) {
+    if (mask < 0) { g_bn_small_forced.store(-1); return SPLICE_OK; }
+    for (unsigned m : BN_SMALL_INSTANCES)
+        if ((unsigned)mask == m) { g_bn_small_forced.store(mask); return SPLICE_OK; }
+    return SPLICE_ERR_ARG;
+}
+// the instance of a launch that needs `need`; -1: a forced instance that lacks a feature the arguments need
+static int bn_small_instance(unsigned need) {
+    const int forced = g_bn_small_forced.load(std::memory_order_relaxed);
+    if (forced >= 0) return (need & ~(unsigned)forced) ? -1 : forced;
+    for (unsigned m : BN_SMALL_INSTANCES)
+        if (!(need & ~m)) return (int)m;
+    return (int)BN_F_ALL;
+}
+#define BN_SMALL_PER_DISPATCH(HW_, KERNEL, F_, GRID, STREAM, ...)                                                 \
     do {                                                                                                          \
-        if ((HW_) <= 256) SPLICE_LAUNCH(KERNEL<1>, GRID, dim3(256), 0, STREAM, __VA_ARGS__);                  \
-        else if ((HW_) <= 1024) SPLICE_LAUNCH(KERNEL<4>, GRID, dim3(256), 0, STREAM, __VA_ARGS__);            \
-        else SPLICE_LAUNCH(KERNEL<16>, GRID, dim3(256), 0, STREAM, __VA_ARGS__);                              \
+        if ((HW_) <= 256) SPLICE_LAUNCH((KERNEL<1, F_>), GRID, dim3(256), 0, STREAM, __VA_ARGS__);            \
+        else if ((HW_) <= 1024) SPLICE_LAUNCH((KERNEL<4, F_>), GRID, dim3(256), 0, STREAM, __VA_ARGS__);      \
+        else SPLICE_LAUNCH((KERNEL<16, F_>), GRID, dim3(256), 0, STREAM, __VA_ARGS__);                        \
     } while (0)
+#define BN_SMALL_DISPATCH(INST_, HW_, KERNEL, GRID, STREAM, ...)                                                                      \
+    switch (INST_) {                                                                                                                  \
+    case 0: BN_SMALL_PER_DISPATCH(HW_, KERNEL, 0u, GRID, STREAM, __VA_ARGS__); break;                                                \
+    case BN_F_SLABS: BN_SMALL_PER_DISPATCH(HW_, KERNEL, BN_F_SLABS, GRID, STREAM, __VA_ARGS__); break;                               \
+    case BN_F_UP: BN_SMALL_PER_DISPATCH(HW_, KERNEL, BN_F_UP, GRID, STREAM, __VA_ARGS__); break;                                     \
+    case BN_F_PRE | BN_F_UP: BN_SMALL_PER_DISPATCH(HW_, KERNEL, BN_F_PRE | BN_F_UP, GRID, STREAM, __VA_ARGS__); break;               \
+    case BN_F_PRE | BN_F_UP | BN_F_SLABS: BN_SMALL_PER_DISPATCH(HW_, KERNEL, BN_F_PRE | BN_F_UP | BN_F_SLABS, GRID, STREAM, __VA_ARGS__); break; \
+    case BN_F_BATCH: BN_SMALL_PER_DISPATCH(HW_, KERNEL, BN_F_BATCH, GRID, STREAM, __VA_ARGS__); break;                               \
+    case BN_F_TAIL: BN_SMALL_PER_DISPATCH(HW_, KERNEL, BN_F_TAIL, GRID, STREAM, __VA_ARGS__); break;                                 \
+    default: BN_SMALL_PER_DISPATCH(HW_, KERNEL, BN_F_ALL, GRID, STREAM, __VA_ARGS__); break;                                         \
+    }
 int bn_part_floats(int N, int C) { return N * C * MAX_PB_V * 2; }
 // segments of a two-stage plane.  Big planes (round 5): segments of <= 4096 pixels moved in 16-byte runs, a count above MAX_PB; everything
 // else keeps the 64-segment scalar layout
@@ -1130,7 +1210,9 @@ int bn_fwd_launch(const BnArgs& a, hipStream_t s) {
         const int ksplit = a.slabs ? a.ksplit : 0;
         const float* bias = a.slabs ? a.bias : nullptr;
         float* y_store = a.slabs ? const_cast<float*>(a.y) : nullptr;
-        BN_SMALL_DISPATCH(HW, bn_small_fwd_kernel, dim3(C, N), s, a.y, a.y_nstride, a.out, a.out_nstride, C, HW, a.gamma, a.beta, a.eps, a.mean, a.rstd, a.slope,
+        const int inst = bn_small_instance((a.batch ? BN_F_BATCH : 0) | (a.slabs || pr.slabs ? BN_F_SLABS : 0) | (pr.y ? BN_F_PRE : 0) | (u.src ? BN_F_UP : 0));
+        if (inst < 0) return SPLICE_ERR_ARG;
+        BN_SMALL_DISPATCH(inst, HW, bn_small_fwd_kernel, dim3(C, N), s, a.y, a.y_nstride, a.out, a.out_nstride, C, HW, a.gamma, a.beta, a.eps, a.mean, a.rstd, a.slope,
                           a.slabs, ksplit, bias, y_store, u, a.p_nstride, a.batch, pr);
         break;
     }
@@ -1159,7 +1241,10 @@ int bn_bwd_launch(const BnArgs& a, hipStream_t s) {
     switch (f.kind) {
     case BnForm::SMALL: {
         const BnSlabs sl = a.da_slabs ? *a.da_slabs : BnSlabs{};
-        BN_SMALL_DISPATCH(HW, bn_small_bwd_kernel, dim3(C, N), s, a.da, a.da_nstride, a.out, a.out_nstride, a.y, a.y_nstride, a.dy, a.dy_nstride, C, HW, N,
+        const int inst = bn_small_instance((a.batch ? BN_F_BATCH : 0) | (!a.batch && !a.p_nstride && N > 1 ? BN_F_TAIL : 0) | (sl.slabs ? BN_F_SLABS : 0) |
+                                           (pr.y ? BN_F_PRE : 0) | (u.d_src ? BN_F_UP : 0));
+        if (inst < 0) return SPLICE_ERR_ARG;
+        BN_SMALL_DISPATCH(inst, HW, bn_small_bwd_kernel, dim3(C, N), s, a.da, a.da_nstride, a.out, a.out_nstride, a.y, a.y_nstride, a.dy, a.dy_nstride, C, HW, N,
                           a.gamma, a.mean, a.rstd, a.slope, a.dgamma, a.dbeta, a.accumulate, u, a.p_nstride, a.batch, pr, sl);
         break;
     }

@@ -147,6 +147,9 @@ struct BnArgs {
 };
 int bn_fwd_launch(const BnArgs& a, hipStream_t s);
 int bn_bwd_launch(const BnArgs& a, hipStream_t s);
+// test hook: the small-plane kernels are instantiated per feature mask (gen_bn.hip, BN_F_*); mask >= 0 makes every small-plane launch take that
+// instance (31 = the fully general one) and fail with SPLICE_ERR_ARG where its arguments need a feature the instance lacks; -1 = automatic again
+int bn_small_force_instance(int mask);
 int upsample2x_fwd_launch(const float* in, size_t in_nstride, float* out, size_t out_nstride, int N, int C, int h, int w, int Ho, int Wo, hipStream_t s);
 int upsample2x_bwd_launch(const float* dout, size_t dout_nstride, float* din, size_t din_nstride, int N, int C, int h, int w, int Ho, int Wo, hipStream_t s);
 // sigmoid backward of the [N][C][HW] head + per-channel sums of the result (the head's bias gradient) in two

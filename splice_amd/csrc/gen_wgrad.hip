@@ -42,11 +42,15 @@ __device__ __forceinline__ void conv_wgrad_body(const WgradArgs& a, int chunk, i
     const int p_begin = ch_in_img * a.pix_per_chunk;
     const int p_end = min(p_begin + a.pix_per_chunk, HWo);
     // per-thread gather descriptors (k = wave + 4*i is wave-uniform): channel + tap displacement
+    // The 3x3 body of 128 output channels is the variant that peaks: one VGPR over the 256 of two waves per SIMD, which made the big class the
+    // generator's only scratch user (every wave of every launch paid the scratch set-up).  Its descriptors are formed from the wave index as
+    // a scalar, so they live in SGPRs: 27 VGPRs less, same values.  The other variants keep their instruction stream.
+    const int wave_g = (KS == 3 && NI == 8) ? __builtin_amdgcn_readfirstlane(wave) : wave;
     int g_coff[NA], g_dy[NA], g_dx[NA];
     unsigned g_cok = 0;
 #pragma unroll
     for (int i = 0; i < NA; ++i) {
-        const int k = wave + 4 * i;
+        const int k = wave_g + 4 * i;
         const int cl = k / T, tap = k % T;
         g_coff[i] = (int)(cl * a.x_cstride);
         g_dy[i] = (ROWS ? krow : tap / KS) - a.pad;
@@ -170,11 +174,26 @@ __device__ __forceinline__ void conv_wgrad_body(const WgradArgs& a, int chunk, i
 // dw[layer][i] (+)= sum_chunk ws[layer][chunk][i] for every conv layer of a backward in one launch
 // n_img > 1 with p_nstride > 0: independent images -- blockIdx.y = image, which sums only ITS chunks (chunk index = image *
 // chunks_per_image + k) into its own gradient arena
-// one chain of a layer's chunk sum: 4 independent partial sums in a FIXED association order, 16 loads in flight
+// one chain of a layer's chunk sum: 4 independent partial sums in a FIXED association order.  The loads of a group go out before its first
+// add, so a walk costs one memory round trip per group: the 224 x 224 layers have 98 chunks and a few hundred weights -- a few dozen
+// threads whose dependent trips ARE the kernel's duration -- hence groups of 32 first (98 chunks: 3 groups + 2 single loads)
+// a loaded value as the register it arrives in, behind every load issued so far: the adds of a group cannot be scheduled in between its
+// loads (left alone the compiler keeps a window of 8 loads in flight, whatever the source order says)
+__device__ __forceinline__ void wgrad_loaded(float& x) { asm volatile("" : "+v"(x) : : "memory"); }
 template <class Load>
 __device__ __forceinline__ float wgrad_chunk_sum(int chunks, Load&& ld) {
     float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
     int c = 0;
+#pragma unroll 1
+    for (; c + 31 < chunks; c += 32) {
+        float v[32];
+#pragma unroll
+        for (int u = 0; u < 32; ++u) v[u] = ld(c + u);
+#pragma unroll
+        for (int u = 0; u < 32; ++u) wgrad_loaded(v[u]);
+#pragma unroll
+        for (int u = 0; u < 32; u += 4) { s0 += v[u]; s1 += v[u + 1]; s2 += v[u + 2]; s3 += v[u + 3]; }
+    }
     for (; c + 15 < chunks; c += 16) {   // 16 loads in flight, added in the order of the 4-wide loop below (same bits)
         float v[16];
 #pragma unroll
@@ -194,27 +213,53 @@ __device__ __forceinline__ float wgrad_chunk_sum(int chunks, Load&& ld) {
 __global__ __launch_bounds__(256) void wgrad_reduce_all_kernel(WgradReduceAll d, const float* __restrict__ ws, float* __restrict__ grads,
                                                                int accumulate, int n_img, size_t p_nstride) {
     const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (gid >= d.total) return;
+    // The layer table is read ONCE per wave -- lane j fetches the entries of layer j (count <= 64, the wave) -- and the search for a thread's
+    // layer runs on registers.  Walking prefix[] in the kernel arguments was one dependent scalar-memory round trip per layer, on lines no
+    // launch has touched before: ~50 of them in the workgroups of the last layers, most of the kernel's 21 us.
+    static_assert(WGRAD_MAX_LAYERS <= 64, "one lane per layer");
+    const int lj = min((int)(threadIdx.x & 63), d.count - 1);
+    const long long hi_j = d.prefix[lj + 1], lo_j = d.prefix[lj], wso_j = d.ws_off[lj], dwo_j = d.dw_off[lj];
+    const int n_j = d.n[lj], chunks_j = d.chunks[lj], vec_j = d.vec[lj];
     int l = 0;
-#pragma unroll 1
-    while (l + 1 < d.count && gid >= d.prefix[l + 1]) ++l;
-    const bool vec = d.vec[l] != 0;
-    const int i = (int)(gid - d.prefix[l]) * (vec ? 4 : 1);
-    const int n = d.n[l];
-    int chunks = d.chunks[l];
-    const float* p = ws + d.ws_off[l] + i;
+    for (int k = 0; k + 1 < d.count; ++k) {   // = while (l + 1 < count && gid >= prefix[l + 1]) ++l: the prefix sums do not decrease
+        const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)hi_j, k);
+        const int hi = __builtin_amdgcn_readlane((int)(hi_j >> 32), k);
+        l += gid >= (long long)(((unsigned long long)(unsigned)hi << 32) | lo) ? 1 : 0;
+    }
+    const long long first = __shfl(lo_j, l), ws_off = __shfl(wso_j, l), dw_off = __shfl(dwo_j, l);
+    const int n = __shfl(n_j, l);
+    int chunks = __shfl(chunks_j, l);
+    const bool vec = __shfl(vec_j, l) != 0;
+    if (gid >= d.total) return;   // (behind the lane exchange: every lane holds a layer)
+    const int i = (int)(gid - first) * (vec ? 4 : 1);
+    const float* p = ws + ws_off + i;
     if (p_nstride) {
         chunks /= n_img;
         p += (size_t)blockIdx.y * chunks * n;
         grads += (size_t)blockIdx.y * p_nstride;
     }
-    float* q = grads + d.dw_off[l] + i;
+    float* q = grads + dw_off + i;
     if (vec) {
         // four neighbouring elements per thread through 16-byte loads (round 4: the reduction streams 15 MB of partials per image and
         // was latency-bound on 4-byte accesses); every element still sums its chunks in the order of the scalar path: same bits
         float4 s = {0.f, 0.f, 0.f, 0.f};
         float4 a0 = s, a1 = s, a2 = s, a3 = s;
         int c = 0;
+#pragma unroll 1
+        for (; c + 31 < chunks; c += 32) {   // (32 x 16 B in flight: the long walks of the 224 x 224 layers, see wgrad_chunk_sum)
+            float4 v[32];
+#pragma unroll
+            for (int u = 0; u < 32; ++u) v[u] = *reinterpret_cast<const float4*>(p + (size_t)(c + u) * n);
+#pragma unroll
+            for (int u = 0; u < 32; ++u) { wgrad_loaded(v[u].x); wgrad_loaded(v[u].y); wgrad_loaded(v[u].z); wgrad_loaded(v[u].w); }
+#pragma unroll
+            for (int u = 0; u < 32; u += 4) {
+                a0.x += v[u].x; a0.y += v[u].y; a0.z += v[u].z; a0.w += v[u].w;
+                a1.x += v[u + 1].x; a1.y += v[u + 1].y; a1.z += v[u + 1].z; a1.w += v[u + 1].w;
+                a2.x += v[u + 2].x; a2.y += v[u + 2].y; a2.z += v[u + 2].z; a2.w += v[u + 2].w;
+                a3.x += v[u + 3].x; a3.y += v[u + 3].y; a3.z += v[u + 3].z; a3.w += v[u + 3].w;
+            }
+        }
         for (; c + 7 < chunks; c += 8) {   // (8 x 16 B in flight; chains by c mod 4 as in wgrad_chunk_sum)
             float4 v[8];
 #pragma unroll
