@@ -471,6 +471,18 @@ typedef struct splice_stop_state {
 int splice_step_set_stop_rule(void* step, int window, float rel, int patience, int min_steps);
 /* copies the handle's [pairs] state records to host memory `out` (synchronises `stream`); all zero / -1 while the rule is off */
 int splice_step_stop_state(void* step, splice_stop_state* out, splice_stream_t stream);
+/* Start a handle at step next_step_idx of a run that other handles carried so far (a resumed run, a compacted engine): sets what a
+ * handle keeps between steps -- whether the global structure and identity terms are on (next_step_idx > cls_warmup; only the run of
+ * step cls_warmup itself switches them on) and the [pairs] stop records, copied from HOST memory `stop` (synchronises `stream`).
+ * `stop` is given exactly when the handle has the stop rule.  Everything else that makes a pair continue (arenas, BatchNorm buffers,
+ * the other rules' records) is the caller's memory.  After the rule setters, before the first splice_step_run. */
+int splice_step_restore(void* step, int next_step_idx, const splice_stop_state* stop, splice_stream_t stream);
+/* Gather form of the input staging: A_crop / B_crop / A_entire of splice_step_run then hold pairs_in pairs (pair-major, as the handle's
+ * own layout), and pair p of the handle takes pair rows[p] of them -- its n_crops A crops, its B crops, its entire image -- in the one
+ * staging launch, the table riding in its by-value arguments.  rows: host, strictly increasing, each < pairs_in; the handle's pairs
+ * <= pairs_in <= SPLICE_STEP_MAX_PAIR_CFGS.  The staged buffers hold the bytes a flat copy of the gathered batches would: captured
+ * graphs and everything downstream are unchanged.  rows NULL: off (the default). */
+int splice_step_set_input_rows(void* step, int pairs_in, const int* rows);
 /* The rule alone, as the step's loss kernel runs it: one step of `pairs` slots.  state: device [pairs] records (the caller starts them
  * as zeros with stop_step -1); losses8: device [pairs][8], element 0 of a row is the slot's loss; counted == 0: nothing happens. */
 int splice_plateau_update(splice_stop_state* state, const float* losses8, int pairs, int window, float rel, int patience, int min_steps,

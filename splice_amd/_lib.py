@@ -240,6 +240,9 @@ _SIGNATURES = {
     "splice_step_set_stop_rule": ([_vp, _i, _f, _i, _i], _i),
     "splice_step_stop_state": ([_vp, _vp, _vp], _i),
     "splice_plateau_update": ([_vp, _vp, _i, _i, _f, _i, _i, _i, _i, _vp], _i),
+    # pair snapshots: start a handle at step k, stage the live pairs out of the caller's larger batches
+    "splice_step_restore": ([_vp, _i, _vp, _vp], _i),
+    "splice_step_set_input_rows": ([_vp, _i, _vp], _i),
     "splice_gen_buffer_count": ([_vp], C.c_longlong),
     "splice_gen_num_buffers": ([_vp], _i),
     "splice_gen_buffer_info": ([_vp, _i, C.POINTER(C.c_char_p), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)], _i),

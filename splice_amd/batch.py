@@ -190,6 +190,12 @@ def _write_result(root, name, res):
     os.replace(tmp, os.path.join(pair_dir, "out", "result.json"))
 
 
+def retry_resumes(overrides):
+    """An item that is retried after a killed worker runs with ``resume: true`` when the batch writes checkpoints (``checkpoint_every`` > 0)."""
+    every = (overrides or {}).get("checkpoint_every", 0)
+    return isinstance(every, int) and not isinstance(every, bool) and every > 0
+
+
 def _worker(gpu, visible_id, root, names, items, head, current, runner, overrides, pin_gpu, group_runner="splice_amd.batch:train_group_runner", redo=None,
             sweep=None):
     if pin_gpu:   # must happen before the HIP runtime starts in this process
@@ -199,7 +205,8 @@ def _worker(gpu, visible_id, root, names, items, head, current, runner, override
     while True:
         with head.get_lock():             # the shared words: index of the next unclaimed work item, and the items handed back
             k = next((j for j in range(len(items)) if redo[j]), None) if redo is not None else None   # (by the parent: their worker was killed)
-            if k is not None:
+            retried = k is not None
+            if retried:
                 redo[k] = 0
             else:
                 k = head.value
@@ -209,14 +216,16 @@ def _worker(gpu, visible_id, root, names, items, head, current, runner, override
         if k >= len(items):
             break
         item = items[k]
+        # an item handed back after its worker was killed continues from the checkpoint that worker left, where the run writes them
+        item_overrides = dict(overrides, resume=True) if retried and retry_resumes(overrides) else dict(overrides)
         if len(item) > 1:                 # one MultiPairEngine for the group
             run_group = run_group or _resolve(group_runner)
-            for i, res in zip(item, run_group([os.path.join(root, names[i]) for i in item], dict(overrides))):
+            for i, res in zip(item, run_group([os.path.join(root, names[i]) for i in item], item_overrides)):
                 _write_result(root, names[i], dict(res, pair=names[i], index=i, gpu=gpu))
         else:
             run = run or _resolve(runner)
             i = item[0]
-            args = (os.path.join(root, names[i]), dict(overrides)) + ((list(sweep),) if sweep is not None else ())
+            args = (os.path.join(root, names[i]), item_overrides) + ((list(sweep),) if sweep is not None else ())
             res = dict(run(*args) or {})
             _write_result(root, names[i], dict(res, pair=names[i], index=i, gpu=gpu))
         current[gpu] = -1
@@ -238,7 +247,8 @@ def run_batch(root, n_gpus=1, overrides=None, runner="splice_amd.batch:train_run
     ``sizes``: per pair ``((A_w, A_h), (B_w, B_h))`` if already known (default: read from the image headers).
     ``pin_gpu=False`` leaves device visibility alone (CPU tests).  A worker KILLED BY A SIGNAL (a crash below Python: the HIP
     runtime's handler thread has done that) is replaced by a fresh process on the same GPU and the item it
-    was running goes back to the queue, at most ``max_retries`` times per item; a worker that ends with a Python error -- a
+    was running goes back to the queue, at most ``max_retries`` times per item -- from step 0, or with ``checkpoint_every`` > 0 in the overrides from the last
+    checkpoint the killed worker wrote (the retry runs with ``resume: true``); a worker that ends with a Python error -- a
     deterministic failure -- or an item out of retries takes the batch down with a RuntimeError naming the pairs it was running and
     the pairs left undone; the other workers drain the rest of the queue first, and finished pairs keep their ``result.json``.
     ``sweep``: a list of variant override dicts, or of ``"KEY=V1,V2"`` specs expanded as ``--sweep`` does (``sweep_variants``): every
@@ -282,10 +292,12 @@ def run_batch(root, n_gpus=1, overrides=None, runner="splice_amd.batch:train_run
     if pin_gpu and len(visible_ids) < n_gpus:
         raise ValueError(f"run_batch: {n_gpus} workers requested, {len(visible_ids)} visible GPUs")
     for name in names:                      # a stale result of an earlier batch must not pass for this one's
-        try:
-            os.remove(os.path.join(root, name, "out", "result.json"))
-        except OSError:
-            pass
+        stale = ["result.json"] + (["checkpoint.pt"] if not (overrides or {}).get("resume") else [])   # (nor a checkpoint, unless the batch asks to resume)
+        for leftover in stale:
+            try:
+                os.remove(os.path.join(root, name, "out", leftover))
+            except OSError:
+                pass
     ctx = mp.get_context("spawn")   # fresh interpreters: the HIP runtime must not be inherited through fork
     head = ctx.Value("i", 0)
     current = ctx.Array("i", [-1] * n_gpus)

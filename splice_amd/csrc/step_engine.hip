@@ -142,6 +142,10 @@ struct SpliceStep {
     splice_lr_state* lr_state = nullptr;
     int* lr_cuts = nullptr;
     float* lr_eff = nullptr;
+    // the row table of the gather staging (splice_step_set_input_rows): pair p of the handle is pair in_rows[p] of the caller's pairs_in
+    // pairs; pairs_in 0: off -- the step launches what it always did
+    int pairs_in = 0;
+    int in_rows[SPLICE_STEP_MAX_PAIR_CFGS] = {};
 };
 
 static size_t arena_floats(const SpliceStep* st) { return st->astride ? st->pairs * st->astride : (size_t)st->nparams; }   // of all pairs' arenas
@@ -313,6 +317,40 @@ __global__ __launch_bounds__(256) void stage_inputs_kernel(StageArgs a) {
         }
     }
     if (gid == 0) {
+        *a.ip = a.iv;
+        if (a.fp) {
+#pragma unroll
+            for (int k = 0; k < SPLICE_STEP_MAX_PAIR_CFGS; ++k)
+                if (k < a.nf) a.fp[k] = a.fv[k];
+        }
+    }
+}
+// The gather form of the staging launch (splice_step_set_input_rows): the caller's batches hold pairs_in pairs, the handle's pair
+// blockIdx.y takes the block of pair rows[blockIdx.y] -- blk[k] floats of buffer k: its nA A crops, its nB B crops, its one entire
+// image.  The staged buffers hold the bytes the flat form would have been handed.  A kernel of its own: stage_inputs_kernel, which
+// every handle without a row table launches, keeps its instructions.  16-byte loads and stores when a pair's block is a multiple of 4
+// floats and both base pointers are aligned (then every pair's block is), else the scalar path, as the flat kernel.
+struct StageRowsArgs { StageArgs a; unsigned long long blk[3]; int rows[SPLICE_STEP_MAX_PAIR_CFGS]; };
+__global__ __launch_bounds__(256) void stage_inputs_rows_kernel(StageRowsArgs r) {
+    const StageArgs& a = r.a;
+    const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+    const size_t row = (size_t)r.rows[blockIdx.y];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        if (!a.src[k]) continue;
+        const size_t n = r.blk[k];
+        const float* src = a.src[k] + row * n;
+        float* dst = a.dst[k] + (size_t)blockIdx.y * n;
+        const bool vec = (n & 3) == 0 && ((reinterpret_cast<size_t>(a.src[k]) | reinterpret_cast<size_t>(a.dst[k])) & 15) == 0;
+        if (vec) {
+            const float4* s4 = reinterpret_cast<const float4*>(src);
+            float4* d4 = reinterpret_cast<float4*>(dst);
+            for (size_t i = gid; i < n / 4; i += stride) d4[i] = s4[i];
+        } else {
+            for (size_t i = gid; i < n; i += stride) dst[i] = src[i];
+        }
+    }
+    if (gid == 0 && blockIdx.y == 0) {
         *a.ip = a.iv;
         if (a.fp) {
 #pragma unroll
@@ -760,6 +798,50 @@ int splice_step_set_lr_plateau(void* h, float factor, int patience, float min_sc
     st->lr_rule = LrRule{factor, patience, min_scale}; st->lr_state = state; st->lr_cuts = cut_steps;
     return SPLICE_OK;
 }
+// Start the handle at step next_step_idx of a run other handles carried so far (a resumed run, a compacted engine; DESIGN.md section
+// 9g).  What a handle keeps from one step to the next, and this call therefore sets, is two things: ssim_id_on, which only the run of step
+// cls_warmup switches on, and the stop records.  Nothing else in the handle is state: dev_t and the lr(s) are staged by every step's
+// first launch, lr_eff is written by each step's loss kernel before the update of that step reads it, the clip partials and the loss
+// partials are scratch of one step, the graphs are captured once the shapes have repeated, and the arenas, the BatchNorm buffers and
+// the other rules' records are the caller's.  stop: host, [pairs] records, given exactly when the handle has the stop rule.  After
+// the rule setters, before the first splice_step_run.
+int splice_step_restore(void* h, int next_step_idx, const splice_stop_state* stop, splice_stream_t stream) {
+    SpliceStep* st = (SpliceStep*)h;
+    if (!st || next_step_idx < 0) return SPLICE_ERR_ARG;
+    if (st->runs > 0) { splice_set_error("splice_step_restore: a handle is restored before its first step"); return SPLICE_ERR_STATE; }
+    if ((stop != nullptr) != (st->stop_rule.window > 0)) {
+        splice_set_error("splice_step_restore: the stop records go with the stop rule (splice_step_set_stop_rule): given exactly when the handle has it");
+        return SPLICE_ERR_ARG;
+    }
+    if (stop) {
+        HIPCHK(hipMemcpyAsync(st->stop, stop, (size_t)st->pairs * sizeof(splice_stop_state), hipMemcpyHostToDevice, (hipStream_t)stream));
+        HIPCHK(hipStreamSynchronize((hipStream_t)stream));   // (the caller's records may go away)
+    }
+    st->ssim_id_on = next_step_idx > st->cfg.cls_warmup ? 1 : 0;
+    return SPLICE_OK;
+}
+// The gather form of the input staging: the caller's crop batches and entire images hold pairs_in pairs, pair p of the handle is pair
+// rows[p] of them (strictly increasing, < pairs_in <= SPLICE_STEP_MAX_PAIR_CFGS).  The table rides in the staging launch's by-value
+// arguments: no device table, no launch more, no synchronisation; the staged bytes -- all a captured graph sees -- are those of a flat
+// copy of the gathered batches.  rows NULL: off.
+int splice_step_set_input_rows(void* h, int pairs_in, const int* rows) {
+    SpliceStep* st = (SpliceStep*)h;
+    if (!st) return SPLICE_ERR_ARG;
+    if (!rows) { st->pairs_in = 0; return SPLICE_OK; }
+    if (st->leader) { splice_set_error("splice_step_set_input_rows: a follower stages no inputs"); return SPLICE_ERR_STATE; }
+    if (pairs_in < st->pairs || pairs_in > SPLICE_STEP_MAX_PAIR_CFGS) {
+        splice_set_error("splice_step_set_input_rows: the caller's %d pairs must be at least the handle's %d and at most %d", pairs_in, st->pairs, SPLICE_STEP_MAX_PAIR_CFGS);
+        return SPLICE_ERR_ARG;
+    }
+    for (int p = 0; p < st->pairs; ++p)
+        if (rows[p] < 0 || rows[p] >= pairs_in || (p > 0 && rows[p] <= rows[p - 1])) {
+            splice_set_error("splice_step_set_input_rows: rows must be strictly increasing in [0, %d), got rows[%d] = %d", pairs_in, p, rows[p]);
+            return SPLICE_ERR_ARG;
+        }
+    st->pairs_in = pairs_in;
+    for (int p = 0; p < st->pairs; ++p) st->in_rows[p] = rows[p];
+    return SPLICE_OK;
+}
 int splice_step_stop_state(void* h, splice_stop_state* out, splice_stream_t stream) {
     SpliceStep* st = (SpliceStep*)h;
     if (!st || !out) return SPLICE_ERR_ARG;
@@ -1124,7 +1206,18 @@ int splice_step_run(void* h, float* params, float* grads, float* m, float* v, co
         } else if (st->lr_set || st->lr_state) {   // (the plateau lr rule reads its lr_in on the device: without a setter the handle stages cfg.lr itself)
             sa.fp = st->dev_lr; sa.nf = 1; sa.fv[0] = st->lr_set ? st->lr : c.lr;
         }
-        SPLICE_LAUNCH(stage_inputs_kernel, dim3(128 * (P > 4 ? 4 : P)), dim3(256), 0, s, sa);
+        if (st->pairs_in > 0) {   // the caller's batches hold pairs_in pairs: gather this handle's (same launch count, same staged bytes)
+            StageRowsArgs ra = {};
+            ra.a = sa;
+            ra.blk[0] = (size_t)st->na * 3 * c.crop_h * c.crop_w;
+            ra.blk[1] = (size_t)st->nb * 3 * st->cropb_h * st->cropb_w;
+            ra.blk[2] = (size_t)3 * c.ent_h * c.ent_w;
+            for (int p = 0; p < st->pairs; ++p) ra.rows[p] = st->in_rows[p];
+            const int per_pair = st->na > st->nb ? st->na : st->nb;
+            SPLICE_LAUNCH(stage_inputs_rows_kernel, dim3(128 * (per_pair > 4 ? 4 : per_pair), st->pairs), dim3(256), 0, s, ra);
+        } else {
+            SPLICE_LAUNCH(stage_inputs_kernel, dim3(128 * (P > 4 ? 4 : P)), dim3(256), 0, s, sa);
+        }
     }
     // Steps whose shapes differ from the previous step's (the reference's random crop sizes) are launched eagerly.  Capturing EVERY such step into a
     // rotation of executables updated in place was built in round 5, is bit-equal and SLOWER (272.1 -> 265.9 steps/s: recording ~600 nodes +

@@ -36,7 +36,14 @@ DEFAULT_CFG = dict(  # conf/default/config.yaml of the reference
     # ... and one row per step and slot of the loss values (and the gradient norm under clipping), kept on the device, off by default
     loss_trace=False,
     # ... and a cut of a slot's learning rate where the stop rule's windows stop getting better, decided in the loss kernel, off by default
-    lr_plateau_factor=0.0, lr_plateau_patience=1, lr_plateau_min_scale=0.0)
+    lr_plateau_factor=0.0, lr_plateau_patience=1, lr_plateau_min_scale=0.0,
+    # ... and pair snapshots: stopped slots leave the launches; a run writes checkpoints and continues from one; off by default
+    stop_compact=False, checkpoint_every=0, resume=False)
+
+SNAPSHOT_FORMAT = 1
+# Keys of a config that do not enter a slot's arithmetic (paths, logging, and how the loop parks and checkpoints): a snapshot is restored
+# into a slot whose config equals its own on every other key.
+SNAPSHOT_FREE_KEYS = ("dataroot", "log_images_freq", "stop_compact", "checkpoint_every", "resume")
 
 
 # Per-slot keys of a sweep (MultiPairEngine(pair_cfgs=...), train.train_sweep): the five loss weights in the order of
@@ -237,6 +244,35 @@ def lr_records(state_dev, cuts_dev):
                  cut_steps=[int(t) for t in raw[p, 4:4 + max(0, min(int(raw[p, 2]), STOP_HISTORY))]]) for p in range(raw.shape[0])]
 
 
+def compact_rule(c):
+    """``stop_compact`` of config ``c``, checked on the host: a bool, and ``True`` only with the plateau stop
+    rule on (``stop_window > 0``) -- only a stopped slot leaves the launches.  Raises ValueError naming the key."""
+    v = c.get("stop_compact", DEFAULT_CFG["stop_compact"])
+    if not isinstance(v, (bool, np.bool_)):
+        raise ValueError(f"'stop_compact' must be true or false, got {v!r}")
+    if v and stop_rule(c)[0] == 0:
+        raise ValueError("'stop_compact' needs the plateau stop rule: 'stop_window' > 0")
+    return bool(v)
+
+
+def checkpoint_rule(c):
+    """``(checkpoint_every, resume)`` of config ``c``, checked on the host: an integer >= 0 (0: no checkpoint is
+    written) and a bool.  Raises ValueError naming the key."""
+    v = c.get("resume", DEFAULT_CFG["resume"])
+    if not isinstance(v, (bool, np.bool_)):
+        raise ValueError(f"'resume' must be true or false, got {v!r}")
+    return _integer(c, "checkpoint_every", 0), bool(v)
+
+
+def snapshot_cfg_mismatch(a, b):
+    """The first key (sorted) on which the configs ``a`` and ``b`` differ among those that enter a slot's arithmetic -- every key but
+    SNAPSHOT_FREE_KEYS, an absent key standing for its default -- or None."""
+    for key in sorted((set(a) | set(b)) - set(SNAPSHOT_FREE_KEYS)):
+        if a.get(key, DEFAULT_CFG.get(key)) != b.get(key, DEFAULT_CFG.get(key)):
+            return key
+    return None
+
+
 def trace_rule(c):
     """``loss_trace`` of config ``c``, checked on the host: a bool.  Raises ValueError naming the key."""
     v = c.get("loss_trace", DEFAULT_CFG["loss_trace"])
@@ -409,8 +445,12 @@ class MultiPairEngine:
         ``pair_cfgs``: one dict of per-slot overrides per pair (a sweep: PAIR_KEYS -- the five lambdas, lr and its schedule; the
         init keys are the caller's business), checked by ``merge_pair_cfgs``.  Slot p then runs, bit for bit, as a
         ``SpliceEngine`` with ``cfgs[p]`` would; ``lr`` becomes a list of P values."""
+        # (what compact() builds the engine of the live slots from)
+        self._ctor = dict(cfg=dict(cfg), crop_hw=crop_hw, entire_hw=entire_hw, device=device, n_crops=n_crops, fp8=fp8, top_cls_only=top_cls_only,
+                          pair_cfgs=None if pair_cfgs is None else [dict(v) for v in pair_cfgs])
         self.cfg = dict(DEFAULT_CFG, **cfg)
         self.stop_rule = stop_rule(self.cfg)   # (host checks first: nothing below this line has touched a GPU yet)
+        self.stop_compact = compact_rule(self.cfg)
         self.ema_rule = ema_rule(self.cfg)
         self.ema = None
         self.grad_clip = grad_clip_rule(self.cfg)
@@ -475,7 +515,8 @@ class MultiPairEngine:
         self.stride = n if P == 1 else (n + 63) // 64 * 64
         self.params = torch.zeros(P * self.stride, device=self.device)
         for p_, st in enumerate(gen_states):
-            self.params[p_ * self.stride: p_ * self.stride + n] = self.gen.flatten(st)
+            if st is not None:   # (None: the slot is filled by restore())
+                self.params[p_ * self.stride: p_ * self.stride + n] = self.gen.flatten(st)
         self.grads = torch.zeros_like(self.params)
         self.m = torch.zeros_like(self.params)
         self.v = torch.zeros_like(self.params)
@@ -485,6 +526,10 @@ class MultiPairEngine:
             if name.endswith("running_var"):
                 self.running[:, off:off + cnt] = 1.0
         self.generator_calls = [0] * len(gen_states)   # per pair: every BatchNorm's num_batches_tracked (one per netG call)
+        # pair snapshots.  The slots keep their external numbers: P_in of them, of which `live` (ascending) are
+        # still in the launches -- P = len(live), slot live[i] is row i of every arena and record -- and `_parked` holds the device
+        # snapshot of every slot compact() took out.  Without stop_compact nothing is ever parked: live = 0 .. P - 1.
+        self.P_in, self.live, self._parked = P, list(range(P)), {}
         Pz = c["dino_global_patch_size"]
         ch, cw = crop_hw
         vh, vw = resize_output_size(ch, cw, Pz, 480)
@@ -591,7 +636,10 @@ class MultiPairEngine:
     def step(self, A_crop, B_crop, A_entire=None, _repeat=False):
         """One optimisation step of every pair, asynchronous on the current stream.  Tensors: fp32 CUDA ``[P,3,h,w]`` in
         [0,1] (``[3,h,w]`` accepted for P = 1).  Returns the device tensor ``[P,8]`` of losses (see LOSS_KEYS).
-        ``_repeat``: another phase of the step just run (``splice_step_set_phases``): no bookkeeping."""
+        ``_repeat``: another phase of the step just run (``splice_step_set_phases``): no bookkeeping.
+        With ``stop_compact`` the inputs keep the ``P_in`` pairs the engine was built for, whatever has been parked since (the
+        staging launch gathers the live pairs), and the returned tensor -- ``losses_dev`` -- has one row per entry of ``engine.live``,
+        in that order; after a step that closes a window the engine calls ``compact()`` itself."""
         if not _repeat:
             self.step_idx += 1
             if self._pair_lr:   # every slot's own schedule; staged per step, re-sent only when a value changes
@@ -605,16 +653,19 @@ class MultiPairEngine:
                     _lib.check(_lib.lib().splice_step_set_lr(self.handle, self.lr), "step_set_lr")
                 if self._lr_list:
                     self.lr = [self.lr] * self.P
+            if self._parked and self._lr_list:   # (a parked slot's entry: its own schedule goes on, as the frozen slot's does)
+                live_lr = dict(zip(self.live, self.lr))
+                self.lr = [live_lr[p] if p in live_lr else self._parked_schedules[p].lr(self.step_idx) for p in range(self.P_in)]
         for t, n in ((A_crop, self.slots_ab[0]), (B_crop, self.slots_ab[1])):
             assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
-            assert t.numel() == n * 3 * t.shape[-2] * t.shape[-1], (tuple(t.shape), n)
+            assert t.numel() == n // self.P * self.P_in * 3 * t.shape[-2] * t.shape[-1], (tuple(t.shape), n)
         crops = tuple(A_crop.shape[-2:]) + tuple(B_crop.shape[-2:])
         if crops != self._cur_crops:   # per-step random crop sizes (data/transforms.py:21-22)
             _lib.check(_lib.lib().splice_step_set_crops(self.handle, *crops), "step_set_crops")
             self._cur_crops = crops
         entire = self.plan_e is not None and self.step_idx % self.cfg["entire_A_every"] == 0
         if A_entire is not None:
-            assert A_entire.is_cuda and A_entire.is_contiguous() and A_entire.numel() == self.P * 3 * self.entire_hw[0] * self.entire_hw[1]
+            assert A_entire.is_cuda and A_entire.is_contiguous() and A_entire.numel() == self.P_in * 3 * self.entire_hw[0] * self.entire_hw[1]
         _lib.check(_lib.lib().splice_step_run(self.handle, _lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(self.m), _lib.ptr(self.v),
                                               _lib.ptr(A_crop), _lib.ptr(B_crop), _lib.ptr(A_entire), self.step_idx,
                                               _lib.ptr(self.losses_dev), _lib.current_stream()), "step_run")
@@ -622,6 +673,8 @@ class MultiPairEngine:
             self.generator_calls = [n + (3 if entire else 2) for n in self.generator_calls]   # models/model.py:15-23: G(A_global) [, G(A)], G(B_global)
             if self.stop_rule[0] > 0 and self.window_closes(self.step_idx):
                 self._stop_dirty = True
+                if self.stop_compact:   # (the host reads the stop records after such a step anyway: no step gains a synchronisation)
+                    self.compact()
         return self.losses_dev
 
     # ---- the plateau stop rule: decided per slot on the device; the host asks only where the answer can change
@@ -633,13 +686,173 @@ class MultiPairEngine:
     def stop_state(self):
         """One dict per slot -- ``stopped_at`` (step index, or None while the slot runs), ``windows`` closed, ``best`` window mean,
         ``bad`` consecutive windows that were not better -- copied from the device (waits for the current stream)."""
+        rec = self._stop_records()
+        self._stopped = [r[5] if r[5] >= 0 else None for r in rec]
+        if self.lr_state_dev is not None:   # (a window closed: the only steps at which a scale can move)
+            self._lr_scale = [float(d["scale"]) for d in MultiPairEngine.lr_state(self)]
+        self._stop_dirty = False
+        return [dict(stopped_at=k, windows=r[2], best=r[3], bad=r[4]) for k, r in zip(self._stopped, rec)]
+
+    def _stop_records(self):
+        """Per external slot the ``splice_stop_state`` record as a tuple ``(sum, count, windows, best, bad, stop_step)``: the live
+        slots' from the device (waits for the current stream), a parked slot's as it stood when the slot was parked -- behind its stop
+        step a slot's record only digests the losses of frozen weights."""
         rec = (_lib.StopState * self.P)()
         _lib.check(_lib.lib().splice_step_stop_state(self.handle, rec, _lib.current_stream()), "step_stop_state")
-        self._stopped = [r.stop_step if r.stop_step >= 0 else None for r in rec]
-        if self.lr_state_dev is not None:   # (a window closed: the only steps at which a scale can move)
-            self._lr_scale = [float(d["scale"]) for d in lr_records(self.lr_state_dev, self.lr_cuts_dev)]
-        self._stop_dirty = False
-        return [dict(stopped_at=k, windows=r.windows, best=r.best, bad=r.bad) for k, r in zip(self._stopped, rec)]
+        return self._per_slot([(r.sum, r.count, r.windows, r.best, r.bad, r.stop_step) for r in rec], lambda s: tuple(s["stop"]))
+
+    # ---- pair snapshots (DESIGN.md section 9g): external slot numbers over the rows of the live slots and the parked states
+    def _parked_states(self):
+        return getattr(self, "_parked", None) or {}
+
+    def _row(self, pair):
+        """Row of external slot ``pair`` in the arenas and records; None: the slot is parked."""
+        live = getattr(self, "live", None)
+        return pair if live is None else live.index(pair) if pair in live else None
+
+    def _per_slot(self, rows, parked):
+        """A list over the external slots: ``rows[i]`` of live slot ``live[i]``, ``parked(state)`` of a parked one."""
+        states = self._parked_states()
+        if not states:
+            return list(rows)
+        return [parked(states[p]) if p in states else rows[self.live.index(p)] for p in range(self.P_in)]
+
+    def snapshot(self, pair, device=None, _stop=None):
+        """Everything that makes external slot ``pair`` continue, as a dict (``format`` 1): the ``numel`` floats of
+        its parameters and optimiser moments, its BatchNorm buffers and ``generator_calls``, and with the rule that keeps them its weight
+        average, best weights and record with the window means, stop record, clip record, lr record with the cut steps, and rows
+        ``0 .. step_idx`` of its loss trace; its last losses row, ``step_idx`` and its config.  The gradient arena is not state: every
+        backward overwrites it.  No arena stride either: a slot continues in an engine of any number of slots (``restore``).
+        ``device="cpu"``: host tensors, a picklable state (waits for the current stream); None: device copies."""
+        states = self._parked_states()
+        if pair in states:
+            # (as the frozen slot of an engine that parks nothing stands now: the step count and the netG calls went on, nothing else did)
+            s = dict(states[pair], step_idx=self.step_idx, generator_calls=self.generator_calls[pair])
+            if "trace" in s:   # (no step behind the stop step writes a frozen slot's rows: they stay NaN)
+                rows = max(0, min(self.step_idx + 1, self.trace_dev.shape[0])) - s["trace"].shape[0]
+                s["trace"] = torch.cat([s["trace"], torch.full((rows, 8), float("nan"), device=s["trace"].device)])
+            return {k: (v.clone() if device is None else v.to(device, copy=True)) if torch.is_tensor(v) else v for k, v in s.items()}
+        if not 0 <= pair < self.P_in:
+            raise ValueError(f"snapshot: no slot {pair} among {self.P_in}")
+        i = self._row(pair)
+        take = (lambda t: t.detach().clone()) if device is None else (lambda t: t.detach().to(device, copy=True))   # (never a view of the engine's memory)
+        s = dict(format=SNAPSHOT_FORMAT, step_idx=self.step_idx, cfg=dict(self.cfgs[pair]), n_crops=tuple(self.n_crops_ab), crop_hw=tuple(self.crop_hw),
+                 entire_hw=tuple(self.entire_hw) if self.plan_e is not None else None, generator_calls=self.generator_calls[pair])
+        arenas = dict(params=self.params, m=self.m, v=self.v, ema=self.ema, best=self.best, best_ema=self.best_ema)
+        for key, arena in arenas.items():
+            if arena is not None:
+                s[key] = take(self._pair_arena(arena, pair, key))
+        rows = dict(running=self.running, losses=self.losses_dev, best_rec=self.best_dev, means=self.means_dev, clip=self.clip_dev,
+                    lr_state=self.lr_state_dev, lr_cuts=self.lr_cuts_dev)
+        for key, table in rows.items():
+            if table is not None:
+                s[key] = take(table[i])
+        if self.trace_dev is not None:
+            s["trace"] = take(self.trace_dev[:max(0, min(self.step_idx + 1, self.trace_dev.shape[0])), i])
+        if self.stop_rule[0] > 0:
+            s["stop"] = tuple((_stop or self._stop_records())[pair])
+        return s
+
+    # what a state holds beside the keys every state has, by the rule that keeps it
+    _STATE_KEYS = dict(ema=("ema",), best=("best", "best_rec", "means"), best_ema=("best_ema",), clip_dev=("clip",), lr_state_dev=("lr_state", "lr_cuts"),
+                       trace_dev=("trace",))
+
+    def _check_states(self, states):
+        """The host side of ``restore``: raises ValueError naming what does not fit, before anything touches a GPU."""
+        states = list(states)
+        if self.step_idx >= 0:
+            raise ValueError(f"restore: the engine has already stepped (step_idx {self.step_idx}); a run is restored into a fresh engine")
+        if len(states) != self.P:
+            raise ValueError(f"restore: {len(states)} states for {self.P} slots (state count)")
+        for k, s in enumerate(states):
+            if not isinstance(s, dict) or s.get("format") != SNAPSHOT_FORMAT:
+                raise ValueError(f"restore: states[{k}] is not a snapshot of 'format' {SNAPSHOT_FORMAT}")
+        if len({s["step_idx"] for s in states}) > 1:
+            raise ValueError(f"restore: the states disagree on 'step_idx' ({[s['step_idx'] for s in states]}): the slots of an engine share the step count")
+        shape = dict(n_crops=tuple(self.n_crops_ab), crop_hw=tuple(self.crop_hw), entire_hw=tuple(self.entire_hw) if self.plan_e is not None else None)
+        for k, s in enumerate(states):
+            key = snapshot_cfg_mismatch(s["cfg"], self.cfgs[self.live[k]])
+            if key is not None:
+                raise ValueError(f"restore: states[{k}] was taken under another '{key}' ({s['cfg'].get(key)!r}, the slot has {self.cfgs[self.live[k]].get(key)!r})")
+            for key, val in shape.items():
+                if s[key] != val:
+                    raise ValueError(f"restore: states[{k}] was taken with '{key}' {s[key]!r}, the engine has {val!r}")
+            for attr, keys in self._STATE_KEYS.items():   # (equal configs keep the same rules: a state that lacks a rule's part is damaged)
+                for key in keys:
+                    if (getattr(self, attr, None) is not None) != (key in s):
+                        raise ValueError(f"restore: states[{k}] {'lacks' if key not in s else 'carries'} '{key}', which this engine's rules {'need' if key not in s else 'do not keep'}")
+            if (self.stop_rule[0] > 0) != ("stop" in s):
+                raise ValueError(f"restore: states[{k}] {'lacks' if 'stop' not in s else 'carries'} 'stop', the stop rule's record")
+        return states
+
+    def restore(self, states):
+        """Continue a run: ``states`` holds one ``snapshot()`` per slot of this engine, which has not stepped; all of one ``step_idx``,
+        each taken under the slot's config (every key but ``SNAPSHOT_FREE_KEYS``) -- else ValueError naming the key, before anything
+        touches the GPU.  Fills the arenas, buffers and records, starts the step handle at ``step_idx + 1`` (``splice_step_restore``)
+        and refreshes the host's copies of the stop steps and lr scales.  The next ``step()`` is, bit for bit, the one the snapshotted
+        engine would have run -- whatever number of slots that engine had."""
+        states = self._check_states(states)
+        n, dev = self.gen.numel, self.device
+        for i, s in enumerate(states):
+            sl = slice(i * self.stride, i * self.stride + n)
+            for key, arena in dict(params=self.params, m=self.m, v=self.v, ema=self.ema, best=self.best, best_ema=self.best_ema).items():
+                if arena is not None:
+                    arena[sl].copy_(s[key])
+            for key, table in dict(running=self.running, losses=self.losses_dev, best_rec=self.best_dev, means=self.means_dev, clip=self.clip_dev,
+                                   lr_state=self.lr_state_dev, lr_cuts=self.lr_cuts_dev).items():
+                if table is not None:
+                    table[i].copy_(s[key])
+            if self.trace_dev is not None:
+                self.trace_dev[:s["trace"].shape[0], i].copy_(s["trace"])
+            self.generator_calls[self.live[i]] = int(s["generator_calls"])
+        self.step_idx = int(states[0]["step_idx"])
+        rec = (_lib.StopState * self.P)(*[_lib.StopState(*s["stop"]) for s in states]) if self.stop_rule[0] > 0 else None
+        _lib.check(_lib.lib().splice_step_restore(self.handle, self.step_idx + 1, rec, _lib.current_stream()), "step_restore")
+        if self.stop_rule[0] > 0:
+            self.stop_state()
+
+    def compact(self):
+        """Take the slots that have stopped out of the launches (``stop_compact`` calls it after every step that closes a window; DESIGN.md
+        section 9g).  Nothing happens -- returns False -- unless some live slot has stopped and some other still runs.  Else every
+        stopped slot's device snapshot is parked, a step handle, ViT contexts and generator plans for the remaining slots are built on
+        the same ``VitEngine``, those slots' state moves over (``snapshot`` / ``restore``, device to device), the handle is told which
+        rows of the caller's batches are its pairs, and the old handle is destroyed.  The slots keep their numbers: ``engine.live``
+        lists those still in the launches, every per-slot accessor answers for a parked slot from its parked state, ``step()`` keeps
+        taking ``P_in`` pairs.  Waits for the device."""
+        if self.stop_rule[0] <= 0 or self.step_idx < 0:
+            return False
+        stops = self._stops()
+        gone = [p for p in self.live if stops[p] is not None]
+        keep = [p for p in self.live if stops[p] is None]
+        if not gone or not keep:
+            return False
+        torch.cuda.synchronize(self.device)
+        rec = self._stop_records()
+        parked = {p: self.snapshot(p, _stop=rec) for p in gone}
+        states = [self.snapshot(p, _stop=rec) for p in keep]
+        ct = self._ctor
+        new = MultiPairEngine(ct["cfg"], None, [None] * len(keep), ct["crop_hw"], ct["entire_hw"], device=ct["device"], vit_engine=self.vit,
+                              n_crops=ct["n_crops"], fp8=ct["fp8"], top_cls_only=ct["top_cls_only"],
+                              pair_cfgs=None if ct["pair_cfgs"] is None else [ct["pair_cfgs"][p] for p in keep])
+        new.P_in, new.live, new.cfgs = self.P_in, keep, self.cfgs   # (the external numbering, before restore() looks the configs up)
+        new.generator_calls = self.generator_calls
+        new.restore(states)
+        new.step_idx = self.step_idx
+        _lib.check(_lib.lib().splice_step_set_input_rows(new.handle, self.P_in, (C.c_int * len(keep))(*keep)), "step_set_input_rows")
+        # this engine becomes the new one: its handle, contexts, plans, arenas and records; the old handle goes the way __del__ sends it
+        # (destroyed in front of the contexts and plans it was built on, which go with the last reference to them below)
+        _lib.lib().splice_step_destroy(self.handle)
+        self.handle = None
+        mine = {k: self.__dict__[k] for k in ("_ctor", "_log_plans", "_logged", "lr", "_parked") if k in self.__dict__}
+        schedules = getattr(self, "_parked_schedules", {})
+        self.__dict__.update(new.__dict__)
+        self.__dict__.update(mine)
+        new.handle = None
+        self._parked.update(parked)
+        self._parked_schedules = {**schedules, **{p: LrSchedule(self.cfgs[p]) for p in gone}}
+        self._lr_scale = [1.0] * self.P_in   # (the host's copies in the external numbering: refreshed from the records by the next question)
+        self._stop_dirty = True
+        return True
 
     def _stops(self):
         if self._stop_dirty:   # (asks the device only if a window closed since the last answer)
@@ -674,7 +887,7 @@ class MultiPairEngine:
         list over the slots for ``pair=None``."""
         if self.lr_state_dev is None:
             raise RuntimeError("lr_state: the lr is not cut on a plateau (lr_plateau_factor == 0)")
-        dicts = lr_records(self.lr_state_dev, self.lr_cuts_dev)
+        dicts = self._per_slot(lr_records(self.lr_state_dev, self.lr_cuts_dev), lambda s: lr_records(s["lr_state"][None], s["lr_cuts"][None])[0])
         return dicts if pair is None else dicts[pair]
 
     # ---- the best window's weights (DESIGN.md section 9d)
@@ -688,12 +901,12 @@ class MultiPairEngine:
         self._need_best("pair_best")
         if ema and self.best_ema is None:
             raise RuntimeError("pair_best: no weight average is kept (ema_decay == 0)")
-        arena = self.best_ema if ema else self.best
-        return arena[pair * self.stride: pair * self.stride + self.gen.numel]
+        return self._pair_arena(self.best_ema if ema else self.best, pair, "best_ema" if ema else "best")
 
     def _best_records(self):
         # one device-to-host copy of the records and the histories (the ints ride as float bit patterns); waits for the current stream
         raw = torch.cat([self.best_dev.view(torch.float32), self.means_dev], dim=1).cpu().numpy()
+        raw = np.stack(self._per_slot(list(raw), lambda s: torch.cat([s["best_rec"].view(torch.float32), s["means"]]).cpu().numpy()))
         return raw[:, :2].copy().view(np.int32), raw[:, 2:]
 
     def best_state(self, pair=None):
@@ -726,13 +939,13 @@ class MultiPairEngine:
         over the slots for ``pair=None``."""
         if self.clip_dev is None:
             raise RuntimeError("clip_state: the gradient is not clipped (grad_clip_norm == 0)")
-        dicts = clip_records(self.clip_dev)
+        dicts = self._per_slot(clip_records(self.clip_dev), lambda s: clip_records(s["clip"][None])[0])
         return dicts if pair is None else dicts[pair]
 
     def losses(self, pair=None):
         """Host dict(s) of the last step's losses with the reference's keys (inactive terms omitted): one dict for ``pair``,
         a list over the pairs for ``pair=None``."""
-        rows = self.losses_dev.cpu().tolist()
+        rows = self._per_slot(self.losses_dev.cpu().tolist(), lambda s: s["losses"].cpu().tolist())   # (a parked slot: its last own row)
         acts = self.active_terms(self.step_idx)
         dicts = [{k: vals[i] for i, k in enumerate(LOSS_KEYS) if act[k]} for vals, act in zip(rows, acts)]
         return dicts if pair is None else dicts[pair]
@@ -740,7 +953,8 @@ class MultiPairEngine:
     def active_terms(self, step_idx):
         """Per slot: which of LOSS_KEYS step ``step_idx`` computes (``engine.active_terms``; a slot's terms follow that slot's own
         lambdas).  Host arithmetic only."""
-        return [active_terms(c, step_idx, self.plan_e is not None) for c in (self.cfgs if len(self.cfgs) == self.P else [self.cfg] * self.P)]
+        slots = getattr(self, "P_in", self.P)
+        return [active_terms(c, step_idx, self.plan_e is not None) for c in (self.cfgs if len(self.cfgs) == slots else [self.cfg] * slots)]
 
     # ---- the loss trace (DESIGN.md section 9e)
     def loss_trace(self, pair=None):
@@ -753,8 +967,9 @@ class MultiPairEngine:
             raise RuntimeError("loss_trace: no trace is kept (loss_trace is off)")
         rows = min(self.step_idx + 1, self.trace_dev.shape[0])
         host = self.trace_dev[:rows].cpu().numpy()
-        stops = self._stops() if self.stop_rule[0] > 0 else [None] * self.P
-        out = [host[:rows if k is None else min(rows, k + 1), p].copy() for p, k in enumerate(stops)]
+        per = self._per_slot([host[:, i] for i in range(host.shape[1])], lambda s: s["trace"].cpu().numpy())
+        stops = self._stops() if self.stop_rule[0] > 0 else [None] * len(per)
+        out = [per[p][:rows if k is None else min(rows, k + 1)].copy() for p, k in enumerate(stops)]
         return out if pair is None else out[pair]
 
     def loss_trace_columns(self):
@@ -767,7 +982,8 @@ class MultiPairEngine:
         cuts = MultiPairEngine.lr_state(self) if self.lr_state_dev is not None else None
         out = []
         for p, rows in enumerate(traces):
-            sch = LrSchedule(self.cfgs[p] if self._pair_lr else self.cfg)   # (a fresh recurrence: the engine's own stays where it is)
+            # (a fresh recurrence: the engine's own stays where it is; a sweep that has parked slots may have left the per-pair path)
+            sch = LrSchedule(self.cfgs[p] if self._pair_lr or self._parked_states() else self.cfg)
             lrs = [sch.lr(s) for s in range(len(rows))]
             if cuts is not None:
                 scales = replay_lr_scales(cuts[p]["cut_steps"], len(rows), self.lr_rule[0], self.lr_rule[2])
@@ -777,16 +993,28 @@ class MultiPairEngine:
 
     def pair_params(self, pair=0):
         """View of one pair's parameter arena (``numel`` floats)."""
-        return self.params[pair * self.stride: pair * self.stride + self.gen.numel]
+        return self._pair_arena(self.params, pair, "params")
+
+    def _pair_arena(self, arena, pair, key):
+        """The ``numel`` floats of external slot ``pair`` in ``arena``, or -- the slot is parked -- its parked tensor ``key``."""
+        row = self._row(pair)
+        if row is None:
+            return self._parked[pair][key]
+        return arena[row * self.stride: row * self.stride + self.gen.numel]
+
+    def _running_row(self, pair):
+        row = self._row(pair)
+        return self._parked[pair]["running"] if row is None else self.running[row]
 
     def pair_grads(self, pair=0):
-        return self.grads[pair * self.stride: pair * self.stride + self.gen.numel]
+        """(the gradient arena is scratch of a step: a parked slot has none)"""
+        return self._pair_arena(self.grads, pair, "grads")
 
     def pair_ema(self, pair=0):
         """View of one pair's weight average (``ema_decay > 0``), laid out like ``pair_params``."""
         if self.ema is None:
             raise RuntimeError("pair_ema: no weight average is kept (ema_decay == 0)")
-        return self.ema[pair * self.stride: pair * self.stride + self.gen.numel]
+        return self._pair_arena(self.ema, pair, "ema")
 
     def generate(self, img, pair=0, track_running_stats=False, ema=False, best=False):
         """netG_pair(img) under no_grad (the logging forward of train.py:70-73); img ``[n,3,H,W]``.  The reference's net
@@ -822,7 +1050,7 @@ class MultiPairEngine:
         if self._frozen(pair):   # (a slot that stopped at an earlier step: its buffers stay those of its last own step)
             return
         plans = (C.c_void_p * 1)(plan.handle)
-        _lib.check(_lib.lib().splice_gen_running_stats_update(plans, 1, _lib.ptr(self.running[pair]), 0, 0.1, _lib.current_stream()), "running_stats_update")
+        _lib.check(_lib.lib().splice_gen_running_stats_update(plans, 1, _lib.ptr(self._running_row(pair)), 0, 0.1, _lib.current_stream()), "running_stats_update")
         self.generator_calls[pair] += 1
 
     def state_dict(self, pair=0, ema=False, best=False):
@@ -836,7 +1064,7 @@ class MultiPairEngine:
             step_calls = lambda k: 2 * (k + 1) + (k // int(self.cfg["entire_A_every"]) + 1 if self.plan_e is not None else 0)
             calls -= step_calls(self.step_idx) - step_calls(self._stops()[pair])
         for name, (off, cnt) in self.gen.buffer_table.items():
-            out[name] = self.running[pair, off:off + cnt].clone()
+            out[name] = self._running_row(pair)[off:off + cnt].clone()
             if name.endswith("running_var"):
                 out[name[:-len("running_var")] + "num_batches_tracked"] = torch.tensor(calls, dtype=torch.long, device=self.device)
         return out
@@ -890,6 +1118,8 @@ class MultiScaleEngine:
     def __init__(self, cfg, vit_state, gen_state, crop_hw, entire_hw=None, scales=(224, 320, 448), device="cuda", vit_engine=None, n_crops=1,
                  fp8=False):
         self.cfg = dict(DEFAULT_CFG, **cfg)
+        if self.cfg.get("stop_compact"):
+            raise NotImplementedError("stop_compact: stopped slots leave the launches of a MultiPairEngine under its stop rule; MultiScaleEngine has one pair and no stop rule")
         if best_rule(self.cfg):
             raise NotImplementedError("stop_keep_best: the snapshot rides in the fused step's own update under its stop rule; MultiScaleEngine updates outside the step")
         self.best = None
@@ -960,6 +1190,14 @@ class MultiScaleEngine:
 
     def book_logged_forward(self):
         self.engines[0].book_logged_forward()
+
+    def snapshot(self, pair=0, device=None):
+        raise NotImplementedError("snapshot: the run state of a MultiScaleEngine is spread over one phase-mode handle per scale and an update outside the step; "
+                                  "pair snapshots are a MultiPairEngine / SpliceEngine feature")
+
+    def restore(self, states):
+        raise NotImplementedError("restore: the run state of a MultiScaleEngine is spread over one phase-mode handle per scale and an update outside the step; "
+                                  "pair snapshots are a MultiPairEngine / SpliceEngine feature")
 
     stopped_at = None   # (no stop rule here)
     lr_rule = (0.0, 1, 0.0)   # (nor the plateau lr rule)

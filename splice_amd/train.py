@@ -7,7 +7,8 @@ image of ``<dataroot>/A`` and ``<dataroot>/B``, runs ``n_epochs`` optimisation s
 ``callback(output[0])`` with the ``[3,H,W]`` float image.  With ``loss_trace`` (an extension) the run ends by writing
 ``<dataroot>/out/losses.csv``, one line per step, from rows its own kernels kept on the device.  With ``ema_decay > 0`` (an extension) the run ends by writing one more image,
 ``<dataroot>/out/output_ema.png``, from the averaged weights; with ``stop_keep_best`` (an extension of the stop rule) ``output_best.png``,
-from the weights of the step that closed the best window.  The step itself is the fused HIP engine (``SpliceEngine``), one host
+from the weights of the step that closed the best window.  With ``checkpoint_every`` K > 0 (an extension) every K-th step leaves
+``<dataroot>/out/checkpoint.pt``, and ``resume: true`` continues a run from it, bit for bit.  The step itself is the fused HIP engine (``SpliceEngine``), one host
 call per step, losses read back only when a progress line is printed.
 
 Data feed: the reference augments PIL images on the CPU every step (``data/Dataset.py:62-70``).
@@ -174,14 +175,60 @@ def _init_generator(cfg):
     return {k: v.detach().clone() for k, v in netG.state_dict().items() if k in netG.engine.table}
 
 
-def _optimise(cfg, engine, next_inputs, As, writers, callback, progress, single=False):
+CHECKPOINT_NAME = "checkpoint.pt"
+
+
+def save_checkpoint(path, engine, feed, epoch):
+    """One file that continues the run (``checkpoint_every``): the host snapshot of every slot, the feed's step and
+    the states of ``random``, NumPy and torch's CPU and CUDA generators, as they stand after ``epoch`` steps.  Written to a temporary
+    file and moved into place: a reader finds the old file or the new one.  The copies wait for the device: a stall per checkpoint."""
+    slots = getattr(engine, "P_in", getattr(engine, "P", 1))
+    state = {"format": 1, "epoch": int(epoch), "states": [engine.snapshot(p, device="cpu") for p in range(slots)],
+             "feed_step": getattr(feed, "step", None),
+             "rng": {"python": random.getstate(), "numpy": np.random.get_state(), "torch": torch.get_rng_state(),
+                     "cuda": torch.cuda.get_rng_state_all() if torch.cuda.is_available() else []}}
+    tmp = path + ".tmp"
+    torch.save(state, tmp)
+    os.replace(tmp, path)
+
+
+def load_checkpoint(path, engine, feed):
+    """Continue from ``save_checkpoint``'s file: restores every slot of the fresh ``engine`` (``engine.restore``: a file written under
+    another config is refused by the name of the key), the feed's step and the random generators; returns the number of steps done."""
+    state = torch.load(path, map_location="cpu", weights_only=False)
+    if not isinstance(state, dict) or state.get("format") != 1:
+        raise ValueError(f"{path}: not a checkpoint of format 1")
+    engine.restore(state["states"])
+    if feed is not None and state["feed_step"] is not None:
+        feed.step = state["feed_step"]
+    rng = state["rng"]
+    random.setstate(rng["python"])
+    np.random.set_state(rng["numpy"])
+    torch.set_rng_state(rng["torch"])
+    if rng["cuda"] and torch.cuda.is_available():
+        torch.cuda.set_rng_state_all(rng["cuda"])
+    return int(state["epoch"])
+
+
+def _optimise(cfg, engine, next_inputs, As, writers, callback, progress, single=False, feed=None):
     """The optimisation loop of every entry point, and the end of a run: ``cfg['n_epochs']`` steps of ``engine`` on the crops
     ``next_inputs()`` returns (the arguments of ``engine.step``); every ``log_images_freq`` steps one image per slot from ``As`` goes to
     the slot's writer and to ``callback(slot, image)``.  ``single``: the engine is a one-pair engine (one loss in the progress line, and
-    the stop is announced).  Closes the writers."""
+    the stop is announced).  Closes the writers.
+    ``checkpoint_every`` K > 0: after every K-th step ``checkpoint.pt`` is written beside the first slot's ``output.png``
+    (``save_checkpoint``; ``feed``: the data feed whose step it keeps); ``resume``: a run that finds the file continues behind the step it
+    holds, bit for bit as the run that wrote it would have."""
+    from .engine import checkpoint_rule
     n_epochs, freq = cfg['n_epochs'], cfg['log_images_freq']
+    every, resume = checkpoint_rule(cfg)
+    ckpt = os.path.join(writers[0].dir, CHECKPOINT_NAME) if every or resume else None
+    done = 0
     try:
-        for epoch in range(1, n_epochs + 1):
+        if resume and os.path.exists(ckpt):
+            done = load_checkpoint(ckpt, engine, feed)
+            if progress:
+                print(f"resuming behind epoch {done} from {ckpt}")
+        for epoch in range(done + 1, n_epochs + 1):
             inputs = next_inputs()
             log = epoch % freq == 0
             # train.py:70-76 generates the logged image between the loss and backward(): with the weights of epoch - 1
@@ -200,6 +247,8 @@ def _optimise(cfg, engine, next_inputs, As, writers, callback, progress, single=
                 # (the plateau lr rule: the factor the loss kernel multiplies that lr by, the host's copy of the last closed window)
                 scale = f" lr_scale={engine.lr_scale}" if getattr(engine, "lr_rule", (0,))[0] > 0 else ""
                 print(f"Epoch {epoch}: loss={losses} lr={engine.lr}{scale}")
+            if every and epoch % every == 0:
+                save_checkpoint(ckpt, engine, feed, epoch)
             # the plateau stop rule (stop_window > 0; decided on the device): the host asks only after a step that closes a window -- no
             # other step can stop a slot -- and ends the run, once every slot has stopped, with an image of each slot's final parameters
             if engine.window_closes(engine.step_idx) and engine.all_stopped():
@@ -245,7 +294,9 @@ def train_model(dataroot, callback=None, cfg_overrides=None, vit_state=None, pro
     scales = [int(x) for x in (cfg.get('dino_global_scales') or [])]
     crops, entire = (_crop_max(A, B),) * 2, tuple(A.shape[1:])
     if len(scales) > 1:
-        from .engine import MultiScaleEngine
+        from .engine import MultiScaleEngine, checkpoint_rule
+        if any(checkpoint_rule(cfg)):
+            raise NotImplementedError("checkpoint_every / resume: a MultiScaleEngine has no pair snapshots (dino_global_scales with several entries)")
         engine = MultiScaleEngine(cfg, vit_state, gen_state, crops, entire, scales=scales, device=device, n_crops=n_crops, vit_engine=vit_engine, fp8=fp8_mode(cfg))
     else:
         _one_scale(cfg)
@@ -254,7 +305,8 @@ def train_model(dataroot, callback=None, cfg_overrides=None, vit_state=None, pro
     def next_inputs():
         inputs = feed.next()
         return inputs['A_global'], inputs['B_global'], inputs['A'][0] if 'A' in inputs else None
-    _optimise(cfg, engine, next_inputs, [feed.get_A()], [AsyncResultWriter(cfg['dataroot'])], callback and (lambda p, image: callback(image)), progress, single=True)
+    _optimise(cfg, engine, next_inputs, [feed.get_A()], [AsyncResultWriter(cfg['dataroot'])], callback and (lambda p, image: callback(image)), progress, single=True,
+              feed=feed)
     return engine
 
 
@@ -369,7 +421,8 @@ def train_pairs(dataroots, callback=None, cfg_overrides=None, vit_state=None, pr
     (the seed is re-applied before each ``define_G``); writes ``<dataroot>/out/output.png`` per pair; ``callback(pair, image)``.
     ``global_{A,B}_crops_n_crops`` (1..8, equal or not) run as one netG call per pair's crops (at most 32 images per side).
     With deterministic full crops (``use_augmentations: False``, ``min_cover: 1``) the result of every pair is bit-identical to
-    its single ``train_model`` run."""
+    its single ``train_model`` run.  With ``stop_compact`` (and the stop rule) pairs that have stopped leave the launches; every file
+    the run writes stays the same.  ``checkpoint_every`` / ``resume``: as ``train_model``, the file in the first pair's ``out/``."""
     from .engine import MAX_GROUP_IMAGES, MultiPairEngine
     cfg = _load_cfg(None, cfg_overrides)
     n_crops = (int(cfg['global_A_crops_n_crops']), int(cfg['global_B_crops_n_crops']))
@@ -400,7 +453,7 @@ def train_pairs(dataroots, callback=None, cfg_overrides=None, vit_state=None, pr
     def next_inputs():
         inputs = feed.next()
         return inputs['A_global'], inputs['B_global'], inputs.get('A')
-    _optimise(cfg, engine, next_inputs, [feed.get_A(p) for p in range(len(dataroots))], [AsyncResultWriter(root) for root in dataroots], callback, progress)
+    _optimise(cfg, engine, next_inputs, [feed.get_A(p) for p in range(len(dataroots))], [AsyncResultWriter(root) for root in dataroots], callback, progress, feed=feed)
     return engine
 
 
@@ -464,7 +517,7 @@ def train_sweep(dataroot, variants, cfg_overrides=None, vit_state=None, callback
     def next_inputs():   # every slot sees the one feed's crops
         inputs = feed.next()
         return tuple(t.expand(K, -1, -1, -1).contiguous() if t is not None else None for t in (inputs['A_global'], inputs['B_global'], inputs.get('A')))
-    _optimise(cfg, engine, next_inputs, [feed.get_A()] * K, [AsyncResultWriter(cfg['dataroot'], out_dir=d) for d in out_dirs], callback, progress)
+    _optimise(cfg, engine, next_inputs, [feed.get_A()] * K, [AsyncResultWriter(cfg['dataroot'], out_dir=d) for d in out_dirs], callback, progress, feed=feed)
     losses = engine.losses() if engine.step_idx >= 0 else [{} for _ in range(K)]
     for k in range(K):
         with open(os.path.join(out_dirs[k], 'variant.json'), 'w') as f:
