@@ -551,6 +551,41 @@ int splice_optim_step_clip(int kind, float* params, float* grads, const float* g
  * or phase mode (splice_step_set_phases), which the rule in turn bars.  0 < max_norm < inf. */
 int splice_step_set_grad_clip(void* step, float max_norm, splice_clip_state* state);
 
+/* ------------------------------------------------------------------ gradient clipping against the pair's own running norm (DESIGN.md section
+ * 9h; an extension of the clipping above).  The threshold is k times a running mean of the pair's gradient norm, kept per pair and per
+ * REGIME of the step -- regime 1: an entire-image step, 0: any other step from cls_warmup on, -1: a step before cls_warmup, which is
+ * observed by neither reference and clipped by the absolute cap alone -- in a second record beside splice_clip_state.  Stages 1 and 2
+ * of the norm are those above; then thread 0 of the pair's workgroup does (fp32, one rounding per operation, r = regime):
+ *   thr_auto = (r >= 0 && count[r] >= warmup && ref[r] > 0) ? k * ref[r] : +inf
+ *   thr      = max_norm > 0 ? fminf(max_norm, thr_auto) : thr_auto
+ *   norm finite:  coef = fminf(1, thr / (norm + 1e-6f)), skip = 0, clipped += coef < 1; and if r >= 0:
+ *                   x = fminf(norm, thr_auto)          (a spike raises the reference by at most the factor k)
+ *                   ref[r] = count[r] == 0 ? x : beta * ref[r] + (1 - beta) * x;  count[r] += 1
+ *   otherwise:    coef = 0, skip = 1, skipped += 1     (ref and count do not move)
+ *   thr and regime of the record = thr, r
+ * The splice_clip_state record keeps its meaning, and the update reads coef / skip from it as above. */
+typedef struct splice_clip_auto_state {
+    float ref[2];     /* running gradient norm of regime 0 (ordinary steps) and 1 (entire-image steps) */
+    int count[2];     /* steps of either regime observed so far (steps with a non-finite norm are not) */
+    float thr;        /* the last step's threshold; +inf: none */
+    int regime;       /* the last step's regime: -1, 0 or 1 */
+} splice_clip_auto_state;
+/* as splice_grad_norm_pairs with the rule above: auto_state: device, [n_pairs] records (zeros at the start of a run).  max_norm: the
+ * absolute cap, finite and >= 0 (0: none); k finite and >= 1; 0 <= beta < 1; warmup >= 1; regime -1, 0 or 1.  A pair frozen at the
+ * step (stop / step_dev) keeps both records. */
+int splice_grad_norm_pairs_auto(const float* grads, const float* g2, int n_pairs, long long stride, long long n, float max_norm, float k,
+                                float beta, int warmup, int regime, float* partials, splice_clip_state* state,
+                                splice_clip_auto_state* auto_state, const splice_stop_state* stop, const int* step_dev,
+                                splice_stream_t stream);
+/* Clip every pair's gradient inside the step by the rule above, the alternative to splice_step_set_grad_clip (a handle takes one of the
+ * two): the same two norm launches, the second one in its instance with the rule; the regime is fixed per launch sequence (graph
+ * variant) of the step, as "counted" is for the stop rule.  state, auto_state: device, [pairs] records each, the caller's (zeros).  No
+ * launch, event or graph node more than splice_step_set_grad_clip has.  A slot frozen by the stop rule keeps both records of its stop
+ * step.  Before the first splice_step_run only; refused on a handle in gradient-only (splice_step_set_mode) or phase mode
+ * (splice_step_set_phases), which the rule in turn bars.  Arguments as splice_grad_norm_pairs_auto. */
+int splice_step_set_grad_clip_auto(void* step, float max_norm, float k, float beta, int warmup, splice_clip_state* state,
+                                   splice_clip_auto_state* auto_state);
+
 /* ------------------------------------------------------------------ keep the best window's weights (an extension of the stop rule).  A slot
  * stops `patience` windows behind the window the rule judged best, so the weights it is frozen with are not those the rule liked.  While
  * a slot is LIVE at a counted step -- its stop_step < 0 on entry to the rule -- the rule also writes, at the close of a window:
@@ -594,7 +629,8 @@ int splice_step_set_keep_best(void* step, float* best_params, float* best_ema, s
  *   words 0-5   the six values the step's loss kernel writes into losses_out[p][0..5] (splice_step_run), with the same bits, stored
  *               by that kernel;
  *   words 6-7   the pair's gradient norm and clip coefficient of the step (splice_clip_state norm / coef), stored by the norm launch
- *               of a handle with gradient clipping (splice_step_set_grad_clip); without it they are not written.
+ *               of a handle with gradient clipping (splice_step_set_grad_clip or splice_step_set_grad_clip_auto); without it they
+ *               are not written.
  * A step with s >= capacity writes nothing and is no error.  A pair frozen by the stop rule is not written behind its stop step: row
  * stop_step is its last.  The row index is read from the step count on the device, so a replayed graph writes its own step's row.  No
  * launch, event or graph node more, and params / m / v / ema / best arenas / rule records / losses are what they are without it.

@@ -56,6 +56,10 @@ class ClipState(C.Structure):   # splice_clip_state
     _fields_ = [("sumsq", C.c_float), ("norm", C.c_float), ("coef", C.c_float), ("skip", C.c_int), ("clipped", C.c_int), ("skipped", C.c_int)]
 
 
+class ClipAutoState(C.Structure):   # splice_clip_auto_state
+    _fields_ = [("ref", C.c_float * 2), ("count", C.c_int * 2), ("thr", C.c_float), ("regime", C.c_int)]
+
+
 class BestState(C.Structure):   # splice_best_state
     _fields_ = [("best_step", C.c_int), ("best_window", C.c_int)]
 
@@ -203,6 +207,9 @@ _SIGNATURES = {
     "splice_optim_step_pairs_clip": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_longlong, C.c_longlong, _vp, _f, _f, _f, _vp, _vp, _i, _f, _i, _vp, _vp], _i),
     "splice_optim_step_clip": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, _f, _vp, _f, _f, _f, _i, _i, _f, _i, _vp, _vp], _i),
     "splice_step_set_grad_clip": ([_vp, _f, _vp], _i),
+    # ... and against the pair's own running norm
+    "splice_grad_norm_pairs_auto": ([_vp, _vp, _i, C.c_longlong, C.c_longlong, _f, _f, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp], _i),
+    "splice_step_set_grad_clip_auto": ([_vp, _f, _f, _f, _i, _vp, _vp], _i),
     # keep the best window's weights under the stop rule
     "splice_plateau_update_best": ([_vp, _vp, _vp, _vp, _i, _i, _f, _i, _i, _i, _i, _vp], _i),
     "splice_optim_step_pairs_best": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_longlong, C.c_longlong, _vp, _f, _f, _f, _vp, _vp, _i, _f, _i, _vp, _vp, _vp, _vp, _vp], _i),

@@ -30,6 +30,11 @@ update; the run then also writes ``out/output_ema.png`` from the averaged weight
 per pair; a step whose norm is not finite does not update the pair); ``result.json`` carries ``grad_clip_norm``, ``clipped_steps`` and
 ``skipped_steps`` per pair (per variant in a sweep).
 
+``--set grad_clip_auto=2`` (with ``grad_clip_auto_beta`` / ``grad_clip_auto_warmup``; shared by the variants of a sweep) clips every pair's
+gradient to that factor times the pair's own running gradient norm, kept on the device -- one for ordinary, one for entire-image steps;
+``grad_clip_norm`` stays as a cap beside it; ``result.json`` then also carries ``grad_clip_auto`` and ``clip_ref``, the two running norms
+the pair ended with.
+
 ``--set stop_keep_best=true`` (with the stop rule on; shared by the variants of a sweep) keeps, on the device, every pair's weights of the
 step that closed the best window the rule has seen: the run also writes ``out/output_best.png`` (``output_best_ema.png`` with an average),
 and ``result.json`` carries ``best_step``, ``best_window_mean`` and ``window_means``.
@@ -40,8 +45,9 @@ multiplies a pair's learning rate by that factor where the stop rule's windows s
 ``losses.csv`` holds the effective learning rate of every step.
 
 ``--set loss_trace=true`` (shared by the variants of a sweep) keeps one row per step and pair on the device -- the six loss values, and the
-gradient norm and clip coefficient with ``grad_clip_norm`` -- written by the step's own kernels: no copy per step.  The run ends by writing
-``out/losses.csv`` (``out/sweep/<k>/losses.csv`` per variant), and ``result.json`` names the file under ``loss_trace``.
+gradient norm and clip coefficient with ``grad_clip_norm`` / ``grad_clip_auto`` -- written by the step's own kernels: no copy per step.
+The run ends by writing ``out/losses.csv`` (``out/sweep/<k>/losses.csv`` per variant), and ``result.json`` names the file under
+``loss_trace``.
 
     python -m splice_amd.batch --root pairs/ --gpus 8 [--pairs-per-gpu P] [--n_epochs 2000] [--set key=value ...]
 

@@ -42,5 +42,14 @@ int optim_launch(const OptimArgs& a, hipStream_t s);
 // The per-pair gradient norm and clip coefficient (include/splice_hip.h has the rule): two launches, partials[pairs][ceil(n / 4096)] then
 // state[pairs].  stop (optional) with step_dev: a frozen pair is left out of both.  trace (optional, with step_dev; the loss trace,
 // [capacity][pairs][8]): the second launch also stores norm and coef into words 6 and 7 of row *step_dev - 1 of every pair it writes.
+// rule (optional; clipping against the pair's own running norm, include/splice_hip.h): the second launch is its AUTO instance, which also
+// keeps records[pairs]; max_norm is then the absolute cap and may be 0 (none).  Without it max_norm must be finite and > 0.
+struct ClipAutoRule {
+    float k, beta;                     // threshold = k * running norm; the running norm's decay
+    int warmup;                        // observations of a regime before its threshold acts
+    int regime;                        // of this step: -1, 0 or 1
+    splice_clip_auto_state* records;   // device, [pairs]
+};
 int grad_norm_launch(const float* g, const float* g2, int pairs, size_t stride, size_t n, float max_norm, float* partials, splice_clip_state* state,
-                     const splice_stop_state* stop, const int* step_dev, hipStream_t s, float* trace = nullptr, int capacity = 0);
+                     const splice_stop_state* stop, const int* step_dev, hipStream_t s, float* trace = nullptr, int capacity = 0,
+                     const ClipAutoRule* rule = nullptr);

@@ -327,11 +327,16 @@ __global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict
 // Stage 2: workgroup = pair.  The partials in fp64 (their order is fixed, the rounding of 254 of them no longer shows in the fp32 result),
 // then the record.  Thread 0 alone writes it.  TRACE (the loss trace): it also stores the norm and the coefficient into
 // words 6 and 7 of row *step_dev - 1 of the pair's trace ([capacity][pairs][8]; words 0-5 belong to total_loss_kernel), a row beyond
-// capacity left out.  The instance without TRACE does not read the two trailing arguments.
-template <bool TRACE>
+// capacity left out.  The instance without TRACE does not read the two trailing arguments.  AUTO (clipping against the pair's own running
+// norm): the threshold is the smaller of max_norm (0: none) and k times the reference of the step's regime in the
+// pair's second record, which thread 0 then moves towards the norm; a frozen pair keeps both records.  The rule lies behind the TRACE
+// arguments as ONE by-value struct -- a struct is not preloaded into SGPRs, so the preloaded arguments, and with them the register the
+// workgroup index arrives in, are those of the instances without AUTO, which do not read it.
+template <bool TRACE, bool AUTO = false>
 __global__ __launch_bounds__(256) void grad_clip_coef_kernel(const float* __restrict__ partials, unsigned chunks, float max_norm,
                                                              splice_clip_state* __restrict__ state, const splice_stop_state* __restrict__ stop,
-                                                             const int* __restrict__ step_dev, float* __restrict__ trace, int capacity) {
+                                                             const int* __restrict__ step_dev, float* __restrict__ trace, int capacity,
+                                                             const ClipAutoRule rule) {
 #pragma clang fp contract(off)
     __shared__ double sd[256];
     const unsigned pair = blockIdx.x, t = threadIdx.x;
@@ -349,16 +354,37 @@ __global__ __launch_bounds__(256) void grad_clip_coef_kernel(const float* __rest
             splice_clip_state r = state[pair];
             r.sumsq = (float)v;
             r.norm = sqrtf(r.sumsq);
+            float thr = max_norm, thr_auto = __builtin_inff(), ref = 0.f;
+            int seen = 0;
+            const int regime = rule.regime;
+            splice_clip_auto_state* const rec = rule.records + pair;
+            if (AUTO) {   // (regime -1: no reference is read or written, the cap alone acts)
+                if (regime >= 0) {
+                    ref = rec->ref[regime];
+                    seen = rec->count[regime];
+                    if (seen >= rule.warmup && ref > 0.f) thr_auto = rule.k * ref;
+                }
+                thr = max_norm > 0.f ? fminf(max_norm, thr_auto) : thr_auto;
+            }
             if (r.norm <= 3.402823466e+38f) {   // finite (a NaN compares false)
-                r.coef = fminf(1.f, max_norm / (r.norm + 1e-6f));
+                r.coef = fminf(1.f, thr / (r.norm + 1e-6f));   // (+inf / x = +inf: coef 1)
                 r.skip = 0;
                 r.clipped += r.coef < 1.f ? 1 : 0;
+                if (AUTO && regime >= 0) {
+                    const float x = fminf(r.norm, thr_auto);   // a spike raises the reference by at most the factor k
+                    rec->ref[regime] = seen == 0 ? x : rule.beta * ref + (1.f - rule.beta) * x;
+                    rec->count[regime] = seen + 1;
+                }
             } else {
                 r.coef = 0.f;
                 r.skip = 1;
                 r.skipped += 1;
             }
             state[pair] = r;
+            if (AUTO) {
+                rec->thr = thr;
+                rec->regime = regime;
+            }
             if (TRACE) {
                 const int row = *step_dev - 1;
                 if (row >= 0 && row < capacity) {
@@ -372,8 +398,19 @@ __global__ __launch_bounds__(256) void grad_clip_coef_kernel(const float* __rest
 }
 
 int grad_norm_launch(const float* g, const float* g2, int pairs, size_t stride, size_t n, float max_norm, float* partials, splice_clip_state* state,
-                     const splice_stop_state* stop, const int* step_dev, hipStream_t s, float* trace, int capacity) {
-    if (!(max_norm > 0.f) || !(max_norm <= 3.402823466e+38f)) {
+                     const splice_stop_state* stop, const int* step_dev, hipStream_t s, float* trace, int capacity, const ClipAutoRule* rule) {
+    if (rule) {   // the cap is optional beside the running norm
+        if (!(max_norm >= 0.f) || !(max_norm <= 3.402823466e+38f)) {
+            splice_set_error("gradient clipping: beside the running norm max_norm must be a finite number >= 0 (0: no cap), got %g", (double)max_norm);
+            return SPLICE_ERR_ARG;
+        }
+        if (!(rule->k >= 1.f) || !(rule->k <= 3.402823466e+38f) || !(rule->beta >= 0.f && rule->beta < 1.f) || rule->warmup < 1 || rule->regime < -1 ||
+            rule->regime > 1 || !rule->records) {
+            splice_set_error("gradient clipping (max_norm %g): the running norm needs a finite k >= 1, 0 <= beta < 1, warmup >= 1, a regime of -1, 0 or 1 and its records, got k %g, beta %g, warmup %d, regime %d",
+                             (double)max_norm, (double)rule->k, (double)rule->beta, rule->warmup, rule->regime);
+            return SPLICE_ERR_ARG;
+        }
+    } else if (!(max_norm > 0.f) || !(max_norm <= 3.402823466e+38f)) {
         splice_set_error("gradient clipping: max_norm must be a finite number > 0, got %g", (double)max_norm);
         return SPLICE_ERR_ARG;
     }
@@ -397,10 +434,18 @@ int grad_norm_launch(const float* g, const float* g2, int pairs, size_t stride, 
     }
     if (pairs == 1) stride = 0;
     SPLICE_LAUNCH(grad_sumsq_kernel, dim3((unsigned)chunks, (unsigned)pairs), dim3(256), 0, s, g, g2, stride, n, partials, stop, step_dev);
-    if (trace)   // (the trace rides in the launch)
-        SPLICE_LAUNCH(grad_clip_coef_kernel<true>, dim3((unsigned)pairs), dim3(256), 0, s, (const float*)partials, (unsigned)chunks, max_norm, state, stop, step_dev, trace, capacity);
-    else
-        SPLICE_LAUNCH(grad_clip_coef_kernel<false>, dim3((unsigned)pairs), dim3(256), 0, s, (const float*)partials, (unsigned)chunks, max_norm, state, stop, step_dev, (float*)nullptr, 0);
+    const ClipAutoRule a = rule ? *rule : ClipAutoRule{0.f, 0.f, 0, 0, nullptr};
+    if (!trace) capacity = 0;
+    // (the trace and the running norm ride in the launch)
+#define CLIP_COEF_LAUNCH(TRACE, AUTO)                                                                                                                   \
+    SPLICE_LAUNCH((grad_clip_coef_kernel<TRACE, AUTO>), dim3((unsigned)pairs), dim3(256), 0, s, (const float*)partials, (unsigned)chunks, max_norm, state, \
+                  stop, step_dev, trace, capacity, a)
+    if (rule) {
+        if (trace) CLIP_COEF_LAUNCH(true, true); else CLIP_COEF_LAUNCH(false, true);
+    } else {
+        if (trace) CLIP_COEF_LAUNCH(true, false); else CLIP_COEF_LAUNCH(false, false);
+    }
+#undef CLIP_COEF_LAUNCH
     return SPLICE_OK;
 }
 
@@ -481,6 +526,13 @@ int splice_grad_norm_pairs(const float* grads, const float* g2, int n_pairs, lon
                            splice_clip_state* state, const splice_stop_state* stop, const int* step_dev, splice_stream_t stream) {
     return grad_norm_launch(grads, g2, n_pairs, stride < 0 ? 1 : (size_t)stride, n < 1 ? 0 : (size_t)n, max_norm, partials, state, stop, step_dev,
                             (hipStream_t)stream);
+}
+int splice_grad_norm_pairs_auto(const float* grads, const float* g2, int n_pairs, long long stride, long long n, float max_norm, float k, float beta,
+                                int warmup, int regime, float* partials, splice_clip_state* state, splice_clip_auto_state* auto_state,
+                                const splice_stop_state* stop, const int* step_dev, splice_stream_t stream) {
+    const ClipAutoRule rule = {k, beta, warmup, regime, auto_state};
+    return grad_norm_launch(grads, g2, n_pairs, stride < 0 ? 1 : (size_t)stride, n < 1 ? 0 : (size_t)n, max_norm, partials, state, stop, step_dev,
+                            (hipStream_t)stream, nullptr, 0, &rule);
 }
 // as splice_optim_step_pairs_ema (ema optional) with the clip records of splice_grad_norm_pairs; one pair: a single arena of n floats
 int splice_optim_step_pairs_clip(int kind, float* params, float* grads, const float* g2, float* m, float* v, float* ema, int n_pairs, long long stride,

@@ -125,6 +125,9 @@ struct SpliceStep {
     splice_clip_state* clip = nullptr;
     float* clip_partials = nullptr;
     float clip_norm = 0.f;
+    // ... against the pair's own running norm (splice_step_set_grad_clip_auto): the rule with the caller's second [pairs] records; its regime
+    // is filled in per launch sequence; records null: the threshold is clip_norm alone
+    ClipAutoRule clip_rule = {0.f, 0.f, 0, 0, nullptr};
     // keep-best (splice_step_set_keep_best): the caller's [pairs] records, window means and best arena(s); null: off -- the step launches what
     // it always did
     splice_best_state* best = nullptr;
@@ -740,10 +743,34 @@ int splice_step_set_grad_clip(void* h, float max_norm, splice_clip_state* state)
         return SPLICE_ERR_ARG;
     }
     if (int rc = rule_setter_ok(st, "splice_step_set_grad_clip", "the rule is set")) return rc;
+    if (st->clip_rule.records) { splice_set_error("splice_step_set_grad_clip: the handle clips against the running norm (splice_step_set_grad_clip_auto); a handle takes one of the two"); return SPLICE_ERR_STATE; }
     if (st->astride % 4) { splice_set_error("splice_step_set_grad_clip: the arena stride must be a multiple of 4"); return SPLICE_ERR_ARG; }
     if (!st->clip_partials) RC(salloc(st, &st->clip_partials, (size_t)st->pairs * (((size_t)st->nparams + SPLICE_CLIP_CHUNK - 1) / SPLICE_CLIP_CHUNK)));
     st->graphs.retire();
     st->clip = state; st->clip_norm = max_norm;
+    return SPLICE_OK;
+}
+// Gradient clipping of every pair against its own running norm (include/splice_hip.h has the rule): splice_step_set_grad_clip with the second
+// records, which the second norm launch keeps in its AUTO instance.  max_norm is the optional cap (0: none).  The regime is not set here:
+// step_body knows it per launch sequence.
+int splice_step_set_grad_clip_auto(void* h, float max_norm, float k, float beta, int warmup, splice_clip_state* state, splice_clip_auto_state* auto_state) {
+    SpliceStep* st = (SpliceStep*)h;
+    if (!st) return SPLICE_ERR_ARG;
+    if (!state || !auto_state || !(max_norm >= 0.f) || !(max_norm <= 3.402823466e+38f)) {
+        splice_set_error("splice_step_set_grad_clip_auto: needs both state records and a finite max_norm >= 0 (0: no cap), got %g", (double)max_norm);
+        return SPLICE_ERR_ARG;
+    }
+    if (!(k >= 1.f) || !(k <= 3.402823466e+38f) || !(beta >= 0.f && beta < 1.f) || warmup < 1) {
+        splice_set_error("splice_step_set_grad_clip_auto: needs a finite k >= 1, 0 <= beta < 1 and warmup >= 1, got k %g, beta %g, warmup %d", (double)k, (double)beta, warmup);
+        return SPLICE_ERR_ARG;
+    }
+    if (int rc = rule_setter_ok(st, "splice_step_set_grad_clip_auto", "the rule is set")) return rc;
+    if (st->clip && !st->clip_rule.records) { splice_set_error("splice_step_set_grad_clip_auto: the handle clips to a fixed norm (splice_step_set_grad_clip); a handle takes one of the two"); return SPLICE_ERR_STATE; }
+    if (st->astride % 4) { splice_set_error("splice_step_set_grad_clip_auto: the arena stride must be a multiple of 4"); return SPLICE_ERR_ARG; }
+    if (!st->clip_partials) RC(salloc(st, &st->clip_partials, (size_t)st->pairs * (((size_t)st->nparams + SPLICE_CLIP_CHUNK - 1) / SPLICE_CLIP_CHUNK)));
+    st->graphs.retire();
+    st->clip = state; st->clip_norm = max_norm;
+    st->clip_rule = ClipAutoRule{k, beta, warmup, 0, auto_state};
     return SPLICE_OK;
 }
 // Keep every pair's best-window weights (include/splice_hip.h has the rule): the loss kernel's rule writes `state` and `means`, the optimiser
@@ -1118,8 +1145,12 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
         if (stop_on) { a.mask = st->stop; a.mask_step = st->dev_t; a.mask_stride = st->astride; }
         if (st->ema) { a.ema = st->ema; a.ema_decay = st->ema_decay; a.ema_start = st->ema_start; }   // (another kernel: the graph pool keys on it)
         if (st->clip) {   // two launches more: the norm of the gradient the update is about to read, frozen slots left out
+            // the running-norm rule keeps one reference per regime of the step -- before cls_warmup (none), entire-image, ordinary -- baked
+            // into the launch sequence like the loss kernel's "counted": a by-value kernel argument, which an update of a pooled executable rewrites
+            ClipAutoRule rule = st->clip_rule;
+            rule.regime = !ssim_on ? -1 : entire ? 1 : 0;
             RC(grad_norm_launch(grads, adam_g2, st->pairs, st->astride, (size_t)st->nparams, st->clip_norm, st->clip_partials, st->clip,
-                                stop_on ? st->stop : nullptr, st->dev_t, s, st->trace, st->trace_cap));
+                                stop_on ? st->stop : nullptr, st->dev_t, s, st->trace, st->trace_cap, rule.records ? &rule : nullptr));
             a.clip = st->clip; a.clip_stride = st->astride;
         }
         // keep-best: the record this launch reads was written by THIS step's loss kernel -- on the side stream's tail, in front of the

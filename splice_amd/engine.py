@@ -31,6 +31,8 @@ DEFAULT_CFG = dict(  # conf/default/config.yaml of the reference
     ema_decay=0.0, ema_start=0,
     # ... and clipping of every pair's gradient by its global norm inside the fused step, off by default
     grad_clip_norm=0.0,
+    # ... and clipping against k times the pair's own running gradient norm, kept per regime on the device, off by default
+    grad_clip_auto=0.0, grad_clip_auto_beta=0.98, grad_clip_auto_warmup=8,
     # ... and the weights of the window the stop rule judged best, kept on the device beside the live ones, off by default
     stop_keep_best=False,
     # ... and one row per step and slot of the loss values (and the gradient norm under clipping), kept on the device, off by default
@@ -356,6 +358,56 @@ def clip_records(clip_dev):
             for p in range(raw.shape[0])]
 
 
+def grad_clip_auto_rule(c):
+    """``(k, beta, warmup)`` of the adaptive gradient clipping in config ``c``, checked on the host:
+    ``grad_clip_auto`` is 0 (off) or a finite float32 number ``k >= 1``, ``grad_clip_auto_beta`` a float32 number in ``[0, 1)`` and
+    ``grad_clip_auto_warmup`` an integer >= 1 (observations per regime before that regime's threshold acts).  Raises ValueError
+    naming the key."""
+    k = float(_number(c, "grad_clip_auto", _REAL, lambda v: v == 0 or 1 <= v < float("inf"), "0 (off) or a finite number >= 1"))
+    beta = float(_number(c, "grad_clip_auto_beta", _REAL, lambda v: 0 <= v < 1, "a number in [0, 1)"))
+    with np.errstate(over="ignore"):   # (the kernel takes both as floats)
+        if not np.isfinite(np.float32(k)):
+            raise ValueError(f"'grad_clip_auto' must be a finite float32 number, got {k!r}")
+        if not np.float32(beta) < 1:
+            raise ValueError(f"'grad_clip_auto_beta' must be a float32 number in [0, 1), got {beta!r}")
+    return k, beta, _integer(c, "grad_clip_auto_warmup", 1)
+
+
+def clip_regime(step_idx, cls_warmup, entire):
+    """The regime of step ``step_idx`` under the adaptive clipping (host arithmetic only): -1 while ``step_idx < cls_warmup`` (the
+    loss has not its full set of terms yet: observed by no reference), 1 on an entire-image step (``entire``), else 0."""
+    return -1 if step_idx < cls_warmup else 1 if entire else 0
+
+
+def np_clip_auto(state, norm, regime, k, beta, warmup, max_norm):
+    """One step of one pair of the adaptive clipping rule (``splice_grad_norm_pairs_auto``; include/splice_hip.h) restated in NumPy
+    float32, one rounding per operation.  ``state``: the pair's ``splice_clip_auto_state`` as a dict ``ref`` (two float32),
+    ``count`` (two ints), ``thr``, ``regime`` -- None: the zeros a run starts from; ``norm``: the float32 gradient norm of the step
+    (``np_grad_clip``); ``max_norm``: the absolute cap, 0 for none.  Returns ``(new_state, coef, skip)``; ``state`` is not written."""
+    f = np.float32
+    ref, count = ([f(0), f(0)], [0, 0]) if state is None else ([f(x) for x in state["ref"]], [int(n) for n in state["count"]])
+    norm, r = f(norm), int(regime)
+    with np.errstate(all="ignore"):
+        thr_auto = f(k) * ref[r] if r >= 0 and count[r] >= warmup and ref[r] > 0 else f(np.inf)
+        thr = np.minimum(f(max_norm), thr_auto) if max_norm > 0 else thr_auto
+        if np.isfinite(norm):
+            coef, skip = np.minimum(f(1), thr / (norm + f(1e-6))), 0
+            if r >= 0:
+                x = np.minimum(norm, thr_auto)   # (a spike raises ref by at most the factor k)
+                ref[r] = x if count[r] == 0 else f(f(beta) * ref[r]) + f((f(1) - f(beta)) * x)
+                count[r] += 1
+        else:
+            coef, skip = f(0), 1
+    return dict(ref=ref, count=count, thr=f(thr), regime=r), f(coef), skip
+
+
+def clip_auto_records(auto_dev):
+    """Host dicts of device ``splice_clip_auto_state`` records held as an int32 tensor ``[P, 6]`` (a synchronising copy)."""
+    raw = auto_dev.cpu().numpy()
+    fl = raw.copy().view(np.float32)
+    return [dict(ref=[fl[p, 0], fl[p, 1]], count=[int(raw[p, 2]), int(raw[p, 3])], thr=fl[p, 4], regime=int(raw[p, 5])) for p in range(raw.shape[0])]
+
+
 def counted_steps(step_idx, cls_warmup, entire_every=0):
     """Steps among 0 .. ``step_idx`` that the stop rule counts: ``step >= cls_warmup`` and not an entire-image step
     (``step % entire_every == 0``; ``entire_every`` 0: the engine has no entire-image branch).  These are the steps whose loss is
@@ -455,6 +507,8 @@ class MultiPairEngine:
         self.ema = None
         self.grad_clip = grad_clip_rule(self.cfg)
         self.clip_dev = None
+        self.clip_auto = grad_clip_auto_rule(self.cfg)
+        self.clip_auto_dev = None
         self.keep_best = best_rule(self.cfg)
         self.best = self.best_ema = self.best_dev = self.means_dev = None
         self.trace_on = trace_rule(self.cfg)
@@ -589,7 +643,13 @@ class MultiPairEngine:
             self.ema = self.params.clone()
             _lib.check(_lib.lib().splice_step_set_ema(self.handle, _lib.ptr(self.ema), *self.ema_rule), "step_set_ema")
         # gradient clipping (shared by the slots): one record per slot on the device, written by the step's norm launches; before the first step
-        if self.grad_clip > 0:
+        # -- against the absolute norm, k times the slot's own running norm (a second record per slot, written by the same launch), or both
+        if self.clip_auto[0] > 0:
+            self.clip_dev = torch.zeros(P, 6, dtype=torch.int32, device=self.device)
+            self.clip_auto_dev = torch.zeros(P, 6, dtype=torch.int32, device=self.device)
+            _lib.check(_lib.lib().splice_step_set_grad_clip_auto(self.handle, self.grad_clip, *self.clip_auto, _lib.ptr(self.clip_dev),
+                                                                 _lib.ptr(self.clip_auto_dev)), "step_set_grad_clip_auto")
+        elif self.grad_clip > 0:
             self.clip_dev = torch.zeros(P, 6, dtype=torch.int32, device=self.device)
             _lib.check(_lib.lib().splice_step_set_grad_clip(self.handle, self.grad_clip, _lib.ptr(self.clip_dev)), "step_set_grad_clip")
         # the best window's weights (shared by the slots): arenas like params / ema -- until a window closes, "best" is the initial weights --
@@ -720,7 +780,7 @@ class MultiPairEngine:
     def snapshot(self, pair, device=None, _stop=None):
         """Everything that makes external slot ``pair`` continue, as a dict (``format`` 1): the ``numel`` floats of
         its parameters and optimiser moments, its BatchNorm buffers and ``generator_calls``, and with the rule that keeps them its weight
-        average, best weights and record with the window means, stop record, clip record, lr record with the cut steps, and rows
+        average, best weights and record with the window means, stop record, clip record(s), lr record with the cut steps, and rows
         ``0 .. step_idx`` of its loss trace; its last losses row, ``step_idx`` and its config.  The gradient arena is not state: every
         backward overwrites it.  No arena stride either: a slot continues in an engine of any number of slots (``restore``).
         ``device="cpu"``: host tensors, a picklable state (waits for the current stream); None: device copies."""
@@ -742,7 +802,7 @@ class MultiPairEngine:
         for key, arena in arenas.items():
             if arena is not None:
                 s[key] = take(self._pair_arena(arena, pair, key))
-        rows = dict(running=self.running, losses=self.losses_dev, best_rec=self.best_dev, means=self.means_dev, clip=self.clip_dev,
+        rows = dict(running=self.running, losses=self.losses_dev, best_rec=self.best_dev, means=self.means_dev, clip=self.clip_dev, clip_auto=self.clip_auto_dev,
                     lr_state=self.lr_state_dev, lr_cuts=self.lr_cuts_dev)
         for key, table in rows.items():
             if table is not None:
@@ -754,7 +814,7 @@ class MultiPairEngine:
         return s
 
     # what a state holds beside the keys every state has, by the rule that keeps it
-    _STATE_KEYS = dict(ema=("ema",), best=("best", "best_rec", "means"), best_ema=("best_ema",), clip_dev=("clip",), lr_state_dev=("lr_state", "lr_cuts"),
+    _STATE_KEYS = dict(ema=("ema",), best=("best", "best_rec", "means"), best_ema=("best_ema",), clip_dev=("clip",), clip_auto_dev=("clip_auto",), lr_state_dev=("lr_state", "lr_cuts"),
                        trace_dev=("trace",))
 
     def _check_states(self, states):
@@ -798,7 +858,7 @@ class MultiPairEngine:
             for key, arena in dict(params=self.params, m=self.m, v=self.v, ema=self.ema, best=self.best, best_ema=self.best_ema).items():
                 if arena is not None:
                     arena[sl].copy_(s[key])
-            for key, table in dict(running=self.running, losses=self.losses_dev, best_rec=self.best_dev, means=self.means_dev, clip=self.clip_dev,
+            for key, table in dict(running=self.running, losses=self.losses_dev, best_rec=self.best_dev, means=self.means_dev, clip=self.clip_dev, clip_auto=self.clip_auto_dev,
                                    lr_state=self.lr_state_dev, lr_cuts=self.lr_cuts_dev).items():
                 if table is not None:
                     table[i].copy_(s[key])
@@ -933,13 +993,23 @@ class MultiPairEngine:
         return out if pair is None else out[pair]
 
     def clip_state(self, pair=None):
-        """The gradient-clipping record(s) of the last step (``grad_clip_norm > 0``), copied from the device (waits for the current
-        stream): ``sumsq`` / ``norm`` of the slot's gradient, the ``coef`` its update multiplied it by, ``skip`` (the norm was not
-        finite, the slot was not updated) and the counts ``clipped`` / ``skipped`` of such steps so far.  One dict for ``pair``, a list
-        over the slots for ``pair=None``."""
+        """The gradient-clipping record(s) of the last step (``grad_clip_norm > 0`` or ``grad_clip_auto > 0``), copied from the device
+        (waits for the current stream): ``sumsq`` / ``norm`` of the slot's gradient, the ``coef`` its update multiplied it by, ``skip``
+        (the norm was not finite, the slot was not updated) and the counts ``clipped`` / ``skipped`` of such steps so far.  One dict for
+        ``pair``, a list over the slots for ``pair=None``."""
         if self.clip_dev is None:
             raise RuntimeError("clip_state: the gradient is not clipped (grad_clip_norm == 0)")
         dicts = self._per_slot(clip_records(self.clip_dev), lambda s: clip_records(s["clip"][None])[0])
+        return dicts if pair is None else dicts[pair]
+
+    def clip_auto_state(self, pair=None):
+        """The record(s) of the adaptive clipping (``grad_clip_auto > 0``), copied from the device (waits for the
+        current stream): ``ref``, the running gradient norm of the ordinary and of the entire-image steps (float32), ``count``, how many
+        steps of either regime it has seen, and ``thr`` / ``regime``, the threshold (inf: none) and the regime (-1: before
+        ``cls_warmup``) of the last step.  One dict for ``pair``, a list over the slots for ``pair=None``."""
+        if self.clip_auto_dev is None:
+            raise RuntimeError("clip_auto_state: the gradient is not clipped against its running norm (grad_clip_auto == 0)")
+        dicts = self._per_slot(clip_auto_records(self.clip_auto_dev), lambda s: clip_auto_records(s["clip_auto"][None])[0])
         return dicts if pair is None else dicts[pair]
 
     def losses(self, pair=None):
@@ -960,7 +1030,7 @@ class MultiPairEngine:
     def loss_trace(self, pair=None):
         """The rows the steps so far wrote (``loss_trace``): per slot a float32 array ``[rows, 8]`` -- the six LOSS_KEYS values of every
         step (inactive terms are 0, as in ``losses_dev``), then the gradient norm and the clip coefficient (NaN without
-        ``grad_clip_norm``) -- with ``rows = min(step_idx + 1, n_epochs)``, cut behind a stopped slot's stop step.  One device-to-host
+        ``grad_clip_norm`` / ``grad_clip_auto``) -- with ``rows = min(step_idx + 1, n_epochs)``, cut behind a stopped slot's stop step.  One device-to-host
         copy (waits for the current stream): call it at the end of a run.  One array for ``pair``, a list over the slots for
         ``pair=None``."""
         if self.trace_dev is None:
@@ -1082,6 +1152,9 @@ class SpliceEngine(MultiPairEngine):
     def clip_state(self, pair=None):
         return super().clip_state(0)
 
+    def clip_auto_state(self, pair=None):
+        return super().clip_auto_state(0)
+
     def loss_trace(self, pair=None):
         return super().loss_trace(0)
 
@@ -1134,11 +1207,13 @@ class MultiScaleEngine:
         self.ema = None
         self.grad_clip = grad_clip_rule(self.cfg)
         self.clip_dev = None
+        self.clip_auto = grad_clip_auto_rule(self.cfg)
+        self.clip_auto_dev = None
         self.scales = tuple(scales)
         self.engines = []
         for k, sz in enumerate(self.scales):
-            # (ema_decay=0, grad_clip_norm=0: the handles are gradient-only, the average and the clipping ride in this engine's own update below)
-            e = SpliceEngine(dict(self.cfg, dino_global_patch_size=sz, ema_decay=0.0, grad_clip_norm=0.0), vit_state if k == 0 else None, gen_state, crop_hw, entire_hw, device=device,
+            # (ema_decay=0, grad_clip_norm=0, grad_clip_auto=0: the handles are gradient-only, the average and the clipping ride in this engine's own update below)
+            e = SpliceEngine(dict(self.cfg, dino_global_patch_size=sz, ema_decay=0.0, grad_clip_norm=0.0, grad_clip_auto=0.0), vit_state if k == 0 else None, gen_state, crop_hw, entire_hw, device=device,
                              vit_engine=vit_engine if k == 0 else self.engines[0].vit, n_crops=n_crops, fp8=fp8)
             _lib.check(_lib.lib().splice_step_set_mode(e.handle, 1, 0), "step_set_mode")
             if k > 0:   # one parameter set: every scale sees the arenas of the first engine; netG bookkeeping once
@@ -1150,8 +1225,10 @@ class MultiScaleEngine:
         self.params, self.grads = self.engines[0].params, self.engines[0].grads
         if self.ema_rule[0] > 0:
             self.ema = self.engines[0].ema = self.params.clone()   # (the leader serves pair_ema / generate / state_dict with it)
-        if self.grad_clip > 0:
+        if self.grad_clip > 0 or self.clip_auto[0] > 0:
             self.clip_dev = torch.zeros(1, 6, dtype=torch.int32, device=self.params.device)
+        if self.clip_auto[0] > 0:
+            self.clip_auto_dev = torch.zeros(1, 6, dtype=torch.int32, device=self.params.device)
         self.step_idx = -1
         self.opt_kind, *self.opt_hp = fused_optimizer(self.cfg)
         self.schedule = LrSchedule(self.cfg)
@@ -1162,6 +1239,12 @@ class MultiScaleEngine:
         if self.clip_dev is None:
             raise RuntimeError("clip_state: the gradient is not clipped (grad_clip_norm == 0)")
         return clip_records(self.clip_dev)[0]
+
+    def clip_auto_state(self, pair=None):
+        """The record of the adaptive clipping, as ``SpliceEngine.clip_auto_state``."""
+        if self.clip_auto_dev is None:
+            raise RuntimeError("clip_auto_state: the gradient is not clipped against its running norm (grad_clip_auto == 0)")
+        return clip_auto_records(self.clip_auto_dev)[0]
 
     def step(self, A_crop, B_crop, A_entire=None):
         from .generator import optim_step
@@ -1174,8 +1257,12 @@ class MultiScaleEngine:
         _lib.check(L.splice_step_set_phases(e0.handle, 4, None), "step_set_phases")
         e0.step(A_crop, B_crop, A_entire, _repeat=True)      # G backward of the summed image gradient
         self.lr = self.schedule.lr(self.step_idx)
+        # (the adaptive clipping's regime is baked into the fused step's graph variants; here the host step index gives it)
+        entire = e0.plan_e is not None and self.step_idx % self.cfg["entire_A_every"] == 0
         optim_step(self.opt_kind, e0.params, e0.grads, e0.m, e0.v, self.lr, *self.opt_hp, self.step_idx + 1, ema=self.ema,
-                   ema_decay=self.ema_rule[0], ema_start=self.ema_rule[1], clip_norm=self.grad_clip, clip_state=self.clip_dev)
+                   ema_decay=self.ema_rule[0], ema_start=self.ema_rule[1], clip_norm=self.grad_clip, clip_state=self.clip_dev,
+                   clip_auto=self.clip_auto if self.clip_auto[0] > 0 else None, clip_regime=clip_regime(self.step_idx, self.cfg["cls_warmup"], entire),
+                   clip_auto_state=self.clip_auto_dev)
 
     def losses(self):
         """Per-scale loss dicts and their sum: ``{"loss": total, "scales": {224: {...}, ...}}``."""

@@ -172,7 +172,7 @@ OPTIMIZER_KINDS = {"adam": 0, "rmsprop": 1, "sgd": 2}   # the `kind` of splice_o
 
 
 def optim_step(kind, params, grads, m, v, lr, hp0, hp1, eps, step, zero_grad=False, g2=None, lr_dev=None, ema=None, ema_decay=0.0, ema_start=0,
-               clip_norm=0.0, clip_state=None):
+               clip_norm=0.0, clip_state=None, clip_auto=None, clip_regime=0, clip_auto_state=None):
     """One fused optimiser step over a flat arena (``splice_optim_step_ex``): kind 0 Adam (hp0 / hp1 = betas, step >= 1),
     1 RMSprop (hp0 = alpha, ``v`` = square_avg, ``m`` unused), 2 SGD (``m`` / ``v`` unused).  ``g2``: second gradient arena
     added to ``grads`` first; ``lr_dev``: one-element device tensor read as the learning rate when the kernel runs.
@@ -180,7 +180,10 @@ def optim_step(kind, params, grads, m, v, lr, hp0, hp1, eps, step, zero_grad=Fal
     parameters just written, later ``ema_decay * ema + (1 - ema_decay) * params``; every kind then needs ``step >= 1``.
     ``clip_norm > 0``: the gradient (``grads + g2``) is clipped to that global norm first, as ``torch.nn.utils.clip_grad_norm_``, and an
     update whose norm is not finite is skipped (``splice_grad_norm_pairs`` then ``splice_optim_step_clip``); ``clip_state``: the int32
-    CUDA tensor of 6 elements that receives the ``splice_clip_state`` record (its two counts are the caller's to start at zero)."""
+    CUDA tensor of 6 elements that receives the ``splice_clip_state`` record (its two counts are the caller's to start at zero).
+    ``clip_auto = (k, beta, warmup)``: the threshold is ``k`` times the running norm of the step's regime ``clip_regime`` (-1, 0 or 1)
+    kept in ``clip_auto_state``, an int32 CUDA tensor of 6 elements like ``clip_state`` (zeros at the start of a run), under the cap
+    ``clip_norm`` where that is > 0 (``splice_grad_norm_pairs_auto``)."""
     if kind not in OPTIMIZER_KINDS.values():
         raise ValueError(f"optim_step: unknown optimiser kind {kind}")
     m = m if kind == 0 else None            # arenas the kind does not touch are not passed
@@ -194,12 +197,21 @@ def optim_step(kind, params, grads, m, v, lr, hp0, hp1, eps, step, zero_grad=Fal
             raise ValueError(f"optim_step: {name} must be a contiguous fp32 CUDA tensor of {n} elements")
     if lr_dev is not None and not (lr_dev.is_cuda and lr_dev.dtype == torch.float32 and lr_dev.numel() >= 1):
         raise ValueError("optim_step: lr_dev must be a fp32 CUDA tensor")
-    if clip_norm:
+    if clip_norm or clip_auto is not None:
         if clip_state is None or not (clip_state.is_cuda and clip_state.dtype == torch.int32 and clip_state.is_contiguous() and clip_state.numel() == 6):
             raise ValueError("optim_step: clip_state must be a contiguous int32 CUDA tensor of 6 elements")
         partials = torch.empty((n + 4095) // 4096, dtype=torch.float32, device=params.device)
-        _lib.check(_lib.lib().splice_grad_norm_pairs(_lib.ptr(grads), _lib.ptr(g2), 1, 0, n, float(clip_norm), _lib.ptr(partials), _lib.ptr(clip_state),
-                                                     None, None, _lib.current_stream()), "grad_norm_pairs")
+        if clip_auto is not None:
+            a = clip_auto_state
+            if a is None or not (a.is_cuda and a.dtype == torch.int32 and a.is_contiguous() and a.numel() == 6):
+                raise ValueError("optim_step: clip_auto_state must be a contiguous int32 CUDA tensor of 6 elements")
+            k, beta, warmup = clip_auto
+            _lib.check(_lib.lib().splice_grad_norm_pairs_auto(_lib.ptr(grads), _lib.ptr(g2), 1, 0, n, float(clip_norm), float(k), float(beta), int(warmup),
+                                                              int(clip_regime), _lib.ptr(partials), _lib.ptr(clip_state), _lib.ptr(a), None, None,
+                                                              _lib.current_stream()), "grad_norm_pairs_auto")
+        else:
+            _lib.check(_lib.lib().splice_grad_norm_pairs(_lib.ptr(grads), _lib.ptr(g2), 1, 0, n, float(clip_norm), _lib.ptr(partials), _lib.ptr(clip_state),
+                                                         None, None, _lib.current_stream()), "grad_norm_pairs")
         _lib.check(_lib.lib().splice_optim_step_clip(int(kind), _lib.ptr(params), _lib.ptr(grads), _lib.ptr(g2), _lib.ptr(m), _lib.ptr(v), _lib.ptr(ema), n,
                                                      float(lr), _lib.ptr(lr_dev), float(hp0), float(hp1), float(eps), int(step), int(zero_grad),
                                                      float(ema_decay), int(ema_start), _lib.ptr(clip_state), _lib.current_stream()), "optim_step_clip")

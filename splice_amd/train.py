@@ -370,7 +370,7 @@ def _loss_traces(cfg, engine, writers):
     if not cfg.get('loss_trace', False) or engine.step_idx < 0:
         return
     for w, (rows, lrs, active) in zip(writers, engine.loss_trace_columns()):
-        write_loss_trace(os.path.join(w.dir, "losses.csv"), rows, lrs, active, engine.grad_clip > 0)
+        write_loss_trace(os.path.join(w.dir, "losses.csv"), rows, lrs, active, engine.grad_clip > 0 or getattr(engine, "clip_auto", (0.0,))[0] > 0)
 
 
 def trace_fields(engine, out_dir=""):
@@ -406,11 +406,17 @@ def best_fields(engine, slot=None):
 def clip_fields(engine, slot=None):
     """What ``result.json`` says about the gradient clipping of a run (``splice_amd.batch``): ``grad_clip_norm`` (0: the gradient was
     not clipped), and for ``slot`` (None: the one pair of the engine) ``clipped_steps`` -- steps whose gradient norm exceeded it --
-    and ``skipped_steps`` -- steps whose norm was not finite and did not update the slot."""
+    and ``skipped_steps`` -- steps whose norm was not finite and did not update the slot.  A run that clipped against the slot's own
+    running norm (``grad_clip_auto > 0``) also says ``grad_clip_auto`` and ``clip_ref``, the two running norms it ended with (ordinary
+    and entire-image steps); ``clipped_steps`` then counts the steps either threshold clipped."""
+    auto = {}
+    if getattr(engine, "clip_auto_dev", None) is not None:
+        ref = engine.clip_auto_state(slot)["ref"] if engine.step_idx >= 0 else [0.0, 0.0]
+        auto = {"grad_clip_auto": engine.clip_auto[0], "clip_ref": [float(x) for x in ref]}
     if engine.clip_dev is None or engine.step_idx < 0:
-        return {"grad_clip_norm": engine.grad_clip, "clipped_steps": 0, "skipped_steps": 0}
+        return {"grad_clip_norm": engine.grad_clip, "clipped_steps": 0, "skipped_steps": 0, **auto}
     rec = engine.clip_state(slot)
-    return {"grad_clip_norm": engine.grad_clip, "clipped_steps": rec["clipped"], "skipped_steps": rec["skipped"]}
+    return {"grad_clip_norm": engine.grad_clip, "clipped_steps": rec["clipped"], "skipped_steps": rec["skipped"], **auto}
 
 
 def train_pairs(dataroots, callback=None, cfg_overrides=None, vit_state=None, progress=True):
