@@ -324,6 +324,41 @@ int splice_optim_step_ema(int kind, float* params, float* grads, const float* g2
                           const float* lr_dev, float hp0, float hp1, float eps, int step, int zero_grad, float ema_decay, int ema_start,
                           splice_stream_t stream);
 
+/* The extended rules of the fused update (extensions; the reference sets none of these): torch.optim's weight_decay, momentum / dampening /
+ * nesterov (SGD), momentum / centered (RMSprop), amsgrad (Adam) and AdamW's decoupled decay (kind 0 with `decoupled`).  A call that
+ * passes this record runs the extended kernels, also when every option is neutral; they then compute the bits of the plain rules
+ * (a zero weight_decay or momentum is a branch, not a multiplication by zero).  An option the kind has no argument for must be neutral. */
+typedef struct splice_optim_ext {
+    float weight_decay;   /* >= 0, finite.  decoupled == 0: L2, added to the gradient the rule sees; decoupled != 0: AdamW */
+    float momentum;       /* >= 0, finite; SGD and RMSprop: the buffer lives in the m arena */
+    float dampening;      /* SGD */
+    int nesterov;         /* SGD; needs momentum > 0 and dampening == 0 */
+    int decoupled;        /* Adam: p = p (1 - lr weight_decay) in front of the update, the moments see the gradient alone (torch.optim.AdamW) */
+    int amsgrad;          /* Adam: the w arena holds max_exp_avg_sq */
+    int centered;         /* RMSprop: the w arena holds grad_avg */
+} splice_optim_ext;
+/* The arithmetic, fp32 with one rounding per operation and no contraction, like the plain rules.  g: the gradient the rule sees today,
+ * fl(grads + g2), times the clip coefficient under clipping; where grads is written back (g2 or zero_grad) it holds exactly what the
+ * plain rules leave there -- the decay term is never written into the gradient arena, and the norm launches see no decay.  t: the
+ * update's step count (>= 1): the device count where the call has one, else `step`; EVERY extended rule needs it.  lr: the slot's
+ * effective learning rate.  wd = weight_decay, mu = momentum.
+ *   SGD      d = wd ? g + wd p : g.  mu > 0: b = (t == 1) ? d : mu b + (1 - dampening) d, kept in m; d = nesterov ? d + mu b : b.
+ *            p -= lr d.  "First step" means t == 1: a slot whose first update was skipped by the non-finite-norm guard starts from
+ *            b = 0 at t == 2, where torch ("the buffer is None") would copy d.
+ *   RMSprop  d as SGD; v = alpha v + (1 - alpha) d d.  centered: a = alpha a + (1 - alpha) d, kept in w; avg = sqrt(v - a a) + eps, not
+ *            clamped, as torch does not clamp it: a gradient that is constant over thousands of steps can round v - a a below 0 and
+ *            the weights then turn NaN.  Else avg = sqrt(v) + eps.  mu > 0: b = mu b + d / avg, kept in m; p -= lr b.  Else p -= lr (d / avg).
+ *   Adam     decoupled and wd > 0: first p = p (1 - lr wd), then d = g; else d = wd ? g + wd p : g.  m and v as splice_optim_step with d
+ *            for g.  amsgrad: w = max(w, v) and denom = sqrt(w) / bc2_sqrt + eps; else denom = sqrt(v) / bc2_sqrt + eps.
+ *            p -= (lr / bc1) (m / denom).
+ * A slot that is frozen by the stop rule or skipped by the clip guard writes none of p, m, v, w, and its decoupled decay is not applied.
+ * The padding floats between two arenas (p = 0, g = 0) stay 0 under every rule.  w is laid out like m and v, is needed exactly with
+ * amsgrad / centered, and takes part in the 16-byte alignment test of the walk like every arena.
+ * splice_optim_step_ext: one arena, as splice_optim_step_ex (step >= 1 for every kind). */
+int splice_optim_step_ext(int kind, float* params, float* grads, const float* g2, float* m, float* v, float* w, long long n, float lr,
+                          const float* lr_dev, float hp0, float hp1, float eps, int step, int zero_grad, const splice_optim_ext* options,
+                          splice_stream_t stream);
+
 /* live timing of one kernel family (bench.py roofline leg, prof.hip): while a family is armed its kernels are launched with
  * a start / stop event pair each (hipExtLaunchKernelGGL: the kernel's own begin / end time stamps, as rocprofv3 reports them).
  * which 1 = fc1 GEMM fwd, 2 = qkv GEMM fwd (layers 0..depth-2), 3 = attention fwd, 4 = fc2 GEMM fwd, 5 = split-K dgrad GEMMs
@@ -614,6 +649,20 @@ int splice_optim_step_pairs_best(int kind, float* params, float* grads, const fl
                                  long long stride, long long n, const float* lr_dev, float hp0, float hp1, float eps, const int* step_dev,
                                  const splice_stop_state* stop, int zero_grad, float ema_decay, int ema_start, const splice_clip_state* clip,
                                  const splice_best_state* best, float* best_params, float* best_ema, splice_stream_t stream);
+/* The extended rules (splice_optim_ext above) for n_pairs arenas with per-pair learning rates, every optional part of the update beside
+ * them: w ([n_pairs][stride] like m and v; NULL where the rule keeps none), step_dev (NULL: the host's `step` counts the update), stop
+ * (needs step_dev), ema, clip, best with best_params and best_ema (needs stop), as splice_optim_step_pairs_best takes them.  One pair:
+ * a single arena of n floats.  Bit for bit n_pairs single-arena calls with each pair's lr. */
+int splice_optim_step_pairs_ext(int kind, float* params, float* grads, const float* g2, float* m, float* v, float* w, float* ema, int n_pairs,
+                                long long stride, long long n, const float* lr_dev, float hp0, float hp1, float eps, int step,
+                                const int* step_dev, const splice_stop_state* stop, int zero_grad, float ema_decay, int ema_start,
+                                const splice_clip_state* clip, const splice_best_state* best, float* best_params, float* best_ema,
+                                const splice_optim_ext* options, splice_stream_t stream);
+/* The extended rules inside the step: the update of every later splice_step_run runs the extended rule of the handle's kind
+ * (splice_step_set_optimizer, called first) under `options`, with w ([P][arena_stride] like m, the caller's, zeros at the start of a
+ * run; NULL unless amsgrad / centered) -- no launch more.  The m arena of splice_step_run then also holds the momentum buffer.  Before
+ * the first splice_step_run only; drops the handle's graphs, as splice_step_set_optimizer does. */
+int splice_step_set_optimizer_ext(void* step, const splice_optim_ext* options, float* w);
 /* Keep every pair's best-window weights inside the step: the loss kernel's rule writes `state` and `means` (device, the caller's: [pairs]
  * records at -1 / -1 and [pairs][SPLICE_STOP_HISTORY] zeros), the optimiser launch of the same step reads the record and writes
  * best_params (and best_ema; both [P][arena_stride] like params, the caller's, they start as copies of params / ema).  No launch more,

@@ -68,6 +68,20 @@ class LrState(C.Structure):   # splice_lr_state
     _fields_ = [("scale", C.c_float), ("bad", C.c_int), ("cuts", C.c_int), ("last_cut_step", C.c_int)]
 
 
+class OptimExt(C.Structure):   # splice_optim_ext
+    _fields_ = [("weight_decay", C.c_float), ("momentum", C.c_float), ("dampening", C.c_float), ("nesterov", C.c_int), ("decoupled", C.c_int),
+                ("amsgrad", C.c_int), ("centered", C.c_int)]
+
+
+def optim_ext(options):
+    """The ``splice_optim_ext`` record of ``options`` (a dict of its field names, ``util.fused_optimizer_ext``; an absent field is neutral)."""
+    if isinstance(options, OptimExt):
+        return options
+    return OptimExt(float(options.get("weight_decay", 0.0)), float(options.get("momentum", 0.0)), float(options.get("dampening", 0.0)),
+                    int(bool(options.get("nesterov", False))), int(bool(options.get("decoupled", False))), int(bool(options.get("amsgrad", False))),
+                    int(bool(options.get("centered", False))))
+
+
 class GenConvArgs(C.Structure):   # splice_gen_conv_args (test hooks)
     _fields_ = [("in", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("out", C.c_void_p)] + \
                [(n, C.c_size_t) for n in ("in_nstride", "in_cstride", "out_nstride", "out_cstride", "w_jstride", "w_cstride", "p_nstride")] + \
@@ -220,6 +234,11 @@ _SIGNATURES = {
     # plateau lr rule
     "splice_step_set_lr_plateau": ([_vp, _f, _i, _f, _vp, _vp], _i),
     "splice_plateau_update_lr": ([_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _f, _i, _i, _f, _i, _f, _i, _i, _vp], _i),
+    # extended optimiser rules (weight decay, momentum, AdamW, amsgrad, centred RMSprop)
+    "splice_optim_step_ext": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, _f, _vp, _f, _f, _f, _i, _i, C.POINTER(OptimExt), _vp], _i),
+    "splice_optim_step_pairs_ext": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_longlong, C.c_longlong, _vp, _f, _f, _f, _i, _vp, _vp, _i, _f, _i, _vp, _vp,
+                                     _vp, _vp, C.POINTER(OptimExt), _vp], _i),
+    "splice_step_set_optimizer_ext": ([_vp, C.POINTER(OptimExt), _vp], _i),
     "splice_prof_begin": ([_i], _i),
     "splice_prof_end": ([C.POINTER(_f), C.POINTER(_i)], _i),
     "splice_prof_end_ex": ([C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)], _i),

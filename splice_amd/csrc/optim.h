@@ -37,6 +37,11 @@ struct OptimArgs {
     const splice_best_state* best = nullptr;
     float* best_p = nullptr;
     float* best_ema = nullptr;
+    // optional (the extended rules, include/splice_hip.h): the option record selects them -- also when every option is neutral -- and w is
+    // the third moment arena, laid out like m and v: Adam's max_exp_avg_sq (amsgrad) or RMSprop's grad_avg (centered); null where the rule
+    // keeps none.  m then also holds the momentum buffer of SGD / RMSprop.  Every extended rule needs the update's step count, as ema does
+    float* w = nullptr;
+    const splice_optim_ext* ext = nullptr;
 };
 int optim_launch(const OptimArgs& a, hipStream_t s);
 // The per-pair gradient norm and clip coefficient (include/splice_hip.h has the rule): two launches, partials[pairs][ceil(n / 4096)] then

@@ -1,6 +1,7 @@
 // Fused multi-tensor optimiser update over the flat parameter arena (K19): torch.optim.Adam / RMSprop / SGD as util/util.py:28-39
 // configures them, plus optimizer.zero_grad (train.py:56) when zero_grad != 0.  One walk over the arena (optim_kernel), one element
-// rule per optimiser, one launcher that validates and selects the instance.
+// rule per optimiser, one launcher that validates and selects the instance.  Beside the three plain rules, torch.optim's further
+// arguments (weight decay, momentum / dampening / nesterov, amsgrad, centred RMSprop, AdamW) as extended rules of the same walk.
 #include "optim.h"
 #include "plateau.h"
 
@@ -9,7 +10,7 @@
 // the rule reads and writes; the walk does not touch (or alignment-test) the others.
 // Adam: no weight decay / amsgrad, eps added after sqrt(v_hat)
 struct AdamRule {
-    static constexpr bool USES_M = true, USES_V = true;
+    static constexpr bool USES_M = true, USES_V = true, USES_W = false, EXT = false;
     float b1, b2, eps, bc1, bc2_sqrt;
     __device__ __forceinline__ AdamRule(float hp0, float hp1, float eps_, float bc1_, float bc2_sqrt_) : b1(hp0), b2(hp1), eps(eps_), bc1(bc1_), bc2_sqrt(bc2_sqrt_) {}
     __device__ __forceinline__ void update(float& pi, float& gi, float& mi_, float& vi_, float g2i, bool has_g2, float lr, int zero_grad) const {
@@ -27,7 +28,7 @@ struct AdamRule {
 // RMSprop (alpha 0.99, eps 1e-8; no momentum, not centred, no weight decay): v = alpha v + (1 - alpha) g^2, p -= lr g / (sqrt(v) + eps);
 // the v arena holds square_avg
 struct RmspropRule {
-    static constexpr bool USES_M = false, USES_V = true;
+    static constexpr bool USES_M = false, USES_V = true, USES_W = false, EXT = false;
     float alpha, eps;
     __device__ __forceinline__ RmspropRule(float hp0, float, float eps_, float, float) : alpha(hp0), eps(eps_) {}
     __device__ __forceinline__ void update(float& pi, float& gi, float&, float& vi_, float g2i, bool has_g2, float lr, int zero_grad) const {
@@ -41,7 +42,7 @@ struct RmspropRule {
 };
 // SGD (no momentum, dampening, nesterov or weight decay): p -= lr g
 struct SgdRule {
-    static constexpr bool USES_M = false, USES_V = false;
+    static constexpr bool USES_M = false, USES_V = false, USES_W = false, EXT = false;
     __device__ __forceinline__ SgdRule(float, float, float, float, float) {}
     __device__ __forceinline__ void update(float& pi, float& gi, float&, float&, float g2i, bool has_g2, float lr, int zero_grad) const {
 #pragma clang fp contract(off)
@@ -50,6 +51,106 @@ struct SgdRule {
         if (zero_grad) gi = 0.f;
     }
 };
+
+// ---- the extended rules (OptimArgs::ext; include/splice_hip.h states them): torch.optim's weight_decay, momentum /
+// dampening / nesterov, amsgrad, centered, and AdamW's decoupled decay.  Which arenas a rule walks is a template property (MOM: the m arena
+// holds SGD's / RMSprop's momentum buffer; AMS / CEN: the third arena w holds max_exp_avg_sq / grad_avg); the scalar options are wave-uniform
+// run-time values, and a zero wd is a BRANCH, never a multiplication by zero: with neutral options a rule computes the plain rule's bits.
+// The decay term enters d alone: where g is written back it holds what the plain rules leave there.  t: the update's step count.
+struct OptimExtArgs {   // the trailing by-value kernel argument (not preloaded into SGPRs: the plain instances do not read it)
+    float* w;
+    float wd, mu, damp;
+    int nesterov, decoupled;
+};
+__device__ __forceinline__ float ext_decay(float gi, float pi, float wd) {
+#pragma clang fp contract(off)
+    return wd != 0.f ? gi + wd * pi : gi;
+}
+template <bool AMS>
+struct AdamExtRule {
+    static constexpr bool USES_M = true, USES_V = true, USES_W = AMS, EXT = true;
+    float b1, b2, eps, bc1, bc2_sqrt, wd;
+    bool decoupled;
+    __device__ __forceinline__ AdamExtRule(float hp0, float hp1, float eps_, float bc1_, float bc2_sqrt_, const OptimExtArgs& x, int)
+        : b1(hp0), b2(hp1), eps(eps_), bc1(bc1_), bc2_sqrt(bc2_sqrt_), wd(x.wd), decoupled(x.decoupled != 0) {}
+    __device__ __forceinline__ void update(float& pi, float& gi, float& mi_, float& vi_, float& wi_, float g2i, bool has_g2, float lr, int zero_grad) const {
+#pragma clang fp contract(off)
+        if (has_g2) gi += g2i;
+        float di = gi;
+        if (decoupled) {
+            if (wd != 0.f) pi = pi * (1.f - lr * wd);   // AdamW: the decay acts on the weights, the moments see the gradient alone
+        } else {
+            di = ext_decay(gi, pi, wd);
+        }
+        const float mi = b1 * mi_ + (1.f - b1) * di;
+        const float vi = b2 * vi_ + (1.f - b2) * di * di;
+        mi_ = mi;
+        vi_ = vi;
+        float vh = vi;
+        if (AMS) { vh = fmaxf(wi_, vi); wi_ = vh; }
+        const float denom = sqrtf(vh) / bc2_sqrt + eps;
+        pi -= (lr / bc1) * (mi / denom);
+        if (zero_grad) gi = 0.f;
+    }
+};
+// RMSprop: the w arena holds grad_avg (CEN), the m arena the momentum buffer (MOM).  sqrt(v - a a) is not clamped, as torch does not
+// clamp it: a gradient that is constant over thousands of steps can round v - a a below 0, and the slot's weights then turn NaN
+template <bool MOM, bool CEN>
+struct RmspropExtRule {
+    static constexpr bool USES_M = MOM, USES_V = true, USES_W = CEN, EXT = true;
+    float alpha, eps, wd, mu;
+    __device__ __forceinline__ RmspropExtRule(float hp0, float, float eps_, float, float, const OptimExtArgs& x, int) : alpha(hp0), eps(eps_), wd(x.wd), mu(x.mu) {}
+    __device__ __forceinline__ void update(float& pi, float& gi, float& mi_, float& vi_, float& wi_, float g2i, bool has_g2, float lr, int zero_grad) const {
+#pragma clang fp contract(off)
+        if (has_g2) gi += g2i;
+        const float di = ext_decay(gi, pi, wd);
+        const float vi = alpha * vi_ + (1.f - alpha) * di * di;
+        vi_ = vi;
+        float avg;
+        if (CEN) {
+            const float ai = alpha * wi_ + (1.f - alpha) * di;
+            wi_ = ai;
+            avg = sqrtf(vi - ai * ai) + eps;
+        } else {
+            avg = sqrtf(vi) + eps;
+        }
+        if (MOM) {
+            const float bi = mu * mi_ + di / avg;
+            mi_ = bi;
+            pi -= lr * bi;
+        } else {
+            pi -= lr * (di / avg);
+        }
+        if (zero_grad) gi = 0.f;
+    }
+};
+// SGD: "first step" is t == 1 (b = d); a slot whose first update the non-finite-norm guard skipped starts from b = 0 at t == 2, where torch's
+// "buffer is None" rule would copy d then
+template <bool MOM>
+struct SgdExtRule {
+    static constexpr bool USES_M = MOM, USES_V = false, USES_W = false, EXT = true;
+    float wd, mu, damp1;
+    bool nesterov, first;
+    __device__ __forceinline__ SgdExtRule(float, float, float, float, float, const OptimExtArgs& x, int t)
+        : wd(x.wd), mu(x.mu), damp1(1.f - x.damp), nesterov(x.nesterov != 0), first(t == 1) {}
+    __device__ __forceinline__ void update(float& pi, float& gi, float& mi_, float&, float&, float g2i, bool has_g2, float lr, int zero_grad) const {
+#pragma clang fp contract(off)
+        if (has_g2) gi += g2i;
+        float di = ext_decay(gi, pi, wd);
+        if (MOM) {
+            const float bi = first ? di : mu * mi_ + damp1 * di;
+            mi_ = bi;
+            di = nesterov ? di + mu * bi : bi;
+        }
+        pi -= lr * di;
+        if (zero_grad) gi = 0.f;
+    }
+};
+template <class Rule>
+__device__ __forceinline__ Rule make_rule(float hp0, float hp1, float eps, float bc1, float bc2_sqrt, const OptimExtArgs& x, int t) {
+    if constexpr (Rule::EXT) return Rule(hp0, hp1, eps, bc1, bc2_sqrt, x, t);
+    else return Rule(hp0, hp1, eps, bc1, bc2_sqrt);
+}
 
 // The weight average (OptimArgs::ema): e follows the parameter just written.  track: the update's step count is <= ema_start, the average
 // still copies the weights.  Afterwards e = d e + (1 - d) p', three roundings like the moment rules.
@@ -95,6 +196,10 @@ __device__ __forceinline__ float clip_scale(float gi, float g2i, bool has_g2, fl
 // registers the ordinary stores hold, no float is computed again.  A frozen slot is skipped before its record is read; a slot skipped by
 // the clip guard still takes, its unchanged p (and e).  best_p / best_e take part in the alignment test like every arena.  The three
 // arguments lie behind the CLIP ones, and the instances without BEST do not read them.
+// Extended rules (Rule::EXT): the options and the third moment arena w (Rule::USES_W; loaded, stored and alignment-tested like m and v,
+// and skipped with them where a slot is frozen or skipped by the clip guard) arrive as ONE trailing by-value struct -- a struct is not
+// preloaded into SGPRs, so the plain instances, which do not read it, keep their registers and, but for the offset of the hidden grid
+// size behind it, their instructions.  An extended rule counts the update's steps as the average does.
 template <class Rule, bool PAIR_LR, bool MASKED, bool EMA, bool CLIP, bool BEST = false>
 __global__ void optim_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, size_t n, float lr,
                              float hp0, float hp1, float eps, float bc1, float bc2_sqrt, int zero_grad, const int* __restrict__ step_ptr,
@@ -102,7 +207,8 @@ __global__ void optim_kernel(float* __restrict__ p, float* __restrict__ g, float
                              const splice_stop_state* __restrict__ mask, const int* __restrict__ mask_step, unsigned mask_stride,
                              float* __restrict__ e, float ema_decay, int ema_start, const int* __restrict__ ema_step_ptr, int ema_step,
                              const splice_clip_state* __restrict__ clip, unsigned clip_stride,
-                             const splice_best_state* __restrict__ best, float* __restrict__ best_p, float* __restrict__ best_e) {
+                             const splice_best_state* __restrict__ best, float* __restrict__ best_p, float* __restrict__ best_e,
+                             const OptimExtArgs ext) {
     static_assert(MASKED || !BEST, "the snapshot needs the stop records and the device step count");
     int step_idx = 0;
     if (MASKED) {
@@ -117,15 +223,24 @@ __global__ void optim_kernel(float* __restrict__ p, float* __restrict__ g, float
     }
     bool ema_track = false;
     if (EMA) ema_track = (ema_step_ptr ? *ema_step_ptr : ema_step) <= ema_start;
-    const Rule rule(hp0, hp1, eps, bc1, bc2_sqrt);
+    // (an extended rule counts the update's steps as the average does)
+    const Rule rule = make_rule<Rule>(hp0, hp1, eps, bc1, bc2_sqrt, ext, Rule::EXT ? (ema_step_ptr ? *ema_step_ptr : ema_step) : 0);
+    float* const w = Rule::USES_W ? ext.w : nullptr;
     // one arena: its record is read once, at the head, with the step count; several: per element group, behind the group's own loads
     float coef = 1.f;
     int skip = 0;
     if (CLIP && !clip_stride) { coef = clip->coef; skip = clip->skip; }
     bool take = false;
     if (BEST && !mask_stride) take = best->best_step == step_idx;
-    auto upd = [&](float& pi, float& gi, float& mi, float& vi, float g2i) {
-        if (CLIP) {
+    auto upd = [&](float& pi, float& gi, float& mi, float& vi, float& wi, float g2i) {
+        if constexpr (Rule::EXT) {
+            if (CLIP) {
+                gi = clip_scale(gi, g2i, g2 != nullptr, coef);
+                rule.update(pi, gi, mi, vi, wi, 0.f, false, lr, zero_grad);
+            } else {
+                rule.update(pi, gi, mi, vi, wi, g2i, g2 != nullptr, lr, zero_grad);
+            }
+        } else if (CLIP) {
             gi = clip_scale(gi, g2i, g2 != nullptr, coef);
             rule.update(pi, gi, mi, vi, 0.f, false, lr, zero_grad);
         } else {
@@ -135,13 +250,15 @@ __global__ void optim_kernel(float* __restrict__ p, float* __restrict__ g, float
     const unsigned lr_stride4 = lr_stride / 4, mask_stride4 = mask_stride / 4, clip_stride4 = clip_stride / 4;
     const size_t align = reinterpret_cast<size_t>(p) | reinterpret_cast<size_t>(g) | (Rule::USES_M ? reinterpret_cast<size_t>(m) : 0) |
                          (Rule::USES_V ? reinterpret_cast<size_t>(v) : 0) | reinterpret_cast<size_t>(g2) | (EMA ? reinterpret_cast<size_t>(e) : 0) |
-                         (BEST ? reinterpret_cast<size_t>(best_p) : 0) | (BEST && EMA ? reinterpret_cast<size_t>(best_e) : 0);
+                         (BEST ? reinterpret_cast<size_t>(best_p) : 0) | (BEST && EMA ? reinterpret_cast<size_t>(best_e) : 0) |
+                         (Rule::USES_W ? reinterpret_cast<size_t>(w) : 0);
     const size_t n4 = (align & 15) ? 0 : n / 4;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
         if (MASKED && mask_stride && stop_frozen(mask + (unsigned)i / mask_stride4, step_idx)) continue;
-        float4 pv = reinterpret_cast<float4*>(p)[i], gv = reinterpret_cast<float4*>(g)[i], mv = {}, vv = {};
+        float4 pv = reinterpret_cast<float4*>(p)[i], gv = reinterpret_cast<float4*>(g)[i], mv = {}, vv = {}, wv = {};
         if (Rule::USES_M) mv = reinterpret_cast<float4*>(m)[i];
         if (Rule::USES_V) vv = reinterpret_cast<float4*>(v)[i];
+        if (Rule::USES_W) wv = reinterpret_cast<float4*>(w)[i];
         const float4 g2v = g2 ? reinterpret_cast<const float4*>(g2)[i] : float4{0.f, 0.f, 0.f, 0.f};
         if (PAIR_LR) lr = lr_ptr[(unsigned)i / lr_stride4];
         if (BEST && mask_stride4) take = best[(unsigned)i / mask_stride4].best_step == step_idx;
@@ -160,7 +277,7 @@ __global__ void optim_kernel(float* __restrict__ p, float* __restrict__ g, float
                 continue;
             }
         }
-        upd(pv.x, gv.x, mv.x, vv.x, g2v.x); upd(pv.y, gv.y, mv.y, vv.y, g2v.y); upd(pv.z, gv.z, mv.z, vv.z, g2v.z); upd(pv.w, gv.w, mv.w, vv.w, g2v.w);
+        upd(pv.x, gv.x, mv.x, vv.x, wv.x, g2v.x); upd(pv.y, gv.y, mv.y, vv.y, wv.y, g2v.y); upd(pv.z, gv.z, mv.z, vv.z, wv.z, g2v.z); upd(pv.w, gv.w, mv.w, vv.w, wv.w, g2v.w);
         reinterpret_cast<float4*>(p)[i] = pv;
         if (BEST && take) reinterpret_cast<float4*>(best_p)[i] = pv;
         if (EMA) {
@@ -173,6 +290,7 @@ __global__ void optim_kernel(float* __restrict__ p, float* __restrict__ g, float
         }
         if (Rule::USES_M) reinterpret_cast<float4*>(m)[i] = mv;
         if (Rule::USES_V) reinterpret_cast<float4*>(v)[i] = vv;
+        if (Rule::USES_W) reinterpret_cast<float4*>(w)[i] = wv;
         if (g2 || zero_grad) reinterpret_cast<float4*>(g)[i] = gv;
     }
     for (size_t i = n4 * 4 + (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
@@ -193,11 +311,12 @@ __global__ void optim_kernel(float* __restrict__ p, float* __restrict__ g, float
                 continue;
             }
         }
-        float pi = p[i], gi = g[i], mi = 0.f, vi = 0.f;
+        float pi = p[i], gi = g[i], mi = 0.f, vi = 0.f, wi = 0.f;
         if (Rule::USES_M) mi = m[i];
         if (Rule::USES_V) vi = v[i];
+        if (Rule::USES_W) wi = w[i];
         if (PAIR_LR) lr = lr_ptr[(unsigned)i / lr_stride];
-        upd(pi, gi, mi, vi, g2 ? g2[i] : 0.f);
+        upd(pi, gi, mi, vi, wi, g2 ? g2[i] : 0.f);
         p[i] = pi;
         if (BEST && take) best_p[i] = pi;
         if (EMA) {
@@ -207,6 +326,7 @@ __global__ void optim_kernel(float* __restrict__ p, float* __restrict__ g, float
         }
         if (Rule::USES_M) m[i] = mi;
         if (Rule::USES_V) v[i] = vi;
+        if (Rule::USES_W) w[i] = wi;
         if (g2 || zero_grad) g[i] = gi;
     }
 }
@@ -230,11 +350,71 @@ int optim_launch(const OptimArgs& a, hipStream_t s) {
     static constexpr decltype(&optim_kernel<AdamRule, false, false, false, false>) best_kernels[3][2][2][2] = {OPTIM_BEST(AdamRule), OPTIM_BEST(RmspropRule), OPTIM_BEST(SgdRule)};
 #undef OPTIM_BEST
 #undef OPTIM_BEST_CLIP
+    // the extended rules: [rule][PAIR_LR][MASKED][EMA][CLIP] and, with the snapshot, [rule][PAIR_LR][EMA][CLIP]; rule = Adam {plain, amsgrad},
+    // RMSprop {plain, momentum, centered, both}, SGD {plain, momentum} -- 128 + 64 instances beside the 72 of the plain rules
+#define OPTIM_CLIP(Rule, PAIR_LR, MASKED, EMA) {optim_kernel<Rule, PAIR_LR, MASKED, EMA, false>, optim_kernel<Rule, PAIR_LR, MASKED, EMA, true>}
+#define OPTIM_EMA(Rule, PAIR_LR, MASKED) {OPTIM_CLIP(Rule, PAIR_LR, MASKED, false), OPTIM_CLIP(Rule, PAIR_LR, MASKED, true)}
+#define OPTIM_INSTANCES(Rule) {{OPTIM_EMA(Rule, false, false), OPTIM_EMA(Rule, false, true)}, {OPTIM_EMA(Rule, true, false), OPTIM_EMA(Rule, true, true)}}
+#define OPTIM_BEST_CLIP(Rule, PAIR_LR, EMA) {optim_kernel<Rule, PAIR_LR, true, EMA, false, true>, optim_kernel<Rule, PAIR_LR, true, EMA, true, true>}
+#define OPTIM_BEST(Rule) {{OPTIM_BEST_CLIP(Rule, false, false), OPTIM_BEST_CLIP(Rule, false, true)}, {OPTIM_BEST_CLIP(Rule, true, false), OPTIM_BEST_CLIP(Rule, true, true)}}
+    using RmsExt = RmspropExtRule<false, false>;
+    using RmsExtMom = RmspropExtRule<true, false>;
+    using RmsExtCen = RmspropExtRule<false, true>;
+    using RmsExtMomCen = RmspropExtRule<true, true>;
+#define OPTIM_EXT_RULES(M) M(AdamExtRule<false>), M(AdamExtRule<true>), M(RmsExt), M(RmsExtMom), M(RmsExtCen), M(RmsExtMomCen), M(SgdExtRule<false>), M(SgdExtRule<true>)
+    static constexpr decltype(&optim_kernel<AdamRule, false, false, false, false>) ext_kernels[8][2][2][2][2] = {OPTIM_EXT_RULES(OPTIM_INSTANCES)};
+    static constexpr decltype(&optim_kernel<AdamRule, false, false, false, false>) ext_best_kernels[8][2][2][2] = {OPTIM_EXT_RULES(OPTIM_BEST)};
+#undef OPTIM_EXT_RULES
+#undef OPTIM_BEST
+#undef OPTIM_BEST_CLIP
+#undef OPTIM_INSTANCES
+#undef OPTIM_EMA
+#undef OPTIM_CLIP
     if (a.kind < SPLICE_OPT_ADAM || a.kind > SPLICE_OPT_SGD) {
         splice_set_error("optimiser: unknown optimiser kind %d", a.kind);
         return SPLICE_ERR_ARG;
     }
     const bool adam = a.kind == SPLICE_OPT_ADAM, host_step = adam && !a.step_dev;
+    // the extended rules (a.ext): the options are checked as torch.optim checks its arguments, then the arenas the selected rule walks
+    int ext_rule = -1;
+    OptimExtArgs x = {nullptr, 0.f, 0.f, 0.f, 0, 0};
+    if (a.ext) {
+        const splice_optim_ext& e = *a.ext;
+        const char* names[3] = {"Adam", "RMSprop", "SGD"};
+        const bool finite = e.weight_decay <= 3.402823466e+38f && e.momentum <= 3.402823466e+38f && e.dampening >= -3.402823466e+38f && e.dampening <= 3.402823466e+38f;
+        if (!(e.weight_decay >= 0.f) || !(e.momentum >= 0.f) || !finite) {
+            splice_set_error("optimiser: weight_decay and momentum must be finite and >= 0, dampening finite, got %g, %g, %g", (double)e.weight_decay,
+                             (double)e.momentum, (double)e.dampening);
+            return SPLICE_ERR_ARG;
+        }
+        if (e.nesterov && (!(e.momentum > 0.f) || e.dampening != 0.f)) {
+            splice_set_error("optimiser: nesterov needs momentum > 0 and dampening == 0, got momentum %g, dampening %g", (double)e.momentum, (double)e.dampening);
+            return SPLICE_ERR_ARG;
+        }
+        const char* alien = (adam && (e.momentum != 0.f || e.dampening != 0.f || e.nesterov)) ? "momentum / dampening / nesterov"
+                            : (adam && e.centered) || (a.kind == SPLICE_OPT_SGD && e.centered) ? "centered"
+                            : (!adam && e.amsgrad) ? "amsgrad"
+                            : (!adam && e.decoupled) ? "decoupled"
+                            : (a.kind == SPLICE_OPT_RMSPROP && (e.dampening != 0.f || e.nesterov)) ? "dampening / nesterov" : nullptr;
+        if (alien) {
+            splice_set_error("optimiser: %s has no %s", names[a.kind], alien);
+            return SPLICE_ERR_ARG;
+        }
+        const bool mom = !adam && e.momentum > 0.f;
+        ext_rule = adam ? (e.amsgrad ? 1 : 0) : a.kind == SPLICE_OPT_RMSPROP ? 2 + (mom ? 1 : 0) + (e.centered ? 2 : 0) : 6 + (mom ? 1 : 0);
+        const bool needs_w = adam ? e.amsgrad != 0 : e.centered != 0;
+        const char* missing = !a.p ? "params" : !a.g ? "grads" : (adam || mom) && !a.m ? "m" : a.kind != SPLICE_OPT_SGD && !a.v ? "v" : needs_w && !a.w ? "w" : nullptr;
+        if (missing) {
+            splice_set_error("optimiser: the %s rule%s%s%s needs the %s arena, got NULL", names[a.kind], mom ? " with momentum" : "", e.amsgrad ? " with amsgrad" : "",
+                             e.centered ? " (centered)" : "", missing);
+            return SPLICE_ERR_ARG;
+        }
+        if (!a.step_dev && !a.mask_step && a.step < 1) {
+            splice_set_error("optimiser: an extended rule needs the update's step count (on the device, or step >= 1), got step %d", a.step);
+            return SPLICE_ERR_ARG;
+        }
+        x = OptimExtArgs{needs_w ? a.w : nullptr, e.weight_decay, e.momentum, e.dampening, e.nesterov ? 1 : 0, e.decoupled ? 1 : 0};
+    }
     if (!a.p || !a.g || a.n < 1 || (adam && !a.m) || (a.kind != SPLICE_OPT_SGD && !a.v) || (host_step && a.step < 1)) return SPLICE_ERR_ARG;
     // per-pair learning rates index lr_dev with a 32-bit element index
     if (a.lr_stride && (!a.lr_dev || a.lr_stride % 4 || a.n > 0xFFFFFFFFull || a.lr_stride > 0xFFFFFFFFull)) {
@@ -267,11 +447,13 @@ int optim_launch(const OptimArgs& a, hipStream_t s) {
     // stays with the form it has)
     const float bc1 = host_step ? 1.0f - powf(a.hp0, (float)a.step) : 1.f;
     const float bc2_sqrt = host_step ? sqrtf(1.0f - powf(a.hp1, (float)a.step)) : 1.f;
-    const auto kernel = a.best ? best_kernels[a.kind][a.lr_stride != 0][a.ema != nullptr][a.clip != nullptr]
-                               : kernels[a.kind][a.lr_stride != 0][a.mask != nullptr][a.ema != nullptr][a.clip != nullptr];
+    const auto kernel = ext_rule >= 0 ? (a.best ? ext_best_kernels[ext_rule][a.lr_stride != 0][a.ema != nullptr][a.clip != nullptr]
+                                                : ext_kernels[ext_rule][a.lr_stride != 0][a.mask != nullptr][a.ema != nullptr][a.clip != nullptr])
+                        : a.best      ? best_kernels[a.kind][a.lr_stride != 0][a.ema != nullptr][a.clip != nullptr]
+                                      : kernels[a.kind][a.lr_stride != 0][a.mask != nullptr][a.ema != nullptr][a.clip != nullptr];
     SPLICE_LAUNCH(kernel, dim3(optim_grid(a.n)), dim3(256), 0, s, a.p, a.g, a.m, a.v, a.n, a.lr, a.hp0, a.hp1, a.eps, bc1, bc2_sqrt, a.zero_grad,
                   adam ? a.step_dev : nullptr, a.g2, a.lr_dev, (unsigned)a.lr_stride, a.mask, a.mask_step, (unsigned)a.mask_stride,
-                  a.ema, a.ema_decay, a.ema_start, ema_step_dev, a.step, a.clip, (unsigned)a.clip_stride, a.best, a.best_p, a.best_ema);
+                  a.ema, a.ema_decay, a.ema_start, ema_step_dev, a.step, a.clip, (unsigned)a.clip_stride, a.best, a.best_p, a.best_ema, x);
     return SPLICE_OK;
 }
 
@@ -556,5 +738,28 @@ int splice_optim_step_pairs_best(int kind, float* params, float* grads, const fl
     }
     return optim_launch(pairs_args(kind, params, grads, g2, m, v, n_pairs, n_pairs > 1 ? (size_t)stride : 0, n, lr_dev, hp0, hp1, eps, 0, step_dev, stop, zero_grad, ema,
                                    ema_decay, ema_start, clip, best, best_params, best_ema), (hipStream_t)stream);
+}
+// the extended rules for one arena: as splice_optim_step_ex with the option record and the third arena w
+int splice_optim_step_ext(int kind, float* params, float* grads, const float* g2, float* m, float* v, float* w, long long n, float lr, const float* lr_dev,
+                          float hp0, float hp1, float eps, int step, int zero_grad, const splice_optim_ext* options, splice_stream_t stream) {
+    if (!options) { splice_set_error("splice_optim_step_ext: needs the option record"); return SPLICE_ERR_ARG; }
+    OptimArgs a = optim_args(kind, params, grads, g2, m, v, n, lr, lr_dev, 0, hp0, hp1, eps, step, zero_grad);
+    a.w = w; a.ext = options;
+    return optim_launch(a, (hipStream_t)stream);
+}
+// ... and for n_pairs arenas with per-pair lrs: the step count from the device (step_dev) or, step_dev NULL, the host's `step`; stop, ema, clip
+// and best (with its arenas) optional, as the fused step composes them
+int splice_optim_step_pairs_ext(int kind, float* params, float* grads, const float* g2, float* m, float* v, float* w, float* ema, int n_pairs, long long stride,
+                                long long n, const float* lr_dev, float hp0, float hp1, float eps, int step, const int* step_dev, const splice_stop_state* stop,
+                                int zero_grad, float ema_decay, int ema_start, const splice_clip_state* clip, const splice_best_state* best, float* best_params,
+                                float* best_ema, const splice_optim_ext* options, splice_stream_t stream) {
+    if (!options || !params || !grads || !lr_dev || n_pairs < 1 || n < 1 || (n_pairs > 1 && (stride < n || stride % 4))) {
+        splice_set_error("splice_optim_step_pairs_ext: needs the option record, a device lr table, n_pairs >= 1, n >= 1 and, for more than one pair, n <= stride with stride a multiple of 4");
+        return SPLICE_ERR_ARG;
+    }
+    OptimArgs a = pairs_args(kind, params, grads, g2, m, v, n_pairs, n_pairs > 1 ? (size_t)stride : 0, n, lr_dev, hp0, hp1, eps, step, step_dev, stop, zero_grad, ema,
+                             ema_decay, ema_start, clip, best, best_params, best_ema);
+    a.w = w; a.ext = options;
+    return optim_launch(a, (hipStream_t)stream);
 }
 }

@@ -83,6 +83,11 @@ struct SpliceStep {
     int pair_lr = 0;
     float lrs[SPLICE_STEP_MAX_PAIR_CFGS] = {};
     float opt_hp0 = 0.f, opt_hp1 = 0.f, opt_eps = 0.f;
+    // the extended rules (splice_step_set_optimizer_ext): the option record and the caller's third moment arena(s); off: the step launches
+    // what it always did
+    int opt_ext_on = 0;
+    splice_optim_ext opt_ext = {};
+    float* opt_w = nullptr;
     hipStream_t own_stream = nullptr;
     // Cross-stream events, a RING of sets: an eager step records its fork / join events twice and the next step records them again
     // ~2 ms later, while waits on the previous record may still be queued; every record site has an event of its own and a set is
@@ -627,6 +632,22 @@ int splice_step_set_optimizer(void* h, int kind, float hp0, float hp1, float eps
     st->opt_kind = kind; st->opt_hp0 = hp0; st->opt_hp1 = hp1; st->opt_eps = eps;
     return SPLICE_OK;
 }
+// The extended rules of the step's update (include/splice_hip.h states them): the update launch of every later step is the extended instance
+// of the handle's kind, with `w` as its third moment arena.  The record is checked by the launcher at the first step (it knows the kind's
+// rules); here only what the handle itself needs.  Before the first step only: the moments belong to a run from step 0.
+int splice_step_set_optimizer_ext(void* h, const splice_optim_ext* options, float* w) {
+    SpliceStep* st = (SpliceStep*)h;
+    if (!st) return SPLICE_ERR_ARG;
+    if (!options) { splice_set_error("splice_step_set_optimizer_ext: needs the option record"); return SPLICE_ERR_ARG; }
+    if ((options->amsgrad || options->centered) && !w) {
+        splice_set_error("splice_step_set_optimizer_ext: amsgrad / centered need the w arena");
+        return SPLICE_ERR_ARG;
+    }
+    if (int rc = rule_setter_ok(st, "splice_step_set_optimizer_ext", "the options are set")) return rc;
+    st->graphs.retire();
+    st->opt_ext_on = 1; st->opt_ext = *options; st->opt_w = w;
+    return SPLICE_OK;
+}
 // The learning rate of the next splice_step_run (a schedule: scheduler.step(), train.py:80).  It is staged into device memory by the
 // step's input-staging launch and read by the optimiser kernel, so a captured graph replays with the lr of every step.  Until the
 // first call the handle keeps cfg.lr as a kernel argument; the first call drops the handle's graphs.
@@ -1156,6 +1177,7 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
         // keep-best: the record this launch reads was written by THIS step's loss kernel -- on the side stream's tail, in front of the
         // EV_JOIN2 wait above, or on the main stream in front of this launch -- so the update of the step that closes a best window sees it
         if (st->best) { a.best = st->best; a.best_p = st->best_p; a.best_ema = st->best_ema; }   // (another kernel, as with the average)
+        if (st->opt_ext_on) { a.ext = &st->opt_ext; a.w = st->opt_w; }   // (another kernel again: the graph pool keys on the rule it selects)
         RC(optim_launch(a, s));
     }
     return SPLICE_OK;
@@ -1273,7 +1295,9 @@ int splice_step_run(void* h, float* params, float* grads, float* m, float* v, co
             // ... and so is the stop rule: its loss-kernel and update nodes are other kernels than those of a handle without it; and the
             // plateau lr rule, whose loss-kernel node is another kernel again
             const unsigned long long salt = (grouped ? ((unsigned long long)st->pairs << 32) | ((unsigned long long)st->na << 16) | (unsigned long long)st->nb : 0) |
-                                            (st->stop_rule.window > 0 ? 1ull << 63 : 0) | (st->lr_state ? 1ull << 62 : 0);
+                                            (st->stop_rule.window > 0 ? 1ull << 63 : 0) | (st->lr_state ? 1ull << 62 : 0) |
+                                            // ... and the extended rule of the update (bits 56-59: off, or 1 + kind with the arenas it walks)
+                                            (st->opt_ext_on ? (unsigned long long)(1 + st->opt_kind + 3 * ((st->opt_ext.momentum > 0.f ? 1 : 0) + 2 * (st->opt_ext.amsgrad || st->opt_ext.centered ? 1 : 0))) << 56 : 0);
             ex = st->graphs.adopt(variant, g, salt);
             if (!ex) return SPLICE_ERR_HIP;
         }

@@ -1,6 +1,6 @@
 """SpliceEngine / MultiPairEngine: the per-pair optimisation loop of ``train.py:34-80`` on one MI355X.
 
-Owns the frozen DINO-ViT engine, the generator arenas (parameters / gradients / Adam moments,
+Owns the frozen DINO-ViT engine, the generator arenas (parameters / gradients / optimiser moments,
 flat fp32 in ``netG.parameters()`` order, one arena per pair) and the fused step handle.  One engine = one
 GPU = one stream; pairs are independent (no collectives): P of them ride one engine's launches
 (``MultiPairEngine``), and GPUs run independent engines (``bench.py --gpus N``, ``splice_amd.batch``).
@@ -12,7 +12,7 @@ import torch
 
 from . import _lib, synth
 from .generator import GeneratorEngine, GeneratorPlan
-from .util import LrSchedule, fused_optimizer
+from .util import OPTIM_EXT_DEFAULTS, LrSchedule, fused_optimizer, fused_optimizer_ext, optim_ext_uses
 from .vit import VitContext, VitEngine, fp8_mode
 
 LOSS_KEYS = ["loss", "loss_global_ssim", "loss_entire_ssim", "loss_entire_cls", "loss_global_cls", "loss_global_id_B"]
@@ -40,7 +40,11 @@ DEFAULT_CFG = dict(  # conf/default/config.yaml of the reference
     # ... and a cut of a slot's learning rate where the stop rule's windows stop getting better, decided in the loss kernel, off by default
     lr_plateau_factor=0.0, lr_plateau_patience=1, lr_plateau_min_scale=0.0,
     # ... and pair snapshots: stopped slots leave the launches; a run writes checkpoints and continues from one; off by default
-    stop_compact=False, checkpoint_every=0, resume=False)
+    stop_compact=False, checkpoint_every=0, resume=False,
+    # ... and torch.optim's further arguments of the config's optimiser, run by the fused update's extended rules (`optimizer`
+    # also takes adamw): neutral by default -- the update is then the reference's, the very kernels it always was
+    optimizer_weight_decay=0.0, optimizer_momentum=0.0, optimizer_dampening=0.0, optimizer_nesterov=False, optimizer_amsgrad=False,
+    optimizer_centered=False)
 
 SNAPSHOT_FORMAT = 1
 # Keys of a config that do not enter a slot's arithmetic (paths, logging, and how the loop parks and checkpoints): a snapshot is restored
@@ -515,6 +519,8 @@ class MultiPairEngine:
         self.trace_dev = None
         self.lr_rule = lr_plateau_rule(self.cfg)
         self.lr_state_dev = self.lr_cuts_dev = None
+        self.opt_ext = fused_optimizer_ext(self.cfg)   # None: the plain rules, today's launches
+        self.w = None
         P_in = len(gen_states)
         self.cfgs = [self.cfg] * P_in
         self._pair_lambdas = self._pair_lr = False
@@ -634,6 +640,12 @@ class MultiPairEngine:
         self.handle = h
         if self.opt_kind != 0:
             _lib.check(_lib.lib().splice_step_set_optimizer(self.handle, self.opt_kind, *self.opt_hp), "step_set_optimizer")
+        # the extended rules (shared by the slots): the option record, and the third moment arena exactly where the rule keeps one (Adam's
+        # max_exp_avg_sq under amsgrad, RMSprop's grad_avg when centered); m then also holds the momentum buffer; before the first step
+        if self.opt_ext is not None:
+            if optim_ext_uses(self.opt_kind, self.opt_ext)[2]:
+                self.w = torch.zeros_like(self.params)
+            _lib.check(_lib.lib().splice_step_set_optimizer_ext(self.handle, C.byref(_lib.optim_ext(self.opt_ext)), _lib.ptr(self.w)), "step_set_optimizer_ext")
         _lib.check(_lib.lib().splice_step_set_running_stats(self.handle, _lib.ptr(self.running), self.running.stride(0)), "step_set_running_stats")
         # the plateau stop rule (shared by the slots; decided per slot on the device): before the first step
         if self.stop_rule[0] > 0:
@@ -798,7 +810,7 @@ class MultiPairEngine:
         take = (lambda t: t.detach().clone()) if device is None else (lambda t: t.detach().to(device, copy=True))   # (never a view of the engine's memory)
         s = dict(format=SNAPSHOT_FORMAT, step_idx=self.step_idx, cfg=dict(self.cfgs[pair]), n_crops=tuple(self.n_crops_ab), crop_hw=tuple(self.crop_hw),
                  entire_hw=tuple(self.entire_hw) if self.plan_e is not None else None, generator_calls=self.generator_calls[pair])
-        arenas = dict(params=self.params, m=self.m, v=self.v, ema=self.ema, best=self.best, best_ema=self.best_ema)
+        arenas = dict(params=self.params, m=self.m, v=self.v, w=self.w, ema=self.ema, best=self.best, best_ema=self.best_ema)
         for key, arena in arenas.items():
             if arena is not None:
                 s[key] = take(self._pair_arena(arena, pair, key))
@@ -814,7 +826,7 @@ class MultiPairEngine:
         return s
 
     # what a state holds beside the keys every state has, by the rule that keeps it
-    _STATE_KEYS = dict(ema=("ema",), best=("best", "best_rec", "means"), best_ema=("best_ema",), clip_dev=("clip",), clip_auto_dev=("clip_auto",), lr_state_dev=("lr_state", "lr_cuts"),
+    _STATE_KEYS = dict(w=("w",), ema=("ema",), best=("best", "best_rec", "means"), best_ema=("best_ema",), clip_dev=("clip",), clip_auto_dev=("clip_auto",), lr_state_dev=("lr_state", "lr_cuts"),
                        trace_dev=("trace",))
 
     def _check_states(self, states):
@@ -855,7 +867,7 @@ class MultiPairEngine:
         n, dev = self.gen.numel, self.device
         for i, s in enumerate(states):
             sl = slice(i * self.stride, i * self.stride + n)
-            for key, arena in dict(params=self.params, m=self.m, v=self.v, ema=self.ema, best=self.best, best_ema=self.best_ema).items():
+            for key, arena in dict(params=self.params, m=self.m, v=self.v, w=self.w, ema=self.ema, best=self.best, best_ema=self.best_ema).items():
                 if arena is not None:
                     arena[sl].copy_(s[key])
             for key, table in dict(running=self.running, losses=self.losses_dev, best_rec=self.best_dev, means=self.means_dev, clip=self.clip_dev, clip_auto=self.clip_auto_dev,
@@ -1209,11 +1221,14 @@ class MultiScaleEngine:
         self.clip_dev = None
         self.clip_auto = grad_clip_auto_rule(self.cfg)
         self.clip_auto_dev = None
+        self.opt_ext = fused_optimizer_ext(self.cfg)
+        self.w = None
         self.scales = tuple(scales)
         self.engines = []
         for k, sz in enumerate(self.scales):
             # (ema_decay=0, grad_clip_norm=0, grad_clip_auto=0: the handles are gradient-only, the average and the clipping ride in this engine's own update below)
-            e = SpliceEngine(dict(self.cfg, dino_global_patch_size=sz, ema_decay=0.0, grad_clip_norm=0.0, grad_clip_auto=0.0), vit_state if k == 0 else None, gen_state, crop_hw, entire_hw, device=device,
+            # (... and the optimiser options neutral: the extended rule rides in that update too)
+            e = SpliceEngine(dict(self.cfg, dino_global_patch_size=sz, ema_decay=0.0, grad_clip_norm=0.0, grad_clip_auto=0.0, **OPTIM_EXT_DEFAULTS), vit_state if k == 0 else None, gen_state, crop_hw, entire_hw, device=device,
                              vit_engine=vit_engine if k == 0 else self.engines[0].vit, n_crops=n_crops, fp8=fp8)
             _lib.check(_lib.lib().splice_step_set_mode(e.handle, 1, 0), "step_set_mode")
             if k > 0:   # one parameter set: every scale sees the arenas of the first engine; netG bookkeeping once
@@ -1231,6 +1246,8 @@ class MultiScaleEngine:
             self.clip_auto_dev = torch.zeros(1, 6, dtype=torch.int32, device=self.params.device)
         self.step_idx = -1
         self.opt_kind, *self.opt_hp = fused_optimizer(self.cfg)
+        if optim_ext_uses(self.opt_kind, self.opt_ext)[2]:
+            self.w = torch.zeros_like(self.params)
         self.schedule = LrSchedule(self.cfg)
         self.lr = None
 
@@ -1262,7 +1279,7 @@ class MultiScaleEngine:
         optim_step(self.opt_kind, e0.params, e0.grads, e0.m, e0.v, self.lr, *self.opt_hp, self.step_idx + 1, ema=self.ema,
                    ema_decay=self.ema_rule[0], ema_start=self.ema_rule[1], clip_norm=self.grad_clip, clip_state=self.clip_dev,
                    clip_auto=self.clip_auto if self.clip_auto[0] > 0 else None, clip_regime=clip_regime(self.step_idx, self.cfg["cls_warmup"], entire),
-                   clip_auto_state=self.clip_auto_dev)
+                   clip_auto_state=self.clip_auto_dev, ext=self.opt_ext, w=self.w)
 
     def losses(self):
         """Per-scale loss dicts and their sum: ``{"loss": total, "scales": {224: {...}, ...}}``."""

@@ -172,7 +172,7 @@ OPTIMIZER_KINDS = {"adam": 0, "rmsprop": 1, "sgd": 2}   # the `kind` of splice_o
 
 
 def optim_step(kind, params, grads, m, v, lr, hp0, hp1, eps, step, zero_grad=False, g2=None, lr_dev=None, ema=None, ema_decay=0.0, ema_start=0,
-               clip_norm=0.0, clip_state=None, clip_auto=None, clip_regime=0, clip_auto_state=None):
+               clip_norm=0.0, clip_state=None, clip_auto=None, clip_regime=0, clip_auto_state=None, ext=None, w=None):
     """One fused optimiser step over a flat arena (``splice_optim_step_ex``): kind 0 Adam (hp0 / hp1 = betas, step >= 1),
     1 RMSprop (hp0 = alpha, ``v`` = square_avg, ``m`` unused), 2 SGD (``m`` / ``v`` unused).  ``g2``: second gradient arena
     added to ``grads`` first; ``lr_dev``: one-element device tensor read as the learning rate when the kernel runs.
@@ -183,14 +183,22 @@ def optim_step(kind, params, grads, m, v, lr, hp0, hp1, eps, step, zero_grad=Fal
     CUDA tensor of 6 elements that receives the ``splice_clip_state`` record (its two counts are the caller's to start at zero).
     ``clip_auto = (k, beta, warmup)``: the threshold is ``k`` times the running norm of the step's regime ``clip_regime`` (-1, 0 or 1)
     kept in ``clip_auto_state``, an int32 CUDA tensor of 6 elements like ``clip_state`` (zeros at the start of a run), under the cap
-    ``clip_norm`` where that is > 0 (``splice_grad_norm_pairs_auto``)."""
+    ``clip_norm`` where that is > 0 (``splice_grad_norm_pairs_auto``).
+    ``ext``: the options of the extended rules (``util.fused_optimizer_ext``: a dict of the ``splice_optim_ext`` fields, or the
+    record itself) -- an explicit ``ext`` ALWAYS takes the extended kernels, also when its options are neutral (they then compute the
+    plain rules' bits); every kind then needs ``step >= 1``.  ``m`` also holds the momentum buffer of SGD / RMSprop, and ``w`` is the
+    third moment arena: Adam's ``max_exp_avg_sq`` under amsgrad, RMSprop's ``grad_avg`` when centered (``splice_optim_step_pairs_ext``)."""
     if kind not in OPTIMIZER_KINDS.values():
         raise ValueError(f"optim_step: unknown optimiser kind {kind}")
-    m = m if kind == 0 else None            # arenas the kind does not touch are not passed
+    rec = None if ext is None else _lib.optim_ext(ext)
+    mom = rec is not None and kind != 0 and rec.momentum > 0
+    needs_w = rec is not None and bool(rec.amsgrad if kind == 0 else rec.centered if kind == 1 else False)
+    m = m if kind == 0 or mom else None     # arenas the rule does not touch are not passed
     v = v if kind in (0, 1) else None
+    w = w if needs_w else None
     n = params.numel()
-    for name, t, needed in (("params", params, True), ("grads", grads, True), ("g2", g2, False), ("m", m, kind == 0), ("v", v, kind in (0, 1)),
-                            ("ema", ema, False)):
+    for name, t, needed in (("params", params, True), ("grads", grads, True), ("g2", g2, False), ("m", m, kind == 0 or mom), ("v", v, kind in (0, 1)),
+                            ("ema", ema, False), ("w", w, needs_w)):
         if t is None and not needed:
             continue
         if t is None or not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n):
@@ -212,9 +220,28 @@ def optim_step(kind, params, grads, m, v, lr, hp0, hp1, eps, step, zero_grad=Fal
         else:
             _lib.check(_lib.lib().splice_grad_norm_pairs(_lib.ptr(grads), _lib.ptr(g2), 1, 0, n, float(clip_norm), _lib.ptr(partials), _lib.ptr(clip_state),
                                                          None, None, _lib.current_stream()), "grad_norm_pairs")
+        if rec is not None:   # (one arena, the host's step count: the pairs form with its one clip record)
+            lr1 = lr_dev if lr_dev is not None else torch.full((1,), float(lr), dtype=torch.float32, device=params.device)
+            _lib.check(_lib.lib().splice_optim_step_pairs_ext(int(kind), _lib.ptr(params), _lib.ptr(grads), _lib.ptr(g2), _lib.ptr(m), _lib.ptr(v), _lib.ptr(w),
+                                                              _lib.ptr(ema), 1, 0, n, _lib.ptr(lr1), float(hp0), float(hp1), float(eps), int(step), None, None,
+                                                              int(zero_grad), float(ema_decay), int(ema_start), _lib.ptr(clip_state), None, None, None,
+                                                              C.byref(rec), _lib.current_stream()), "optim_step_pairs_ext")
+            return
         _lib.check(_lib.lib().splice_optim_step_clip(int(kind), _lib.ptr(params), _lib.ptr(grads), _lib.ptr(g2), _lib.ptr(m), _lib.ptr(v), _lib.ptr(ema), n,
                                                      float(lr), _lib.ptr(lr_dev), float(hp0), float(hp1), float(eps), int(step), int(zero_grad),
                                                      float(ema_decay), int(ema_start), _lib.ptr(clip_state), _lib.current_stream()), "optim_step_clip")
+        return
+    if rec is not None and ema is not None:
+        lr1 = lr_dev if lr_dev is not None else torch.full((1,), float(lr), dtype=torch.float32, device=params.device)
+        _lib.check(_lib.lib().splice_optim_step_pairs_ext(int(kind), _lib.ptr(params), _lib.ptr(grads), _lib.ptr(g2), _lib.ptr(m), _lib.ptr(v), _lib.ptr(w),
+                                                          _lib.ptr(ema), 1, 0, n, _lib.ptr(lr1), float(hp0), float(hp1), float(eps), int(step), None, None,
+                                                          int(zero_grad), float(ema_decay), int(ema_start), None, None, None, None, C.byref(rec),
+                                                          _lib.current_stream()), "optim_step_pairs_ext")
+        return
+    if rec is not None:
+        _lib.check(_lib.lib().splice_optim_step_ext(int(kind), _lib.ptr(params), _lib.ptr(grads), _lib.ptr(g2), _lib.ptr(m), _lib.ptr(v), _lib.ptr(w), n,
+                                                    float(lr), _lib.ptr(lr_dev), float(hp0), float(hp1), float(eps), int(step), int(zero_grad), C.byref(rec),
+                                                    _lib.current_stream()), "optim_step_ext")
         return
     if ema is not None:
         _lib.check(_lib.lib().splice_optim_step_ema(int(kind), _lib.ptr(params), _lib.ptr(grads), _lib.ptr(g2), _lib.ptr(m), _lib.ptr(v), _lib.ptr(ema), n,

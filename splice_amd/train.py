@@ -392,6 +392,14 @@ def lr_fields(engine, slot=None):
     return {"lr_plateau_factor": factor, "lr_cuts": rec["cuts"], "lr_cut_steps": list(rec["cut_steps"]), "lr_scale": float(rec["scale"])}
 
 
+def optim_fields(engine):
+    """What ``result.json`` / ``variant.json`` say about the optimiser of a run (shared by the slots): ``optimizer``, and every
+    ``optimizer_*`` option (``util.OPTIM_EXT_DEFAULTS``) the run set to another value than its default."""
+    from .util import OPTIM_EXT_DEFAULTS
+    cfg = getattr(engine, "cfg", None) or {}
+    return {"optimizer": cfg.get("optimizer", "adam"), **{k: cfg[k] for k, d in OPTIM_EXT_DEFAULTS.items() if k in cfg and cfg[k] != d}}
+
+
 def best_fields(engine, slot=None):
     """What ``result.json`` says about the stop rule's windows (``splice_amd.batch``) of a run with ``stop_keep_best``: ``best_step`` (the
     step whose weights ``output_best.png`` shows; None: no window closed, they are the initial weights), ``best_window_mean`` and
@@ -527,7 +535,7 @@ def train_sweep(dataroot, variants, cfg_overrides=None, vit_state=None, callback
     losses = engine.losses() if engine.step_idx >= 0 else [{} for _ in range(K)]
     for k in range(K):
         with open(os.path.join(out_dirs[k], 'variant.json'), 'w') as f:
-            json.dump({"index": k, "overrides": variants[k], "seed": seeds[k], "losses": losses[k], "stopped_at": engine.stopped_at[k], **trace_fields(engine), **lr_fields(engine, k)}, f)
+            json.dump({"index": k, "overrides": variants[k], "seed": seeds[k], "losses": losses[k], "stopped_at": engine.stopped_at[k], **trace_fields(engine), **lr_fields(engine, k), **optim_fields(engine)}, f)
     return engine
 
 

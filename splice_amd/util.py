@@ -24,10 +24,63 @@ _SCHEDULERS = {
     'cosine': lambda opt, n_epochs=None, **_: lr_scheduler.CosineAnnealingLR(opt, T_max=n_epochs, eta_min=0),
     'none': lambda opt, **_: lr_scheduler.LambdaLR(opt, lr_lambda=lambda _epoch: 1),
 }
+# The optimiser options beyond the reference's three constructor calls (extensions), every one at torch.optim's
+# neutral value by default; which optimiser takes which key: OPTIM_EXT_TAKES.
+OPTIM_EXT_DEFAULTS = dict(optimizer_weight_decay=0.0, optimizer_momentum=0.0, optimizer_dampening=0.0, optimizer_nesterov=False,
+                          optimizer_amsgrad=False, optimizer_centered=False)
+OPTIM_EXT_TAKES = {
+    'adam': ('optimizer_weight_decay', 'optimizer_amsgrad'),
+    'adamw': ('optimizer_weight_decay', 'optimizer_amsgrad'),
+    'rmsprop': ('optimizer_weight_decay', 'optimizer_momentum', 'optimizer_centered'),
+    'sgd': ('optimizer_weight_decay', 'optimizer_momentum', 'optimizer_dampening', 'optimizer_nesterov'),
+}
+
+
+def optimizer_options(cfg):
+    """The optimiser options of config ``cfg`` (the OPTIM_EXT_DEFAULTS keys, an absent key standing for its default), checked on the
+    host as torch.optim checks its arguments: ``optimizer_weight_decay`` and ``optimizer_momentum`` finite and >= 0,
+    ``optimizer_dampening`` finite, the three flags bools, ``optimizer_nesterov`` only with momentum > 0 and dampening == 0, and no key
+    at a non-default value for an optimiser that has no such argument.  Returns ``{key: value}``; raises ValueError naming the key
+    (an unknown optimiser is left to ``fused_optimizer`` / ``get_optimizer``)."""
+    opts = {}
+    for key, default in OPTIM_EXT_DEFAULTS.items():
+        v = cfg.get(key, default)
+        if isinstance(default, bool):
+            if not isinstance(v, (bool, np.bool_)):
+                raise ValueError(f"'{key}' must be true or false, got {v!r}")
+            v = bool(v)
+        else:
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v):
+                raise ValueError(f"'{key}' must be a finite number, got {v!r}")
+            if key != 'optimizer_dampening' and v < 0:
+                raise ValueError(f"'{key}' must be >= 0, got {v!r}")
+            v = float(v)
+        opts[key] = v
+    name = cfg.get('optimizer', 'adam')
+    takes = OPTIM_EXT_TAKES.get(name)
+    if takes is not None:
+        for key, v in opts.items():
+            if key not in takes and v != OPTIM_EXT_DEFAULTS[key]:
+                hint = " ('optimizer_beta1' is its momentum)" if key == 'optimizer_momentum' and name in ('adam', 'adamw') else ""
+                raise ValueError(f"'{key}' = {v!r}: optimizer [{name}] has no such argument{hint}")
+    if opts['optimizer_nesterov'] and (opts['optimizer_momentum'] <= 0 or opts['optimizer_dampening'] != 0):
+        raise ValueError("'optimizer_nesterov' needs 'optimizer_momentum' > 0 and 'optimizer_dampening' == 0")
+    return opts
+
+
+def _torch_options(cfg):
+    """The torch.optim keyword arguments of ``optimizer_options(cfg)`` for the config's optimiser."""
+    names = dict(optimizer_weight_decay='weight_decay', optimizer_momentum='momentum', optimizer_dampening='dampening',
+                 optimizer_nesterov='nesterov', optimizer_amsgrad='amsgrad', optimizer_centered='centered')
+    opts = optimizer_options(cfg)
+    return {names[k]: opts[k] for k in OPTIM_EXT_TAKES[cfg['optimizer']]}
+
+
 _OPTIMIZERS = {
-    'adam': lambda cfg, params: torch.optim.Adam(params, lr=cfg['lr'], betas=(cfg['optimizer_beta1'], cfg['optimizer_beta2'])),
-    'rmsprop': lambda cfg, params: torch.optim.RMSprop(params, lr=cfg['lr']),
-    'sgd': lambda cfg, params: torch.optim.SGD(params, lr=cfg['lr']),
+    'adam': lambda cfg, params: torch.optim.Adam(params, lr=cfg['lr'], betas=(cfg['optimizer_beta1'], cfg['optimizer_beta2']), **_torch_options(cfg)),
+    'adamw': lambda cfg, params: torch.optim.AdamW(params, lr=cfg['lr'], betas=(cfg['optimizer_beta1'], cfg['optimizer_beta2']), **_torch_options(cfg)),
+    'rmsprop': lambda cfg, params: torch.optim.RMSprop(params, lr=cfg['lr'], **_torch_options(cfg)),
+    'sgd': lambda cfg, params: torch.optim.SGD(params, lr=cfg['lr'], **_torch_options(cfg)),
 }
 
 
@@ -108,13 +161,86 @@ def fused_optimizer(cfg):
     """``(kind, hp0, hp1, eps)`` of the config's ``optimizer`` for the fused update (splice_optim_step): the torch.optim
     arguments get_optimizer uses, every other one at torch's default."""
     name = cfg.get("optimizer", "adam")
-    if name == "adam":
+    if name in ("adam", "adamw"):   # (adamw: Adam's kind, the decoupled flag of fused_optimizer_ext)
         return 0, cfg["optimizer_beta1"], cfg["optimizer_beta2"], 1e-8
     if name == "rmsprop":
         return 1, 0.99, 0.0, 1e-8
     if name == "sgd":
         return 2, 0.0, 0.0, 0.0
     raise NotImplementedError(f"optimizer [{name}] is not implemented")
+
+
+OPTIM_EXT_FIELDS = ("weight_decay", "momentum", "dampening", "nesterov", "decoupled", "amsgrad", "centered")   # splice_optim_ext
+OPTIM_EXT_NEUTRAL = dict(weight_decay=0.0, momentum=0.0, dampening=0.0, nesterov=False, decoupled=False, amsgrad=False, centered=False)
+
+
+def fused_optimizer_ext(cfg):
+    """The option record of the fused update's extended rules (``splice_optim_ext``) for config ``cfg``, as a
+    dict of OPTIM_EXT_FIELDS -- or None when every option is neutral: the engine then launches the plain rules, exactly what it
+    launched before the options existed.  ``adamw`` is Adam with ``decoupled`` set; with ``optimizer_weight_decay`` 0 it is Adam,
+    bit for bit, and counts as neutral.  Checked by ``optimizer_options`` (ValueError naming the key)."""
+    o = optimizer_options(cfg)
+    ext = dict(weight_decay=o["optimizer_weight_decay"], momentum=o["optimizer_momentum"], dampening=o["optimizer_dampening"],
+               nesterov=o["optimizer_nesterov"], decoupled=cfg.get("optimizer", "adam") == "adamw" and o["optimizer_weight_decay"] > 0,
+               amsgrad=o["optimizer_amsgrad"], centered=o["optimizer_centered"])
+    return None if ext == OPTIM_EXT_NEUTRAL else ext
+
+
+def optim_ext_uses(kind, ext):
+    """``(m, v, w)``: which moment arenas the rule of ``kind`` keeps under the options ``ext`` (None: the plain rule).  ``w`` holds
+    Adam's ``max_exp_avg_sq`` (amsgrad) or RMSprop's ``grad_avg`` (centered); ``m`` also the momentum buffer of SGD and RMSprop."""
+    e = ext or OPTIM_EXT_NEUTRAL
+    mom = e["momentum"] > 0
+    return (kind == 0 or mom, kind in (0, 1), (kind == 0 and bool(e["amsgrad"])) or (kind == 1 and bool(e["centered"])))
+
+
+def np_optim_step(kind, p, g, m, v, w, lr, hp0, hp1, eps, t, ext=None, dtype=np.float32):
+    """One update of the fused optimiser's rules (include/splice_hip.h) restated in NumPy at ``dtype``, one
+    rounding per operation in the kernel's association: kind 0 Adam / AdamW (hp0, hp1 = betas), 1 RMSprop (hp0 = alpha), 2 SGD.
+    ``g``: the gradient the rule sees (the sum of the two arenas, times the clip coefficient under clipping); ``t``: the update's
+    step count (>= 1); ``ext``: the options (a dict of OPTIM_EXT_FIELDS; None: neutral); ``m`` / ``v`` / ``w``: the moment arenas
+    (None where the rule keeps none, see ``optim_ext_uses``).  Returns the new ``(p, m, v, w)``; the arguments are not written."""
+    f = np.dtype(dtype).type
+    e = dict(OPTIM_EXT_NEUTRAL, **(ext or {}))
+    arr = lambda x: None if x is None else np.array(x, dtype=f)
+    p, g, m, v, w = arr(p), arr(g), arr(m), arr(v), arr(w)
+    lr, hp0, hp1, eps, one = f(lr), f(hp0), f(hp1), f(eps), f(1)
+    wd, mu, damp = f(e["weight_decay"]), f(e["momentum"]), f(e["dampening"])
+    with np.errstate(all="ignore"):
+        if kind == 0 and e["decoupled"] and wd != 0:
+            p = p * (one - lr * wd)
+        d = g + wd * p if wd != 0 and not (kind == 0 and e["decoupled"]) else g
+        if kind == 2:
+            if mu > 0:
+                m = d.copy() if t == 1 else mu * m + (one - damp) * d
+                d = d + mu * m if e["nesterov"] else m
+            p = p - lr * d
+        elif kind == 1:
+            v = hp0 * v + (one - hp0) * d * d
+            if e["centered"]:
+                w = hp0 * w + (one - hp0) * d
+                avg = np.sqrt(v - w * w) + eps
+            else:
+                avg = np.sqrt(v) + eps
+            if mu > 0:
+                m = mu * m + d / avg
+                p = p - lr * m
+            else:
+                p = p - lr * (d / avg)
+        elif kind == 0:
+            bc1 = one - hp0 ** f(t)
+            bc2_sqrt = np.sqrt(one - hp1 ** f(t))
+            m = hp0 * m + (one - hp0) * d
+            v = hp1 * v + (one - hp1) * d * d
+            if e["amsgrad"]:
+                w = np.maximum(w, v)
+                denom = np.sqrt(w) / bc2_sqrt + eps
+            else:
+                denom = np.sqrt(v) / bc2_sqrt + eps
+            p = p - (lr / bc1) * (m / denom)
+        else:
+            raise ValueError(f"np_optim_step: unknown optimiser kind {kind}")
+    return p, m, v, w
 
 
 def write_loss_trace(path, rows, lrs, active, clip):
