@@ -434,7 +434,8 @@ void splice_step_destroy(void* step);
 /* params / grads / m / v: [P][arena_stride] (one flat arena for P = 1); A_crop, B_crop: [P][3][h][w] at the current crop
  * sizes; A_entire: [P][3][ent_h][ent_w] or NULL (needed when step_idx % entire_every == 0).
  * losses_out: device fp32 [P][8], per pair {loss, loss_global_ssim, loss_entire_ssim, loss_entire_cls, loss_global_cls,
- * loss_global_id_B, 0, 0} -- the keys of the dict LossG.forward returns.  Written by the step's own loss kernel; the
+ * loss_global_id_B, 0, 0} -- the keys of the dict LossG.forward returns (words 6-7: the two image-space terms on a handle with
+ * splice_step_set_image_terms).  Written by the step's own loss kernel; the
  * captured hipGraph is bound to the arena pointers AND to losses_out, so keep passing the same buffers (a different
  * pointer re-captures; two consecutive steps with identical pointers and crop sizes are needed before a graph is used). */
 int splice_step_run(void* step, float* params, float* grads, float* m, float* v, const float* A_crop, const float* B_crop,
@@ -774,6 +775,44 @@ int splice_mse_pairs(const float* a, int lda, size_t a_ps, const float* b, int l
 int splice_total_loss_pairs(float* lbase, size_t lstride, int lp, float w_ssim, float w_essim, float w_ecls, float w_cls, float w_id,
                             float* out8, int pairs, int n_a, int n_b, int n_c, int n_e, const float* wtab, int ssim_on, int entire,
                             splice_stream_t stream);
+/* ------------------------------------------------------------------ the image-space loss terms: two regularisers on the
+ * generator's outputs at the crops' own resolution, beside the five terms seen through the ViT.  Per pair, fp32 images [3][h][w]:
+ *   loss_global_tv        sum over the pair's A crops of TV(x'_i), x' = G(A_crop):
+ *                           TV(x) = mean |x[:,1:,:] - x[:,:-1,:]| + mean |x[:,:,1:] - x[:,:,:-1]|,
+ *                         each mean over its own count 3 (h - 1) w / 3 h (w - 1); a direction without differences contributes 0.  The
+ *                         derivative takes sign(0) = 0, the sign being that of the fp32 difference of the two fp32 pixels.
+ *   loss_global_pix_id_B  sum over the pair's B crops of mean((y'_i - B_crop_i)^2) over 3 h w, y' = G(B_crop), B_crop the staged input;
+ *                         gradient 2 (y' - B_crop) / (3 h w).
+ * Both act on every step from step 0 (cls_warmup does not gate them, entire-image steps change nothing; the entire-image output G(A) gets
+ * neither).  The raw values are words 6 and 7 of the pair's losses_out row; the total becomes
+ *   fma(lambda_pix, raw_7, fma(lambda_tv, raw_6, total of the five terms)),
+ * so the stop rule, the plateau lr rule, keep-best and word 0 of a trace row see it.  Trace words 6-7 stay the clip norm and coefficient:
+ * the two raw values are not traced.  The weights are shared by all pairs of the handle (splice_step_set_pair_weights has no column for
+ * them).  Launches added with a weight > 0: one value launch at the loss stage (both terms), one gradient-add launch on that term's
+ * backward chain between the un-resize of the ViT's image gradient and the generator backward; the loss kernel runs its IMG instance
+ * (448 threads).  With both 0 the handle launches what it launches without the call.  Accepted before the first splice_step_run only;
+ * refused: a negative or non-finite weight, a handle in gradient-only (splice_step_set_mode) or phase mode or with a leader
+ * (splice_step_set_phases) -- a follower adds its image gradients into its leader's, which would count the terms once per follower --
+ * and such a handle in turn refuses those two calls. */
+int splice_step_set_image_terms(void* step, float lambda_tv, float lambda_pix);
+/* test hook: the step's value launch on caller buffers.  x ([n_x][3][xh][xw]; NULL: TV off) and y, b ([n_y][3][yh][yw]; y NULL: pixel
+ * identity off) are the images; lbase is a partials buffer in the layout of splice_total_loss_pairs with lstride >= 8 + 8 * lp, zeroed
+ * by the caller.  Image i's chunk c (SPLICE_IMAGE_TERMS_CHUNK consecutive floats of the image, counted from its start) writes
+ * lbase[i * lstride + 8 + k * lp + c], k = 6 (TV: chunk's vertical addends / (3 (h - 1) w) + its horizontal addends / (3 h (w - 1)),
+ * a pixel's addends being those with its lower and its right neighbour) or 7 (sum of squared differences / (3 h w)); the other slots are
+ * not written.  Refused before anything is launched: a missing operand, a size < 1, more than lp chunks per image. */
+#define SPLICE_IMAGE_TERMS_CHUNK 4096
+int splice_image_terms_value(const float* x, int n_x, int xh, int xw, const float* y, const float* b, int n_y, int yh, int yw, float* lbase,
+                             size_t lstride, int lp, splice_stream_t stream);
+/* test hook: the step's gradient-add launch: d[n_img][3][h][w] += lambda * dTV/dx(x) (b NULL) or += lambda * 2 (x - b) / (3 h w) (b
+ * given), in place; the term's gradient is formed in double and rounded to fp32 once before the add.  lambda finite, >= 0. */
+int splice_image_terms_grad_add(const float* x, const float* b, float* d, int n_img, int h, int w, float lambda, splice_stream_t stream);
+/* test hook: splice_total_loss_pairs as a handle with image-space terms launches it (the IMG instance): terms 6 (n_a slots per pair) and
+ * 7 (n_b slots) of the partials are summed as the others, slot p's values [6..7] and out8[p][6..7] receive raw_6 and raw_7, and
+ * total = fma(w_pix, raw_7, fma(w_tv, raw_6, the total of splice_total_loss_pairs)).  lstride >= 8 + 8 * lp. */
+int splice_total_loss_pairs_img(float* lbase, size_t lstride, int lp, float w_ssim, float w_essim, float w_ecls, float w_cls, float w_id,
+                                float* out8, int pairs, int n_a, int n_b, int n_c, int n_e, const float* wtab, int ssim_on, int entire,
+                                float w_tv, float w_pix, splice_stream_t stream);
 /* splice_total_loss_pairs as a handle with a loss trace launches it (splice_step_set_loss_trace): dev_t (device) holds step index + 1,
  * and words 0-5 of row step index of trace ([capacity][pairs][8], device) receive pair p's out8 values, a row at or beyond capacity
  * left out.  stop (may be NULL; device, [pairs] records) runs the instance of a handle with the stop rule, whose rule is window (>= 1),

@@ -239,6 +239,11 @@ _SIGNATURES = {
     "splice_optim_step_pairs_ext": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_longlong, C.c_longlong, _vp, _f, _f, _f, _i, _vp, _vp, _i, _f, _i, _vp, _vp,
                                      _vp, _vp, C.POINTER(OptimExt), _vp], _i),
     "splice_step_set_optimizer_ext": ([_vp, C.POINTER(OptimExt), _vp], _i),
+    # image-space loss terms (total variation of x', pixel identity of y')
+    "splice_step_set_image_terms": ([_vp, _f, _f], _i),
+    "splice_image_terms_value": ([_vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _sz, _i, _vp], _i),
+    "splice_image_terms_grad_add": ([_vp, _vp, _vp, _i, _i, _i, _f, _vp], _i),
+    "splice_total_loss_pairs_img": ([_vp, _sz, _i, _f, _f, _f, _f, _f, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _f, _f, _vp], _i),
     "splice_prof_begin": ([_i], _i),
     "splice_prof_end": ([C.POINTER(_f), C.POINTER(_i)], _i),
     "splice_prof_end_ex": ([C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)], _i),

@@ -53,6 +53,10 @@ The run ends by writing ``out/losses.csv`` (``out/sweep/<k>/losses.csv`` per var
 ``optimizer_momentum`` / ``optimizer_centered`` for rmsprop, ``optimizer_amsgrad`` for adam / adamw; shared by the variants of a sweep) run torch.optim's
 further arguments inside the fused update; ``result.json`` carries ``optimizer`` and every such option that is not at its default.
 
+``--set lambda_global_tv=0.1`` / ``--set lambda_global_pixel_identity=1`` (shared by the variants of a sweep) add two loss terms on the generated
+crops themselves inside the fused step -- the total variation of G(A_crop) and mse(G(B_crop), B_crop); ``result.json`` carries each key that
+is not 0, and a pair's losses then hold ``loss_global_tv`` / ``loss_global_pix_id_B``.
+
     python -m splice_amd.batch --root pairs/ --gpus 8 [--pairs-per-gpu P] [--n_epochs 2000] [--set key=value ...]
 
 ``--pairs-per-gpu P`` works with ``--set global_A_crops_n_crops=n`` (and ``global_B_crops_n_crops``): each pair's n crops are one
@@ -106,11 +110,12 @@ def _slot_fields(eng, slot=None):
     (steps that updated the slot) and ``stopped_at`` (the step index it stopped at, or None).  The weight average: ``ema_decay`` (0: none
     was kept, there is no ``output_ema.png``).  Gradient clipping, the best window, the loss trace and the plateau lr rule:
     ``train.clip_fields`` / ``train.best_fields`` / ``train.trace_fields`` / ``train.lr_fields``.  The optimiser: ``optimizer`` and every
-    ``optimizer_*`` option that is not at its default (``train.optim_fields``)."""
-    from .train import best_fields, clip_fields, lr_fields, optim_fields, trace_fields
+    ``optimizer_*`` option that is not at its default (``train.optim_fields``).  The image-space loss terms: each of their two lambdas that
+    is not 0 (``train.image_terms_fields``)."""
+    from .train import best_fields, clip_fields, image_terms_fields, lr_fields, optim_fields, trace_fields
     at = eng.stopped_at if slot is None else eng.stopped_at[slot]
     return {"steps_run": eng.step_idx + 1 if at is None else at + 1, "stopped_at": at, "ema_decay": eng.ema_rule[0],
-            **clip_fields(eng, slot), **best_fields(eng, slot), **trace_fields(eng), **lr_fields(eng, slot), **optim_fields(eng)}
+            **clip_fields(eng, slot), **best_fields(eng, slot), **trace_fields(eng), **lr_fields(eng, slot), **optim_fields(eng), **image_terms_fields(eng)}
 
 
 def _timed(train, *args, **kw):

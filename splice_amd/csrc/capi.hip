@@ -163,6 +163,24 @@ int splice_mse_pairs(const float* a, int lda, size_t a_ps, const float* b, int l
                   "splice_mse_pairs");
 }
 
+/* test hooks: the image-space terms' launchers (image_terms.hip) on caller-owned buffers, in the step's partials layout */
+static_assert(SPLICE_IMAGE_TERMS_CHUNK == IMAGE_TERMS_CHUNK, "the header states the value kernel's chunk");
+int splice_image_terms_value(const float* x, int n_x, int xh, int xw, const float* y, const float* b, int n_y, int yh, int yw, float* lbase,
+                             size_t lstride, int lp, splice_stream_t stream) {
+    const char* who = "splice_image_terms_value";
+    if (!lbase || lp < 1 || lstride < 8 + (size_t)8 * lp || (!x && !y) || (y && !b)) return finish(SPLICE_ERR_ARG, who);
+    const int rc = image_terms_value_launch(x, n_x, xh, xw, lbase + 8 + (size_t)6 * lp, y, b, n_y, yh, yw, lbase + 8 + (size_t)7 * lp, lstride, (size_t)lp,
+                                            ST(stream));
+    if (rc != SPLICE_OK) return rc;   // (the launcher's own message stays)
+    return finish(rc, who);
+}
+int splice_image_terms_grad_add(const float* x, const float* b, float* d, int n_img, int h, int w, float lambda, splice_stream_t stream) {
+    if (!(lambda <= 3.402823466e+38f)) return finish(SPLICE_ERR_ARG, "splice_image_terms_grad_add");
+    const int rc = b ? image_pix_grad_add_launch(x, b, d, n_img, h, w, lambda, ST(stream)) : image_tv_grad_add_launch(x, d, n_img, h, w, lambda, ST(stream));
+    if (rc != SPLICE_OK) return rc;
+    return finish(rc, "splice_image_terms_grad_add");
+}
+
 /* test hooks: the [CLS]-tail launchers of the top ViT block (vit_cls.hip) on caller-owned buffers.  They only validate and forward. */
 static bool attn_cls_args_ok(const void* qkv, const void* qkvT, int ldt, int B, int T, int Tld, int D, int H, size_t lds) {
     if (!qkv || !qkvT || B < 1 || T < 1 || T > Tld || Tld % 32 || ldt % 8 || (long long)ldt < (long long)B * Tld || D < 64 || D % 64 || H != D / 64)

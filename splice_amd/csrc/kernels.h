@@ -153,3 +153,14 @@ int mse_partials_launch(const float* a, int lda, const float* b, int ldb, int ro
                         float* part, float* grad, int ldg, hipStream_t s);
 int mse2_launch(const float* a, int lda, const float* b, int ldb, int rows, int cols, float loss_weight, float grad_weight,
                 float* loss_accum, float* grad, int ldg, hipStream_t s);
+
+// ---- image_terms.hip: the image-space loss terms of the step (total variation of x', pixel identity of y') ----
+#define IMAGE_TERMS_CHUNK 4096   // floats of an image per workgroup (and per partial slot) of the value kernel
+// Partial sums of TV(x_i) (x: [n_x][3][xh][xw]; NULL: term off) into part_tv + i * part_istride and of mean((y_i - b_i)^2) (y, b:
+// [n_y][3][yh][yw]; y NULL: term off) into part_pix + i * part_istride: chunk c of an image writes slot c, ceil(3 h w / IMAGE_TERMS_CHUNK) <=
+// part_cap slots per image, each already divided by its mean's count; the other slots are not written.  One launch; none with both off.
+int image_terms_value_launch(const float* x, int n_x, int xh, int xw, float* part_tv, const float* y, const float* b, int n_y, int yh, int yw,
+                             float* part_pix, size_t part_istride, size_t part_cap, hipStream_t s);
+// d += lambda * dTV/dx  and  d += lambda * 2 (y - b) / (3 h w)  on [n_img][3][h][w], in place
+int image_tv_grad_add_launch(const float* x, float* d, int n_img, int h, int w, float lambda, hipStream_t s);
+int image_pix_grad_add_launch(const float* y, const float* b, float* d, int n_img, int h, int w, float lambda, hipStream_t s);

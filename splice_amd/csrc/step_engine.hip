@@ -28,6 +28,9 @@
 // the host [P][5] lambdas of splice_step_set_pair_weights (and in pw_any).  PW_*: row ([P] floats each) of the device tables built from them --
 // e_scale of the two structure terms, gradient weights of the three MSE terms -- followed at row PW_LAMBDAS by a copy of the [P][5] lambdas.
 enum { L_TOTAL = 0, L_GLOBAL_SSIM = 1, L_ENTIRE_SSIM = 2, L_ENTIRE_CLS = 3, L_GLOBAL_CLS = 4, L_GLOBAL_ID = 5, L_TERMS = 6 };
+// the two image-space terms (splice_step_set_image_terms; image_terms.hip): slots 6 and 7 of the losses row and of the partials, outside the
+// tables above -- their weights are the handle's two scalars, shared by the slots of a sweep, and no schedule gates them
+enum { L_GLOBAL_TV = 6, L_GLOBAL_PIX = 7 };
 enum { LAM_CLS = 0, LAM_SSIM = 1, LAM_ID = 2, LAM_ECLS = 3, LAM_ESSIM = 4 };
 enum { PW_ESCALE_G = 0, PW_ESCALE_E = 1, PW_CLS = 2, PW_ID = 3, PW_ECLS = 4, PW_LAMBDAS = 5, PW_ROWS = 10 };
 static const int TERM_LAM[L_TERMS] = {-1, LAM_SSIM, LAM_ESSIM, LAM_ECLS, LAM_CLS, LAM_ID};          // by L_*
@@ -154,6 +157,9 @@ struct SpliceStep {
     // pairs; pairs_in 0: off -- the step launches what it always did
     int pairs_in = 0;
     int in_rows[SPLICE_STEP_MAX_PAIR_CFGS] = {};
+    // the image-space terms (splice_step_set_image_terms): lambda_global_tv on x' = G(A_crop), lambda_global_pixel_identity on y' = G(B_crop)
+    // against B_crop; both 0: off -- the step launches what it always did
+    float lambda_tv = 0.f, lambda_pix = 0.f;
 };
 
 static size_t arena_floats(const SpliceStep* st) { return st->astride ? st->pairs * st->astride : (size_t)st->nparams; }   // of all pairs' arenas
@@ -217,17 +223,21 @@ static int view_init(SpliceStep* st, VitView& v, void* ctx, int want_B) {
 // EVERY step it writes lr_eff[pair] = lr_in[pair * lr_in_stride] * scale (lr_in: the staged per-pair table, stride 1, or the one staged
 // lr, stride 0), on counted steps the stop rule follows and the pair's lr record takes its verdict.  The instances without LRP do not
 // read the six trailing arguments.
-template <bool MONITOR, bool TRACE, bool LRP = false>
-__global__ __launch_bounds__(320) void total_loss_kernel(float* lbase, size_t lstride, int lp, float w_ssim, float w_essim, float w_ecls, float w_cls,
+// IMG (the image-space terms): two waves more own terms 6 (total variation, the pair's n_a slots) and 7 (pixel identity,
+// its n_b slots); their raw sums go to words 6-7 of the row and of out8 and into the total as fmaf(w_pix, raw_7, fmaf(w_tv, raw_6, total of
+// the five)).  The two weights are not in wtab: a sweep's slots share them.  The instances without IMG do not read the two trailing
+// arguments and launch with 320 threads, as before.
+template <bool MONITOR, bool TRACE, bool LRP = false, bool IMG = false>
+__global__ __launch_bounds__(IMG ? 448 : 320) void total_loss_kernel(float* lbase, size_t lstride, int lp, float w_ssim, float w_essim, float w_ecls, float w_cls,
                                                          float w_id, float* out8, int n_a, int n_b, int n_c, int n_e, const float* wtab, int ssim_on,
                                                          int entire, splice_stop_state* stop, const int* dev_t, StopRule rule, splice_best_state* kb,
                                                          float* means, float* trace, int capacity, LrRule lr_rule, splice_lr_state* lr_state, int* lr_cuts,
-                                                         const float* lr_in, int lr_in_stride, float* lr_eff) {
+                                                         const float* lr_in, int lr_in_stride, float* lr_eff, float w_tv, float w_pix) {
     static_assert(MONITOR || !LRP, "the lr rule rides on the stop rule");
     __shared__ float raw[8];
     float* l = lbase + (size_t)blockIdx.x * lstride;
-    const int k = 1 + (threadIdx.x >> 6), lane = threadIdx.x & 63;   // wave k-1 owns term k (5 waves)
-    const int n_slots = k == L_GLOBAL_SSIM ? n_a : k == L_GLOBAL_ID ? n_b : k == L_GLOBAL_CLS ? n_c : n_e;
+    const int k = 1 + (threadIdx.x >> 6), lane = threadIdx.x & 63;   // wave k-1 owns term k (5 waves; 7 with IMG)
+    const int n_slots = k == L_GLOBAL_SSIM ? n_a : k == L_GLOBAL_ID ? n_b : k == L_GLOBAL_CLS ? n_c : (IMG && k == L_GLOBAL_TV) ? n_a : (IMG && k == L_GLOBAL_PIX) ? n_b : n_e;
     const float* lp0 = lbase + (size_t)blockIdx.x * n_slots * lstride;   // the pair's first slot of this term
     float tot = 0.f;
     for (int slot = 0; slot < n_slots; ++slot) {
@@ -253,11 +263,15 @@ __global__ __launch_bounds__(320) void total_loss_kernel(float* lbase, size_t ls
         // of `w_ssim * raw_1 + w_essim * raw_2 + ...` in every instance before the lr rule, and would not make of it in the LRP instances)
         l[L_TOTAL] = __builtin_fmaf(w_id, raw[L_GLOBAL_ID], __builtin_fmaf(w_cls, raw[L_GLOBAL_CLS], __builtin_fmaf(w_ecls, raw[L_ENTIRE_CLS],
                          __builtin_fmaf(w_ssim, raw[L_GLOBAL_SSIM], w_essim * raw[L_ENTIRE_SSIM]))));
+        if (IMG) {
+            l[L_GLOBAL_TV] = raw[L_GLOBAL_TV]; l[L_GLOBAL_PIX] = raw[L_GLOBAL_PIX];
+            l[L_TOTAL] = __builtin_fmaf(w_pix, raw[L_GLOBAL_PIX], __builtin_fmaf(w_tv, raw[L_GLOBAL_TV], l[L_TOTAL]));
+        }
         if (out8) {   // the caller's losses buffer, written here instead of by a copy behind the step
             float* o = out8 + (size_t)blockIdx.x * 8;
             o[0] = l[L_TOTAL];
             for (int t = 1; t <= 5; ++t) o[t] = raw[t];
-            o[6] = 0.f; o[7] = 0.f;
+            o[6] = IMG ? raw[L_GLOBAL_TV] : 0.f; o[7] = IMG ? raw[L_GLOBAL_PIX] : 0.f;
         }
         if (TRACE) {
             const int row = *dev_t - 1;
@@ -285,6 +299,16 @@ __global__ __launch_bounds__(64) void plateau_update_kernel(splice_stop_state* s
 }
 // the six trailing arguments of a total_loss_kernel launch without the plateau lr rule
 #define NO_LR_RULE LrRule{}, (splice_lr_state*)nullptr, (int*)nullptr, (const float*)nullptr, 0, (float*)nullptr
+// the two trailing arguments behind them of a launch without the image-space terms
+#define NO_IMG_TERMS 0.f, 0.f
+// the step's instance by what the handle carries (the lr rule rides on the stop rule)
+using TotalLossKernel = decltype(&total_loss_kernel<false, false>);
+template <bool IMG>
+static TotalLossKernel total_loss_instance(bool lr_rule, bool trace, bool stop) {
+    return lr_rule ? (trace ? total_loss_kernel<true, true, true, IMG> : total_loss_kernel<true, false, true, IMG>)
+           : trace ? (stop ? total_loss_kernel<true, true, false, IMG> : total_loss_kernel<false, true, false, IMG>)
+                   : (stop ? total_loss_kernel<true, false, false, IMG> : total_loss_kernel<false, false, false, IMG>);
+}
 // the two rules alone on a caller's [pairs][8] losses (splice_plateau_update_lr): one thread per slot, the loss kernel's device function
 __global__ __launch_bounds__(64) void plateau_update_lr_kernel(splice_stop_state* stop, splice_lr_state* lr_state, int* lr_cuts, const float* losses8, int pairs,
                                                                StopRule rule, LrRule lr_rule, int step_idx, int counted, const float* lr_in, int lr_in_stride,
@@ -597,7 +621,8 @@ int splice_step_set_crops(void* h, int a_h, int a_w, int b_h, int b_w) {
 // mode), named for an error text; null: none.
 static const char* whole_step_rule(const SpliceStep* st) {
     return st->stop_rule.window > 0 ? "with a stop rule" : st->ema ? "with a weight average" : st->clip ? "with gradient clipping"
-           : st->best ? "that keeps the best weights" : st->trace ? "with a loss trace" : nullptr;
+           : st->best ? "that keeps the best weights" : st->trace ? "with a loss trace"
+           : (st->lambda_tv > 0.f || st->lambda_pix > 0.f) ? "with image-space loss terms" : nullptr;
 }
 // The shared opening of the rule setters below: before the first step only (`what` of the rule, for the error text), and not on a
 // gradient-only or phase-mode handle.  Callers return its code plainly, not through RC(): the message stays the last error.
@@ -846,6 +871,29 @@ int splice_step_set_lr_plateau(void* h, float factor, int patience, float min_sc
     st->lr_rule = LrRule{factor, patience, min_scale}; st->lr_state = state; st->lr_cuts = cut_steps;
     return SPLICE_OK;
 }
+// The image-space loss terms of every pair of the handle (include/splice_hip.h has the terms): one value launch at the loss stage, one
+// gradient-add launch per backward chain whose weight is > 0, and the IMG instance of the loss kernel.  Before the first step only, and not
+// on a gradient-only or phase-mode handle: a follower adds its image gradients into its leader's, which would count the terms once per
+// follower.  The value kernel writes one partial per IMAGE_TERMS_CHUNK floats of an image: a handle whose largest crop needs more slots
+// than the other terms do gets a wider partials buffer here (zeros added to a fixed-order sum change no bit of the other terms).
+int splice_step_set_image_terms(void* h, float lambda_tv, float lambda_pix) {
+    SpliceStep* st = (SpliceStep*)h;
+    if (!st) return SPLICE_ERR_ARG;
+    if (!(lambda_tv >= 0.f) || !(lambda_tv <= 3.402823466e+38f) || !(lambda_pix >= 0.f) || !(lambda_pix <= 3.402823466e+38f)) {
+        splice_set_error("splice_step_set_image_terms: needs finite lambda_tv >= 0 and lambda_pix >= 0, got %g, %g", (double)lambda_tv, (double)lambda_pix);
+        return SPLICE_ERR_ARG;
+    }
+    if (int rc = rule_setter_ok(st, "splice_step_set_image_terms", "the terms are set")) return rc;
+    const size_t chunks = ((size_t)3 * st->max_crop_h * st->max_crop_w + IMAGE_TERMS_CHUNK - 1) / IMAGE_TERMS_CHUNK;
+    if ((lambda_tv > 0.f || lambda_pix > 0.f) && chunks > st->lp) {
+        float* wider = nullptr;
+        RC(salloc(st, &wider, (size_t)st->P * (8 + 8 * chunks)));
+        st->losses = wider; st->lp = chunks; st->lstride = 8 + 8 * chunks;   // (the narrower buffer stays with the handle until it goes)
+    }
+    st->graphs.retire();
+    st->lambda_tv = lambda_tv; st->lambda_pix = lambda_pix;
+    return SPLICE_OK;
+}
 // Start the handle at step next_step_idx of a run other handles carried so far (a resumed run, a compacted engine; DESIGN.md section
 // 9g).  What a handle keeps from one step to the next, and this call therefore sets, is two things: ssim_id_on, which only the run of step
 // cls_warmup switches on, and the stop records.  Nothing else in the handle is state: dev_t and the lr(s) are staged by every step's
@@ -938,7 +986,21 @@ int splice_total_loss_pairs(float* lbase, size_t lstride, int lp, float w_ssim, 
     const auto kernel = total_loss_kernel<false, false>;
     SPLICE_LAUNCH(kernel, dim3(pairs), dim3(320), 0, (hipStream_t)stream, lbase, lstride, lp, w_ssim, w_essim, w_ecls, w_cls, w_id, out8,
                   n_a, n_b, n_c, n_e, wtab, ssim_on, entire, (splice_stop_state*)nullptr, (const int*)nullptr, StopRule{}, (splice_best_state*)nullptr,
-                  (float*)nullptr, (float*)nullptr, 0, NO_LR_RULE);
+                  (float*)nullptr, (float*)nullptr, 0, NO_LR_RULE, NO_IMG_TERMS);
+    return SPLICE_OK;
+}
+// test hook: the same launch with the image-space terms (the IMG instance, 448 threads): terms 6 / 7 of the partials (lstride >= 8 + 8 lp)
+int splice_total_loss_pairs_img(float* lbase, size_t lstride, int lp, float w_ssim, float w_essim, float w_ecls, float w_cls, float w_id, float* out8,
+                                int pairs, int n_a, int n_b, int n_c, int n_e, const float* wtab, int ssim_on, int entire, float w_tv, float w_pix,
+                                splice_stream_t stream) {
+    if (!lbase || pairs < 1 || lp < 1 || lstride < 8 + (size_t)8 * lp || n_a < 1 || n_b < 1 || n_c < 1 || n_e < 1 || !(w_tv >= 0.f) || !(w_pix >= 0.f)) {
+        splice_set_error("splice_total_loss_pairs_img: invalid argument");
+        return SPLICE_ERR_ARG;
+    }
+    const auto kernel = total_loss_kernel<false, false, false, true>;
+    SPLICE_LAUNCH(kernel, dim3(pairs), dim3(448), 0, (hipStream_t)stream, lbase, lstride, lp, w_ssim, w_essim, w_ecls, w_cls, w_id, out8,
+                  n_a, n_b, n_c, n_e, wtab, ssim_on, entire, (splice_stop_state*)nullptr, (const int*)nullptr, StopRule{}, (splice_best_state*)nullptr,
+                  (float*)nullptr, (float*)nullptr, 0, NO_LR_RULE, w_tv, w_pix);
     return SPLICE_OK;
 }
 // test hook: the same launch with the loss trace (the TRACE instances): dev_t holds step index + 1 on the device; stop (optional, with its
@@ -958,7 +1020,7 @@ int splice_total_loss_pairs_trace(float* lbase, size_t lstride, int lp, float w_
     const auto kernel = stop ? total_loss_kernel<true, true> : total_loss_kernel<false, true>;
     SPLICE_LAUNCH(kernel, dim3(pairs), dim3(320), 0, (hipStream_t)stream, lbase, lstride, lp, w_ssim, w_essim, w_ecls, w_cls, w_id, out8, n_a, n_b, n_c, n_e, wtab,
                   ssim_on, entire, stop, dev_t, stop ? StopRule{window, rel, patience, min_steps} : StopRule{}, (splice_best_state*)nullptr, (float*)nullptr, trace,
-                  capacity, NO_LR_RULE);
+                  capacity, NO_LR_RULE, NO_IMG_TERMS);
     return SPLICE_OK;
 }
 
@@ -994,16 +1056,21 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
     const StepPtrs ip = step_ptrs(st);
     // a follower (splice_step_set_phases) sees the leader's images and adds its image gradients to the leader's
     const StepPtrs src = st->leader ? step_ptrs(st->leader) : ip;
+    const bool img_on = st->lambda_tv > 0.f || st->lambda_pix > 0.f;   // (whole-step handles without a leader only: src == ip)
     const bool do_gf = (st->phases & 1) != 0, do_v = (st->phases & 2) != 0, do_gb = (st->phases & 4) != 0;
     const bool gen_fwd = do_gf && !(st->ablate & 1), gen_bwd = do_gb && !(st->ablate & 2);
     // Backward of one image chain on stream q: ViT data gradient of passes [p0, p1) of view vw (`vit`), un-resized into the gradient d_img of
     // the chain's generated images [h][w], added to the leader's d_lead by a follower; then (`gen`) the generator backward of `plan` into `arena`.
+    // `img_term` (L_GLOBAL_TV on the x' chain, L_GLOBAL_PIX on the y' chain, 0 on the entire-image chain): with that term's weight > 0 its
+    // gradient is added into d_img in place, one launch, from the chain's saved generator output.
     auto chain_bwd = [&](VitView& vw, int p0, int p1, bool vit, float* d_img, int h, int w, float* d_lead, void* plan, float* arena, int accumulate,
-                         bool gen, hipStream_t q) -> int {
+                         bool gen, int img_term, hipStream_t q) -> int {
         if (do_v) {
             if (vit) RC(splice_vit_backward(vw.ctx, p0, p1, vw.pb.data(), nullptr, vw.pk.data(), vw.d_imgs, 1, q));
             RC(unplace_grads(vw.d_imgs + (size_t)p0 * 3 * vw.H * vw.W, vw.H, vw.W, d_img, h, w, p1 - p0, q));
             if (st->leader) RC(add_f32_launch(d_lead, d_img, (size_t)(p1 - p0) * 3 * h * w, q));
+            if (img_term == L_GLOBAL_TV && st->lambda_tv > 0.f) RC(image_tv_grad_add_launch(ip.x, d_img, p1 - p0, h, w, st->lambda_tv, q));
+            if (img_term == L_GLOBAL_PIX && st->lambda_pix > 0.f) RC(image_pix_grad_add_launch(ip.y, ip.b_in, d_img, p1 - p0, h, w, st->lambda_pix, q));
         }
         if (gen) RC(splice_gen_backward(plan, params, d_img, arena, accumulate, q));
         return SPLICE_OK;
@@ -1073,6 +1140,11 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
         if (t[L_GLOBAL_ID].on)    // keys of y' against keys of B' (util/losses.py:96-105): mean over h*T*d = T*D
             RC(mse_batched_launch(keys_ptr(vg, qkv_g, pY), 3 * vg.D, 3 * passD, keys_ptr(vg, qkv_g, pB), 3 * vg.D, 3 * passD, vg.T, vg.D, 1.0f, t[L_GLOBAL_ID].lambda,
                                   loss_part(st, L_GLOBAL_ID), st->lstride, vg.d_keys + pY * passD, vg.D, passD, Pb, s, t[L_GLOBAL_ID].tab));
+        // the image-space terms, at the crops' own resolution: image i's partials into terms 6 / 7 of slot i, every step (no schedule)
+        if (img_on)
+            RC(image_terms_value_launch(st->lambda_tv > 0.f ? ip.x : nullptr, Pa, c.crop_h, c.crop_w, loss_part(st, L_GLOBAL_TV),
+                                        st->lambda_pix > 0.f ? ip.y : nullptr, ip.b_in, Pb, st->cropb_h, st->cropb_w, loss_part(st, L_GLOBAL_PIX),
+                                        st->lstride, st->lp, s));
     }
     // ---- entire-image branch (every entire_every-th step): passes [0, pairs) A_entire', [pairs, 2 pairs) x_entire'
     if (entire) {
@@ -1106,14 +1178,13 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
             const bool grouped = st->crops_mode && pairs > 1;
             const int n1 = st->crops_mode ? P : 1;
             // (the rule and the trace ride in the launch: no node more)
-            const auto kernel = st->lr_state ? (st->trace ? total_loss_kernel<true, true, true> : total_loss_kernel<true, false, true>)
-                                : st->trace  ? (stop_on ? total_loss_kernel<true, true> : total_loss_kernel<false, true>)
-                                             : (stop_on ? total_loss_kernel<true, false> : total_loss_kernel<false, false>);
-            SPLICE_LAUNCH(kernel, dim3(pairs), dim3(320), 0, q, st->losses, st->lstride, (int)st->lp, t[L_GLOBAL_SSIM].lambda, t[L_ENTIRE_SSIM].lambda,
+            const auto kernel = img_on ? total_loss_instance<true>(st->lr_state != nullptr, st->trace != nullptr, stop_on)
+                                       : total_loss_instance<false>(st->lr_state != nullptr, st->trace != nullptr, stop_on);
+            SPLICE_LAUNCH(kernel, dim3(pairs), dim3(img_on ? 448 : 320), 0, q, st->losses, st->lstride, (int)st->lp, t[L_GLOBAL_SSIM].lambda, t[L_ENTIRE_SSIM].lambda,
                           t[L_ENTIRE_CLS].lambda, t[L_GLOBAL_CLS].lambda, t[L_GLOBAL_ID].lambda, st->losses_out, grouped ? st->na : n1, grouped ? st->nb : n1, grouped ? nc : n1,
                           grouped ? 1 : n1, st->pw ? st->pw + (size_t)PW_LAMBDAS * P : nullptr, (int)ssim_on, (int)entire, st->stop, st->dev_t, st->stop_rule, st->best, st->best_means,
                           st->trace, st->trace_cap, st->lr_rule, st->lr_state, st->lr_cuts, (const float*)(st->pair_lr ? st->dev_lrs : st->dev_lr), st->pair_lr ? 1 : 0,
-                          st->lr_eff);
+                          st->lr_eff, st->lambda_tv, st->lambda_pix);
         }
         if (!st->running || !gen_fwd) return SPLICE_OK;
         void* plans[3] = {st->plan_a, st->plan_b, nullptr};
@@ -1132,12 +1203,12 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
             HIPCHK(hipEventRecord(st->ev(SpliceStep::EV_FORK2), s));
             HIPCHK(hipStreamWaitEvent(s2, st->ev(SpliceStep::EV_FORK2), 0));
         }
-        RC(chain_bwd(vg, pY, pEnd, !(st->ablate & 32), ip.dy, st->cropb_h, st->cropb_w, src.dy, st->plan_b, st->grads_b, 0, gen_bwd, s2));
+        RC(chain_bwd(vg, pY, pEnd, !(st->ablate & 32), ip.dy, st->cropb_h, st->cropb_w, src.dy, st->plan_b, st->grads_b, 0, gen_bwd, L_GLOBAL_PIX, s2));
         if (side_tail) {
             RC(bookkeeping(s2));
             HIPCHK(hipEventRecord(st->ev(SpliceStep::EV_JOIN2), s2));
         }
-        RC(chain_bwd(vg, pX, pY, true, ip.dx, c.crop_h, c.crop_w, src.dx, st->plan_a, grads, st->accumulate, gen_bwd, s));
+        RC(chain_bwd(vg, pX, pY, true, ip.dx, c.crop_h, c.crop_w, src.dx, st->plan_a, grads, st->accumulate, gen_bwd, L_GLOBAL_TV, s));
         if (overlap) HIPCHK(hipStreamWaitEvent(s, st->ev(SpliceStep::EV_JOIN2), 0));
         // grads = g(A) + g(B): folded into the Adam kernel on ordinary steps; a separate add when the entire-image branch
         // still has to accumulate into the sum (same association order either way)
@@ -1146,7 +1217,7 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
             else adam_g2 = st->grads_b;
         }
     }
-    if (entire) RC(chain_bwd(ve, pairs, 2 * pairs, true, ip.dxe, c.ent_h, c.ent_w, src.dxe, st->plan_e, grads, 1, do_gb, s));
+    if (entire) RC(chain_bwd(ve, pairs, 2 * pairs, true, ip.dxe, c.ent_h, c.ent_w, src.dxe, st->plan_e, grads, 1, do_gb, 0, s));
     if (!side_tail) RC(bookkeeping(s));
     // ---- optimizer.step() (train.py:79) over every pair's arena; Adam's step count (>= 1) and a scheduled lr are read from the device at
     // execution time
@@ -1187,7 +1258,7 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
 // params/grads/m/v: the generator arenas, [P][arena_stride] (one flat arena when P = 1).  A_crop / B_crop: [P][3][h][w]
 // at the current crop sizes; A_entire [P][3][ent_h][ent_w] (may be NULL on steps where step_idx % entire_every != 0).
 // losses_out: device fp32 [P][8], per pair {loss, loss_global_ssim, loss_entire_ssim, loss_entire_cls, loss_global_cls,
-// loss_global_id_B, 0, 0} (inactive terms are 0).
+// loss_global_id_B, loss_global_tv, loss_global_pix_id_B} (inactive terms are 0; the last two only with splice_step_set_image_terms).
 // The launch sequence (~500 kernels) is captured once per regime (first step / ordinary / entire-image) into a hipGraph
 // and replayed; inputs are staged into handle-owned buffers first so the graph only ever sees the same pointers.
 int splice_step_run(void* h, float* params, float* grads, float* m, float* v, const float* A_crop, const float* B_crop,
@@ -1296,6 +1367,8 @@ int splice_step_run(void* h, float* params, float* grads, float* m, float* v, co
             // plateau lr rule, whose loss-kernel node is another kernel again
             const unsigned long long salt = (grouped ? ((unsigned long long)st->pairs << 32) | ((unsigned long long)st->na << 16) | (unsigned long long)st->nb : 0) |
                                             (st->stop_rule.window > 0 ? 1ull << 63 : 0) | (st->lr_state ? 1ull << 62 : 0) |
+                                            // ... and the two image-space terms, a launch each (and another loss-kernel instance)
+                                            (st->lambda_tv > 0.f ? 1ull << 61 : 0) | (st->lambda_pix > 0.f ? 1ull << 60 : 0) |
                                             // ... and the extended rule of the update (bits 56-59: off, or 1 + kind with the arenas it walks)
                                             (st->opt_ext_on ? (unsigned long long)(1 + st->opt_kind + 3 * ((st->opt_ext.momentum > 0.f ? 1 : 0) + 2 * (st->opt_ext.amsgrad || st->opt_ext.centered ? 1 : 0))) << 56 : 0);
             ex = st->graphs.adopt(variant, g, salt);

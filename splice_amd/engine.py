@@ -16,6 +16,9 @@ from .util import OPTIM_EXT_DEFAULTS, LrSchedule, fused_optimizer, fused_optimiz
 from .vit import VitContext, VitEngine, fp8_mode
 
 LOSS_KEYS = ["loss", "loss_global_ssim", "loss_entire_ssim", "loss_entire_cls", "loss_global_cls", "loss_global_id_B"]
+# words 6 and 7 of a losses row: the image-space terms, reported exactly when their lambda is > 0
+IMAGE_LOSS_KEYS = ["loss_global_tv", "loss_global_pix_id_B"]
+IMAGE_LAMBDA_KEYS = ("lambda_global_tv", "lambda_global_pixel_identity")   # (the weight of IMAGE_LOSS_KEYS[i])
 
 DEFAULT_CFG = dict(  # conf/default/config.yaml of the reference
     init_type="xavier", init_gain=0.02,
@@ -44,7 +47,9 @@ DEFAULT_CFG = dict(  # conf/default/config.yaml of the reference
     # ... and torch.optim's further arguments of the config's optimiser, run by the fused update's extended rules (`optimizer`
     # also takes adamw): neutral by default -- the update is then the reference's, the very kernels it always was
     optimizer_weight_decay=0.0, optimizer_momentum=0.0, optimizer_dampening=0.0, optimizer_nesterov=False, optimizer_amsgrad=False,
-    optimizer_centered=False)
+    optimizer_centered=False,
+    # ... and two loss terms on the generated crops themselves: total variation of G(A_crop), mse(G(B_crop), B_crop); off by default
+    lambda_global_tv=0.0, lambda_global_pixel_identity=0.0)
 
 SNAPSHOT_FORMAT = 1
 # Keys of a config that do not enter a slot's arithmetic (paths, logging, and how the loop parks and checkpoints): a snapshot is restored
@@ -295,7 +300,50 @@ def active_terms(c, step_idx, entire_branch):
     ent = bool(entire_branch) and step_idx % c["entire_A_every"] == 0
     return {"loss": True, "loss_global_ssim": on and c["lambda_global_ssim"] > 0, "loss_entire_ssim": ent and c["lambda_entire_ssim"] > 0,
             "loss_entire_cls": ent and c["lambda_entire_cls"] > 0, "loss_global_cls": c["lambda_global_cls"] > 0,
-            "loss_global_id_B": on and c["lambda_global_identity"] > 0}
+            "loss_global_id_B": on and c["lambda_global_identity"] > 0,
+            # the image-space terms: every step, no schedule
+            **{k: c.get(lam, 0.0) > 0 for k, lam in zip(IMAGE_LOSS_KEYS, IMAGE_LAMBDA_KEYS)}}
+
+
+def image_terms_rule(c):
+    """``(lambda_tv, lambda_pix)`` of the image-space loss terms in config ``c``, checked on the host: finite
+    numbers ``lambda_global_tv >= 0`` and ``lambda_global_pixel_identity >= 0`` (0: the term is off; both 0: the step launches what it
+    launches without the keys).  Shared by the slots of a sweep (``merge_pair_cfgs`` refuses a per-slot value).  Raises ValueError
+    naming the key."""
+    out = []
+    for key in IMAGE_LAMBDA_KEYS:
+        v = _number(c, key, _REAL, lambda v: 0 <= v < float("inf"), "a finite number >= 0")
+        with np.errstate(over="ignore"):
+            if not np.isfinite(np.float32(v)):   # (the kernels take it as a float)
+                raise ValueError(f"'{key}' must be a finite float32 number, got {v!r}")
+        out.append(float(v))
+    return tuple(out)
+
+
+def np_image_terms(x, y=None, b=None):
+    """The image-space terms (include/splice_hip.h) restated in NumPy float64, value and gradient, for ONE image each:
+    ``x`` ``[3, h, w]`` -> ``TV(x) = mean|x[:,1:,:] - x[:,:-1,:]| + mean|x[:,:,1:] - x[:,:,:-1]|`` (each mean over its own count, a
+    direction without differences contributes 0) and ``dTV/dx`` with ``sign(0) = 0``; ``y``, ``b`` -> ``mean((y - b)^2)`` and
+    ``2 (y - b) / (3 h w)``.  The differences are taken in the inputs' own dtype (the sign of an fp32 difference is exact), everything
+    else in float64.  Returns ``(tv, dtv, pix, dpix)``, the pair of an absent input as ``None``."""
+    tv = dtv = pix = dpix = None
+    if x is not None:
+        x = np.asarray(x)
+        dv, dh = (x[:, 1:, :] - x[:, :-1, :]).astype(np.float64), (x[:, :, 1:] - x[:, :, :-1]).astype(np.float64)
+        tv, dtv = 0.0, np.zeros(x.shape, dtype=np.float64)
+        if dv.size:
+            tv += np.abs(dv).sum() / dv.size
+            dtv[:, 1:, :] += np.sign(dv) / dv.size
+            dtv[:, :-1, :] -= np.sign(dv) / dv.size
+        if dh.size:
+            tv += np.abs(dh).sum() / dh.size
+            dtv[:, :, 1:] += np.sign(dh) / dh.size
+            dtv[:, :, :-1] -= np.sign(dh) / dh.size
+        tv = float(tv)
+    if y is not None:
+        d = np.asarray(y).astype(np.float64) - np.asarray(b).astype(np.float64)
+        pix, dpix = float((d * d).sum() / d.size), 2.0 * d / d.size
+    return tv, dtv, pix, dpix
 
 
 CLIP_CHUNK = 4096   # SPLICE_CLIP_CHUNK
@@ -521,6 +569,7 @@ class MultiPairEngine:
         self.lr_state_dev = self.lr_cuts_dev = None
         self.opt_ext = fused_optimizer_ext(self.cfg)   # None: the plain rules, today's launches
         self.w = None
+        self.image_terms = image_terms_rule(self.cfg)
         P_in = len(gen_states)
         self.cfgs = [self.cfg] * P_in
         self._pair_lambdas = self._pair_lr = False
@@ -686,6 +735,10 @@ class MultiPairEngine:
             self.lr_cuts_dev = torch.full((P, STOP_HISTORY), -1, dtype=torch.int32, device=self.device)
             _lib.check(_lib.lib().splice_step_set_lr_plateau(self.handle, *self.lr_rule, _lib.ptr(self.lr_state_dev), _lib.ptr(self.lr_cuts_dev)),
                        "step_set_lr_plateau")
+        # the image-space terms (shared by the slots): a value launch, a gradient-add launch per chain, another loss-kernel instance; before
+        # the first step.  Both 0: the call is not made and the handle launches what it always did
+        if max(self.image_terms) > 0:
+            _lib.check(_lib.lib().splice_step_set_image_terms(self.handle, *self.image_terms), "step_set_image_terms")
         self._lr_scale = [1.0] * P   # the host's copy of every slot's lr scale, refreshed with the stop steps
         self._stopped = [None] * P   # the host's copy of every slot's stop step, refreshed by stop_state()
         self._stop_dirty = False     # a window has closed since the last stop_state(): the copy may be behind
@@ -1029,11 +1082,11 @@ class MultiPairEngine:
         a list over the pairs for ``pair=None``."""
         rows = self._per_slot(self.losses_dev.cpu().tolist(), lambda s: s["losses"].cpu().tolist())   # (a parked slot: its last own row)
         acts = self.active_terms(self.step_idx)
-        dicts = [{k: vals[i] for i, k in enumerate(LOSS_KEYS) if act[k]} for vals, act in zip(rows, acts)]
+        dicts = [{k: vals[i] for i, k in enumerate(LOSS_KEYS + IMAGE_LOSS_KEYS) if act[k]} for vals, act in zip(rows, acts)]
         return dicts if pair is None else dicts[pair]
 
     def active_terms(self, step_idx):
-        """Per slot: which of LOSS_KEYS step ``step_idx`` computes (``engine.active_terms``; a slot's terms follow that slot's own
+        """Per slot: which of LOSS_KEYS and IMAGE_LOSS_KEYS step ``step_idx`` computes (``engine.active_terms``; a slot's terms follow that slot's own
         lambdas).  Host arithmetic only."""
         slots = getattr(self, "P_in", self.P)
         return [active_terms(c, step_idx, self.plan_e is not None) for c in (self.cfgs if len(self.cfgs) == slots else [self.cfg] * slots)]
@@ -1215,6 +1268,10 @@ class MultiScaleEngine:
             raise NotImplementedError("lr_plateau_factor > 0: the plateau lr rule lives in the fused step's loss kernel and its own update; MultiScaleEngine updates outside the step")
         if stop_rule(self.cfg)[0] > 0:
             raise NotImplementedError("stop_window > 0: the plateau stop rule lives in the fused step's own update; MultiScaleEngine updates outside the step")
+        for key, lam in zip(IMAGE_LAMBDA_KEYS, image_terms_rule(self.cfg)):
+            if lam > 0:
+                raise NotImplementedError(f"{key} > 0: the term's gradient is added to a whole fused step's image gradient; MultiScaleEngine's per-scale "
+                                          "follower handles add theirs into the leader's, which would count the term once per scale")
         self.ema_rule = ema_rule(self.cfg)
         self.ema = None
         self.grad_clip = grad_clip_rule(self.cfg)

@@ -52,6 +52,13 @@ class GlobalTransform:
         return (img - mean) / std
 
 
+def total_variation(img):
+    """``mean|img[..., 1:, :] - img[..., :-1, :]| + mean|img[..., :, 1:] - img[..., :, :-1]|`` of one image ``[3, h, w]``, each mean over
+    its own count; a direction without differences contributes 0."""
+    dv, dh = img[..., 1:, :] - img[..., :-1, :], img[..., :, 1:] - img[..., :, :-1]
+    return (dv.abs().mean() if dv.numel() else 0.0) + (dh.abs().mean() if dh.numel() else 0.0)
+
+
 # One row per entry of the dict LossG.forward returns (util/losses.py:46-72), in the reference's evaluation order:
 # (dict key, lambda name, feature compared, key of the generated batch in `outputs`, key of the target batch in `inputs`)
 _TERMS = (
@@ -60,6 +67,12 @@ _TERMS = (
     ("loss_entire_cls", "lambda_entire_cls", "cls", "x_entire", "B_global"),
     ("loss_global_cls", "lambda_global_cls", "cls", "x_global", "B_global"),
     ("loss_global_id_B", "lambda_global_identity", "keys", "y_global", "B_global"),
+)
+# The image-space terms (an extension beyond the reference), on the generated crops themselves, every step, no
+# schedule: (dict key, lambda name, key of the generated batch in `outputs`, key of the compared batch in `inputs` or None)
+_IMAGE_TERMS = (
+    ("loss_global_tv", "lambda_global_tv", "x_global", None),
+    ("loss_global_pix_id_B", "lambda_global_pixel_identity", "y_global", "B_global"),
 )
 _SCHEDULED_AT_WARMUP = ("lambda_global_ssim", "lambda_global_identity")
 _SCHEDULED_PERIODIC = ("lambda_entire_ssim", "lambda_entire_cls")
@@ -101,6 +114,15 @@ class LossG(torch.nn.Module):
             lam = self.lambdas[lam_name]
             if lam > 0:
                 losses[key] = self._feature_mse(feature, outputs[out_key], inputs[in_key])
+                total = total + lam * losses[key]
+        # the two image-space terms, summed over the crops as the others: what the fused step adds under the same two keys
+        for key, lam_name, out_key, in_key in _IMAGE_TERMS:
+            lam = self.cfg.get(lam_name, 0)
+            if lam > 0:
+                if in_key is None:
+                    losses[key] = sum(total_variation(img) for img in outputs[out_key])
+                else:
+                    losses[key] = sum(F.mse_loss(img, ref.to(img.device)) for img, ref in zip(outputs[out_key], inputs[in_key]))
                 total = total + lam * losses[key]
         losses['loss'] = total
         return losses

@@ -400,6 +400,14 @@ def optim_fields(engine):
     return {"optimizer": cfg.get("optimizer", "adam"), **{k: cfg[k] for k, d in OPTIM_EXT_DEFAULTS.items() if k in cfg and cfg[k] != d}}
 
 
+def image_terms_fields(engine):
+    """What ``result.json`` / ``variant.json`` say about the image-space loss terms of a run (shared by the slots; DESIGN.md section
+    9j): ``lambda_global_tv`` / ``lambda_global_pixel_identity`` where the run set them to another value than 0."""
+    from .engine import IMAGE_LAMBDA_KEYS
+    cfg = getattr(engine, "cfg", None) or {}
+    return {k: cfg[k] for k in IMAGE_LAMBDA_KEYS if cfg.get(k, 0) != 0}
+
+
 def best_fields(engine, slot=None):
     """What ``result.json`` says about the stop rule's windows (``splice_amd.batch``) of a run with ``stop_keep_best``: ``best_step`` (the
     step whose weights ``output_best.png`` shows; None: no window closed, they are the initial weights), ``best_window_mean`` and
@@ -535,7 +543,7 @@ def train_sweep(dataroot, variants, cfg_overrides=None, vit_state=None, callback
     losses = engine.losses() if engine.step_idx >= 0 else [{} for _ in range(K)]
     for k in range(K):
         with open(os.path.join(out_dirs[k], 'variant.json'), 'w') as f:
-            json.dump({"index": k, "overrides": variants[k], "seed": seeds[k], "losses": losses[k], "stopped_at": engine.stopped_at[k], **trace_fields(engine), **lr_fields(engine, k), **optim_fields(engine)}, f)
+            json.dump({"index": k, "overrides": variants[k], "seed": seeds[k], "losses": losses[k], "stopped_at": engine.stopped_at[k], **trace_fields(engine), **lr_fields(engine, k), **optim_fields(engine), **image_terms_fields(engine)}, f)
     return engine
 
 
