@@ -17,6 +17,18 @@ def test_resize_output_size_matches_oracle_resize():
             assert tuple(out.shape[-2:]) == resize_output_size(h, w, size, 480), (h, w, size)
 
 
+def test_the_rules_module_needs_neither_the_generator_nor_the_vit():
+    """``import splice_amd.rules`` in a fresh interpreter: the config checks, restatements and decoders load without the engines."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import sys, splice_amd.rules as r; assert r.DEFAULT_CFG and r.stop_rule({})[0] == 0; "
+            "print(sorted(m for m in ('splice_amd.generator', 'splice_amd.vit', 'splice_amd.engine') if m in sys.modules))")
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=root, env=dict(os.environ, PYTHONPATH=root), timeout=300)
+    assert r.returncode == 0 and r.stdout.strip() == "[]", (r.stdout, r.stderr[-2000:])
+
+
 def test_pos_embed_interpolation_matches_oracle():
     m = dino_vit.VisionTransformer(8, 384, 1, 6, img_size=64).eval()
     with torch.no_grad():

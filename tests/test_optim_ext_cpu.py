@@ -114,7 +114,7 @@ def test_a_snapshot_from_before_the_options_restores_into_a_default_config():
     assert snapshot_cfg_mismatch(old, dict(DEFAULT_CFG)) is None and snapshot_cfg_mismatch(dict(DEFAULT_CFG), old) is None
     assert snapshot_cfg_mismatch(old, dict(DEFAULT_CFG, optimizer="sgd", optimizer_momentum=0.9)) == "optimizer"
     assert snapshot_cfg_mismatch(dict(old, optimizer="sgd"), dict(DEFAULT_CFG, optimizer="sgd", optimizer_momentum=0.9)) == "optimizer_momentum"
-    assert "w" in MultiPairEngine._STATE_KEYS and MultiPairEngine._STATE_KEYS["w"] == ("w",)
+    assert ("w", "w") in MultiPairEngine.SLOT_ARENAS   # the third moment arena is kept under the state key `w`
 
 
 def test_exports_declared_bound_and_present():

@@ -43,7 +43,7 @@ def _same_state(a, b, what=()):
             assert a[k] == b[k], what + (k, a[k], b[k])
 
 
-TABLES = ("params", "m", "v", "ema", "best", "best_ema", "running", "losses_dev", "best_dev", "means_dev", "clip_dev", "lr_state_dev", "lr_cuts_dev", "trace_dev")
+TABLES = tuple(attr for _, attr in MultiPairEngine.SLOT_ARENAS + MultiPairEngine.SLOT_ROWS) + ("trace_dev",)   # the engine's own list of what a slot owns
 
 
 def _same_engine(a, b, what=()):
@@ -217,6 +217,32 @@ def test_restore_is_refused_on_the_device_too(vit):
         eng.restore([eng.snapshot(p) for p in range(2)])
     plain = SpliceEngine(_cfg(), None, synth.generator_params(70, 0.02), (64, 64), None, vit_engine=vit)
     assert L.splice_step_restore(plain.handle, 3, rec, _lib.current_stream()) != 0 and L.splice_step_restore(plain.handle, 3, None, _lib.current_stream()) == 0
+
+
+# ------------------------------------------------------------------------------------------------ the list of what a slot owns
+def test_every_per_slot_tensor_is_in_the_slot_tables(vit):
+    """Three slots (no unrelated tensor's leading dimension is 3) with every rule that keeps state on -- the third moment arena and both
+    clipping records among them -- after two steps: (a) every device tensor of the engine with one row per slot, or ``stride`` floats
+    per slot, is named by the engine's tables, or is the gradient arena (scratch of a step) or the trace; (b) a snapshot holds exactly
+    the tables' keys, the trace, the stop record and the seven fixed entries.  A tensor a rule allocates per slot and forgets in the
+    tables fails (a); a table row that snapshot() does not walk fails (b)."""
+    rules = dict(ALL_RULES, optimizer="adam", optimizer_amsgrad=True, grad_clip_auto=2.0)
+    gens = [synth.generator_params(70 + p, 0.02) for p in range(3)]
+    eng = MultiPairEngine(_cfg(**rules), None, gens, (64, 64), (64, 64), vit_engine=vit)
+    A, B = synth.smooth_image_pair(62, 0, 64, 64)
+    A3 = torch.from_numpy(A).to(DEV)[None].expand(3, -1, -1, -1).contiguous()
+    B3 = torch.from_numpy(B).to(DEV)[None].expand(3, -1, -1, -1).contiguous()
+    for _ in range(2):
+        eng.step(A3, B3, A3)
+    torch.cuda.synchronize()
+    tables = MultiPairEngine.SLOT_ARENAS + MultiPairEngine.SLOT_ROWS
+    assert eng.P == 3 and all(getattr(eng, attr) is not None for _, attr in tables) and eng.trace_dev is not None   # (the premise: every rule is on)
+    named = {attr for _, attr in tables} | {"grads", "trace_dev"}
+    per_slot = [name for name, t in vars(eng).items()
+                if isinstance(t, torch.Tensor) and t.is_cuda and t.dim() > 0 and (t.shape[0] == eng.P or t.numel() == eng.P * eng.stride)]
+    assert len(per_slot) == len(tables) + 1 and set(per_slot) <= named, sorted(set(per_slot) - named)   # (+ 1: grads; the trace is time-major)
+    fixed = {"format", "step_idx", "cfg", "n_crops", "crop_hw", "entire_hw", "generator_calls"}
+    assert set(eng.snapshot(0)) == {key for key, _ in tables} | {"trace", "stop"} | fixed
 
 
 # ------------------------------------------------------------------------------------------------- a move between batch sizes
