@@ -771,8 +771,14 @@ static void attn_fwd_x32_go(const AttnArgs* a, hipStream_t s) {
     SPLICE_LAUNCH((attn_fwd_x32_kernel<NW, FOLD>), dim3(nx * a->H * a->B), dim3(64 * NW), X32<NW>::LDS_BYTES, s, *a, nx);
 }
 
+// Every launcher below refuses what its kernels do not bound on their own -- no pass, no token, more tokens than the row pitch holds, a NULL
+// operand -- before anything is launched (the kernels clamp rows to Tld - 1 and mask keys against T; T > Tld would walk past the buffers).
+static bool attn_shape_bad(const AttnArgs* a) {
+    return a->B < 1 || a->T < 1 || a->T > a->Tld || a->Tld % 32 || a->D % 64 || a->D / 64 != a->H;
+}
+
 int attn_fwd_launch(const AttnArgs* a, hipStream_t s) {
-    if (a->Tld % 32 || a->D % 64 || a->D / 64 != a->H) return SPLICE_ERR_ARG;
+    if (attn_shape_bad(a) || !a->out || !a->lse || (!a->qkv && !a->qkv8)) return SPLICE_ERR_ARG;
     if (!a->qkv8) {
         // bf16: the 32x32x16 kernel (attn_x32.h), four waves (128 queries) per workgroup.  Every form of it gives a query the same bits
         // (the arithmetic does not depend on the wave count: tests/test_ops_gpu.py forces 2 / 4 / 8), so a pass's output does not
@@ -812,7 +818,7 @@ static const int kAttnBwdMergeMaxX32 = 1400;   // workgroups of the merged 32x32
 static const int kAttnBwdMergeMax16 = 768;     // the same bound for the 16x16x32 halves
 
 int attn_bwd_launch(const AttnArgs* a, hipStream_t s) {
-    if (a->Tld % 32 || a->D % 64 || a->D / 64 != a->H) return SPLICE_ERR_ARG;
+    if (attn_shape_bad(a) || !a->qkv || !a->lse || !a->dout || !a->delta || !a->dqkv || (!a->delta_ready && !a->out)) return SPLICE_ERR_ARG;
     const int nx = cdiv(a->Tld, 64);
     if (!a->delta_ready) SPLICE_LAUNCH(attn_delta_kernel, dim3(cdiv(a->B * a->Tld * a->H, 256)), dim3(256), 0, s, *a);
     if (a->qfold && g_attn_bwd_variant != 1) {   // the 32x32x16 halves (attn_bwd_x32.h): what the engine runs
@@ -849,6 +855,7 @@ int attn_bwd_launch(const AttnArgs* a, hipStream_t s) {
 }
 
 int attn_probs_launch(const AttnArgs* a, float* probs, hipStream_t s) {
+    if (attn_shape_bad(a) || !a->qkv || !a->lse || !probs) return SPLICE_ERR_ARG;
     dim3 grid(a->T, a->H, a->B);
     SPLICE_LAUNCH(attn_probs_kernel, grid, dim3(128), 0, s, *a, probs);
     return SPLICE_OK;
