@@ -228,6 +228,11 @@ int splice_vit_ctx_info(void* ctx, int* T, int* Tld, int* rows);
  * undefined for layer depth-1, and d_block[depth-1] must be zero outside the [CLS] rows.  splice_step_create switches its
  * contexts to this mode; the extractor API (models/extractor.py:81-103 hands out every token) never does. */
 int splice_vit_ctx_set_top_cls_only(void* ctx, int on);
+/* The blocks (n distinct indices in [0, depth)) whose QKV projection also writes the transposed bf16 copy of its output, [3D][rows], as
+ * the top block's always does -- what the structure loss over the keys of those blocks multiplies in its dK product
+ * (splice_step_set_ssim_layers calls this on its contexts).  Before the context's first forward only.  splice_vit_get_tensor kind 8
+ * returns the copies; a context without this call runs the launches it always ran. */
+int splice_vit_ctx_set_transposed_layers(void* ctx, int n, const int* layers);
 /* precision of THIS context's forward: 0 bf16 (default); 1 = QKV / fc1 / fc2 projections on the fp8 MFMA; 3 = those + the attention
  * forward (Q K^T, P V) on the fp8 MFMA.  Needs splice_vit_enable_fp8 on the engine.  The backward is bf16 in every mode. */
 int splice_vit_ctx_set_fp8(void* ctx, int mode);
@@ -243,7 +248,8 @@ int splice_vit_forward_passes(void* ctx, const float* img, int normalize, int gr
                               splice_stream_t stream);
 /* kind 0: block output l fp32 [rows][D] (models/extractor.py:56-60) | 1: raw qkv l bf16
  * [rows][3D] (:68-72) | 2: attention output l bf16 [rows][D] | 3: last-layer qkv fp32
- * [rows][3D] | 4: lse l fp32 [B][H][Tld] | 5: embedded tokens fp32 [rows][D] | 6: raw qkv l transposed, bf16 [3D][rows] | 7: as 1.
+ * [rows][3D] | 4: lse l fp32 [B][H][Tld] | 5: embedded tokens fp32 [rows][D] | 6: raw qkv l transposed, bf16 [3D][rows] (l = depth - 1
+ * only) | 7: as 1 | 8: as 6, of the top block or a block named by splice_vit_ctx_set_transposed_layers (any other is refused).
  * ZERO-COPY: the pointers are the engine's own buffers, so the q columns of kinds 1 / 3 / 6 / 7 carry the factor splice_vit_qscale()
  * (a C caller that wants the reference's q divides it out, or calls splice_vit_read_tensor, whose copies of kinds 1 and 3
  * are un-scaled -- in bf16 for kind 1: one more rounding; Python's VitExtractor reads kind 7 and divides in fp32). */
@@ -818,6 +824,31 @@ int splice_image_terms_grad_add(const float* x, const float* b, float* d, int n_
 int splice_total_loss_pairs_img(float* lbase, size_t lstride, int lp, float w_ssim, float w_essim, float w_ecls, float w_cls, float w_id,
                                 float* out8, int pairs, int n_a, int n_b, int n_c, int n_e, const float* wtab, int ssim_on, int entire,
                                 float w_tv, float w_pix, splice_stream_t stream);
+/* ------------------------------------------------------------------ the structure loss over the keys of several ViT blocks (DESIGN.md section
+ * 9k).  With n ascending distinct block indices `layers` in [0, depth) and n finite weights > 0, every structure term of the step -- the
+ * global one on every A crop, the entire-image one -- becomes
+ *     raw = sum over i ascending of weights[i] * mean((cos-sim(keys of block layers[i] of the generated image) - the target's)^2),
+ * reported as word 1 / 2 of the losses row and multiplied by the term's lambda in the total as before.  The key-identity term and both
+ * [CLS] terms stay on the top block.  The layers ride in the three self-similarity launches a term has (grid z = layer); block i's
+ * tile partials are slots [i tiles, (i + 1) tiles) of the term's partial row, tiles = nt (nt + 1) / 2, nt = ceil(T / 64).  Before the first
+ * splice_step_run only; refused on a handle in gradient-only or phase mode or with a leader (which in turn refuses those calls), with
+ * fp8_selfsim, and a second time.  A handle without the call launches what it always did. */
+int splice_step_set_ssim_layers(void* step, int n, const int* layers, const float* weights);
+/* The per-layer addends of word `term` (1: loss_global_ssim, 2: loss_entire_ssim) of the last step: out (device, [n][pairs]),
+ * out[i * pairs + p] = pair p's sum of block i's slot range, the slots added in order (a pair's crops in crop order) -- weights[i] times the
+ * block's mean squared difference.  With one crop per pair the reported word is their float32 sum over i ascending, exactly. */
+int splice_step_ssim_layer_values(void* step, int term, float* out, splice_stream_t stream);
+/* test hook: splice_selfsim_loss_pairs with the step's layer table: n_layers problems per pair in the same three launches.  k_tgt, k_x,
+ * kT_x, dk, ws: host arrays of n_layers device pointers, each as the single-layer call takes it (ws[i]:
+ * splice_selfsim_loss_pairs_ws_bytes(T, D, pairs) bytes of its own); the leading dimensions and pair strides are shared.  weights[i]
+ * (host; finite, > 0) multiplies loss_scale and e_scale (or the pair's e_scale_tab entry) of layer i, one fp32 product each.  Layer i
+ * writes slots [i tiles, (i + 1) tiles) of pair p's row of loss_part (part_pstride >= n_layers * tiles) and dk[i]; both have the bits of
+ * the layer's own n_layers = 1 call, and with weight 1 those of splice_selfsim_loss_pairs.  bf16 only.  Refusals as there, before
+ * anything is launched. */
+int splice_selfsim_loss_layers(int n_layers, const splice_bf16* const* k_tgt, const splice_bf16* const* k_x, const splice_bf16* const* kT_x,
+                               const float* weights, int ldk, size_t k_pstride, int ldt, size_t kT_pstride, int T, int D, int pairs, float lambda,
+                               const float* e_scale_tab, float eps, float* loss_part, size_t part_pstride, float* const* dk, int lddk,
+                               size_t dk_pstride, void* const* ws, splice_stream_t stream);
 /* splice_total_loss_pairs as a handle with a loss trace launches it (splice_step_set_loss_trace): dev_t (device) holds step index + 1,
  * and words 0-5 of row step index of trace ([capacity][pairs][8], device) receive pair p's out8 values, a row at or beyond capacity
  * left out.  stop (may be NULL; device, [pairs] records) runs the instance of a handle with the stop rule, whose rule is window (>= 1),

@@ -154,6 +154,42 @@ int splice_selfsim_loss_pairs(const splice_bf16* k_tgt, const splice_bf16* k_x, 
     if (rc != SPLICE_OK) return finish(rc, who);
     return finish(selfsim_loss_launch(b, ST(stream)), who);
 }
+/* the same two launchers with the layer table of the step (splice_step_set_ssim_layers): n_layers problems in the same three launches */
+int splice_selfsim_loss_layers(int n_layers, const splice_bf16* const* k_tgt, const splice_bf16* const* k_x, const splice_bf16* const* kT_x,
+                               const float* weights, int ldk, size_t k_pstride, int ldt, size_t kT_pstride, int T, int D, int pairs, float lambda,
+                               const float* e_scale_tab, float eps, float* loss_part, size_t part_pstride, float* const* dk, int lddk,
+                               size_t dk_pstride, void* const* ws, splice_stream_t stream) {
+    const char* who = "splice_selfsim_loss_layers";
+    if (n_layers < 1 || n_layers > SELFSIM_MAX_LAYERS || !k_tgt || !k_x || !kT_x || !weights || !loss_part || !dk || !ws || T < 1 || pairs < 1 || D < 64 ||
+        D % 64 || ldk < D || ldk % 8 || ldt % 8 || k_pstride % 8 || kT_pstride % 8 || lddk < D)
+        return finish(SPLICE_ERR_ARG, who);
+    const int nt = (T + 63) / 64;
+    if ((size_t)n_layers * (nt * (nt + 1) / 2) > part_pstride) return finish(SPLICE_ERR_ARG, who);
+    SelfSimBatch b = {};
+    SelfSimLayers tab = {};
+    tab.n = n_layers;
+    for (int i = 0; i < n_layers; ++i) {
+        if (!k_tgt[i] || !k_x[i] || !kT_x[i] || !dk[i] || !ws[i] || !(weights[i] > 0.f) || !(weights[i] <= 3.402823466e+38f)) return finish(SPLICE_ERR_ARG, who);
+        SelfSimBatch w = {};
+        selfsim_batch_carve(ws[i], T, D, pairs, &w);
+        if (i == 0) b = w;
+        SelfSimLayer& e = tab.e[i];
+        e.k_tgt = k_tgt[i]; e.k_x = k_x[i]; e.kT_x = kT_x[i];
+        e.S_tgt = w.S_tgt; e.wmat = w.wmat; e.norm_x = w.norm_x; e.rpart = w.rpart;
+        e.dk = dk[i]; e.weight = weights[i];
+    }
+    b.ldk = ldk; b.ldt = ldt; b.k_pstride = k_pstride; b.kT_pstride = kT_pstride;
+    b.k_tgt = k_tgt[0]; b.k_x = k_x[0]; b.kT_x = kT_x[0];
+    b.loss_part = loss_part; b.part_pstride = part_pstride;
+    b.dk = dk[0]; b.dk_pstride = dk_pstride; b.lddk = lddk;
+    b.eps = eps;
+    b.loss_scale = 1.0f / ((float)T * (float)T);   // the fp32 expressions of the step's ssim_batch
+    b.e_scale = 4.0f * lambda * b.loss_scale;
+    b.e_scale_tab = e_scale_tab;
+    const int rc = selfsim_target_launch(b, ST(stream), &tab);
+    if (rc != SPLICE_OK) return finish(rc, who);
+    return finish(selfsim_loss_launch(b, ST(stream), &tab), who);
+}
 int splice_mse_pairs(const float* a, int lda, size_t a_ps, const float* b, int ldb, size_t b_ps, int rows, int cols, float loss_weight,
                      float grad_weight, float* part, size_t part_ps, float* grad, int ldg, size_t g_ps, int pairs, const float* grad_tab,
                      splice_stream_t stream) {

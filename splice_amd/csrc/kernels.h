@@ -134,10 +134,23 @@ struct SelfSimBatch {
     uint8_t *k8_tgt, *k8_x;         // [pairs][Tp][D] e4m3 rows (workspace)
     float *qnorm_tgt, *qnorm_x;     // [pairs][Tp] norms of the quantised rows
 };
+// The structure term over the keys of several ViT blocks: a by-value table, one entry per layer, of what differs
+// between the layers' problems -- the layer is one more grid dimension of the same three launches.  Entry i's tile partials go to slots
+// [i tiles, (i + 1) tiles) of b.loss_part's row (tiles = nt (nt + 1) / 2); its weight multiplies loss_scale and e_scale.  bf16 only.
+#define SELFSIM_MAX_LAYERS 12
+struct SelfSimLayer {
+    const bf16_t *k_tgt, *k_x, *kT_x;   // as in SelfSimBatch, of this layer's qkv buffers
+    float* S_tgt; bf16_t* wmat;         // the layer's own workspace (a selfsim_batch_carve of its own)
+    float *norm_x, *rpart;
+    float* dk;
+    float weight;
+};
+struct SelfSimLayers { int n; SelfSimLayer e[SELFSIM_MAX_LAYERS]; };
 size_t selfsim_batch_ws_bytes(int T, int D, int pairs);
 void selfsim_batch_carve(void* base, int T, int D, int pairs, SelfSimBatch* b);   // fills T, Tp, D, pairs and the workspace pointers
-int selfsim_target_launch(const SelfSimBatch& b, hipStream_t s);   // S* with the row norms taken inside the Gram kernel (1 launch; 2 on the fp8 path)
-int selfsim_loss_launch(const SelfSimBatch& b, hipStream_t s);     // fused S / loss / W (norms in-kernel) + dK (2 launches; 3 on the fp8 path)
+// layers (optional): every entry of the table in the same launches (grid z); b's own operand pointers are then not read
+int selfsim_target_launch(const SelfSimBatch& b, hipStream_t s, const SelfSimLayers* layers = nullptr);   // S* with the row norms taken inside the Gram kernel (1 launch; 2 on the fp8 path)
+int selfsim_loss_launch(const SelfSimBatch& b, hipStream_t s, const SelfSimLayers* layers = nullptr);     // fused S / loss / W (norms in-kernel) + dK (2 launches; 3 on the fp8 path)
 // grad_tab (optional, [pairs]): per-pair gradient weight, the value grad_weight / (rows * cols) takes otherwise; a pair whose entry
 // is 0 writes no partials and no gradient
 int mse_batched_launch(const float* a, int lda, size_t a_ps, const float* b, int ldb, size_t b_ps, int rows, int cols, float loss_weight,

@@ -275,9 +275,18 @@ __device__ __forceinline__ void tile_norms(const float (&ssa)[FMt], const float 
     for (int j = 0; j < FNt; ++j) nc[j] = sqrtf(ssb[j]);   // B row = output column j * 16 + (lane & 15)
 }
 
-template <bool FP8>
-__global__ __launch_bounds__(256) void selfsim_tgt_kernel(SelfSimBatch b) {
+// LAYERS (the structure term over the keys of several ViT blocks): blockIdx.z = entry of `tab`, whose operands
+// replace b's -- the layers' qkv buffers are separate allocations, no stride reaches them -- before the single-layer code runs unchanged:
+// layer i's tiles, their order and every sum inside them are those of its own launch.  The instances without LAYERS do not read `tab`
+// (a by-value struct behind the arguments: it is not preloaded into SGPRs, so they keep their code and registers).
+template <bool FP8, bool LAYERS = false>
+__global__ __launch_bounds__(256) void selfsim_tgt_kernel(SelfSimBatch b, SelfSimLayers tab) {
     extern __shared__ __attribute__((aligned(16))) bf16_t selfsim_smem[];
+    static_assert(!(FP8 && LAYERS), "the layer table carries no e4m3 workspace");
+    if constexpr (LAYERS) {
+        const SelfSimLayer& e = tab.e[blockIdx.z];
+        b.k_tgt = e.k_tgt; b.S_tgt = e.S_tgt;
+    }
     const int T = b.T, nt = (T + 63) / 64, pair = blockIdx.y;
     if (b.e_scale_tab && b.e_scale_tab[pair] == 0.f) return;   // a pair without this term
     int tm, tn;
@@ -315,15 +324,25 @@ __global__ __launch_bounds__(256) void selfsim_tgt_kernel(SelfSimBatch b) {
     }
 }
 
-template <bool FP8>
-__global__ __launch_bounds__(256) void selfsim_loss_kernel(SelfSimBatch b) {
+// LAYERS: as in selfsim_tgt_kernel; entry i's tile partials go to slots [i tiles, (i + 1) tiles) of the pair's partial row, and its weight
+// enters where loss_scale and e_scale (or the pair's e_scale_tab entry) do: one fp32 factor each
+template <bool FP8, bool LAYERS = false>
+__global__ __launch_bounds__(256) void selfsim_loss_kernel(SelfSimBatch b, SelfSimLayers tab) {
     extern __shared__ __attribute__((aligned(16))) bf16_t selfsim_smem[];
+    static_assert(!(FP8 && LAYERS), "the layer table carries no e4m3 workspace");
+    if constexpr (LAYERS) {
+        const SelfSimLayer& e = tab.e[blockIdx.z];
+        b.k_x = e.k_x; b.S_tgt = e.S_tgt; b.wmat = e.wmat; b.norm_x = e.norm_x; b.rpart = e.rpart;
+        b.loss_part += (size_t)blockIdx.z * gridDim.x;   // gridDim.x = the upper-triangular tiles of one layer
+        b.loss_scale *= e.weight;
+    }
     const int T = b.T, Tp = b.Tp, nt = Tp / 64, pair = blockIdx.y;
     float e_scale = b.e_scale;
     if (b.e_scale_tab) {   // per-pair table: a pair whose entry is 0 does not take part (no partials, no W)
         e_scale = b.e_scale_tab[pair];
         if (e_scale == 0.f) return;
     }
+    if constexpr (LAYERS) e_scale *= tab.e[blockIdx.z].weight;
     const int tile_id = xcd_remap(blockIdx.x, gridDim.x);
     int tm, tn;
     tri_tile(tile_id, nt, tm, tn);
@@ -439,9 +458,14 @@ __global__ __launch_bounds__(256) void selfsim_loss_kernel(SelfSimBatch b) {
 }
 
 // dK = W K - diag(r) K for every pair: dk[pair][T][lddk] fp32
-__global__ __launch_bounds__(256) void selfsim_dk_kernel(SelfSimBatch b) {
+template <bool LAYERS = false>
+__global__ __launch_bounds__(256) void selfsim_dk_kernel(SelfSimBatch b, SelfSimLayers tab) {
     extern __shared__ __attribute__((aligned(16))) bf16_t selfsim_smem[];
     __shared__ float rdot[64];
+    if constexpr (LAYERS) {   // as in selfsim_tgt_kernel: entry blockIdx.z's W, r, keys and key gradient
+        const SelfSimLayer& e = tab.e[blockIdx.z];
+        b.k_x = e.k_x; b.kT_x = e.kT_x; b.wmat = e.wmat; b.norm_x = e.norm_x; b.rpart = e.rpart; b.dk = e.dk;
+    }
     const int T = b.T, Tp = b.Tp, D = b.D, nt = Tp / 64, pair = blockIdx.y;
     if (b.e_scale_tab && b.e_scale_tab[pair] == 0.f) return;   // a pair without this term: its key gradient is left alone
     const int tiles_n = D / 64;
@@ -478,31 +502,45 @@ int selfsim_norms_launch(const bf16_t* k, int ldk, size_t k_pstride, int T, int 
     SPLICE_LAUNCH(selfsim_rownorm_kernel, dim3(cdiv(Tp, 4), pairs), dim3(256), 0, s, k, ldk, k_pstride, T, Tp, D, norm);
     return SPLICE_OK;
 }
-int selfsim_target_launch(const SelfSimBatch& b, hipStream_t s) {
+static bool layers_ok(const SelfSimBatch& b, const SelfSimLayers* layers) {
+    return !layers || (layers->n >= 1 && layers->n <= SELFSIM_MAX_LAYERS && !b.fp8);
+}
+int selfsim_target_launch(const SelfSimBatch& b, hipStream_t s, const SelfSimLayers* layers) {
     SpliceProfScope prof_scope(8); SPLICE_DEV_REGION(18);
     const int nt = b.Tp / 64;
+    if (!layers_ok(b, layers)) return SPLICE_ERR_ARG;
+    if (layers) {   // every layer of the table in this one launch
+        SPLICE_LAUNCH((selfsim_tgt_kernel<false, true>), dim3(nt * (nt + 1) / 2, b.pairs, layers->n), dim3(256), SS_LDS, s, b, *layers);
+        return SPLICE_OK;
+    }
     if (b.fp8) {
         if (b.D % 128) return SPLICE_ERR_ARG;
         RC_SS(quantize_keys_fp8_launch(b.k_tgt, b.ldk, b.k_pstride, b.k8_tgt, b.D, (size_t)b.Tp * b.D, b.qnorm_tgt, b.T, b.Tp, b.D, b.pairs, s));
-        SPLICE_LAUNCH(selfsim_tgt_kernel<true>, dim3(nt * (nt + 1) / 2, b.pairs), dim3(256), SS_LDS, s, b);
+        SPLICE_LAUNCH(selfsim_tgt_kernel<true>, dim3(nt * (nt + 1) / 2, b.pairs), dim3(256), SS_LDS, s, b, SelfSimLayers{});
         return SPLICE_OK;
     }
-    SPLICE_LAUNCH(selfsim_tgt_kernel<false>, dim3(nt * (nt + 1) / 2, b.pairs), dim3(256), SS_LDS, s, b);
+    SPLICE_LAUNCH(selfsim_tgt_kernel<false>, dim3(nt * (nt + 1) / 2, b.pairs), dim3(256), SS_LDS, s, b, SelfSimLayers{});
     return SPLICE_OK;
 }
-int selfsim_loss_launch(const SelfSimBatch& b, hipStream_t s) {
+int selfsim_loss_launch(const SelfSimBatch& b, hipStream_t s, const SelfSimLayers* layers) {
     SpliceProfScope prof_scope(8); SPLICE_DEV_REGION(18);
     const int nt = b.Tp / 64;
-    if (nt * (nt + 1) / 2 > (int)b.part_pstride) return SPLICE_ERR_ARG;
+    if (!layers_ok(b, layers)) return SPLICE_ERR_ARG;
+    if ((size_t)(nt * (nt + 1) / 2) * (layers ? layers->n : 1) > b.part_pstride) return SPLICE_ERR_ARG;
+    if (layers) {   // two launches for all layers: layer = blockIdx.z
+        SPLICE_LAUNCH((selfsim_loss_kernel<false, true>), dim3(nt * (nt + 1) / 2, b.pairs, layers->n), dim3(256), SS_LDS, s, b, *layers);
+        SPLICE_LAUNCH(selfsim_dk_kernel<true>, dim3(nt * (b.D / 64), b.pairs, layers->n), dim3(256), SS_LDS, s, b, *layers);
+        return SPLICE_OK;
+    }
     if (b.fp8) {
         if (b.D % 128) return SPLICE_ERR_ARG;
         RC_SS(selfsim_norms_launch(b.k_x, b.ldk, b.k_pstride, b.T, b.D, b.norm_x, b.pairs, s));   // true norms: W and r are in key units either way
         RC_SS(quantize_keys_fp8_launch(b.k_x, b.ldk, b.k_pstride, b.k8_x, b.D, (size_t)b.Tp * b.D, b.qnorm_x, b.T, b.Tp, b.D, b.pairs, s));
-        SPLICE_LAUNCH(selfsim_loss_kernel<true>, dim3(nt * (nt + 1) / 2, b.pairs), dim3(256), SS_LDS, s, b);
+        SPLICE_LAUNCH(selfsim_loss_kernel<true>, dim3(nt * (nt + 1) / 2, b.pairs), dim3(256), SS_LDS, s, b, SelfSimLayers{});
     } else {
-        SPLICE_LAUNCH(selfsim_loss_kernel<false>, dim3(nt * (nt + 1) / 2, b.pairs), dim3(256), SS_LDS, s, b);
+        SPLICE_LAUNCH(selfsim_loss_kernel<false>, dim3(nt * (nt + 1) / 2, b.pairs), dim3(256), SS_LDS, s, b, SelfSimLayers{});
     }
-    SPLICE_LAUNCH(selfsim_dk_kernel, dim3(nt * (b.D / 64), b.pairs), dim3(256), SS_LDS, s, b);
+    SPLICE_LAUNCH(selfsim_dk_kernel<false>, dim3(nt * (b.D / 64), b.pairs), dim3(256), SS_LDS, s, b, SelfSimLayers{});
     return SPLICE_OK;
 }
 size_t selfsim_batch_ws_bytes(int T, int D, int pairs) {

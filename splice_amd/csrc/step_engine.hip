@@ -44,6 +44,7 @@ struct VitView {
     float* imgs = nullptr;      // [B][3][H][W]
     float* d_imgs = nullptr;    // [B][3][H][W]
     std::vector<const float*> pb, pk;   // per-layer pointer tables
+    float* dk_layer[SELFSIM_MAX_LAYERS] = {};   // splice_step_set_ssim_layers: the key-gradient buffer of entry i of the layer list (d_keys for the top block)
 };
 
 struct SpliceStep {
@@ -160,6 +161,13 @@ struct SpliceStep {
     // the image-space terms (splice_step_set_image_terms): lambda_global_tv on x' = G(A_crop), lambda_global_pixel_identity on y' = G(B_crop)
     // against B_crop; both 0: off -- the step launches what it always did
     float lambda_tv = 0.f, lambda_pix = 0.f;
+    // the blocks whose keys the two structure terms read (splice_step_set_ssim_layers): ascending block indices, their
+    // weights, and one SelfSimBatch workspace per entry (entry 0: ssim_ws); 0 entries: off -- the top block alone, the step launches what it
+    // always did
+    int n_ssim_layers = 0;
+    int ssim_layers[SELFSIM_MAX_LAYERS] = {};
+    float ssim_weights[SELFSIM_MAX_LAYERS] = {};
+    void* ssim_ws_layer[SELFSIM_MAX_LAYERS] = {};
 };
 
 static size_t arena_floats(const SpliceStep* st) { return st->astride ? st->pairs * st->astride : (size_t)st->nparams; }   // of all pairs' arenas
@@ -227,12 +235,23 @@ static int view_init(SpliceStep* st, VitView& v, void* ctx, int want_B) {
 // its n_b slots); their raw sums go to words 6-7 of the row and of out8 and into the total as fmaf(w_pix, raw_7, fmaf(w_tv, raw_6, total of
 // the five)).  The two weights are not in wtab: a sweep's slots share them.  The instances without IMG do not read the two trailing
 // arguments and launch with 320 threads, as before.
-template <bool MONITOR, bool TRACE, bool LRP = false, bool IMG = false>
+// LYR (the structure terms over the keys of several ViT blocks): a slot's partials of terms 1 and 2 are n_layers
+// ranges of tiles_g / tiles_e slots, one per layer in ascending order.  Each range is added in slot order (ssim_layer_sum, the function
+// splice_step_ssim_layer_values reports with), the layers' sums in ascending order, the pair's crops in crop order as before -- so with
+// one crop per pair the reported word IS the float32 sum of the reported per-layer values.  The instances without LYR do not read the
+// three trailing arguments.
+__device__ __forceinline__ float ssim_layer_sum(const float* part, int tiles) {
+    float acc = 0.f;
+    for (int i = 0; i < tiles; ++i) acc += part[i];
+    return acc;
+}
+template <bool MONITOR, bool TRACE, bool LRP = false, bool IMG = false, bool LYR = false>
 __global__ __launch_bounds__(IMG ? 448 : 320) void total_loss_kernel(float* lbase, size_t lstride, int lp, float w_ssim, float w_essim, float w_ecls, float w_cls,
                                                          float w_id, float* out8, int n_a, int n_b, int n_c, int n_e, const float* wtab, int ssim_on,
                                                          int entire, splice_stop_state* stop, const int* dev_t, StopRule rule, splice_best_state* kb,
                                                          float* means, float* trace, int capacity, LrRule lr_rule, splice_lr_state* lr_state, int* lr_cuts,
-                                                         const float* lr_in, int lr_in_stride, float* lr_eff, float w_tv, float w_pix) {
+                                                         const float* lr_in, int lr_in_stride, float* lr_eff, float w_tv, float w_pix, int n_layers,
+                                                         int tiles_g, int tiles_e) {
     static_assert(MONITOR || !LRP, "the lr rule rides on the stop rule");
     __shared__ float raw[8];
     float* l = lbase + (size_t)blockIdx.x * lstride;
@@ -242,6 +261,13 @@ __global__ __launch_bounds__(IMG ? 448 : 320) void total_loss_kernel(float* lbas
     float tot = 0.f;
     for (int slot = 0; slot < n_slots; ++slot) {
         const float* part = lp0 + (size_t)slot * lstride + 8 + (size_t)k * lp;
+        if (LYR && (k == L_GLOBAL_SSIM || k == L_ENTIRE_SSIM)) {   // (wave-uniform: every lane walks the same slots)
+            const int tiles = k == L_GLOBAL_SSIM ? tiles_g : tiles_e;
+            float v = 0.f;
+            for (int i = 0; i < n_layers; ++i) v += ssim_layer_sum(part + (size_t)i * tiles, tiles);
+            tot += v;
+            continue;
+        }
         float acc = 0.f;
         for (int i = lane; i < lp; i += 64) acc += part[i];
         tot += wave_sum(acc);
@@ -301,13 +327,26 @@ __global__ __launch_bounds__(64) void plateau_update_kernel(splice_stop_state* s
 #define NO_LR_RULE LrRule{}, (splice_lr_state*)nullptr, (int*)nullptr, (const float*)nullptr, 0, (float*)nullptr
 // the two trailing arguments behind them of a launch without the image-space terms
 #define NO_IMG_TERMS 0.f, 0.f
+// the three trailing arguments behind those of a launch without structure layers
+#define NO_SSIM_LAYERS 0, 0, 0
 // the step's instance by what the handle carries (the lr rule rides on the stop rule)
 using TotalLossKernel = decltype(&total_loss_kernel<false, false>);
-template <bool IMG>
+template <bool IMG, bool LYR = false>
 static TotalLossKernel total_loss_instance(bool lr_rule, bool trace, bool stop) {
-    return lr_rule ? (trace ? total_loss_kernel<true, true, true, IMG> : total_loss_kernel<true, false, true, IMG>)
-           : trace ? (stop ? total_loss_kernel<true, true, false, IMG> : total_loss_kernel<false, true, false, IMG>)
-                   : (stop ? total_loss_kernel<true, false, false, IMG> : total_loss_kernel<false, false, false, IMG>);
+    return lr_rule ? (trace ? total_loss_kernel<true, true, true, IMG, LYR> : total_loss_kernel<true, false, true, IMG, LYR>)
+           : trace ? (stop ? total_loss_kernel<true, true, false, IMG, LYR> : total_loss_kernel<false, true, false, IMG, LYR>)
+                   : (stop ? total_loss_kernel<true, false, false, IMG, LYR> : total_loss_kernel<false, false, false, IMG, LYR>);
+}
+// one thread per (layer, pair): the pair's crops' sums of layer i's slot range of `term`, added in crop order (splice_step_ssim_layer_values)
+__global__ __launch_bounds__(64) void ssim_layer_values_kernel(const float* lbase, size_t lstride, int lp, int term, int n_layers, int tiles, int pairs,
+                                                               int n_slots, float* out) {
+    const int id = blockIdx.x * 64 + threadIdx.x;
+    if (id >= n_layers * pairs) return;
+    const int i = id / pairs, p = id % pairs;
+    float tot = 0.f;
+    for (int slot = 0; slot < n_slots; ++slot)
+        tot += ssim_layer_sum(lbase + ((size_t)p * n_slots + slot) * lstride + 8 + (size_t)term * lp + (size_t)i * tiles, tiles);
+    out[id] = tot;
 }
 // the two rules alone on a caller's [pairs][8] losses (splice_plateau_update_lr): one thread per slot, the loss kernel's device function
 __global__ __launch_bounds__(64) void plateau_update_lr_kernel(splice_stop_state* stop, splice_lr_state* lr_state, int* lr_cuts, const float* losses8, int pairs,
@@ -391,6 +430,7 @@ __global__ __launch_bounds__(256) void stage_inputs_rows_kernel(StageRowsArgs r)
         }
     }
 }
+static int tri_tiles(int T) { const int nt = (T + 63) / 64; return nt * (nt + 1) / 2; }   // upper-triangular 64 x 64 tiles of a [T][T] matrix
 static float* loss_part(SpliceStep* st, int slot) { return st->losses + 8 + (size_t)slot * st->lp; }   // pair 0; pair p at + p * lstride
 
 // `n_img` images [3][h][w] -> [3][oh][ow] each (contiguous batches on both sides)
@@ -460,8 +500,29 @@ static void step_terms(const SpliceStep* st, bool ssim_on, bool entire, Term t[L
 
 // The structure term of P pairs (util/losses.py:74-83): targets = passes [pass_tgt, pass_tgt + P), generated = passes
 // [pass_x, pass_x + P) of view v.  `b` is carved over st->ssim_ws for v's token count.
-static int ssim_batch(SpliceStep* st, VitView& v, int pass_tgt, int pass_x, int count, const Term& term, int slot, SelfSimBatch* b) {
+// `tab` (a handle with splice_step_set_ssim_layers): entry i = the same operands of block ssim_layers[i] -- its qkv and transposed copy, the
+// workspace and key-gradient buffer of its own, its weight; the launchers then take every operand pointer from the table.
+static int ssim_batch(SpliceStep* st, VitView& v, int pass_tgt, int pass_x, int count, const Term& term, int slot, SelfSimBatch* b,
+                      SelfSimLayers* tab = nullptr) {
     bf16_t *qkv = nullptr, *qkvT = nullptr;
+    if (tab) {
+        tab->n = st->n_ssim_layers;
+        const size_t pass_rows = (size_t)v.Tld * 3 * v.D;
+        for (int i = 0; i < tab->n; ++i) {
+            const int l = st->ssim_layers[i];
+            SelfSimBatch w = {};
+            RC(splice_vit_get_tensor(v.ctx, 1, l, (void**)&qkv));
+            RC(splice_vit_get_tensor(v.ctx, 8, l, (void**)&qkvT));
+            selfsim_batch_carve(st->ssim_ws_layer[i], v.T, v.D, count, &w);
+            SelfSimLayer& e = tab->e[i];
+            e.k_tgt = qkv + (size_t)pass_tgt * pass_rows + v.D;
+            e.k_x = qkv + (size_t)pass_x * pass_rows + v.D;
+            e.kT_x = qkvT + (size_t)v.D * v.rows + (size_t)pass_x * v.Tld;
+            e.S_tgt = w.S_tgt; e.wmat = w.wmat; e.norm_x = w.norm_x; e.rpart = w.rpart;
+            e.dk = v.dk_layer[i] + (size_t)pass_x * v.Tld * v.D;
+            e.weight = st->ssim_weights[i];
+        }
+    }
     RC(splice_vit_get_tensor(v.ctx, 1, v.depth - 1, (void**)&qkv));
     RC(splice_vit_get_tensor(v.ctx, 6, v.depth - 1, (void**)&qkvT));
     selfsim_batch_carve(st->ssim_ws, v.T, v.D, count, b);
@@ -622,7 +683,8 @@ int splice_step_set_crops(void* h, int a_h, int a_w, int b_h, int b_w) {
 static const char* whole_step_rule(const SpliceStep* st) {
     return st->stop_rule.window > 0 ? "with a stop rule" : st->ema ? "with a weight average" : st->clip ? "with gradient clipping"
            : st->best ? "that keeps the best weights" : st->trace ? "with a loss trace"
-           : (st->lambda_tv > 0.f || st->lambda_pix > 0.f) ? "with image-space loss terms" : nullptr;
+           : (st->lambda_tv > 0.f || st->lambda_pix > 0.f) ? "with image-space loss terms"
+           : st->n_ssim_layers > 0 ? "with structure layers" : nullptr;
 }
 // The shared opening of the rule setters below: before the first step only (`what` of the rule, for the error text), and not on a
 // gradient-only or phase-mode handle.  Callers return its code plainly, not through RC(): the message stays the last error.
@@ -894,6 +956,87 @@ int splice_step_set_image_terms(void* h, float lambda_tv, float lambda_pix) {
     st->lambda_tv = lambda_tv; st->lambda_pix = lambda_pix;
     return SPLICE_OK;
 }
+static unsigned long long ssim_layers_salt(const SpliceStep* st) {
+    if (!st->n_ssim_layers) return 0;
+    unsigned long long h = 1469598103934665603ull;   // FNV-1a over (block, weight bits) in list order
+    for (int i = 0; i < st->n_ssim_layers; ++i) {
+        unsigned w;
+        memcpy(&w, &st->ssim_weights[i], sizeof(w));
+        for (unsigned long long v : {(unsigned long long)st->ssim_layers[i], (unsigned long long)w})
+            for (int k = 0; k < 8; ++k) { h ^= (v >> (8 * k)) & 0xff; h *= 1099511628211ull; }
+    }
+    return ((h ^ (h >> 15) ^ (h >> 30) ^ (h >> 45)) & 0x7fffull) << 40 | 1ull << 55;
+}
+// The blocks whose keys the two structure terms read, and their weights (include/splice_hip.h has the term): n ascending distinct block
+// indices, n finite weights > 0.  The three self-similarity launches of a structure term then cover every named block (grid z), the ViT
+// contexts write the transposed qkv copy of each, every block gets a key-gradient buffer and a workspace of its own for both views, and
+// the ViT backward adds each block's dK where it always could (pk[l]).  Before the first step only; not on a gradient-only or phase-mode
+// handle (such a handle in turn refuses splice_step_set_mode / splice_step_set_phases); not with fp8_selfsim (the table carries no e4m3
+// workspace).  A layer list needs n tiles slots of a term's partial row: a handle whose row is narrower gets a wider partials buffer
+// here -- the appended slots are zero, and in total_loss_kernel's lane-strided walk (slot i on lane i % 64, ascending) they reach each
+// lane behind its existing addends, so no bit of any other term moves.
+int splice_step_set_ssim_layers(void* h, int n, const int* layers, const float* weights) {
+    SpliceStep* st = (SpliceStep*)h;
+    const char* who = "splice_step_set_ssim_layers";
+    if (!st || !layers || !weights) return SPLICE_ERR_ARG;
+    const int depth = st->vg.depth;
+    if (n < 1 || n > depth || n > SELFSIM_MAX_LAYERS) { splice_set_error("%s: needs 1..%d layers, got %d", who, depth < SELFSIM_MAX_LAYERS ? depth : SELFSIM_MAX_LAYERS, n); return SPLICE_ERR_ARG; }
+    for (int i = 0; i < n; ++i) {
+        if (layers[i] < 0 || layers[i] >= depth || (i > 0 && layers[i] <= layers[i - 1])) {
+            splice_set_error("%s: layers must be ascending distinct block indices in [0, %d), got layers[%d] = %d", who, depth, i, layers[i]);
+            return SPLICE_ERR_ARG;
+        }
+        if (!(weights[i] > 0.f) || !(weights[i] <= 3.402823466e+38f)) {
+            splice_set_error("%s: weights must be finite and > 0, got weights[%d] = %g", who, i, (double)weights[i]);
+            return SPLICE_ERR_ARG;
+        }
+    }
+    if (int rc = rule_setter_ok(st, who, "the layers are set")) return rc;
+    if (st->cfg.fp8_selfsim) { splice_set_error("%s: not with fp8_selfsim (the e4m3 Gram path reads the top block alone)", who); return SPLICE_ERR_STATE; }
+    if (st->n_ssim_layers) { splice_set_error("%s: the layers are set once", who); return SPLICE_ERR_STATE; }
+    const int Tmax = st->plan_e && st->ve.T > st->vg.T ? st->ve.T : st->vg.T;
+    for (VitView* v : {&st->vg, &st->ve}) {
+        if (!v->ctx) continue;
+        RC(splice_vit_ctx_set_transposed_layers(v->ctx, n, layers));
+        for (int i = 0; i < n; ++i) {
+            if (layers[i] == v->depth - 1) { v->dk_layer[i] = v->d_keys; continue; }
+            RC(salloc(st, &v->dk_layer[i], (size_t)v->rows * v->D));
+            HIPCHK(hipMemset(v->dk_layer[i], 0, (size_t)v->rows * v->D * sizeof(float)));   // padding rows read as zero gradient
+        }
+        for (int i = 0; i < n; ++i) v->pk[layers[i]] = v->dk_layer[i];   // (the top block's entry stays: the key-identity term seeds it whatever is named)
+    }
+    for (int i = 0; i < n; ++i) {
+        if (i == 0) { st->ssim_ws_layer[0] = st->ssim_ws; continue; }
+        char* ws = nullptr;
+        RC(salloc(st, &ws, selfsim_batch_ws_bytes(Tmax, st->vg.D, st->P)));
+        st->ssim_ws_layer[i] = ws;
+    }
+    const size_t need = (size_t)n * tri_tiles(Tmax);
+    if (need > st->lp) {
+        float* wider = nullptr;
+        RC(salloc(st, &wider, (size_t)st->P * (8 + 8 * need)));
+        st->losses = wider; st->lp = need; st->lstride = 8 + 8 * need;   // (the narrower buffer stays with the handle until it goes)
+    }
+    st->graphs.retire();
+    st->n_ssim_layers = n;
+    for (int i = 0; i < n; ++i) { st->ssim_layers[i] = layers[i]; st->ssim_weights[i] = weights[i]; }
+    return SPLICE_OK;
+}
+// The per-layer values of the last step's structure term `term` (1: global, 2: entire-image): out[i * pairs + p] (device, [n][pairs]) =
+// pair p's sum of layer i's slot range of the term's partial row, added in slot order, the pair's crops in crop order -- the addends
+// w_i mse(S_i, S*_i) whose ascending sum total_loss_kernel reports as word `term` of the losses row.
+int splice_step_ssim_layer_values(void* h, int term, float* out, splice_stream_t stream) {
+    SpliceStep* st = (SpliceStep*)h;
+    const char* who = "splice_step_ssim_layer_values";
+    if (!st || !out || (term != L_GLOBAL_SSIM && term != L_ENTIRE_SSIM)) { splice_set_error("%s: needs a handle, out and term 1 or 2", who); return SPLICE_ERR_ARG; }
+    if (!st->n_ssim_layers) { splice_set_error("%s: the handle has no structure layers (splice_step_set_ssim_layers)", who); return SPLICE_ERR_STATE; }
+    if (term == L_ENTIRE_SSIM && !st->plan_e) { splice_set_error("%s: the handle has no entire-image branch", who); return SPLICE_ERR_STATE; }
+    const int n = st->n_ssim_layers, tiles = tri_tiles(term == L_GLOBAL_SSIM ? st->vg.T : st->ve.T);
+    const int n_slots = term == L_GLOBAL_SSIM && st->crops_mode ? (st->pairs > 1 ? st->na : st->P) : 1;
+    SPLICE_LAUNCH(ssim_layer_values_kernel, dim3((n * st->pairs + 63) / 64), dim3(64), 0, (hipStream_t)stream, (const float*)st->losses, st->lstride, (int)st->lp, term, n,
+                  tiles, st->pairs, n_slots, out);
+    return SPLICE_OK;
+}
 // Start the handle at step next_step_idx of a run other handles carried so far (a resumed run, a compacted engine; DESIGN.md section
 // 9g).  What a handle keeps from one step to the next, and this call therefore sets, is two things: ssim_id_on, which only the run of step
 // cls_warmup switches on, and the stop records.  Nothing else in the handle is state: dev_t and the lr(s) are staged by every step's
@@ -986,7 +1129,7 @@ int splice_total_loss_pairs(float* lbase, size_t lstride, int lp, float w_ssim, 
     const auto kernel = total_loss_kernel<false, false>;
     SPLICE_LAUNCH(kernel, dim3(pairs), dim3(320), 0, (hipStream_t)stream, lbase, lstride, lp, w_ssim, w_essim, w_ecls, w_cls, w_id, out8,
                   n_a, n_b, n_c, n_e, wtab, ssim_on, entire, (splice_stop_state*)nullptr, (const int*)nullptr, StopRule{}, (splice_best_state*)nullptr,
-                  (float*)nullptr, (float*)nullptr, 0, NO_LR_RULE, NO_IMG_TERMS);
+                  (float*)nullptr, (float*)nullptr, 0, NO_LR_RULE, NO_IMG_TERMS, NO_SSIM_LAYERS);
     return SPLICE_OK;
 }
 // test hook: the same launch with the image-space terms (the IMG instance, 448 threads): terms 6 / 7 of the partials (lstride >= 8 + 8 lp)
@@ -1000,7 +1143,7 @@ int splice_total_loss_pairs_img(float* lbase, size_t lstride, int lp, float w_ss
     const auto kernel = total_loss_kernel<false, false, false, true>;
     SPLICE_LAUNCH(kernel, dim3(pairs), dim3(448), 0, (hipStream_t)stream, lbase, lstride, lp, w_ssim, w_essim, w_ecls, w_cls, w_id, out8,
                   n_a, n_b, n_c, n_e, wtab, ssim_on, entire, (splice_stop_state*)nullptr, (const int*)nullptr, StopRule{}, (splice_best_state*)nullptr,
-                  (float*)nullptr, (float*)nullptr, 0, NO_LR_RULE, w_tv, w_pix);
+                  (float*)nullptr, (float*)nullptr, 0, NO_LR_RULE, w_tv, w_pix, NO_SSIM_LAYERS);
     return SPLICE_OK;
 }
 // test hook: the same launch with the loss trace (the TRACE instances): dev_t holds step index + 1 on the device; stop (optional, with its
@@ -1020,7 +1163,7 @@ int splice_total_loss_pairs_trace(float* lbase, size_t lstride, int lp, float w_
     const auto kernel = stop ? total_loss_kernel<true, true> : total_loss_kernel<false, true>;
     SPLICE_LAUNCH(kernel, dim3(pairs), dim3(320), 0, (hipStream_t)stream, lbase, lstride, lp, w_ssim, w_essim, w_ecls, w_cls, w_id, out8, n_a, n_b, n_c, n_e, wtab,
                   ssim_on, entire, stop, dev_t, stop ? StopRule{window, rel, patience, min_steps} : StopRule{}, (splice_best_state*)nullptr, (float*)nullptr, trace,
-                  capacity, NO_LR_RULE, NO_IMG_TERMS);
+                  capacity, NO_LR_RULE, NO_IMG_TERMS, NO_SSIM_LAYERS);
     return SPLICE_OK;
 }
 
@@ -1042,6 +1185,8 @@ static int place_passes(VitView& v, const float* src, int h, int w, int pass, in
 static int zero_seeds(VitView& v, int pass, int n, hipStream_t s) {
     const size_t passD = (size_t)v.Tld * v.D;
     RC(dev_zero_launch(v.d_block + pass * passD, n * passD * sizeof(float), s));
+    for (float* dk : v.dk_layer)   // the lower blocks of splice_step_set_ssim_layers (the top block's entry is d_keys itself)
+        if (dk && dk != v.d_keys) RC(dev_zero_launch(dk + pass * passD, n * passD * sizeof(float), s));
     return dev_zero_launch(v.d_keys + pass * passD, n * passD * sizeof(float), s);
 }
 
@@ -1097,6 +1242,9 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
     RC(splice_vit_get_tensor(vg.ctx, 3, vg.depth - 1, (void**)&qkv_g));
     const size_t passD = (size_t)vg.Tld * vg.D;
     SelfSimBatch sb = {};
+    // structure layers (splice_step_set_ssim_layers): the tables of the two views' launches; null: the top block alone, the plain launches
+    SelfSimLayers sl = {}, sle = {};
+    const bool layered = st->n_ssim_layers > 0;
     if (do_v) {
         RC(place_passes(vg, src.a_in, c.crop_h, c.crop_w, pA, Pa, s2));
         RC(place_passes(vg, src.b_in, st->cropb_h, st->cropb_w, pB, Pb, s2));
@@ -1105,8 +1253,8 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
         RC(dev_zero_launch(st->losses, (size_t)P * st->lstride * sizeof(float), s2));
         RC(zero_seeds(vg, pX, Pa + Pb, s2));
         if (t[L_GLOBAL_SSIM].on) {   // target self-similarity S* of A' (util/losses.py:79)
-            RC(ssim_batch(st, vg, pA, pX, Pa, t[L_GLOBAL_SSIM], L_GLOBAL_SSIM, &sb));
-            RC(selfsim_target_launch(sb, s2));
+            RC(ssim_batch(st, vg, pA, pX, Pa, t[L_GLOBAL_SSIM], L_GLOBAL_SSIM, &sb, layered ? &sl : nullptr));
+            RC(selfsim_target_launch(sb, s2, layered ? &sl : nullptr));
         }
     }
     if (overlap) HIPCHK(hipEventRecord(st->ev(SpliceStep::EV_JOIN), s2));
@@ -1123,7 +1271,7 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
     if (overlap) HIPCHK(hipStreamWaitEvent(s, st->ev(SpliceStep::EV_JOIN), 0));
     // ---- losses on the global batch
     if (do_v) {
-        if (t[L_GLOBAL_SSIM].on) RC(selfsim_loss_launch(sb, s));
+        if (t[L_GLOBAL_SSIM].on) RC(selfsim_loss_launch(sb, s, layered ? &sl : nullptr));
         if (t[L_GLOBAL_CLS].on) {   // [CLS] of block 11, before the final LayerNorm (util/losses.py:90-93)
             if (pairs > 1 && st->na != st->nb) {
                 // several pairs with nA != nB crops: one launch per crop index i (pair p's x'_i against its B'_i into slot p nc + i); every
@@ -1159,9 +1307,9 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
             RC(zero_seeds(ve, pairs, pairs, s));
             if (t[L_ENTIRE_SSIM].on) {
                 SelfSimBatch se = {};
-                RC(ssim_batch(st, ve, 0, pairs, pairs, t[L_ENTIRE_SSIM], L_ENTIRE_SSIM, &se));
-                RC(selfsim_target_launch(se, s));
-                RC(selfsim_loss_launch(se, s));
+                RC(ssim_batch(st, ve, 0, pairs, pairs, t[L_ENTIRE_SSIM], L_ENTIRE_SSIM, &se, layered ? &sle : nullptr));
+                RC(selfsim_target_launch(se, s, layered ? &sle : nullptr));
+                RC(selfsim_loss_launch(se, s, layered ? &sle : nullptr));
             }
             if (t[L_ENTIRE_CLS].on)   // target is the B_global crop's CLS (util/losses.py:60; with n_crops > 1 the zip pairs x_entire with the FIRST crop of its pair)
                 RC(mse_batched_launch(blk_e + pairs * epassD, ve.D, epassD, blk_g + pB * passD, vg.D, st->nb * passD, 1, ve.D, 1.0f, t[L_ENTIRE_CLS].lambda,
@@ -1178,13 +1326,14 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
             const bool grouped = st->crops_mode && pairs > 1;
             const int n1 = st->crops_mode ? P : 1;
             // (the rule and the trace ride in the launch: no node more)
-            const auto kernel = img_on ? total_loss_instance<true>(st->lr_state != nullptr, st->trace != nullptr, stop_on)
-                                       : total_loss_instance<false>(st->lr_state != nullptr, st->trace != nullptr, stop_on);
+            const bool lrp = st->lr_state != nullptr, trc = st->trace != nullptr;
+            const auto kernel = layered ? (img_on ? total_loss_instance<true, true>(lrp, trc, stop_on) : total_loss_instance<false, true>(lrp, trc, stop_on))
+                                        : (img_on ? total_loss_instance<true>(lrp, trc, stop_on) : total_loss_instance<false>(lrp, trc, stop_on));
             SPLICE_LAUNCH(kernel, dim3(pairs), dim3(img_on ? 448 : 320), 0, q, st->losses, st->lstride, (int)st->lp, t[L_GLOBAL_SSIM].lambda, t[L_ENTIRE_SSIM].lambda,
                           t[L_ENTIRE_CLS].lambda, t[L_GLOBAL_CLS].lambda, t[L_GLOBAL_ID].lambda, st->losses_out, grouped ? st->na : n1, grouped ? st->nb : n1, grouped ? nc : n1,
                           grouped ? 1 : n1, st->pw ? st->pw + (size_t)PW_LAMBDAS * P : nullptr, (int)ssim_on, (int)entire, st->stop, st->dev_t, st->stop_rule, st->best, st->best_means,
                           st->trace, st->trace_cap, st->lr_rule, st->lr_state, st->lr_cuts, (const float*)(st->pair_lr ? st->dev_lrs : st->dev_lr), st->pair_lr ? 1 : 0,
-                          st->lr_eff, st->lambda_tv, st->lambda_pix);
+                          st->lr_eff, st->lambda_tv, st->lambda_pix, st->n_ssim_layers, tri_tiles(vg.T), st->plan_e ? tri_tiles(ve.T) : 0);
         }
         if (!st->running || !gen_fwd) return SPLICE_OK;
         void* plans[3] = {st->plan_a, st->plan_b, nullptr};
@@ -1369,6 +1518,9 @@ int splice_step_run(void* h, float* params, float* grads, float* m, float* v, co
                                             (st->stop_rule.window > 0 ? 1ull << 63 : 0) | (st->lr_state ? 1ull << 62 : 0) |
                                             // ... and the two image-space terms, a launch each (and another loss-kernel instance)
                                             (st->lambda_tv > 0.f ? 1ull << 61 : 0) | (st->lambda_pix > 0.f ? 1ull << 60 : 0) |
+                                            // ... and the structure layers (bits 40-55: bit 55 on, 15 bits of a hash of the blocks and their weights): another
+                                            // grid, other zeroing launches and key-gradient adds, another loss-kernel instance
+                                            ssim_layers_salt(st) |
                                             // ... and the extended rule of the update (bits 56-59: off, or 1 + kind with the arenas it walks)
                                             (st->opt_ext_on ? (unsigned long long)(1 + st->opt_kind + 3 * ((st->opt_ext.momentum > 0.f ? 1 : 0) + 2 * (st->opt_ext.amsgrad || st->opt_ext.centered ? 1 : 0))) << 56 : 0);
             ex = st->graphs.adopt(variant, g, salt);

@@ -63,6 +63,8 @@ struct SpliceVitCtx {
     std::vector<bf16_t*> qkv, attn_out, hpre;  // depth
     bf16_t* qkvT_last = nullptr;   // [3D][rows] transpose of the LAST layer's qkv (the [CLS]-row kernels of vit_cls.hip read token-contiguous K / V);
                                    // the attention kernels proper transpose inside LDS and need no such copy
+    std::vector<bf16_t*> qkvT_extra;   // depth x [3D][rows]: the same copy of the blocks below the top that splice_vit_ctx_set_transposed_layers named
+                                   // (the structure loss over their keys, selfsim.hip); null: the layer's QKV GEMM writes none, as always
     std::vector<float*> lse;               // depth x [B][H][Tld]
     float* qkv_last_f32 = nullptr;         // [rows][3D]
     bf16_t* ln_out = nullptr;              // [rows][D]   transient
@@ -308,7 +310,7 @@ int splice_vit_ctx_create(void* h, int B, int H, int W, const float* pos_TD, int
     A(c->pos_eff, (size_t)c->Tld * D);
     A(c->patches, rows * pp3);
     c->xs.resize(L + 1); c->xmid.resize(L); c->mean1.resize(L); c->rstd1.resize(L); c->mean2.resize(L); c->rstd2.resize(L);
-    c->qkv.resize(L); c->attn_out.resize(L); c->hpre.resize(L); c->lse.resize(L);
+    c->qkv.resize(L); c->attn_out.resize(L); c->hpre.resize(L); c->lse.resize(L); c->qkvT_extra.assign(L, nullptr);
     for (int l = 0; l <= L; ++l) A(c->xs[l], rows * D);
     for (int l = 0; l < L; ++l) {
         A(c->xmid[l], rows * D);
@@ -365,6 +367,34 @@ int splice_vit_ctx_set_top_cls_only(void* ctx, int on) {
     SpliceVitCtx* c = (SpliceVitCtx*)ctx;
     if (!c) return SPLICE_ERR_ARG;
     c->top_cls_only = on ? 1 : 0;
+    return SPLICE_OK;
+}
+
+// The layers (n distinct block indices in [0, depth)) whose QKV projection also writes the transposed bf16 copy of its output, bf16
+// [3D][rows], through the epilogue form the top block's always uses -- what the structure loss over the keys of those layers reads in its
+// dK product (selfsim.hip).  The top block keeps its own copy whether it is named or not.  Before the context's first forward only: a
+// later forward would otherwise leave a named layer's copy unwritten for the passes that ran earlier.  Tensor kind 8 returns the copies.
+int splice_vit_ctx_set_transposed_layers(void* ctx, int n, const int* layers) {
+    SpliceVitCtx* c = (SpliceVitCtx*)ctx;
+    const char* who = "splice_vit_ctx_set_transposed_layers";
+    if (!c || !layers || n < 1 || n > c->vit->depth) { splice_set_error("%s: needs a context and 1..depth layers", who); return SPLICE_ERR_ARG; }
+    if (c->forward_done) { splice_set_error("%s: the layers are named before the context's first forward", who); return SPLICE_ERR_STATE; }
+    for (int i = 0; i < n; ++i) {
+        bool dup = false;
+        for (int j = 0; j < i; ++j) dup |= layers[j] == layers[i];
+        if (layers[i] < 0 || layers[i] >= c->vit->depth || dup) {
+            splice_set_error("%s: layers must be distinct and in [0, %d), got layers[%d] = %d", who, c->vit->depth, i, layers[i]);
+            return SPLICE_ERR_ARG;
+        }
+    }
+    if (c->rows % 8) { splice_set_error("%s: the transposed copy needs rows %% 8 == 0", who); return SPLICE_ERR_ARG; }
+    for (int i = 0; i < n; ++i) {
+        const int l = layers[i];
+        if (l == c->vit->depth - 1 || c->qkvT_extra[l]) continue;
+        RC(dev_alloc(c->allocs, &c->qkvT_extra[l], (size_t)c->rows * 3 * c->vit->dim));
+        // (columns of padding tokens are written by every forward; passes a caller never runs stay finite: the loss reads them times zero)
+        HIPCHK(hipMemset(c->qkvT_extra[l], 0, (size_t)c->rows * 3 * c->vit->dim * sizeof(bf16_t)));
+    }
     return SPLICE_OK;
 }
 
@@ -457,6 +487,9 @@ int splice_vit_forward_passes(void* ctx, const float* img, int normalize, int gr
                 fl |= EPI_OUT_T | EPI_COLS_F32;
                 e.out_bf_t = c->qkvT_last + r0; e.ldt = c->rows;
                 e.out_f32_cols = c->qkv_last_f32 + r0 * 3 * D; e.ld_cols = 3 * D; e.col_lo = 0; e.col_hi = 3 * D;
+            } else if (c->qkvT_extra[l]) {   // a named layer: the same transposed copy, into its own buffer
+                fl |= EPI_OUT_T;
+                e.out_bf_t = c->qkvT_extra[l] + r0; e.ldt = c->rows;
             }
             SpliceProfScope ps(l == L - 1 ? 0 : 2); SPLICE_DEV_REGION(2);
             if (fp8) {   // e4m3 LayerNorm output (per-token scale) x e4m3 weights (per-channel scale) on the fp8 MFMA
@@ -567,6 +600,7 @@ int splice_vit_forward_passes(void* ctx, const float* img, int normalize, int gr
 // kind 4: lse          l  fp32 [B][H][Tld]
 // kind 5: embedded tokens fp32 [rows][D]
 // kind 6: raw qkv l, transposed  bf16 [3D][rows]   (row = feature, column = pass * Tld + token)
+// kind 8: the same of a layer named by splice_vit_ctx_set_transposed_layers (kind 6 serves the top block alone, as before)
 int splice_vit_get_tensor(void* ctx, int kind, int layer, void** out) {
     SpliceVitCtx* c = (SpliceVitCtx*)ctx;
     if (!c || !out || layer < 0 || layer >= c->vit->depth) return SPLICE_ERR_ARG;
@@ -579,6 +613,10 @@ int splice_vit_get_tensor(void* ctx, int kind, int layer, void** out) {
         case 5: *out = c->xs[0]; break;
         case 6: if (layer != c->vit->depth - 1) return SPLICE_ERR_ARG; *out = c->qkvT_last; break;   // only the last layer keeps a transposed copy
         case 7: *out = c->qkv[layer]; break;   // as kind 1; splice_vit_read_tensor copies it AS STORED (q columns pre-scaled by splice_vit_qscale)
+        case 8:   // as kind 6, of a layer splice_vit_ctx_set_transposed_layers named (the top block: its own copy, always there)
+            *out = layer == c->vit->depth - 1 ? c->qkvT_last : c->qkvT_extra[layer];
+            if (!*out) { splice_set_error("splice_vit_get_tensor: layer %d keeps no transposed qkv copy (splice_vit_ctx_set_transposed_layers)", layer); return SPLICE_ERR_ARG; }
+            break;
         default: return SPLICE_ERR_ARG;
     }
     return SPLICE_OK;

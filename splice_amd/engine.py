@@ -66,6 +66,14 @@ class MultiPairEngine:
         self.opt_ext = fused_optimizer_ext(self.cfg)   # None: the plain rules, today's launches
         self.w = None
         self.image_terms = image_terms_rule(self.cfg)
+        # the blocks of the structure terms: None -- the top block, today's launches -- or the canonical (layers, weights),
+        # which the config then holds too (what a snapshot is compared on)
+        depth = vit_engine.depth if vit_engine is not None else synth.DINO_CONFIGS[self.cfg["dino_model_name"]][2]
+        self.ssim_layers = ssim_layers_rule(self.cfg, depth)
+        if self.ssim_layers is not None:
+            if fp8_mode(fp8):
+                raise ValueError("'dino_ssim_layers': not with fp8 -- the e4m3 Gram path of the structure term reads the top block alone")
+            self.cfg.update(dino_ssim_layers=list(self.ssim_layers[0]), dino_ssim_layer_weights=list(self.ssim_layers[1]))
         P_in = len(gen_states)
         self.cfgs = [self.cfg] * P_in
         self._pair_lambdas = self._pair_lr = False
@@ -235,6 +243,12 @@ class MultiPairEngine:
         # the first step.  Both 0: the call is not made and the handle launches what it always did
         if max(self.image_terms) > 0:
             _lib.check(_lib.lib().splice_step_set_image_terms(self.handle, *self.image_terms), "step_set_image_terms")
+        # the blocks of the structure terms (shared by the slots): the layer is one more grid dimension of the three self-similarity launches;
+        # before the first step.  The default: the call is not made and the handle launches what it always did
+        if self.ssim_layers is not None:
+            n = len(self.ssim_layers[0])
+            _lib.check(_lib.lib().splice_step_set_ssim_layers(self.handle, n, (C.c_int * n)(*self.ssim_layers[0]), (C.c_float * n)(*self.ssim_layers[1])),
+                       "step_set_ssim_layers")
         self._lr_scale = [1.0] * P   # the host's copy of every slot's lr scale, refreshed with the stop steps
         self._stopped = [None] * P   # the host's copy of every slot's stop step, refreshed by stop_state()
         self._stop_dirty = False     # a window has closed since the last stop_state(): the copy may be behind
@@ -585,6 +599,27 @@ class MultiPairEngine:
         acts = self.active_terms(self.step_idx)
         return self._pick([{k: vals[i] for i, k in enumerate(LOSS_KEYS + IMAGE_LOSS_KEYS) if act[k]} for vals, act in zip(rows, acts)], pair)
 
+    def ssim_layer_values(self, pair=None, entire=False):
+        """The per-layer addends of the last step's structure term (``dino_ssim_layers``), copied from the device
+        (waits for the current stream): a float32 array with one entry per block of the canonical list, ``w_l * mse(S_l, S*_l)`` as the
+        loss kernels summed it -- ``loss_global_ssim`` (``entire=True``: ``loss_entire_ssim``) is their float32 sum in that order
+        (``np_ssim_layers``), exactly so with one crop per pair.  Zeros at a step that does not compute the term.  One array for ``pair``,
+        a list over the live slots for ``pair=None``."""
+        if self.ssim_layers is None:
+            raise RuntimeError("ssim_layer_values: the structure terms read the top block alone ('dino_ssim_layers' is null or the default)")
+        if entire and self.plan_e is None:
+            raise RuntimeError("ssim_layer_values: the engine has no entire-image branch")
+        out = torch.zeros(len(self.ssim_layers[0]), self.P, device=self.device)
+        _lib.check(_lib.lib().splice_step_ssim_layer_values(self.handle, 2 if entire else 1, _lib.ptr(out), _lib.current_stream()), "step_ssim_layer_values")
+        host = out.cpu().numpy()
+        rows = [host[:, i].copy() for i in range(self.P)]
+        if pair is None and self.PAIR_NONE is None:
+            return rows
+        row = self._row(self.PAIR_NONE if pair is None else pair)
+        if row is None:
+            raise RuntimeError(f"ssim_layer_values: slot {pair} is parked (stop_compact): its partials left the device with its handle")
+        return rows[row]
+
     def active_terms(self, step_idx):
         """Per slot: which of LOSS_KEYS and IMAGE_LOSS_KEYS step ``step_idx`` computes (``engine.active_terms``; a slot's terms follow that slot's own
         lambdas).  Host arithmetic only."""
@@ -744,6 +779,9 @@ class MultiScaleEngine:
             if lam > 0:
                 raise NotImplementedError(f"{key} > 0: the term's gradient is added to a whole fused step's image gradient; MultiScaleEngine's per-scale "
                                           "follower handles add theirs into the leader's, which would count the term once per scale")
+        if ssim_layers_rule(self.cfg, vit_engine.depth if vit_engine is not None else synth.DINO_CONFIGS[self.cfg["dino_model_name"]][2]) is not None:
+            raise NotImplementedError("dino_ssim_layers: the layer table is set on a whole fused step; MultiScaleEngine runs each scale as a gradient-only "
+                                      "or phase-mode handle, which refuses it")
         self.ema_rule = ema_rule(self.cfg)
         self.ema = None
         self.grad_clip = grad_clip_rule(self.cfg)

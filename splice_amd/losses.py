@@ -8,8 +8,9 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
-from .engine import resize_output_size
+from .engine import SSIM_LAYER_KEYS, resize_output_size, ssim_layers_rule
 from .extractor import VitExtractor
+from .synth import DINO_CONFIGS
 
 device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
 
@@ -92,6 +93,9 @@ class LossG(torch.nn.Module):
         # only the [CLS] appearance term is live before the warm-up step (util/losses.py:25-32)
         self.lambdas = {name: 0 for _, name, _, _, _ in _TERMS}
         self.lambdas['lambda_global_cls'] = cfg['lambda_global_cls']
+        # the blocks of the two structure terms (an extension beyond the reference): None -- the top block -- or the
+        # canonical (layers, weights), what the fused step minimises under the same two keys
+        self.ssim_layers = ssim_layers_rule({k: cfg.get(k) for k in SSIM_LAYER_KEYS}, DINO_CONFIGS[cfg['dino_model_name']][2])
         self._features = {
             "self_sim": lambda img: self.extractor.get_keys_self_sim_from_input(img, layer_num=_LAST_LAYER),
             "cls": lambda img: self.extractor.get_feature_from_input(img)[-1][0, 0, :],
@@ -129,6 +133,8 @@ class LossG(torch.nn.Module):
 
     def _feature_mse(self, feature, generated, targets):
         """sum over crops of mse(feature(T(generated_i)), feature(T(target_i))), target side under no_grad."""
+        if feature == "self_sim" and self.ssim_layers is not None:
+            return self._layered_self_sim_mse(generated, targets)
         f = self._features[feature]
         acc = 0.0
         for gen_img, tgt_img in zip(generated, targets):   # one crop at a time: the extractor is batch-1
@@ -136,6 +142,19 @@ class LossG(torch.nn.Module):
                 want = f(self.global_transform(tgt_img).unsqueeze(0).to(device))
             got = f(self.global_transform(gen_img).unsqueeze(0).to(device))
             acc = acc + F.mse_loss(got, want)
+        return acc
+
+    def _layered_self_sim_mse(self, generated, targets):
+        """The structure term over ``dino_ssim_layers``: per crop, sum over the blocks ascending of w_l mse(S_l(generated), S_l(target))."""
+        acc = 0.0
+        for gen_img, tgt_img in zip(generated, targets):
+            tgt, gen = self.global_transform(tgt_img).unsqueeze(0).to(device), self.global_transform(gen_img).unsqueeze(0).to(device)
+            crop = 0.0
+            for layer, w in zip(*self.ssim_layers):
+                with torch.no_grad():
+                    want = self.extractor.get_keys_self_sim_from_input(tgt, layer_num=layer)
+                crop = crop + w * F.mse_loss(self.extractor.get_keys_self_sim_from_input(gen, layer_num=layer), want)
+            acc = acc + crop
         return acc
 
     # the reference's public per-term entry points (argument order as in util/losses.py:74,85,96)

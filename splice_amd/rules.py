@@ -44,7 +44,11 @@ DEFAULT_CFG = dict(  # conf/default/config.yaml of the reference
     optimizer_weight_decay=0.0, optimizer_momentum=0.0, optimizer_dampening=0.0, optimizer_nesterov=False, optimizer_amsgrad=False,
     optimizer_centered=False,
     # ... and two loss terms on the generated crops themselves: total variation of G(A_crop), mse(G(B_crop), B_crop); off by default
-    lambda_global_tv=0.0, lambda_global_pixel_identity=0.0)
+    lambda_global_tv=0.0, lambda_global_pixel_identity=0.0,
+    # ... and the ViT blocks whose keys the two structure terms compare, with a weight each; null: the top block, weight 1
+    dino_ssim_layers=None, dino_ssim_layer_weights=None)
+SSIM_LAYER_KEYS = ("dino_ssim_layers", "dino_ssim_layer_weights")
+MAX_SSIM_LAYERS = 12   # SELFSIM_MAX_LAYERS: entries of the loss kernels' by-value layer table
 
 SNAPSHOT_FORMAT = 1
 # Keys of a config that do not enter a slot's arithmetic (paths, logging, and how the loop parks and checkpoints): a snapshot is restored
@@ -190,6 +194,52 @@ def image_terms_rule(c):
                 raise ValueError(f"'{key}' must be a finite float32 number, got {v!r}")
         out.append(float(v))
     return tuple(out)
+
+
+def ssim_layers_rule(c, depth):
+    """The blocks of the structure terms in config ``c`` for a ViT of ``depth`` blocks, checked on the host:
+    ``None`` -- both keys null: the top block with weight 1, the step launches what it launches without the keys -- or
+    ``(layers, weights)``, the canonical form: the block indices ascending, each weight beside its block.  ``dino_ssim_layers`` is a list
+    of 1..``depth`` distinct integers in ``[0, depth)`` (at most MAX_SSIM_LAYERS); ``dino_ssim_layer_weights`` a list of as many finite
+    float32 numbers > 0 (null: all 1), refused without ``dino_ssim_layers``.  ``[depth - 1]`` with weight 1 is the default and also
+    returns ``None``.  Shared by the slots of a sweep (``merge_pair_cfgs`` refuses a per-slot value).  Raises ValueError naming the
+    key."""
+    layers, weights = (c.get(k, DEFAULT_CFG[k]) for k in SSIM_LAYER_KEYS)
+    if layers is None:
+        if weights is not None:
+            raise ValueError("'dino_ssim_layer_weights' needs 'dino_ssim_layers': a weight goes with a named block")
+        return None
+    if isinstance(layers, (str, bytes)) or not isinstance(layers, (list, tuple)) or not 1 <= len(layers) <= min(depth, MAX_SSIM_LAYERS):
+        raise ValueError(f"'dino_ssim_layers' must be a list of 1..{min(depth, MAX_SSIM_LAYERS)} block indices, got {layers!r}")
+    for l in layers:
+        if isinstance(l, bool) or not isinstance(l, _INT) or not 0 <= l < depth:
+            raise ValueError(f"'dino_ssim_layers' must hold integers in [0, {depth}), got {l!r}")
+    layers = [int(l) for l in layers]
+    if len(set(layers)) != len(layers):
+        raise ValueError(f"'dino_ssim_layers' must hold distinct block indices, got {layers!r}")
+    if weights is None:
+        weights = [1.0] * len(layers)
+    if isinstance(weights, (str, bytes)) or not isinstance(weights, (list, tuple)) or len(weights) != len(layers):
+        raise ValueError(f"'dino_ssim_layer_weights' must be a list of {len(layers)} numbers, one per entry of 'dino_ssim_layers', got {weights!r}")
+    for w in weights:
+        with np.errstate(over="ignore"):   # (the kernels take it as a float)
+            if isinstance(w, bool) or not isinstance(w, _REAL) or not 0 < w < float("inf") or not 0 < np.float32(w) < np.float32("inf"):
+                raise ValueError(f"'dino_ssim_layer_weights' must hold finite float32 numbers > 0, got {w!r}")
+    order = sorted(range(len(layers)), key=layers.__getitem__)
+    layers, weights = [layers[i] for i in order], [float(weights[i]) for i in order]
+    if layers == [depth - 1] and weights == [1.0]:
+        return None
+    return layers, weights
+
+
+def np_ssim_layers(values, weights=None):
+    """Word 1 / 2 of a losses row from the per-layer addends ``engine.ssim_layer_values`` reports (already weighted; ``weights`` given:
+    unweighted values, multiplied in float32 first): their float32 sum over the blocks ascending, one rounding per addition, from 0."""
+    f = np.float32
+    acc = f(0)
+    for i, v in enumerate(values):
+        acc = f(acc + (f(v) if weights is None else f(f(weights[i]) * f(v))))
+    return acc
 
 
 def snapshot_cfg_mismatch(a, b):
