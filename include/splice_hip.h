@@ -233,6 +233,13 @@ int splice_vit_ctx_set_top_cls_only(void* ctx, int on);
  * (splice_step_set_ssim_layers calls this on its contexts).  Before the context's first forward only.  splice_vit_get_tensor kind 8
  * returns the copies; a context without this call runs the launches it always ran. */
 int splice_vit_ctx_set_transposed_layers(void* ctx, int n, const int* layers);
+/* [CLS]-row gradient seeds of block outputs: seeds = [depth] device pointers, each [B][D] fp32 (row p: the gradient w.r.t. row 0 of block
+ * l's output of pass p) or NULL, armed for the passes [pass_begin, pass_end).  A later splice_vit_backward whose range meets the armed
+ * one adds seeds[l]'s rows into row 0 of those passes of its gradient stream in front of block l's backward (g += seed, g_bf = bf16(g);
+ * where the stream is not live yet it starts there, zero outside those rows): what a d_block[l] that is zero outside row 0 gives,
+ * element for element, without the [rows][D] buffer.  A backward the armed range does not meet launches what it always did.  The
+ * pointer table is copied; seeds NULL or an empty range disarms.  Needs a context created with need_grad. */
+int splice_vit_ctx_set_cls_seeds(void* ctx, const float* const* seeds, int pass_begin, int pass_end);
 /* precision of THIS context's forward: 0 bf16 (default); 1 = QKV / fc1 / fc2 projections on the fp8 MFMA; 3 = those + the attention
  * forward (Q K^T, P V) on the fp8 MFMA.  Needs splice_vit_enable_fp8 on the engine.  The backward is bf16 in every mode. */
 int splice_vit_ctx_set_fp8(void* ctx, int mode);
@@ -849,6 +856,33 @@ int splice_selfsim_loss_layers(int n_layers, const splice_bf16* const* k_tgt, co
                                const float* weights, int ldk, size_t k_pstride, int ldt, size_t kT_pstride, int T, int D, int pairs, float lambda,
                                const float* e_scale_tab, float eps, float* loss_part, size_t part_pstride, float* const* dk, int lddk,
                                size_t dk_pstride, void* const* ws, splice_stream_t stream);
+/* ------------------------------------------------------------------ the [CLS] appearance loss over several ViT blocks.
+ * With n ascending distinct block indices `layers` in [0, depth) and n finite weights > 0, both appearance terms of the step -- the global
+ * one on every (x', B') crop pair, the entire-image one -- become
+ *     raw = sum over i ascending of weights[i] * mean((row 0 of block layers[i]'s output of the generated image - the target's)^2),
+ * reported as word 4 / 3 of the losses row and multiplied by the term's lambda in the total as before.  One launch per term covers every
+ * named block; a block below the top hands its gradient to the ViT backward as one seed row per pass (splice_vit_ctx_set_cls_seeds), the
+ * top block through the [CLS]-only tail as always.  The top block need not be named.  Before the first splice_step_run only; refused on
+ * a handle in gradient-only or phase mode or with a leader (which in turn refuses those calls), with fp8_selfsim, and a second time.  A
+ * handle without the call launches what it always did. */
+int splice_step_set_cls_layers(void* step, int n, const int* layers, const float* weights);
+/* The per-layer addends of the appearance term (entire 0: loss_global_cls; else: loss_entire_cls) of the last step that computed it,
+ * copied to the host behind a device-wide wait: out[s * n + i] = slot s's weights[i] times block i's mean squared [CLS] difference; the
+ * slots are the pairs (entire, or one crop per pair), else the pairs * min(nA, nB) pair-crops, pair-major.  cap: the floats out holds
+ * (>= slots * n).  A slot's partial -- with one crop per pair the reported word -- is the float32 sum of its row, ascending, exactly; a
+ * slot that never took part reads 0. */
+int splice_step_cls_layer_values(void* step, int entire, float* out, int cap);
+/* test hook: the layered launch of the step on caller buffers.  x, tgt, seeds: host arrays of n_layers (1..12) device pointers -- the
+ * first slot's row of D floats on the generated side, on the target side, and of the layer's seed buffer; slot s is x_pstride / t_pstride
+ * / seed_pstride (>= D) floats further on.  weights: host, finite, > 0.  For slot s and layer i, with g = lambda / (float)D or
+ * grad_tab[s] (may be NULL; device, [slots]; a slot whose entry is 0 writes nothing):
+ *   values[s * n_layers + i] = (sum of d^2 over the D columns, a fixed tree) * (weights[i] / (float)D),   d = x - tgt
+ *   seeds[i][s * seed_pstride + c] = 2 * (g * weights[i]) * d[c]
+ *   part[s * part_pstride]  = the float32 sum of the slot's values, ascending from 0 (no other slot of part is written).
+ * Layer i has the bits of its own n_layers = 1 call.  Refusals launch nothing. */
+int splice_cls_loss_layers(int n_layers, const float* const* x, const float* const* tgt, const float* weights, size_t x_pstride, size_t t_pstride,
+                           int D, int slots, float lambda, const float* grad_tab, float* part, size_t part_pstride, float* const* seeds,
+                           size_t seed_pstride, float* values, splice_stream_t stream);
 /* splice_total_loss_pairs as a handle with a loss trace launches it (splice_step_set_loss_trace): dev_t (device) holds step index + 1,
  * and words 0-5 of row step index of trace ([capacity][pairs][8], device) receive pair p's out8 values, a row at or beyond capacity
  * left out.  stop (may be NULL; device, [pairs] records) runs the instance of a handle with the stop rule, whose rule is window (>= 1),

@@ -189,6 +189,7 @@ _SIGNATURES = {
     "splice_vit_ctx_info": ([_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)], _i),
     "splice_vit_ctx_set_top_cls_only": ([_vp, _i], _i),
     "splice_vit_ctx_set_transposed_layers": ([_vp, _i, _vp], _i),
+    "splice_vit_ctx_set_cls_seeds": ([_vp, _vp, _i, _i], _i),
     "splice_vit_ctx_set_fp8": ([_vp, _i], _i),
     "splice_vit_forward": ([_vp, _vp, _i, _vp], _i),
     "splice_vit_forward_ex": ([_vp, _vp, _i, _i, _vp], _i),
@@ -245,6 +246,10 @@ _SIGNATURES = {
     "splice_step_set_ssim_layers": ([_vp, _i, _vp, _vp], _i),
     "splice_step_ssim_layer_values": ([_vp, _i, _vp, _vp], _i),
     "splice_selfsim_loss_layers": ([_i, _vp, _vp, _vp, _vp, _i, _sz, _i, _sz, _i, _i, _i, _f, _vp, _f, _vp, _sz, _vp, _i, _sz, _vp, _vp], _i),
+    # the [CLS] appearance terms over several ViT blocks
+    "splice_step_set_cls_layers": ([_vp, _i, _vp, _vp], _i),
+    "splice_step_cls_layer_values": ([_vp, _i, _vp, _i], _i),
+    "splice_cls_loss_layers": ([_i, _vp, _vp, _vp, _sz, _sz, _i, _i, _f, _vp, _vp, _sz, _vp, _sz, _vp, _vp], _i),
     "splice_image_terms_value": ([_vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _sz, _i, _vp], _i),
     "splice_image_terms_grad_add": ([_vp, _vp, _vp, _i, _i, _i, _f, _vp], _i),
     "splice_total_loss_pairs_img": ([_vp, _sz, _i, _f, _f, _f, _f, _f, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _f, _f, _vp], _i),

@@ -190,6 +190,21 @@ int splice_selfsim_loss_layers(int n_layers, const splice_bf16* const* k_tgt, co
     if (rc != SPLICE_OK) return finish(rc, who);
     return finish(selfsim_loss_launch(b, ST(stream), &tab), who);
 }
+/* the layered [CLS] launch of the step (splice_step_set_cls_layers) on caller buffers */
+int splice_cls_loss_layers(int n_layers, const float* const* x, const float* const* tgt, const float* weights, size_t x_pstride, size_t t_pstride,
+                           int D, int slots, float lambda, const float* grad_tab, float* part, size_t part_pstride, float* const* seeds,
+                           size_t seed_pstride, float* values, splice_stream_t stream) {
+    const char* who = "splice_cls_loss_layers";
+    if (n_layers < 1 || n_layers > CLS_MAX_LAYERS || !x || !tgt || !weights || !seeds || !part || !values || D < 1 || slots < 1 || seed_pstride < (size_t)D)
+        return finish(SPLICE_ERR_ARG, who);
+    ClsLayers tab = {};
+    tab.n = n_layers; tab.D = D; tab.x_ps = x_pstride; tab.t_ps = t_pstride; tab.seed_step = 1;
+    for (int i = 0; i < n_layers; ++i) {
+        ClsLayer& e = tab.e[i];
+        e.x = x[i]; e.tgt = tgt[i]; e.seed = seeds[i]; e.seed_ps = seed_pstride; e.weight = weights[i];
+    }
+    return finish(cls_layers_launch(tab, slots, lambda / (float)(size_t)D, grad_tab, part, part_pstride, values, (size_t)n_layers, ST(stream)), who);
+}
 int splice_mse_pairs(const float* a, int lda, size_t a_ps, const float* b, int ldb, size_t b_ps, int rows, int cols, float loss_weight,
                      float grad_weight, float* part, size_t part_ps, float* grad, int ldg, size_t g_ps, int pairs, const float* grad_tab,
                      splice_stream_t stream) {

@@ -156,6 +156,29 @@ int selfsim_loss_launch(const SelfSimBatch& b, hipStream_t s, const SelfSimLayer
 int mse_batched_launch(const float* a, int lda, size_t a_ps, const float* b, int ldb, size_t b_ps, int rows, int cols, float loss_weight,
                        float grad_weight, float* part, size_t part_ps, float* grad, int ldg, size_t g_ps, int pairs, hipStream_t s,
                        const float* grad_tab = nullptr);
+// ---- cls_layers.hip: the [CLS] appearance term over several ViT blocks ----
+// A by-value table, one entry per layer in ascending block order, of what differs between the layers' problems, and the strides they
+// share.  Slot s (a pair, or a pair-crop) compares row x + s * x_ps with row tgt + s * t_ps (D floats each), writes entry i's addend
+// S_i * (weight_i / D) to values[s * values_ps + i], the seed row 2 * (g * weight_i) * d to seed + s * seed_step * seed_ps, and the
+// ascending fp32 sum of the addends to part[s * part_ps] -- slot 0 of the slot's term row, whose other slots the step's zeroing left at 0.
+#define CLS_MAX_LAYERS 12
+struct ClsLayer {
+    const float* x;     // [CLS] row of the first slot's generated pass, block output of this layer
+    const float* tgt;   // the same of its target pass
+    float* seed;        // the first slot's seed row: a [passes][D] seed buffer (seed_ps = D), or row 0 of a [rows][D] gradient buffer (seed_ps = Tld * D)
+    size_t seed_ps;     // floats between the seed rows of consecutive passes
+    float weight;
+};
+struct ClsLayers {
+    int n, D;
+    size_t x_ps, t_ps;   // floats between the rows of consecutive slots on the two sides
+    int seed_step;       // passes between consecutive slots on the generated side (1, or the crops per pair of a per-crop-index launch)
+    ClsLayer e[CLS_MAX_LAYERS];
+};
+// g: the gradient weight of the plain path, lambda / (float)D; grad_tab (optional, [slots]): the slot's own, a slot whose entry is 0
+// takes no part (nothing of it is written).  One launch, one 256-thread workgroup per slot.
+int cls_layers_launch(const ClsLayers& tab, int slots, float g, const float* grad_tab, float* part, size_t part_ps, float* values,
+                      size_t values_ps, hipStream_t s);
 // 2-D strided MSE: loss_accum[0] += weight * mean((a-b)^2); grad (optional) = weight * 2 (a-b) / (rows*cols)
 int mse_launch(const float* a, int lda, const float* b, int ldb, int rows, int cols, float weight, float* loss_accum,
                float* grad, int ldg, hipStream_t s);

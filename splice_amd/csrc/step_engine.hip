@@ -45,6 +45,11 @@ struct VitView {
     float* d_imgs = nullptr;    // [B][3][H][W]
     std::vector<const float*> pb, pk;   // per-layer pointer tables
     float* dk_layer[SELFSIM_MAX_LAYERS] = {};   // splice_step_set_ssim_layers: the key-gradient buffer of entry i of the layer list (d_keys for the top block)
+    // splice_step_set_cls_layers: entry i's [CLS]-row seed buffer [B][D] (null for the top block, which keeps row 0 of d_block), the [depth]
+    // table of them the context is armed with, and the per-layer addends [slots][n] of the view's appearance term
+    float* cls_seed[CLS_MAX_LAYERS] = {};
+    std::vector<const float*> cls_seed_tab;
+    float* cls_values = nullptr;
 };
 
 struct SpliceStep {
@@ -168,6 +173,11 @@ struct SpliceStep {
     int ssim_layers[SELFSIM_MAX_LAYERS] = {};
     float ssim_weights[SELFSIM_MAX_LAYERS] = {};
     void* ssim_ws_layer[SELFSIM_MAX_LAYERS] = {};
+    // the blocks whose [CLS] row the two appearance terms read (splice_step_set_cls_layers): ascending block indices and
+    // their weights; 0 entries: off -- the top block alone, the step launches what it always did
+    int n_cls_layers = 0;
+    int cls_layers[CLS_MAX_LAYERS] = {};
+    float cls_weights[CLS_MAX_LAYERS] = {};
 };
 
 static size_t arena_floats(const SpliceStep* st) { return st->astride ? st->pairs * st->astride : (size_t)st->nparams; }   // of all pairs' arenas
@@ -541,6 +551,27 @@ static int ssim_batch(SpliceStep* st, VitView& v, int pass_tgt, int pass_x, int 
     return SPLICE_OK;
 }
 
+// The appearance term over the handle's [CLS] layers (splice_step_set_cls_layers): the table of one launch.  Generated rows: passes pass_x,
+// pass_x + x_step, ... of view vx; targets: passes pass_t, pass_t + t_step, ... of the global view.  Entry i reads block cls_layers[i]'s output
+// on both sides and seeds the view's buffer of that block -- the top block row 0 of d_block, as the plain path does.
+static int cls_table(SpliceStep* st, VitView& vx, int pass_x, int x_step, int pass_t, int t_step, ClsLayers* tab) {
+    VitView& vg = st->vg;
+    const size_t xpass = (size_t)vx.Tld * vx.D, tpass = (size_t)vg.Tld * vg.D;
+    tab->n = st->n_cls_layers; tab->D = vx.D;
+    tab->x_ps = (size_t)x_step * xpass; tab->t_ps = (size_t)t_step * tpass; tab->seed_step = x_step;
+    for (int i = 0; i < tab->n; ++i) {
+        float *bx = nullptr, *bt = nullptr;
+        RC(splice_vit_get_tensor(vx.ctx, 0, st->cls_layers[i], (void**)&bx));
+        RC(splice_vit_get_tensor(vg.ctx, 0, st->cls_layers[i], (void**)&bt));
+        ClsLayer& e = tab->e[i];
+        e.x = bx + (size_t)pass_x * xpass; e.tgt = bt + (size_t)pass_t * tpass;
+        if (vx.cls_seed[i]) { e.seed = vx.cls_seed[i] + (size_t)pass_x * vx.D; e.seed_ps = (size_t)vx.D; }
+        else { e.seed = vx.d_block + (size_t)pass_x * xpass; e.seed_ps = xpass; }
+        e.weight = st->cls_weights[i];
+    }
+    return SPLICE_OK;
+}
+
 extern "C" {
 
 int splice_step_create(const splice_step_config* cfg, void* vit_ctx_global, void* vit_ctx_entire, void* gen_plan_a, void* gen_plan_b,
@@ -684,7 +715,7 @@ static const char* whole_step_rule(const SpliceStep* st) {
     return st->stop_rule.window > 0 ? "with a stop rule" : st->ema ? "with a weight average" : st->clip ? "with gradient clipping"
            : st->best ? "that keeps the best weights" : st->trace ? "with a loss trace"
            : (st->lambda_tv > 0.f || st->lambda_pix > 0.f) ? "with image-space loss terms"
-           : st->n_ssim_layers > 0 ? "with structure layers" : nullptr;
+           : st->n_ssim_layers > 0 ? "with structure layers" : st->n_cls_layers > 0 ? "with [CLS] layers" : nullptr;
 }
 // The shared opening of the rule setters below: before the first step only (`what` of the rule, for the error text), and not on a
 // gradient-only or phase-mode handle.  Callers return its code plainly, not through RC(): the message stays the last error.
@@ -1037,6 +1068,78 @@ int splice_step_ssim_layer_values(void* h, int term, float* out, splice_stream_t
                   tiles, st->pairs, n_slots, out);
     return SPLICE_OK;
 }
+static unsigned long long cls_layers_salt(const SpliceStep* st) {
+    if (!st->n_cls_layers) return 0;
+    unsigned long long h = 1469598103934665603ull;   // FNV-1a over (block, weight bits) in list order
+    for (int i = 0; i < st->n_cls_layers; ++i) {
+        unsigned w;
+        memcpy(&w, &st->cls_weights[i], sizeof(w));
+        for (unsigned long long v : {(unsigned long long)st->cls_layers[i], (unsigned long long)w})
+            for (int k = 0; k < 8; ++k) { h ^= (v >> (8 * k)) & 0xff; h *= 1099511628211ull; }
+    }
+    return h | 1ull;   // (never 0: a handle with layers is never keyed like one without)
+}
+// The blocks whose [CLS] row the two appearance terms read, and their weights (include/splice_hip.h has the term): n ascending distinct
+// block indices, n finite weights > 0.  One launch per appearance term then covers every named block (cls_layers.hip) in place of the
+// term's mse_batched_launch; a block below the top gets a [CLS]-row seed buffer [B][D] per view, set to zero (-0.0f) here once -- the loss kernel
+// overwrites the rows it owns each step, no step writes the rows of other passes -- which the ViT backward of the x' chain (global view) and
+// of the x_entire' chain (entire view) adds in front of the block (splice_vit_ctx_set_cls_seeds).  The top block, when named, keeps row 0 of
+// d_block and the [CLS]-only tail; when it is not, that row stays at the zero the step's zeroing wrote.  Before the first step only; not on
+// a gradient-only or phase-mode handle (which in turn refuses those calls); not with fp8_selfsim; not a second time.
+int splice_step_set_cls_layers(void* h, int n, const int* layers, const float* weights) {
+    SpliceStep* st = (SpliceStep*)h;
+    const char* who = "splice_step_set_cls_layers";
+    if (!st || !layers || !weights) return SPLICE_ERR_ARG;
+    const int depth = st->vg.depth;
+    if (n < 1 || n > depth || n > CLS_MAX_LAYERS) { splice_set_error("%s: needs 1..%d layers, got %d", who, depth < CLS_MAX_LAYERS ? depth : CLS_MAX_LAYERS, n); return SPLICE_ERR_ARG; }
+    for (int i = 0; i < n; ++i) {
+        if (layers[i] < 0 || layers[i] >= depth || (i > 0 && layers[i] <= layers[i - 1])) {
+            splice_set_error("%s: layers must be ascending distinct block indices in [0, %d), got layers[%d] = %d", who, depth, i, layers[i]);
+            return SPLICE_ERR_ARG;
+        }
+        if (!(weights[i] > 0.f) || !(weights[i] <= 3.402823466e+38f)) {
+            splice_set_error("%s: weights must be finite and > 0, got weights[%d] = %g", who, i, (double)weights[i]);
+            return SPLICE_ERR_ARG;
+        }
+    }
+    if (int rc = rule_setter_ok(st, who, "the layers are set")) return rc;
+    if (st->cfg.fp8_selfsim) { splice_set_error("%s: not with fp8 (the e4m3 forward is validated against the top block's [CLS] row alone)", who); return SPLICE_ERR_STATE; }
+    if (st->n_cls_layers) { splice_set_error("%s: the layers are set once", who); return SPLICE_ERR_STATE; }
+    for (VitView* v : {&st->vg, &st->ve}) {
+        if (!v->ctx) continue;
+        v->cls_seed_tab.assign(v->depth, nullptr);
+        for (int i = 0; i < n; ++i) {
+            if (layers[i] == v->depth - 1) continue;
+            RC(salloc(st, &v->cls_seed[i], (size_t)v->B * v->D));
+            // (-0.0f, the identity of the backward's g += seed for every g: a row no loss launch ever writes -- another chain's pass, a sweep
+            // slot whose lambda is 0 -- leaves even the sign of a zero alone)
+            HIPCHK(hipMemsetD32((hipDeviceptr_t)v->cls_seed[i], (int)0x80000000u, (size_t)v->B * v->D));
+            v->cls_seed_tab[layers[i]] = v->cls_seed[i];
+        }
+        RC(salloc(st, &v->cls_values, (size_t)st->P * n));
+        HIPCHK(hipMemset(v->cls_values, 0, (size_t)st->P * n * sizeof(float)));
+    }
+    st->graphs.retire();
+    st->n_cls_layers = n;
+    for (int i = 0; i < n; ++i) { st->cls_layers[i] = layers[i]; st->cls_weights[i] = weights[i]; }
+    return SPLICE_OK;
+}
+// The per-layer addends of the appearance term of the last step that computed it (entire = 0: loss_global_cls, word 4; else
+// loss_entire_cls, word 3), copied to the HOST behind a device-wide wait: out[s * n + i] = slot s's w_i * mse of block i's [CLS] rows, n the
+// layer count; slots = the pairs (entire, or one crop per pair), else pairs * min(nA, nB) pair-crops in pair-major order.  cap: floats
+// `out` holds.  A slot's partial is the float32 sum of its row, ascending, exactly; a slot that never took part reads zeros.
+int splice_step_cls_layer_values(void* h, int entire, float* out, int cap) {
+    SpliceStep* st = (SpliceStep*)h;
+    const char* who = "splice_step_cls_layer_values";
+    if (!st || !out) { splice_set_error("%s: needs a handle and out", who); return SPLICE_ERR_ARG; }
+    if (!st->n_cls_layers) { splice_set_error("%s: the handle has no [CLS] layers (splice_step_set_cls_layers)", who); return SPLICE_ERR_STATE; }
+    if (entire && !st->plan_e) { splice_set_error("%s: the handle has no entire-image branch", who); return SPLICE_ERR_STATE; }
+    const int nc = st->na < st->nb ? st->na : st->nb, slots = entire ? st->pairs : st->pairs * nc;
+    if (cap < slots * st->n_cls_layers) { splice_set_error("%s: out holds %d floats, needs %d", who, cap, slots * st->n_cls_layers); return SPLICE_ERR_ARG; }
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, entire ? st->ve.cls_values : st->vg.cls_values, (size_t)slots * st->n_cls_layers * sizeof(float), hipMemcpyDeviceToHost));
+    return SPLICE_OK;
+}
 // Start the handle at step next_step_idx of a run other handles carried so far (a resumed run, a compacted engine; DESIGN.md section
 // 9g).  What a handle keeps from one step to the next, and this call therefore sets, is two things: ssim_id_on, which only the run of step
 // cls_warmup switches on, and the stop records.  Nothing else in the handle is state: dev_t and the lr(s) are staged by every step's
@@ -1208,9 +1311,12 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
     // the chain's generated images [h][w], added to the leader's d_lead by a follower; then (`gen`) the generator backward of `plan` into `arena`.
     // `img_term` (L_GLOBAL_TV on the x' chain, L_GLOBAL_PIX on the y' chain, 0 on the entire-image chain): with that term's weight > 0 its
     // gradient is added into d_img in place, one launch, from the chain's saved generator output.
+    // `cls_term` ([CLS] layers only; L_GLOBAL_CLS on the x' chain, L_ENTIRE_CLS on the entire-image chain, 0 on the y' chain): the chain's passes
+    // are armed with the view's seed buffers when that term ran this step, and disarmed otherwise -- a chain without seeds gains no launch.
     auto chain_bwd = [&](VitView& vw, int p0, int p1, bool vit, float* d_img, int h, int w, float* d_lead, void* plan, float* arena, int accumulate,
-                         bool gen, int img_term, hipStream_t q) -> int {
+                         bool gen, int img_term, int cls_term, hipStream_t q) -> int {
         if (do_v) {
+            if (vit && st->n_cls_layers) RC(splice_vit_ctx_set_cls_seeds(vw.ctx, cls_term && t[cls_term].on ? vw.cls_seed_tab.data() : nullptr, p0, p1));
             if (vit) RC(splice_vit_backward(vw.ctx, p0, p1, vw.pb.data(), nullptr, vw.pk.data(), vw.d_imgs, 1, q));
             RC(unplace_grads(vw.d_imgs + (size_t)p0 * 3 * vw.H * vw.W, vw.H, vw.W, d_img, h, w, p1 - p0, q));
             if (st->leader) RC(add_f32_launch(d_lead, d_img, (size_t)(p1 - p0) * 3 * h * w, q));
@@ -1272,7 +1378,21 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
     // ---- losses on the global batch
     if (do_v) {
         if (t[L_GLOBAL_SSIM].on) RC(selfsim_loss_launch(sb, s, layered ? &sl : nullptr));
-        if (t[L_GLOBAL_CLS].on) {   // [CLS] of block 11, before the final LayerNorm (util/losses.py:90-93)
+        if (t[L_GLOBAL_CLS].on && st->n_cls_layers) {   // [CLS] of the named blocks: one launch for all of them, the call structure of the plain path below
+            const int n = st->n_cls_layers;
+            const float g = t[L_GLOBAL_CLS].lambda / (float)(size_t)vg.D;
+            ClsLayers ct = {};
+            if (pairs > 1 && st->na != st->nb) {
+                for (int i = 0; i < nc; ++i) {
+                    RC(cls_table(st, vg, pX + i, st->na, pB + i, st->nb, &ct));
+                    RC(cls_layers_launch(ct, pairs, g, nullptr, loss_part(st, L_GLOBAL_CLS) + (size_t)i * st->lstride, (size_t)nc * st->lstride,
+                                         vg.cls_values + (size_t)i * n, (size_t)nc * n, s));
+                }
+            } else {
+                RC(cls_table(st, vg, pX, 1, pB, 1, &ct));
+                RC(cls_layers_launch(ct, Pc, g, t[L_GLOBAL_CLS].tab, loss_part(st, L_GLOBAL_CLS), st->lstride, vg.cls_values, (size_t)n, s));
+            }
+        } else if (t[L_GLOBAL_CLS].on) {   // [CLS] of block 11, before the final LayerNorm (util/losses.py:90-93)
             if (pairs > 1 && st->na != st->nb) {
                 // several pairs with nA != nB crops: one launch per crop index i (pair p's x'_i against its B'_i into slot p nc + i); every
                 // pair-crop is its own workgroups, as in one launch
@@ -1311,7 +1431,12 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
                 RC(selfsim_target_launch(se, s, layered ? &sle : nullptr));
                 RC(selfsim_loss_launch(se, s, layered ? &sle : nullptr));
             }
-            if (t[L_ENTIRE_CLS].on)   // target is the B_global crop's CLS (util/losses.py:60; with n_crops > 1 the zip pairs x_entire with the FIRST crop of its pair)
+            if (t[L_ENTIRE_CLS].on && st->n_cls_layers) {   // the same over the named blocks (one launch)
+                ClsLayers ct = {};
+                RC(cls_table(st, ve, pairs, 1, pB, st->nb, &ct));
+                RC(cls_layers_launch(ct, pairs, t[L_ENTIRE_CLS].lambda / (float)(size_t)ve.D, t[L_ENTIRE_CLS].tab, loss_part(st, L_ENTIRE_CLS), st->lstride,
+                                     ve.cls_values, (size_t)st->n_cls_layers, s));
+            } else if (t[L_ENTIRE_CLS].on)   // target is the B_global crop's CLS (util/losses.py:60; with n_crops > 1 the zip pairs x_entire with the FIRST crop of its pair)
                 RC(mse_batched_launch(blk_e + pairs * epassD, ve.D, epassD, blk_g + pB * passD, vg.D, st->nb * passD, 1, ve.D, 1.0f, t[L_ENTIRE_CLS].lambda,
                                       loss_part(st, L_ENTIRE_CLS), st->lstride, ve.d_block + pairs * epassD, ve.D, epassD, pairs, s, t[L_ENTIRE_CLS].tab));
         }
@@ -1352,12 +1477,12 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
             HIPCHK(hipEventRecord(st->ev(SpliceStep::EV_FORK2), s));
             HIPCHK(hipStreamWaitEvent(s2, st->ev(SpliceStep::EV_FORK2), 0));
         }
-        RC(chain_bwd(vg, pY, pEnd, !(st->ablate & 32), ip.dy, st->cropb_h, st->cropb_w, src.dy, st->plan_b, st->grads_b, 0, gen_bwd, L_GLOBAL_PIX, s2));
+        RC(chain_bwd(vg, pY, pEnd, !(st->ablate & 32), ip.dy, st->cropb_h, st->cropb_w, src.dy, st->plan_b, st->grads_b, 0, gen_bwd, L_GLOBAL_PIX, 0, s2));
         if (side_tail) {
             RC(bookkeeping(s2));
             HIPCHK(hipEventRecord(st->ev(SpliceStep::EV_JOIN2), s2));
         }
-        RC(chain_bwd(vg, pX, pY, true, ip.dx, c.crop_h, c.crop_w, src.dx, st->plan_a, grads, st->accumulate, gen_bwd, L_GLOBAL_TV, s));
+        RC(chain_bwd(vg, pX, pY, true, ip.dx, c.crop_h, c.crop_w, src.dx, st->plan_a, grads, st->accumulate, gen_bwd, L_GLOBAL_TV, L_GLOBAL_CLS, s));
         if (overlap) HIPCHK(hipStreamWaitEvent(s, st->ev(SpliceStep::EV_JOIN2), 0));
         // grads = g(A) + g(B): folded into the Adam kernel on ordinary steps; a separate add when the entire-image branch
         // still has to accumulate into the sum (same association order either way)
@@ -1366,7 +1491,7 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
             else adam_g2 = st->grads_b;
         }
     }
-    if (entire) RC(chain_bwd(ve, pairs, 2 * pairs, true, ip.dxe, c.ent_h, c.ent_w, src.dxe, st->plan_e, grads, 1, do_gb, 0, s));
+    if (entire) RC(chain_bwd(ve, pairs, 2 * pairs, true, ip.dxe, c.ent_h, c.ent_w, src.dxe, st->plan_e, grads, 1, do_gb, 0, L_ENTIRE_CLS, s));
     if (!side_tail) RC(bookkeeping(s));
     // ---- optimizer.step() (train.py:79) over every pair's arena; Adam's step count (>= 1) and a scheduled lr are read from the device at
     // execution time
@@ -1523,7 +1648,8 @@ int splice_step_run(void* h, float* params, float* grads, float* m, float* v, co
                                             ssim_layers_salt(st) |
                                             // ... and the extended rule of the update (bits 56-59: off, or 1 + kind with the arenas it walks)
                                             (st->opt_ext_on ? (unsigned long long)(1 + st->opt_kind + 3 * ((st->opt_ext.momentum > 0.f ? 1 : 0) + 2 * (st->opt_ext.amsgrad || st->opt_ext.centered ? 1 : 0))) << 56 : 0);
-            ex = st->graphs.adopt(variant, g, salt);
+            // ... and the [CLS] layers: a 64-bit hash of the blocks and their weight bits folded over the word (another loss launch, the seed adds)
+            ex = st->graphs.adopt(variant, g, salt ^ cls_layers_salt(st));
             if (!ex) return SPLICE_ERR_HIP;
         }
         HIPCHK(hipGraphLaunch(ex, s));

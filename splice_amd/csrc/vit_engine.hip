@@ -65,6 +65,8 @@ struct SpliceVitCtx {
                                    // the attention kernels proper transpose inside LDS and need no such copy
     std::vector<bf16_t*> qkvT_extra;   // depth x [3D][rows]: the same copy of the blocks below the top that splice_vit_ctx_set_transposed_layers named
                                    // (the structure loss over their keys, selfsim.hip); null: the layer's QKV GEMM writes none, as always
+    std::vector<const float*> cls_seeds;   // depth x [B][D] fp32 or null: [CLS]-row gradient seeds of block outputs (splice_vit_ctx_set_cls_seeds),
+    int seed_p0 = 0, seed_p1 = 0;          // armed for the passes [seed_p0, seed_p1); empty: the backward launches what it always did
     std::vector<float*> lse;               // depth x [B][H][Tld]
     float* qkv_last_f32 = nullptr;         // [rows][3D]
     bf16_t* ln_out = nullptr;              // [rows][D]   transient
@@ -150,6 +152,28 @@ __global__ void grad_stream_kernel(float* g, bf16_t* g_bf, const float* add, siz
         if (add) v += add[i];
         g[i] = v;
         g_bf[i] = f2bf(v);
+    }
+}
+// [CLS]-row seeds (splice_vit_ctx_set_cls_seeds): row 0 of each of `np` passes, from pass `lo` of the range g starts at, takes
+// g += seed ; g_bf = bf16(g) -- grad_stream_kernel's arithmetic on the only row a [CLS] gradient lives on.  init (the stream is not live
+// yet): every element of the range's n_all floats is written instead, zero outside those rows.
+__global__ void cls_seed_kernel(float* g, bf16_t* g_bf, const float* seed, int D, size_t pass_floats, int lo, int np, size_t n_all, int init) {
+    if (init) {
+        for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_all; i += (size_t)gridDim.x * blockDim.x) {
+            const size_t p = i / pass_floats, r = i - p * pass_floats;
+            float v = 0.f;
+            if (r < (size_t)D && p >= (size_t)lo && p < (size_t)(lo + np)) v += seed[(p - lo) * D + r];
+            g[i] = v;
+            g_bf[i] = f2bf(v);
+        }
+        return;
+    }
+    const size_t n = (size_t)np * D;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t p = i / D, c = i - p * D, at = (lo + p) * pass_floats + c;
+        const float v = g[at] + seed[i];
+        g[at] = v;
+        g_bf[at] = f2bf(v);
     }
 }
 __global__ void scale_cols_bf16_kernel(bf16_t* x, int ld, int rows, int cols, float f) {
@@ -395,6 +419,24 @@ int splice_vit_ctx_set_transposed_layers(void* ctx, int n, const int* layers) {
         // (columns of padding tokens are written by every forward; passes a caller never runs stay finite: the loss reads them times zero)
         HIPCHK(hipMemset(c->qkvT_extra[l], 0, (size_t)c->rows * 3 * c->vit->dim * sizeof(bf16_t)));
     }
+    return SPLICE_OK;
+}
+
+// [CLS]-row gradient seeds of block outputs: seeds = [depth] device pointers, each [B][D] fp32 (row p = the gradient w.r.t. row 0 of block
+// l's output of pass p) or null, armed for the passes [pass_begin, pass_end).  A later splice_vit_backward whose range meets the armed one
+// adds, in front of block l's backward, seeds[l]'s rows into row 0 of those passes of its gradient stream -- one small launch per seeded
+// block, the arithmetic of a d_block[l] that is zero outside row 0 without its [rows][D] buffer, zeroing and add.  A backward whose range
+// the armed one does not meet, and every context without the call, launches what it always did.  The pointers are copied and read at
+// every backward until the next call; seeds == NULL (or an empty range) disarms.  The context must have been created with need_grad.
+int splice_vit_ctx_set_cls_seeds(void* ctx, const float* const* seeds, int pass_begin, int pass_end) {
+    SpliceVitCtx* c = (SpliceVitCtx*)ctx;
+    const char* who = "splice_vit_ctx_set_cls_seeds";
+    if (!c) return SPLICE_ERR_ARG;
+    if (!seeds || pass_begin == pass_end) { c->cls_seeds.clear(); c->seed_p0 = c->seed_p1 = 0; return SPLICE_OK; }
+    if (!c->need_grad) { splice_set_error("%s: the context was created without need_grad", who); return SPLICE_ERR_STATE; }
+    if (pass_begin < 0 || pass_end > c->B || pass_begin > pass_end) { splice_set_error("%s: passes [%d, %d) are not in [0, %d)", who, pass_begin, pass_end, c->B); return SPLICE_ERR_ARG; }
+    c->cls_seeds.assign(seeds, seeds + c->vit->depth);
+    c->seed_p0 = pass_begin; c->seed_p1 = pass_end;
     return SPLICE_OK;
 }
 
@@ -666,6 +708,9 @@ int splice_vit_backward(void* ctx, int pass_begin, int pass_end, const float* co
     // gradient of an image must not depend on how many images (pairs) share the backward.
     const int tiles1 = cdiv(c->Tld, 64) * cdiv(D, 64);
     const int ks = (tiles1 * 3 <= 640 && D % 192 == 0) ? 3 : (tiles1 <= 640 && D % 128 == 0) ? 2 : 1;
+    // the armed [CLS]-row seeds that fall into this range (splice_vit_ctx_set_cls_seeds); empty: no launch more
+    const int seed_lo = !c->cls_seeds.empty() && c->seed_p0 > pass_begin ? c->seed_p0 : pass_begin;
+    const int seed_hi = c->cls_seeds.empty() ? seed_lo : (c->seed_p1 < pass_end ? c->seed_p1 : pass_end);
     for (int l = L - 1; l >= 0; --l) {
         const LayerW& W = v->layers[l];
         const float* db = d_block ? d_block[l] : nullptr;
@@ -673,6 +718,12 @@ int splice_vit_backward(void* ctx, int pass_begin, int pass_end, const float* co
         const float* dk = d_keys ? d_keys[l] : nullptr;
         if (db) {
             SPLICE_LAUNCH(grad_stream_kernel, dim3(grid_n((size_t)R * D)), dim3(256), 0, s, g, g_bf, db + r0 * D, (size_t)R * D, g_live ? 0 : 1);
+            g_live = true;
+        }
+        if (seed_hi > seed_lo && c->cls_seeds[l]) {   // a [CLS]-row seed of this block's output, for the armed passes of this range
+            const int np = seed_hi - seed_lo;
+            SPLICE_LAUNCH(cls_seed_kernel, dim3(grid_n(g_live ? (size_t)np * D : (size_t)R * D)), dim3(256), 0, s, g, g_bf, c->cls_seeds[l] + (size_t)seed_lo * D, D,
+                          (size_t)c->Tld * D, seed_lo - pass_begin, np, (size_t)R * D, g_live ? 0 : 1);
             g_live = true;
         }
         if (!g_live && !dq && !dk) continue;

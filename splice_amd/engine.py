@@ -74,6 +74,12 @@ class MultiPairEngine:
             if fp8_mode(fp8):
                 raise ValueError("'dino_ssim_layers': not with fp8 -- the e4m3 Gram path of the structure term reads the top block alone")
             self.cfg.update(dino_ssim_layers=list(self.ssim_layers[0]), dino_ssim_layer_weights=list(self.ssim_layers[1]))
+        # the blocks of the two appearance terms, likewise: None -- the top block's [CLS] row, today's launches
+        self.cls_layers = cls_layers_rule(self.cfg, depth)
+        if self.cls_layers is not None:
+            if fp8_mode(fp8):
+                raise ValueError("'dino_cls_layers': not with fp8 -- the e4m3 forward is validated against the top block's [CLS] row alone")
+            self.cfg.update(dino_cls_layers=list(self.cls_layers[0]), dino_cls_layer_weights=list(self.cls_layers[1]))
         P_in = len(gen_states)
         self.cfgs = [self.cfg] * P_in
         self._pair_lambdas = self._pair_lr = False
@@ -249,6 +255,12 @@ class MultiPairEngine:
             n = len(self.ssim_layers[0])
             _lib.check(_lib.lib().splice_step_set_ssim_layers(self.handle, n, (C.c_int * n)(*self.ssim_layers[0]), (C.c_float * n)(*self.ssim_layers[1])),
                        "step_set_ssim_layers")
+        # the blocks of the appearance terms (shared by the slots): one layered launch per term, [CLS]-row seeds into the ViT backward; before
+        # the first step.  The default: the call is not made and the handle launches what it always did
+        if self.cls_layers is not None:
+            n = len(self.cls_layers[0])
+            _lib.check(_lib.lib().splice_step_set_cls_layers(self.handle, n, (C.c_int * n)(*self.cls_layers[0]), (C.c_float * n)(*self.cls_layers[1])),
+                       "step_set_cls_layers")
         self._lr_scale = [1.0] * P   # the host's copy of every slot's lr scale, refreshed with the stop steps
         self._stopped = [None] * P   # the host's copy of every slot's stop step, refreshed by stop_state()
         self._stop_dirty = False     # a window has closed since the last stop_state(): the copy may be behind
@@ -620,6 +632,34 @@ class MultiPairEngine:
             raise RuntimeError(f"ssim_layer_values: slot {pair} is parked (stop_compact): its partials left the device with its handle")
         return rows[row]
 
+    def cls_layer_values(self, pair=None, entire=False):
+        """The per-layer addends of the appearance term (``dino_cls_layers``) of the last step that computed it, copied
+        from the device (waits for the device): a float32 array with one entry per block of the canonical list, ``w_l * mse(cls_l(generated),
+        cls_l(B'))`` as the loss kernel formed it -- ``loss_global_cls`` (``entire=True``: ``loss_entire_cls``) is their float32 sum in that
+        order (``np_cls_layers``), exactly so with one crop per pair; with several crops the pair's crops are added per layer in crop order.
+        Zeros for a slot whose term never ran.  One array for ``pair``, a list over the live slots for ``pair=None``."""
+        if self.cls_layers is None:
+            raise RuntimeError("cls_layer_values: the appearance terms read the top block alone ('dino_cls_layers' is null or the default)")
+        if entire and self.plan_e is None:
+            raise RuntimeError("cls_layer_values: the engine has no entire-image branch")
+        n = len(self.cls_layers[0])
+        nc = 1 if entire or self.n_crops == 1 else min(self.n_crops_ab)
+        buf = (C.c_float * (self.P * nc * n))()
+        _lib.check(_lib.lib().splice_step_cls_layer_values(self.handle, 1 if entire else 0, buf, len(buf)), "step_cls_layer_values")
+        host = np.frombuffer(buf, dtype=np.float32).reshape(self.P, nc, n)
+        rows = []
+        for p in range(self.P):
+            acc = host[p, 0].copy()
+            for i in range(1, nc):
+                acc = (acc + host[p, i]).astype(np.float32)
+            rows.append(acc)
+        if pair is None and self.PAIR_NONE is None:
+            return rows
+        row = self._row(self.PAIR_NONE if pair is None else pair)
+        if row is None:
+            raise RuntimeError(f"cls_layer_values: slot {pair} is parked (stop_compact): its values left the device with its handle")
+        return rows[row]
+
     def active_terms(self, step_idx):
         """Per slot: which of LOSS_KEYS and IMAGE_LOSS_KEYS step ``step_idx`` computes (``engine.active_terms``; a slot's terms follow that slot's own
         lambdas).  Host arithmetic only."""
@@ -781,6 +821,9 @@ class MultiScaleEngine:
                                           "follower handles add theirs into the leader's, which would count the term once per scale")
         if ssim_layers_rule(self.cfg, vit_engine.depth if vit_engine is not None else synth.DINO_CONFIGS[self.cfg["dino_model_name"]][2]) is not None:
             raise NotImplementedError("dino_ssim_layers: the layer table is set on a whole fused step; MultiScaleEngine runs each scale as a gradient-only "
+                                      "or phase-mode handle, which refuses it")
+        if cls_layers_rule(self.cfg, vit_engine.depth if vit_engine is not None else synth.DINO_CONFIGS[self.cfg["dino_model_name"]][2]) is not None:
+            raise NotImplementedError("dino_cls_layers: the layer table is set on a whole fused step; MultiScaleEngine runs each scale as a gradient-only "
                                       "or phase-mode handle, which refuses it")
         self.ema_rule = ema_rule(self.cfg)
         self.ema = None

@@ -8,7 +8,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
-from .engine import SSIM_LAYER_KEYS, resize_output_size, ssim_layers_rule
+from .engine import CLS_LAYER_KEYS, SSIM_LAYER_KEYS, cls_layers_rule, resize_output_size, ssim_layers_rule
 from .extractor import VitExtractor
 from .synth import DINO_CONFIGS
 
@@ -96,6 +96,8 @@ class LossG(torch.nn.Module):
         # the blocks of the two structure terms (an extension beyond the reference): None -- the top block -- or the
         # canonical (layers, weights), what the fused step minimises under the same two keys
         self.ssim_layers = ssim_layers_rule({k: cfg.get(k) for k in SSIM_LAYER_KEYS}, DINO_CONFIGS[cfg['dino_model_name']][2])
+        # ... and the blocks of the two appearance terms, likewise
+        self.cls_layers = cls_layers_rule({k: cfg.get(k) for k in CLS_LAYER_KEYS}, DINO_CONFIGS[cfg['dino_model_name']][2])
         self._features = {
             "self_sim": lambda img: self.extractor.get_keys_self_sim_from_input(img, layer_num=_LAST_LAYER),
             "cls": lambda img: self.extractor.get_feature_from_input(img)[-1][0, 0, :],
@@ -135,6 +137,8 @@ class LossG(torch.nn.Module):
         """sum over crops of mse(feature(T(generated_i)), feature(T(target_i))), target side under no_grad."""
         if feature == "self_sim" and self.ssim_layers is not None:
             return self._layered_self_sim_mse(generated, targets)
+        if feature == "cls" and self.cls_layers is not None:
+            return self._layered_cls_mse(generated, targets)
         f = self._features[feature]
         acc = 0.0
         for gen_img, tgt_img in zip(generated, targets):   # one crop at a time: the extractor is batch-1
@@ -154,6 +158,21 @@ class LossG(torch.nn.Module):
                 with torch.no_grad():
                     want = self.extractor.get_keys_self_sim_from_input(tgt, layer_num=layer)
                 crop = crop + w * F.mse_loss(self.extractor.get_keys_self_sim_from_input(gen, layer_num=layer), want)
+            acc = acc + crop
+        return acc
+
+    def _layered_cls_mse(self, generated, targets):
+        """The appearance term over ``dino_cls_layers``: per crop, sum over the blocks ascending of w_l mse(cls_l(generated), cls_l(target)),
+        cls_l = the [CLS] row of block l's output."""
+        acc = 0.0
+        for gen_img, tgt_img in zip(generated, targets):
+            tgt, gen = self.global_transform(tgt_img).unsqueeze(0).to(device), self.global_transform(gen_img).unsqueeze(0).to(device)
+            with torch.no_grad():
+                want = self.extractor.get_feature_from_input(tgt)
+            got = self.extractor.get_feature_from_input(gen)
+            crop = 0.0
+            for layer, w in zip(*self.cls_layers):
+                crop = crop + w * F.mse_loss(got[layer][0, 0, :], want[layer][0, 0, :])
             acc = acc + crop
         return acc
 
