@@ -233,6 +233,13 @@ int splice_vit_ctx_set_top_cls_only(void* ctx, int on);
  * (splice_step_set_ssim_layers calls this on its contexts).  Before the context's first forward only.  splice_vit_get_tensor kind 8
  * returns the copies; a context without this call runs the launches it always ran. */
 int splice_vit_ctx_set_transposed_layers(void* ctx, int n, const int* layers);
+/* The blocks (n distinct indices in [0, depth)) below the top whose QKV projection also writes the KEY columns of its output in fp32,
+ * [rows][D] -- the values its bf16 qkv rounds -- what the key-identity loss over those blocks compares (splice_step_set_id_layers calls
+ * this on its global context).  The top block may be named and changes nothing: its fp32 keys stay columns [D, 2D) of kind 3.  Before
+ * the context's first forward only; refused on an fp8 context (which in turn refuses fp8 behind it).  splice_vit_get_tensor kind 9
+ * returns the buffers; every tensor the context wrote before keeps its bits, and a context without this call runs the launches it
+ * always ran. */
+int splice_vit_ctx_set_key_f32_layers(void* ctx, int n, const int* layers);
 /* [CLS]-row gradient seeds of block outputs: seeds = [depth] device pointers, each [B][D] fp32 (row p: the gradient w.r.t. row 0 of block
  * l's output of pass p) or NULL, armed for the passes [pass_begin, pass_end).  A later splice_vit_backward whose range meets the armed
  * one adds seeds[l]'s rows into row 0 of those passes of its gradient stream in front of block l's backward (g += seed, g_bf = bf16(g);
@@ -256,7 +263,9 @@ int splice_vit_forward_passes(void* ctx, const float* img, int normalize, int gr
 /* kind 0: block output l fp32 [rows][D] (models/extractor.py:56-60) | 1: raw qkv l bf16
  * [rows][3D] (:68-72) | 2: attention output l bf16 [rows][D] | 3: last-layer qkv fp32
  * [rows][3D] | 4: lse l fp32 [B][H][Tld] | 5: embedded tokens fp32 [rows][D] | 6: raw qkv l transposed, bf16 [3D][rows] (l = depth - 1
- * only) | 7: as 1 | 8: as 6, of the top block or a block named by splice_vit_ctx_set_transposed_layers (any other is refused).
+ * only) | 7: as 1 | 8: as 6, of the top block or a block named by splice_vit_ctx_set_transposed_layers (any other is refused) | 9: the
+ * key columns of raw qkv l in fp32, [rows][D], of a block below the top named by splice_vit_ctx_set_key_f32_layers (any other is refused;
+ * the top block's fp32 keys are columns [D, 2D) of kind 3).
  * ZERO-COPY: the pointers are the engine's own buffers, so the q columns of kinds 1 / 3 / 6 / 7 carry the factor splice_vit_qscale()
  * (a C caller that wants the reference's q divides it out, or calls splice_vit_read_tensor, whose copies of kinds 1 and 3
  * are un-scaled -- in bf16 for kind 1: one more rounding; Python's VitExtractor reads kind 7 and divides in fp32). */
@@ -883,6 +892,37 @@ int splice_step_cls_layer_values(void* step, int entire, float* out, int cap);
 int splice_cls_loss_layers(int n_layers, const float* const* x, const float* const* tgt, const float* weights, size_t x_pstride, size_t t_pstride,
                            int D, int slots, float lambda, const float* grad_tab, float* part, size_t part_pstride, float* const* seeds,
                            size_t seed_pstride, float* values, splice_stream_t stream);
+/* ------------------------------------------------------------------ the key-identity loss over several ViT blocks.
+ * With n ascending distinct block indices `layers` in [0, depth) and n finite weights > 0, the identity term of the step -- on every
+ * (y', B') crop pair, from cls_warmup on -- becomes
+ *     raw = sum over i ascending of weights[i] * mean((keys of block layers[i] of the generated crop - the target's)^2),
+ * keys = the key columns of the block's raw qkv in fp32, T * D values; reported as word 5 of the losses row and multiplied by
+ * lambda_global_identity (or the slot's own) in the total as before.  Two launches cover every named block; the key gradients reach the ViT
+ * backward of the y' chain where it always took them (d_keys[l]), the x' and entire-image chains launch what they launched.  The top block
+ * need not be named.  Before the first splice_step_run only, and behind splice_step_set_ssim_layers where both are called; refused on a
+ * handle in gradient-only or phase mode or with a leader (which in turn refuses those calls), with fp8_selfsim, and a second time.  A
+ * handle without the call launches what it always did. */
+int splice_step_set_id_layers(void* step, int n, const int* layers, const float* weights);
+/* The per-layer addends of the identity term of the last step that computed it, copied to the host behind a device-wide wait:
+ * out[s * n + i] = slot s's weights[i] times block i's mean squared key difference; the slots are the B crops, pairs * nB in pair-major
+ * order.  cap: the floats out holds (>= slots * n).  A slot's partial -- with one crop per pair the reported word -- is the float32 sum
+ * of its row, ascending, exactly; a slot that never took part reads 0. */
+int splice_step_id_layer_values(void* step, float* out, int cap);
+/* test hook: the two layered launches of the step on caller buffers.  x, tgt, grad: host arrays of n_layers (1..12) device pointers -- the
+ * first slot's T x D keys on the generated side (rows ldx[i] floats apart), on the target side (ldt[i]), and its rows of the layer's
+ * gradient buffer (ldg); slot s is x_rstride / t_rstride / g_rstride ROWS further on.  weights: host, finite, > 0.  D % 4 == 0 and every
+ * pointer and leading dimension a multiple of 16 bytes, else refused.  G = min(max_wg ? max_wg : 64, ceil(T * D / 1024)) workgroups walk a
+ * (slot, layer) grid-stride; scratch (scratch_floats >= slots * n_layers * G) takes their partials.  For slot s and layer i, with
+ * g = lambda / (float)(T * D) or grad_tab[s] (may be NULL; device, [slots]; a slot whose entry is 0 reads and writes nothing):
+ *   grad[i][(s * g_rstride + r) * ldg + c] = 2 * (g * weights[i]) * d[r][c],   d = x - tgt
+ *   scratch[(s * n_layers + i) * G + b]    = workgroup b's sum of d^2, a fixed tree
+ *   values[s * n_layers + i] = (the G partials added in index order) * (weights[i] / (float)(T * D))
+ *   part[s * part_pstride]   = the float32 sum of the slot's values, ascending from 0 (no other slot of part is written).
+ * Layer i has the bits of its own n_layers = 1 call.  Refusals launch nothing. */
+int splice_id_loss_layers(int n_layers, const float* const* x, const int* ldx, const float* const* tgt, const int* ldt, const float* weights,
+                          size_t x_rstride, size_t t_rstride, int T, int D, int slots, float lambda, const float* grad_tab, float* const* grad, int ldg,
+                          size_t g_rstride, float* scratch, size_t scratch_floats, float* values, float* part, size_t part_pstride, int max_wg,
+                          splice_stream_t stream);
 /* splice_total_loss_pairs as a handle with a loss trace launches it (splice_step_set_loss_trace): dev_t (device) holds step index + 1,
  * and words 0-5 of row step index of trace ([capacity][pairs][8], device) receive pair p's out8 values, a row at or beyond capacity
  * left out.  stop (may be NULL; device, [pairs] records) runs the instance of a handle with the stop rule, whose rule is window (>= 1),

@@ -190,6 +190,7 @@ _SIGNATURES = {
     "splice_vit_ctx_set_top_cls_only": ([_vp, _i], _i),
     "splice_vit_ctx_set_transposed_layers": ([_vp, _i, _vp], _i),
     "splice_vit_ctx_set_cls_seeds": ([_vp, _vp, _i, _i], _i),
+    "splice_vit_ctx_set_key_f32_layers": ([_vp, _i, _vp], _i),
     "splice_vit_ctx_set_fp8": ([_vp, _i], _i),
     "splice_vit_forward": ([_vp, _vp, _i, _vp], _i),
     "splice_vit_forward_ex": ([_vp, _vp, _i, _i, _vp], _i),
@@ -250,6 +251,10 @@ _SIGNATURES = {
     "splice_step_set_cls_layers": ([_vp, _i, _vp, _vp], _i),
     "splice_step_cls_layer_values": ([_vp, _i, _vp, _i], _i),
     "splice_cls_loss_layers": ([_i, _vp, _vp, _vp, _sz, _sz, _i, _i, _f, _vp, _vp, _sz, _vp, _sz, _vp, _vp], _i),
+    # the key-identity term over several ViT blocks
+    "splice_step_set_id_layers": ([_vp, _i, _vp, _vp], _i),
+    "splice_step_id_layer_values": ([_vp, _vp, _i], _i),
+    "splice_id_loss_layers": ([_i, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _i, _i, _i, _f, _vp, _vp, _i, _sz, _vp, _sz, _vp, _vp, _sz, _i, _vp], _i),
     "splice_image_terms_value": ([_vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _sz, _i, _vp], _i),
     "splice_image_terms_grad_add": ([_vp, _vp, _vp, _i, _i, _i, _f, _vp], _i),
     "splice_total_loss_pairs_img": ([_vp, _sz, _i, _f, _f, _f, _f, _f, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _f, _f, _vp], _i),

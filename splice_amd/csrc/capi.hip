@@ -205,6 +205,27 @@ int splice_cls_loss_layers(int n_layers, const float* const* x, const float* con
     }
     return finish(cls_layers_launch(tab, slots, lambda / (float)(size_t)D, grad_tab, part, part_pstride, values, (size_t)n_layers, ST(stream)), who);
 }
+/* the two layered identity launches of the step (splice_step_set_id_layers) on caller buffers */
+int splice_id_loss_layers(int n_layers, const float* const* x, const int* ldx, const float* const* tgt, const int* ldt, const float* weights,
+                          size_t x_rstride, size_t t_rstride, int T, int D, int slots, float lambda, const float* grad_tab, float* const* grad, int ldg,
+                          size_t g_rstride, float* scratch, size_t scratch_floats, float* values, float* part, size_t part_pstride, int max_wg,
+                          splice_stream_t stream) {
+    const char* who = "splice_id_loss_layers";
+    if (n_layers < 1 || n_layers > ID_MAX_LAYERS || !x || !ldx || !tgt || !ldt || !weights || !grad || !scratch || !values || !part || T < 1 || D < 4 ||
+        slots < 1 || max_wg < 0)
+        return finish(SPLICE_ERR_ARG, who);
+    const int G = id_layers_wg(T, D, max_wg);
+    if (G < 1 || scratch_floats < (size_t)slots * n_layers * G) return finish(SPLICE_ERR_ARG, who);
+    IdLayers tab = {};
+    tab.n = n_layers; tab.T = T; tab.D = D; tab.x_rs = x_rstride; tab.t_rs = t_rstride; tab.g_rs = g_rstride;
+    for (int i = 0; i < n_layers; ++i) {
+        IdLayer& e = tab.e[i];
+        e.x = x[i]; e.tgt = tgt[i]; e.grad = grad[i]; e.ldx = ldx[i]; e.ldt = ldt[i]; e.ldg = ldg; e.weight = weights[i];
+    }
+    const int rc = id_layers_launch(tab, slots, lambda / (float)((size_t)T * D), grad_tab, scratch, max_wg, ST(stream));
+    if (rc != SPLICE_OK) return finish(rc, who);
+    return finish(id_layers_finish_launch(tab, slots, grad_tab, scratch, max_wg, values, (size_t)n_layers, part, part_pstride, ST(stream)), who);
+}
 int splice_mse_pairs(const float* a, int lda, size_t a_ps, const float* b, int ldb, size_t b_ps, int rows, int cols, float loss_weight,
                      float grad_weight, float* part, size_t part_ps, float* grad, int ldg, size_t g_ps, int pairs, const float* grad_tab,
                      splice_stream_t stream) {

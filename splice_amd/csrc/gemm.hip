@@ -103,6 +103,7 @@ int gemm_nt_launch(unsigned flags, const bf16_t* A, int lda, const bf16_t* B, in
     switch (flags) {
         CASE(EPI_BIAS | EPI_OUT_BF | EPI_OUT_T);                  // qkv
         CASE(EPI_BIAS | EPI_OUT_BF | EPI_OUT_T | EPI_COLS_F32);   // qkv, layer 11 (fp32 keys too)
+        CASE(EPI_BIAS | EPI_OUT_BF | EPI_COLS_F32);               // qkv of a lower layer named for fp32 keys alone
         CASE(EPI_BIAS | EPI_OUT_F32);                             // keys-only projection
         CASE(EPI_BIAS | EPI_OUT_BF);
         CASE(EPI_BIAS | EPI_RESID | EPI_OUT_F32);                 // proj / fc2 / patch-embed

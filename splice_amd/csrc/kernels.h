@@ -179,6 +179,36 @@ struct ClsLayers {
 // takes no part (nothing of it is written).  One launch, one 256-thread workgroup per slot.
 int cls_layers_launch(const ClsLayers& tab, int slots, float g, const float* grad_tab, float* part, size_t part_ps, float* values,
                       size_t values_ps, hipStream_t s);
+// ---- id_layers.hip: the key-identity term over several ViT blocks ----
+// A by-value table, one entry per layer in ascending block order.  Slot s (a B crop) compares the T x D fp32 keys at x + s * x_rs * ldx
+// (rows ldx apart) with those at tgt + s * t_rs * ldt (rows ldt apart) and writes 2 * (g * weight) * (x - tgt) to grad + s * g_rs * ldg
+// (rows ldg apart): the slot strides are counted in ROWS, since the top block's keys sit inside [rows][3D] and a lower block's in [rows][D].
+// Every pointer and leading dimension is a multiple of 16 bytes, D of 4: the kernel moves float4s.
+#define ID_MAX_LAYERS 12
+#define ID_MAX_WG 64   // workgroups per (slot, layer) of the main launch unless the caller caps them lower
+struct IdLayer {
+    const float* x;     // keys of the first slot's generated pass: the key columns of qkv_last_f32 (ldx = 3D), or a block's [rows][D] fp32 key buffer
+    const float* tgt;   // the same of its target pass
+    float* grad;        // the first slot's rows of the block's key-gradient buffer
+    int ldx, ldt, ldg;
+    float weight;
+};
+struct IdLayers {
+    int n, T, D;
+    size_t x_rs, t_rs, g_rs;   // rows between consecutive slots on the generated, the target and the gradient side
+    IdLayer e[ID_MAX_LAYERS];
+};
+// Workgroups per (slot, layer): one per 256 float4s of a slot's T * D keys, at most max_wg (0: ID_MAX_WG) -- a function of one slot's
+// size alone, never of the batch.
+int id_layers_wg(int T, int D, int max_wg);
+// The main launch, grid (G, slots, n): workgroup b of (slot, layer) writes its fixed-tree sum of d^2 to scratch[(slot * n + layer) * G + b].
+// g: the gradient weight of the plain path, lambda / (float)(T * D); grad_tab (optional, [slots]): the slot's own, a slot whose entry is
+// 0 takes no part (nothing of it is read or written, in either launch).  Refuses a table that is not 16-byte aligned throughout.
+int id_layers_launch(const IdLayers& tab, int slots, float g, const float* grad_tab, float* scratch, int max_wg, hipStream_t s);
+// The finish launch, one wave per slot: values[s * values_ps + i] = (layer i's G partials added in index order) * (weight_i / (float)(T * D)),
+// part[s * part_ps] = the fp32 sum of the slot's values, ascending from 0.
+int id_layers_finish_launch(const IdLayers& tab, int slots, const float* grad_tab, const float* scratch, int max_wg, float* values,
+                            size_t values_ps, float* part, size_t part_ps, hipStream_t s);
 // 2-D strided MSE: loss_accum[0] += weight * mean((a-b)^2); grad (optional) = weight * 2 (a-b) / (rows*cols)
 int mse_launch(const float* a, int lda, const float* b, int ldb, int rows, int cols, float weight, float* loss_accum,
                float* grad, int ldg, hipStream_t s);

@@ -50,6 +50,12 @@ struct VitView {
     float* cls_seed[CLS_MAX_LAYERS] = {};
     std::vector<const float*> cls_seed_tab;
     float* cls_values = nullptr;
+    // splice_step_set_id_layers (global view only): the key-gradient buffer of entry i of the identity list -- d_keys for the top block, the
+    // structure list's buffer of a block both lists name, else one of its own (then also in dk_id_own: its y' passes are zeroed each step) --
+    // and the y' chain's key-gradient table: pk plus the identity blocks
+    float* dk_id[ID_MAX_LAYERS] = {};
+    float* dk_id_own[ID_MAX_LAYERS] = {};
+    std::vector<const float*> pk_y;
 };
 
 struct SpliceStep {
@@ -178,6 +184,13 @@ struct SpliceStep {
     int n_cls_layers = 0;
     int cls_layers[CLS_MAX_LAYERS] = {};
     float cls_weights[CLS_MAX_LAYERS] = {};
+    // the blocks whose keys the identity term reads (splice_step_set_id_layers): ascending block indices and their
+    // weights; 0 entries: off -- the top block alone, the step launches what it always did.  id_scratch: the workgroup partials of the term's
+    // main launch, [Pb][n][G]; id_values: the per-layer addends, [Pb][n]
+    int n_id_layers = 0;
+    int id_layers[ID_MAX_LAYERS] = {};
+    float id_weights[ID_MAX_LAYERS] = {};
+    float *id_scratch = nullptr, *id_values = nullptr;
 };
 
 static size_t arena_floats(const SpliceStep* st) { return st->astride ? st->pairs * st->astride : (size_t)st->nparams; }   // of all pairs' arenas
@@ -572,6 +585,31 @@ static int cls_table(SpliceStep* st, VitView& vx, int pass_x, int x_step, int pa
     return SPLICE_OK;
 }
 
+// The identity term over the handle's identity layers (splice_step_set_id_layers): the table of its two launches.  Generated keys: the y'
+// passes pass_y, pass_y + 1, ... of the global view; targets: its B' passes from pass_b on.  The top block's entry points into the key
+// columns of qkv_last_f32 (ld 3D) and d_keys, as the plain path does; a lower block's into its [rows][D] fp32 key buffer and its
+// key-gradient buffer.
+static int id_table(SpliceStep* st, int pass_y, int pass_b, IdLayers* tab) {
+    VitView& v = st->vg;
+    tab->n = st->n_id_layers; tab->T = v.T; tab->D = v.D;
+    tab->x_rs = tab->t_rs = tab->g_rs = (size_t)v.Tld;
+    for (int i = 0; i < tab->n; ++i) {
+        const int l = st->id_layers[i];
+        IdLayer& e = tab->e[i];
+        float* k = nullptr;
+        if (l == v.depth - 1) {
+            RC(splice_vit_get_tensor(v.ctx, 3, l, (void**)&k));
+            e.x = keys_ptr(v, k, pass_y); e.tgt = keys_ptr(v, k, pass_b); e.ldx = e.ldt = 3 * v.D;
+        } else {
+            RC(splice_vit_get_tensor(v.ctx, 9, l, (void**)&k));
+            e.x = k + (size_t)pass_y * v.Tld * v.D; e.tgt = k + (size_t)pass_b * v.Tld * v.D; e.ldx = e.ldt = v.D;
+        }
+        e.grad = v.dk_id[i] + (size_t)pass_y * v.Tld * v.D; e.ldg = v.D;
+        e.weight = st->id_weights[i];
+    }
+    return SPLICE_OK;
+}
+
 extern "C" {
 
 int splice_step_create(const splice_step_config* cfg, void* vit_ctx_global, void* vit_ctx_entire, void* gen_plan_a, void* gen_plan_b,
@@ -715,7 +753,8 @@ static const char* whole_step_rule(const SpliceStep* st) {
     return st->stop_rule.window > 0 ? "with a stop rule" : st->ema ? "with a weight average" : st->clip ? "with gradient clipping"
            : st->best ? "that keeps the best weights" : st->trace ? "with a loss trace"
            : (st->lambda_tv > 0.f || st->lambda_pix > 0.f) ? "with image-space loss terms"
-           : st->n_ssim_layers > 0 ? "with structure layers" : st->n_cls_layers > 0 ? "with [CLS] layers" : nullptr;
+           : st->n_ssim_layers > 0 ? "with structure layers" : st->n_cls_layers > 0 ? "with [CLS] layers"
+           : st->n_id_layers > 0 ? "with identity layers" : nullptr;
 }
 // The shared opening of the rule setters below: before the first step only (`what` of the rule, for the error text), and not on a
 // gradient-only or phase-mode handle.  Callers return its code plainly, not through RC(): the message stays the last error.
@@ -1025,6 +1064,7 @@ int splice_step_set_ssim_layers(void* h, int n, const int* layers, const float* 
     if (int rc = rule_setter_ok(st, who, "the layers are set")) return rc;
     if (st->cfg.fp8_selfsim) { splice_set_error("%s: not with fp8_selfsim (the e4m3 Gram path reads the top block alone)", who); return SPLICE_ERR_STATE; }
     if (st->n_ssim_layers) { splice_set_error("%s: the layers are set once", who); return SPLICE_ERR_STATE; }
+    if (st->n_id_layers) { splice_set_error("%s: call it in front of splice_step_set_id_layers (the identity term shares this list's key-gradient buffers)", who); return SPLICE_ERR_STATE; }
     const int Tmax = st->plan_e && st->ve.T > st->vg.T ? st->ve.T : st->vg.T;
     for (VitView* v : {&st->vg, &st->ve}) {
         if (!v->ctx) continue;
@@ -1138,6 +1178,81 @@ int splice_step_cls_layer_values(void* h, int entire, float* out, int cap) {
     if (cap < slots * st->n_cls_layers) { splice_set_error("%s: out holds %d floats, needs %d", who, cap, slots * st->n_cls_layers); return SPLICE_ERR_ARG; }
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(out, entire ? st->ve.cls_values : st->vg.cls_values, (size_t)slots * st->n_cls_layers * sizeof(float), hipMemcpyDeviceToHost));
+    return SPLICE_OK;
+}
+static unsigned long long id_layers_salt(const SpliceStep* st) {
+    if (!st->n_id_layers) return 0;
+    unsigned long long h = 1469598103934665603ull ^ 0x9e3779b97f4a7c15ull;   // FNV-1a over (block, weight bits) in list order, from a basis of its own
+    for (int i = 0; i < st->n_id_layers; ++i) {
+        unsigned w;
+        memcpy(&w, &st->id_weights[i], sizeof(w));
+        for (unsigned long long v : {(unsigned long long)st->id_layers[i], (unsigned long long)w})
+            for (int k = 0; k < 8; ++k) { h ^= (v >> (8 * k)) & 0xff; h *= 1099511628211ull; }
+    }
+    return h | 2ull;   // (never 0: a handle with layers is never keyed like one without)
+}
+// The blocks whose keys the identity term reads, and their weights (include/splice_hip.h has the term): n ascending distinct block indices,
+// n finite weights > 0.  Two launches then cover every named block (id_layers.hip) in place of the term's mse_batched_launch; the global
+// ViT context writes the fp32 keys of each named block below the top (splice_vit_ctx_set_key_f32_layers).  Key-gradient buffers are per
+// BLOCK: the top block's is d_keys, a block the structure list names too shares that list's buffer -- the structure term writes its x'
+// passes, this term its y' passes, the way d_keys is shared at the top -- and any other block gets one of its own, zeroed here (padding rows
+// read as zero gradient for good) and over its y' passes at every step (DESIGN.md section 9m says why).  The y' chain's backward reads
+// pk_y = pk + the identity blocks; the x' chain and the entire-image chain keep pk, so a block named only here adds no launch to them.
+// Before the first step only; not on a gradient-only or phase-mode handle (which in turn refuses those calls); not with fp8_selfsim; not
+// a second time; and behind splice_step_set_ssim_layers where both are called, so that the shared buffers exist.
+int splice_step_set_id_layers(void* h, int n, const int* layers, const float* weights) {
+    SpliceStep* st = (SpliceStep*)h;
+    const char* who = "splice_step_set_id_layers";
+    if (!st || !layers || !weights) return SPLICE_ERR_ARG;
+    VitView& v = st->vg;
+    const int depth = v.depth;
+    if (n < 1 || n > depth || n > ID_MAX_LAYERS) { splice_set_error("%s: needs 1..%d layers, got %d", who, depth < ID_MAX_LAYERS ? depth : ID_MAX_LAYERS, n); return SPLICE_ERR_ARG; }
+    for (int i = 0; i < n; ++i) {
+        if (layers[i] < 0 || layers[i] >= depth || (i > 0 && layers[i] <= layers[i - 1])) {
+            splice_set_error("%s: layers must be ascending distinct block indices in [0, %d), got layers[%d] = %d", who, depth, i, layers[i]);
+            return SPLICE_ERR_ARG;
+        }
+        if (!(weights[i] > 0.f) || !(weights[i] <= 3.402823466e+38f)) {
+            splice_set_error("%s: weights must be finite and > 0, got weights[%d] = %g", who, i, (double)weights[i]);
+            return SPLICE_ERR_ARG;
+        }
+    }
+    if (int rc = rule_setter_ok(st, who, "the layers are set")) return rc;
+    if (st->cfg.fp8_selfsim) { splice_set_error("%s: not with fp8 (the e4m3 forward keeps fp32 keys of the top block alone)", who); return SPLICE_ERR_STATE; }
+    if (st->n_id_layers) { splice_set_error("%s: the layers are set once", who); return SPLICE_ERR_STATE; }
+    if (v.D % 4) { splice_set_error("%s: needs an embedding width that is a multiple of 4, got %d", who, v.D); return SPLICE_ERR_ARG; }
+    RC(splice_vit_ctx_set_key_f32_layers(v.ctx, n, layers));
+    v.pk_y = v.pk;
+    for (int i = 0; i < n; ++i) {
+        const int l = layers[i];
+        if (v.pk[l]) { v.dk_id[i] = const_cast<float*>(v.pk[l]); continue; }   // the top block (d_keys), or a block of the structure list
+        RC(salloc(st, &v.dk_id_own[i], (size_t)v.rows * v.D));
+        HIPCHK(hipMemset(v.dk_id_own[i], 0, (size_t)v.rows * v.D * sizeof(float)));
+        v.dk_id[i] = v.dk_id_own[i];
+        v.pk_y[l] = v.dk_id[i];
+    }
+    const int G = id_layers_wg(v.T, v.D, 0);
+    RC(salloc(st, &st->id_scratch, (size_t)st->Pb * n * G));
+    RC(salloc(st, &st->id_values, (size_t)st->Pb * n));
+    HIPCHK(hipMemset(st->id_scratch, 0, (size_t)st->Pb * n * G * sizeof(float)));
+    HIPCHK(hipMemset(st->id_values, 0, (size_t)st->Pb * n * sizeof(float)));
+    st->graphs.retire();
+    st->n_id_layers = n;
+    for (int i = 0; i < n; ++i) { st->id_layers[i] = layers[i]; st->id_weights[i] = weights[i]; }
+    return SPLICE_OK;
+}
+// The per-layer addends of the identity term (loss_global_id_B, word 5) of the last step that computed it, copied to the HOST behind a
+// device-wide wait: out[s * n + i] = slot s's w_i * mse of block i's keys, n the layer count; the slots are the B crops, pairs * nB of
+// them in pair-major order.  cap: floats `out` holds.  A slot's partial -- with one crop per pair the reported word -- is the float32 sum
+// of its row, ascending, exactly; a slot that never took part reads zeros.
+int splice_step_id_layer_values(void* h, float* out, int cap) {
+    SpliceStep* st = (SpliceStep*)h;
+    const char* who = "splice_step_id_layer_values";
+    if (!st || !out) { splice_set_error("%s: needs a handle and out", who); return SPLICE_ERR_ARG; }
+    if (!st->n_id_layers) { splice_set_error("%s: the handle has no identity layers (splice_step_set_id_layers)", who); return SPLICE_ERR_STATE; }
+    if (cap < st->Pb * st->n_id_layers) { splice_set_error("%s: out holds %d floats, needs %d", who, cap, st->Pb * st->n_id_layers); return SPLICE_ERR_ARG; }
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, st->id_values, (size_t)st->Pb * st->n_id_layers * sizeof(float), hipMemcpyDeviceToHost));
     return SPLICE_OK;
 }
 // Start the handle at step next_step_idx of a run other handles carried so far (a resumed run, a compacted engine; DESIGN.md section
@@ -1311,13 +1426,15 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
     // the chain's generated images [h][w], added to the leader's d_lead by a follower; then (`gen`) the generator backward of `plan` into `arena`.
     // `img_term` (L_GLOBAL_TV on the x' chain, L_GLOBAL_PIX on the y' chain, 0 on the entire-image chain): with that term's weight > 0 its
     // gradient is added into d_img in place, one launch, from the chain's saved generator output.
+    // `pk`: the chain's key-gradient table -- the view's, or on the y' chain of a step whose identity term ran over named blocks that table plus
+    // those blocks (pk_y).
     // `cls_term` ([CLS] layers only; L_GLOBAL_CLS on the x' chain, L_ENTIRE_CLS on the entire-image chain, 0 on the y' chain): the chain's passes
     // are armed with the view's seed buffers when that term ran this step, and disarmed otherwise -- a chain without seeds gains no launch.
     auto chain_bwd = [&](VitView& vw, int p0, int p1, bool vit, float* d_img, int h, int w, float* d_lead, void* plan, float* arena, int accumulate,
-                         bool gen, int img_term, int cls_term, hipStream_t q) -> int {
+                         bool gen, int img_term, int cls_term, const std::vector<const float*>& pk, hipStream_t q) -> int {
         if (do_v) {
             if (vit && st->n_cls_layers) RC(splice_vit_ctx_set_cls_seeds(vw.ctx, cls_term && t[cls_term].on ? vw.cls_seed_tab.data() : nullptr, p0, p1));
-            if (vit) RC(splice_vit_backward(vw.ctx, p0, p1, vw.pb.data(), nullptr, vw.pk.data(), vw.d_imgs, 1, q));
+            if (vit) RC(splice_vit_backward(vw.ctx, p0, p1, vw.pb.data(), nullptr, pk.data(), vw.d_imgs, 1, q));
             RC(unplace_grads(vw.d_imgs + (size_t)p0 * 3 * vw.H * vw.W, vw.H, vw.W, d_img, h, w, p1 - p0, q));
             if (st->leader) RC(add_f32_launch(d_lead, d_img, (size_t)(p1 - p0) * 3 * h * w, q));
             if (img_term == L_GLOBAL_TV && st->lambda_tv > 0.f) RC(image_tv_grad_add_launch(ip.x, d_img, p1 - p0, h, w, st->lambda_tv, q));
@@ -1351,6 +1468,8 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
     // structure layers (splice_step_set_ssim_layers): the tables of the two views' launches; null: the top block alone, the plain launches
     SelfSimLayers sl = {}, sle = {};
     const bool layered = st->n_ssim_layers > 0;
+    IdLayers idt = {};   // identity layers (splice_step_set_id_layers): the table of the term's two launches
+    const bool id_layered = do_v && t[L_GLOBAL_ID].on && st->n_id_layers > 0;
     if (do_v) {
         RC(place_passes(vg, src.a_in, c.crop_h, c.crop_w, pA, Pa, s2));
         RC(place_passes(vg, src.b_in, st->cropb_h, st->cropb_w, pB, Pb, s2));
@@ -1358,6 +1477,8 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
         // everything of the loss stage that does not need the generated images also runs here, off the critical path
         RC(dev_zero_launch(st->losses, (size_t)P * st->lstride * sizeof(float), s2));
         RC(zero_seeds(vg, pX, Pa + Pb, s2));
+        for (float* dk : vg.dk_id_own)   // the blocks only the identity list names: their y' passes alone (no x' chain reads them)
+            if (dk) RC(dev_zero_launch(dk + pY * passD, Pb * passD * sizeof(float), s2));
         if (t[L_GLOBAL_SSIM].on) {   // target self-similarity S* of A' (util/losses.py:79)
             RC(ssim_batch(st, vg, pA, pX, Pa, t[L_GLOBAL_SSIM], L_GLOBAL_SSIM, &sb, layered ? &sl : nullptr));
             RC(selfsim_target_launch(sb, s2, layered ? &sl : nullptr));
@@ -1405,7 +1526,10 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
                                       loss_part(st, L_GLOBAL_CLS), st->lstride, vg.d_block + pX * passD, vg.D, passD, Pc, s, t[L_GLOBAL_CLS].tab));
             }
         }
-        if (t[L_GLOBAL_ID].on)    // keys of y' against keys of B' (util/losses.py:96-105): mean over h*T*d = T*D
+        if (t[L_GLOBAL_ID].on && st->n_id_layers) {   // keys of the named blocks: one launch for all of them; its finish launch rides in bookkeeping
+            RC(id_table(st, pY, pB, &idt));
+            RC(id_layers_launch(idt, Pb, t[L_GLOBAL_ID].lambda / (float)((size_t)vg.T * vg.D), t[L_GLOBAL_ID].tab, st->id_scratch, 0, s));
+        } else if (t[L_GLOBAL_ID].on)    // keys of y' against keys of B' (util/losses.py:96-105): mean over h*T*d = T*D
             RC(mse_batched_launch(keys_ptr(vg, qkv_g, pY), 3 * vg.D, 3 * passD, keys_ptr(vg, qkv_g, pB), 3 * vg.D, 3 * passD, vg.T, vg.D, 1.0f, t[L_GLOBAL_ID].lambda,
                                   loss_part(st, L_GLOBAL_ID), st->lstride, vg.d_keys + pY * passD, vg.D, passD, Pb, s, t[L_GLOBAL_ID].tab));
         // the image-space terms, at the crops' own resolution: image i's partials into terms 6 / 7 of slot i, every step (no schedule)
@@ -1452,6 +1576,10 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
             const int n1 = st->crops_mode ? P : 1;
             // (the rule and the trace ride in the launch: no node more)
             const bool lrp = st->lr_state != nullptr, trc = st->trace != nullptr;
+            // the identity layers' finish launch: the slots' addends, and their sum into partial slot 0 of the term's zeroed row
+            if (id_layered)
+                RC(id_layers_finish_launch(idt, Pb, t[L_GLOBAL_ID].tab, st->id_scratch, 0, st->id_values, (size_t)st->n_id_layers, loss_part(st, L_GLOBAL_ID),
+                                           st->lstride, q));
             const auto kernel = layered ? (img_on ? total_loss_instance<true, true>(lrp, trc, stop_on) : total_loss_instance<false, true>(lrp, trc, stop_on))
                                         : (img_on ? total_loss_instance<true>(lrp, trc, stop_on) : total_loss_instance<false>(lrp, trc, stop_on));
             SPLICE_LAUNCH(kernel, dim3(pairs), dim3(img_on ? 448 : 320), 0, q, st->losses, st->lstride, (int)st->lp, t[L_GLOBAL_SSIM].lambda, t[L_ENTIRE_SSIM].lambda,
@@ -1477,12 +1605,12 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
             HIPCHK(hipEventRecord(st->ev(SpliceStep::EV_FORK2), s));
             HIPCHK(hipStreamWaitEvent(s2, st->ev(SpliceStep::EV_FORK2), 0));
         }
-        RC(chain_bwd(vg, pY, pEnd, !(st->ablate & 32), ip.dy, st->cropb_h, st->cropb_w, src.dy, st->plan_b, st->grads_b, 0, gen_bwd, L_GLOBAL_PIX, 0, s2));
+        RC(chain_bwd(vg, pY, pEnd, !(st->ablate & 32), ip.dy, st->cropb_h, st->cropb_w, src.dy, st->plan_b, st->grads_b, 0, gen_bwd, L_GLOBAL_PIX, 0, id_layered ? vg.pk_y : vg.pk, s2));
         if (side_tail) {
             RC(bookkeeping(s2));
             HIPCHK(hipEventRecord(st->ev(SpliceStep::EV_JOIN2), s2));
         }
-        RC(chain_bwd(vg, pX, pY, true, ip.dx, c.crop_h, c.crop_w, src.dx, st->plan_a, grads, st->accumulate, gen_bwd, L_GLOBAL_TV, L_GLOBAL_CLS, s));
+        RC(chain_bwd(vg, pX, pY, true, ip.dx, c.crop_h, c.crop_w, src.dx, st->plan_a, grads, st->accumulate, gen_bwd, L_GLOBAL_TV, L_GLOBAL_CLS, vg.pk, s));
         if (overlap) HIPCHK(hipStreamWaitEvent(s, st->ev(SpliceStep::EV_JOIN2), 0));
         // grads = g(A) + g(B): folded into the Adam kernel on ordinary steps; a separate add when the entire-image branch
         // still has to accumulate into the sum (same association order either way)
@@ -1491,7 +1619,7 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
             else adam_g2 = st->grads_b;
         }
     }
-    if (entire) RC(chain_bwd(ve, pairs, 2 * pairs, true, ip.dxe, c.ent_h, c.ent_w, src.dxe, st->plan_e, grads, 1, do_gb, 0, L_ENTIRE_CLS, s));
+    if (entire) RC(chain_bwd(ve, pairs, 2 * pairs, true, ip.dxe, c.ent_h, c.ent_w, src.dxe, st->plan_e, grads, 1, do_gb, 0, L_ENTIRE_CLS, ve.pk, s));
     if (!side_tail) RC(bookkeeping(s));
     // ---- optimizer.step() (train.py:79) over every pair's arena; Adam's step count (>= 1) and a scheduled lr are read from the device at
     // execution time
@@ -1649,7 +1777,8 @@ int splice_step_run(void* h, float* params, float* grads, float* m, float* v, co
                                             // ... and the extended rule of the update (bits 56-59: off, or 1 + kind with the arenas it walks)
                                             (st->opt_ext_on ? (unsigned long long)(1 + st->opt_kind + 3 * ((st->opt_ext.momentum > 0.f ? 1 : 0) + 2 * (st->opt_ext.amsgrad || st->opt_ext.centered ? 1 : 0))) << 56 : 0);
             // ... and the [CLS] layers: a 64-bit hash of the blocks and their weight bits folded over the word (another loss launch, the seed adds)
-            ex = st->graphs.adopt(variant, g, salt ^ cls_layers_salt(st));
+            // ... and the identity layers, likewise (two other loss launches, the key-gradient tables of the y' chain, a zeroing launch per own block)
+            ex = st->graphs.adopt(variant, g, salt ^ cls_layers_salt(st) ^ id_layers_salt(st));
             if (!ex) return SPLICE_ERR_HIP;
         }
         HIPCHK(hipGraphLaunch(ex, s));

@@ -65,7 +65,10 @@ struct SpliceVitCtx {
                                    // the attention kernels proper transpose inside LDS and need no such copy
     std::vector<bf16_t*> qkvT_extra;   // depth x [3D][rows]: the same copy of the blocks below the top that splice_vit_ctx_set_transposed_layers named
                                    // (the structure loss over their keys, selfsim.hip); null: the layer's QKV GEMM writes none, as always
+    std::vector<float*> keys_f32_extra;   // depth x [rows][D] fp32: the key columns of the raw qkv of the blocks below the top that splice_vit_ctx_set_key_f32_layers
+                                   // named (the key-identity loss over those blocks, id_layers.hip); null: the layer's QKV GEMM writes none, as always
     std::vector<const float*> cls_seeds;   // depth x [B][D] fp32 or null: [CLS]-row gradient seeds of block outputs (splice_vit_ctx_set_cls_seeds),
+    bool key_f32_named = false;            // splice_vit_ctx_set_key_f32_layers was called: the context stays bf16
     int seed_p0 = 0, seed_p1 = 0;          // armed for the passes [seed_p0, seed_p1); empty: the backward launches what it always did
     std::vector<float*> lse;               // depth x [B][H][Tld]
     float* qkv_last_f32 = nullptr;         // [rows][3D]
@@ -334,7 +337,7 @@ int splice_vit_ctx_create(void* h, int B, int H, int W, const float* pos_TD, int
     A(c->pos_eff, (size_t)c->Tld * D);
     A(c->patches, rows * pp3);
     c->xs.resize(L + 1); c->xmid.resize(L); c->mean1.resize(L); c->rstd1.resize(L); c->mean2.resize(L); c->rstd2.resize(L);
-    c->qkv.resize(L); c->attn_out.resize(L); c->hpre.resize(L); c->lse.resize(L); c->qkvT_extra.assign(L, nullptr);
+    c->qkv.resize(L); c->attn_out.resize(L); c->hpre.resize(L); c->lse.resize(L); c->qkvT_extra.assign(L, nullptr); c->keys_f32_extra.assign(L, nullptr);
     for (int l = 0; l <= L; ++l) A(c->xs[l], rows * D);
     for (int l = 0; l < L; ++l) {
         A(c->xmid[l], rows * D);
@@ -422,6 +425,35 @@ int splice_vit_ctx_set_transposed_layers(void* ctx, int n, const int* layers) {
     return SPLICE_OK;
 }
 
+// The blocks below the top whose QKV projection also writes the key columns of its output in fp32, [rows][D] -- the values its bf16 qkv
+// rounds, through the column-range epilogue the top block's always uses (there into qkv_last_f32, which stays what it is) -- what the
+// key-identity loss over those blocks compares (id_layers.hip).  The top block may be named and changes nothing.  Before the context's
+// first forward only, and not on an fp8 context (no e4m3 instance carries the column range below the top).  The buffers are zeroed
+// once: passes a caller never runs and padding rows a forward never reaches stay finite.  Tensor kind 9 returns them.
+int splice_vit_ctx_set_key_f32_layers(void* ctx, int n, const int* layers) {
+    SpliceVitCtx* c = (SpliceVitCtx*)ctx;
+    const char* who = "splice_vit_ctx_set_key_f32_layers";
+    if (!c || !layers || n < 1 || n > c->vit->depth) { splice_set_error("%s: needs a context and 1..depth layers", who); return SPLICE_ERR_ARG; }
+    if (c->forward_done) { splice_set_error("%s: the layers are named before the context's first forward", who); return SPLICE_ERR_STATE; }
+    if (c->fp8) { splice_set_error("%s: not on an fp8 context (its QKV projections keep fp32 keys of the top block alone)", who); return SPLICE_ERR_STATE; }
+    for (int i = 0; i < n; ++i) {
+        bool dup = false;
+        for (int j = 0; j < i; ++j) dup |= layers[j] == layers[i];
+        if (layers[i] < 0 || layers[i] >= c->vit->depth || dup) {
+            splice_set_error("%s: layers must be distinct and in [0, %d), got layers[%d] = %d", who, c->vit->depth, i, layers[i]);
+            return SPLICE_ERR_ARG;
+        }
+    }
+    for (int i = 0; i < n; ++i) {
+        const int l = layers[i];
+        if (l == c->vit->depth - 1 || c->keys_f32_extra[l]) continue;
+        RC(dev_alloc(c->allocs, &c->keys_f32_extra[l], (size_t)c->rows * c->vit->dim));
+        HIPCHK(hipMemset(c->keys_f32_extra[l], 0, (size_t)c->rows * c->vit->dim * sizeof(float)));
+    }
+    c->key_f32_named = true;
+    return SPLICE_OK;
+}
+
 // [CLS]-row gradient seeds of block outputs: seeds = [depth] device pointers, each [B][D] fp32 (row p = the gradient w.r.t. row 0 of block
 // l's output of pass p) or null, armed for the passes [pass_begin, pass_end).  A later splice_vit_backward whose range meets the armed one
 // adds, in front of block l's backward, seeds[l]'s rows into row 0 of those passes of its gradient stream -- one small launch per seeded
@@ -447,6 +479,7 @@ int splice_vit_ctx_set_fp8(void* ctx, int mode) {
     SpliceVitCtx* c = (SpliceVitCtx*)ctx;
     if (!c || mode < 0 || mode > 3 || mode == 2) return SPLICE_ERR_ARG;
     if (mode && !c->vit->fp8) { splice_set_error("splice_vit_ctx_set_fp8: the engine has no e4m3 weights (splice_vit_enable_fp8 first)"); return SPLICE_ERR_STATE; }
+    if (mode && c->key_f32_named) { splice_set_error("splice_vit_ctx_set_fp8: not on a context with fp32 key layers (splice_vit_ctx_set_key_f32_layers)"); return SPLICE_ERR_STATE; }
     const size_t rows = c->rows;
     if (mode && !c->ln_out8) {
         RC(dev_alloc(c->allocs, &c->ln_out8, rows * c->vit->dim));
@@ -532,6 +565,10 @@ int splice_vit_forward_passes(void* ctx, const float* img, int normalize, int gr
             } else if (c->qkvT_extra[l]) {   // a named layer: the same transposed copy, into its own buffer
                 fl |= EPI_OUT_T;
                 e.out_bf_t = c->qkvT_extra[l] + r0; e.ldt = c->rows;
+            }
+            if (l != L - 1 && c->keys_f32_extra[l]) {   // a layer named for fp32 keys: the key columns of the same values, into its own [rows][D] buffer
+                fl |= EPI_COLS_F32;
+                e.out_f32_cols = c->keys_f32_extra[l] + r0 * D; e.ld_cols = D; e.col_lo = D; e.col_hi = 2 * D;
             }
             SpliceProfScope ps(l == L - 1 ? 0 : 2); SPLICE_DEV_REGION(2);
             if (fp8) {   // e4m3 LayerNorm output (per-token scale) x e4m3 weights (per-channel scale) on the fp8 MFMA
@@ -643,6 +680,8 @@ int splice_vit_forward_passes(void* ctx, const float* img, int normalize, int gr
 // kind 5: embedded tokens fp32 [rows][D]
 // kind 6: raw qkv l, transposed  bf16 [3D][rows]   (row = feature, column = pass * Tld + token)
 // kind 8: the same of a layer named by splice_vit_ctx_set_transposed_layers (kind 6 serves the top block alone, as before)
+// kind 9: fp32 keys l  fp32 [rows][D]  of a layer below the top named by splice_vit_ctx_set_key_f32_layers (the top block's are columns
+//         [D, 2D) of kind 3)
 int splice_vit_get_tensor(void* ctx, int kind, int layer, void** out) {
     SpliceVitCtx* c = (SpliceVitCtx*)ctx;
     if (!c || !out || layer < 0 || layer >= c->vit->depth) return SPLICE_ERR_ARG;
@@ -658,6 +697,10 @@ int splice_vit_get_tensor(void* ctx, int kind, int layer, void** out) {
         case 8:   // as kind 6, of a layer splice_vit_ctx_set_transposed_layers named (the top block: its own copy, always there)
             *out = layer == c->vit->depth - 1 ? c->qkvT_last : c->qkvT_extra[layer];
             if (!*out) { splice_set_error("splice_vit_get_tensor: layer %d keeps no transposed qkv copy (splice_vit_ctx_set_transposed_layers)", layer); return SPLICE_ERR_ARG; }
+            break;
+        case 9:   // the fp32 keys of a layer splice_vit_ctx_set_key_f32_layers named (the top block keeps them inside kind 3: refused here)
+            *out = c->keys_f32_extra[layer];
+            if (!*out) { splice_set_error("splice_vit_get_tensor: layer %d keeps no fp32 key buffer (splice_vit_ctx_set_key_f32_layers; the top block's keys are in kind 3)", layer); return SPLICE_ERR_ARG; }
             break;
         default: return SPLICE_ERR_ARG;
     }

@@ -80,6 +80,12 @@ class MultiPairEngine:
             if fp8_mode(fp8):
                 raise ValueError("'dino_cls_layers': not with fp8 -- the e4m3 forward is validated against the top block's [CLS] row alone")
             self.cfg.update(dino_cls_layers=list(self.cls_layers[0]), dino_cls_layer_weights=list(self.cls_layers[1]))
+        # the blocks of the key-identity term, likewise: None -- the top block's keys, today's launches
+        self.id_layers = id_layers_rule(self.cfg, depth)
+        if self.id_layers is not None:
+            if fp8_mode(fp8):
+                raise ValueError("'dino_id_layers': not with fp8 -- the e4m3 forward keeps fp32 keys of the top block alone")
+            self.cfg.update(dino_id_layers=list(self.id_layers[0]), dino_id_layer_weights=list(self.id_layers[1]))
         P_in = len(gen_states)
         self.cfgs = [self.cfg] * P_in
         self._pair_lambdas = self._pair_lr = False
@@ -261,6 +267,12 @@ class MultiPairEngine:
             n = len(self.cls_layers[0])
             _lib.check(_lib.lib().splice_step_set_cls_layers(self.handle, n, (C.c_int * n)(*self.cls_layers[0]), (C.c_float * n)(*self.cls_layers[1])),
                        "step_set_cls_layers")
+        # the blocks of the identity term (shared by the slots): two layered launches, fp32 keys and key gradients of the named blocks on the
+        # y' chain; before the first step, behind the structure layers (shared buffers).  The default: the call is not made
+        if self.id_layers is not None:
+            n = len(self.id_layers[0])
+            _lib.check(_lib.lib().splice_step_set_id_layers(self.handle, n, (C.c_int * n)(*self.id_layers[0]), (C.c_float * n)(*self.id_layers[1])),
+                       "step_set_id_layers")
         self._lr_scale = [1.0] * P   # the host's copy of every slot's lr scale, refreshed with the stop steps
         self._stopped = [None] * P   # the host's copy of every slot's stop step, refreshed by stop_state()
         self._stop_dirty = False     # a window has closed since the last stop_state(): the copy may be behind
@@ -660,6 +672,32 @@ class MultiPairEngine:
             raise RuntimeError(f"cls_layer_values: slot {pair} is parked (stop_compact): its values left the device with its handle")
         return rows[row]
 
+    def id_layer_values(self, pair=None):
+        """The per-layer addends of the key-identity term (``dino_id_layers``) of the last step that computed it, copied
+        from the device (waits for the device): a float32 array with one entry per block of the canonical list, ``w_l * mse(k_l(G(B_crop)),
+        k_l(B_crop))`` as the finish launch formed it -- ``loss_global_id_B`` is their float32 sum in that order (``np_id_layers``), exactly so
+        with one crop per pair; with several crops the pair's crops are added per layer in crop order.  Zeros for a slot whose term never
+        ran.  One array for ``pair``, a list over the live slots for ``pair=None``."""
+        if self.id_layers is None:
+            raise RuntimeError("id_layer_values: the identity term reads the top block alone ('dino_id_layers' is null or the default)")
+        n = len(self.id_layers[0])
+        nb = self.n_crops_ab[1]
+        buf = (C.c_float * (self.P * nb * n))()
+        _lib.check(_lib.lib().splice_step_id_layer_values(self.handle, buf, len(buf)), "step_id_layer_values")
+        host = np.frombuffer(buf, dtype=np.float32).reshape(self.P, nb, n)
+        rows = []
+        for p in range(self.P):
+            acc = host[p, 0].copy()
+            for i in range(1, nb):
+                acc = (acc + host[p, i]).astype(np.float32)
+            rows.append(acc)
+        if pair is None and self.PAIR_NONE is None:
+            return rows
+        row = self._row(self.PAIR_NONE if pair is None else pair)
+        if row is None:
+            raise RuntimeError(f"id_layer_values: slot {pair} is parked (stop_compact): its values left the device with its handle")
+        return rows[row]
+
     def active_terms(self, step_idx):
         """Per slot: which of LOSS_KEYS and IMAGE_LOSS_KEYS step ``step_idx`` computes (``engine.active_terms``; a slot's terms follow that slot's own
         lambdas).  Host arithmetic only."""
@@ -824,6 +862,9 @@ class MultiScaleEngine:
                                       "or phase-mode handle, which refuses it")
         if cls_layers_rule(self.cfg, vit_engine.depth if vit_engine is not None else synth.DINO_CONFIGS[self.cfg["dino_model_name"]][2]) is not None:
             raise NotImplementedError("dino_cls_layers: the layer table is set on a whole fused step; MultiScaleEngine runs each scale as a gradient-only "
+                                      "or phase-mode handle, which refuses it")
+        if id_layers_rule(self.cfg, vit_engine.depth if vit_engine is not None else synth.DINO_CONFIGS[self.cfg["dino_model_name"]][2]) is not None:
+            raise NotImplementedError("dino_id_layers: the layer table is set on a whole fused step; MultiScaleEngine runs each scale as a gradient-only "
                                       "or phase-mode handle, which refuses it")
         self.ema_rule = ema_rule(self.cfg)
         self.ema = None

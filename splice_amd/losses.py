@@ -8,7 +8,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
-from .engine import CLS_LAYER_KEYS, SSIM_LAYER_KEYS, cls_layers_rule, resize_output_size, ssim_layers_rule
+from .engine import CLS_LAYER_KEYS, ID_LAYER_KEYS, SSIM_LAYER_KEYS, cls_layers_rule, id_layers_rule, resize_output_size, ssim_layers_rule
 from .extractor import VitExtractor
 from .synth import DINO_CONFIGS
 
@@ -98,6 +98,8 @@ class LossG(torch.nn.Module):
         self.ssim_layers = ssim_layers_rule({k: cfg.get(k) for k in SSIM_LAYER_KEYS}, DINO_CONFIGS[cfg['dino_model_name']][2])
         # ... and the blocks of the two appearance terms, likewise
         self.cls_layers = cls_layers_rule({k: cfg.get(k) for k in CLS_LAYER_KEYS}, DINO_CONFIGS[cfg['dino_model_name']][2])
+        # ... and the blocks of the key-identity term
+        self.id_layers = id_layers_rule({k: cfg.get(k) for k in ID_LAYER_KEYS}, DINO_CONFIGS[cfg['dino_model_name']][2])
         self._features = {
             "self_sim": lambda img: self.extractor.get_keys_self_sim_from_input(img, layer_num=_LAST_LAYER),
             "cls": lambda img: self.extractor.get_feature_from_input(img)[-1][0, 0, :],
@@ -139,6 +141,8 @@ class LossG(torch.nn.Module):
             return self._layered_self_sim_mse(generated, targets)
         if feature == "cls" and self.cls_layers is not None:
             return self._layered_cls_mse(generated, targets)
+        if feature == "keys" and self.id_layers is not None:
+            return self._layered_keys_mse(generated, targets)
         f = self._features[feature]
         acc = 0.0
         for gen_img, tgt_img in zip(generated, targets):   # one crop at a time: the extractor is batch-1
@@ -173,6 +177,20 @@ class LossG(torch.nn.Module):
             crop = 0.0
             for layer, w in zip(*self.cls_layers):
                 crop = crop + w * F.mse_loss(got[layer][0, 0, :], want[layer][0, 0, :])
+            acc = acc + crop
+        return acc
+
+    def _layered_keys_mse(self, generated, targets):
+        """The identity term over ``dino_id_layers``: per crop, sum over the blocks ascending of w_l mse(k_l(generated), k_l(target)),
+        k_l = the keys of block l."""
+        acc = 0.0
+        for gen_img, tgt_img in zip(generated, targets):
+            tgt, gen = self.global_transform(tgt_img).unsqueeze(0).to(device), self.global_transform(gen_img).unsqueeze(0).to(device)
+            crop = 0.0
+            for layer, w in zip(*self.id_layers):
+                with torch.no_grad():
+                    want = self.extractor.get_keys_from_input(tgt, layer_num=layer)
+                crop = crop + w * F.mse_loss(self.extractor.get_keys_from_input(gen, layer_num=layer), want)
             acc = acc + crop
         return acc
 

@@ -48,11 +48,15 @@ DEFAULT_CFG = dict(  # conf/default/config.yaml of the reference
     # ... and the ViT blocks whose keys the two structure terms compare, with a weight each; null: the top block, weight 1
     dino_ssim_layers=None, dino_ssim_layer_weights=None,
     # ... and the blocks whose [CLS] row the two appearance terms compare, with a weight each; null: the top block, weight 1
-    dino_cls_layers=None, dino_cls_layer_weights=None)
+    dino_cls_layers=None, dino_cls_layer_weights=None,
+    # ... and the blocks whose keys the identity term compares, with a weight each; null: the top block, weight 1
+    dino_id_layers=None, dino_id_layer_weights=None)
 SSIM_LAYER_KEYS = ("dino_ssim_layers", "dino_ssim_layer_weights")
 MAX_SSIM_LAYERS = 12   # SELFSIM_MAX_LAYERS: entries of the loss kernels' by-value layer table
 CLS_LAYER_KEYS = ("dino_cls_layers", "dino_cls_layer_weights")
 MAX_CLS_LAYERS = 12    # CLS_MAX_LAYERS: entries of the layered [CLS] loss kernel's by-value table
+ID_LAYER_KEYS = ("dino_id_layers", "dino_id_layer_weights")
+MAX_ID_LAYERS = 12     # ID_MAX_LAYERS: entries of the layered key-identity kernels' by-value table
 
 SNAPSHOT_FORMAT = 1
 # Keys of a config that do not enter a slot's arithmetic (paths, logging, and how the loop parks and checkpoints): a snapshot is restored
@@ -212,7 +216,7 @@ def ssim_layers_rule(c, depth):
 
 
 def _layers_rule(c, depth, keys, most):
-    """A (layers, weights) pair of config keys ``keys`` (``ssim_layers_rule`` / ``cls_layers_rule`` state the rule), at most ``most`` entries."""
+    """A (layers, weights) pair of config keys ``keys`` (``ssim_layers_rule`` / ``cls_layers_rule`` / ``id_layers_rule`` state the rule), at most ``most`` entries."""
     lk, wk = keys
     layers, weights = (c.get(k, DEFAULT_CFG[k]) for k in keys)
     if layers is None:
@@ -250,6 +254,22 @@ def cls_layers_rule(c, depth):
     as many finite float32 numbers > 0 (null: all 1), refused without ``dino_cls_layers``.  Shared by the slots of a sweep
     (``merge_pair_cfgs`` refuses a per-slot value).  Raises ValueError naming the key."""
     return _layers_rule(c, depth, CLS_LAYER_KEYS, MAX_CLS_LAYERS)
+
+
+def id_layers_rule(c, depth):
+    """The blocks of the key-identity term in config ``c`` for a ViT of ``depth`` blocks, checked on the host:
+    ``None`` -- both keys null, or ``[depth - 1]`` with weight 1: the top block, the step launches what it launches without the keys -- or
+    ``(layers, weights)``, the canonical form: the block indices ascending, each weight beside its block.  ``dino_id_layers`` is a list of
+    1..``min(depth, MAX_ID_LAYERS)`` distinct integers in ``[0, depth)``, the top block not required; ``dino_id_layer_weights`` a list of
+    as many finite float32 numbers > 0 (null: all 1), refused without ``dino_id_layers``.  Shared by the slots of a sweep
+    (``merge_pair_cfgs`` refuses a per-slot value).  Raises ValueError naming the key."""
+    return _layers_rule(c, depth, ID_LAYER_KEYS, MAX_ID_LAYERS)
+
+
+def np_id_layers(values, weights=None):
+    """Word 5 of a losses row from the per-layer addends ``engine.id_layer_values`` reports (already weighted; ``weights`` given:
+    unweighted values, multiplied in float32 first): their float32 sum over the blocks ascending, one rounding per addition, from 0."""
+    return np_ssim_layers(values, weights)
 
 
 def np_cls_layers(values, weights=None):

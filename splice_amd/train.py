@@ -422,6 +422,13 @@ def cls_layers_fields(engine):
     return {} if rule is None else {"dino_cls_layers": list(rule[0]), "dino_cls_layer_weights": list(rule[1])}
 
 
+def id_layers_fields(engine):
+    """What ``result.json`` / ``variant.json`` say about the blocks of the key-identity term of a run (shared by the slots; DESIGN.md
+    section 9m): ``dino_id_layers`` / ``dino_id_layer_weights`` in canonical order where the run named other blocks than the default."""
+    rule = getattr(engine, "id_layers", None)
+    return {} if rule is None else {"dino_id_layers": list(rule[0]), "dino_id_layer_weights": list(rule[1])}
+
+
 def best_fields(engine, slot=None):
     """What ``result.json`` says about the stop rule's windows (``splice_amd.batch``) of a run with ``stop_keep_best``: ``best_step`` (the
     step whose weights ``output_best.png`` shows; None: no window closed, they are the initial weights), ``best_window_mean`` and
@@ -557,7 +564,7 @@ def train_sweep(dataroot, variants, cfg_overrides=None, vit_state=None, callback
     losses = engine.losses() if engine.step_idx >= 0 else [{} for _ in range(K)]
     for k in range(K):
         with open(os.path.join(out_dirs[k], 'variant.json'), 'w') as f:
-            json.dump({"index": k, "overrides": variants[k], "seed": seeds[k], "losses": losses[k], "stopped_at": engine.stopped_at[k], **trace_fields(engine), **lr_fields(engine, k), **optim_fields(engine), **image_terms_fields(engine), **ssim_layers_fields(engine), **cls_layers_fields(engine)}, f)
+            json.dump({"index": k, "overrides": variants[k], "seed": seeds[k], "losses": losses[k], "stopped_at": engine.stopped_at[k], **trace_fields(engine), **lr_fields(engine, k), **optim_fields(engine), **image_terms_fields(engine), **ssim_layers_fields(engine), **cls_layers_fields(engine), **id_layers_fields(engine)}, f)
     return engine
 
 
