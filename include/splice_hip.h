@@ -923,6 +923,35 @@ int splice_id_loss_layers(int n_layers, const float* const* x, const int* ldx, c
                           size_t x_rstride, size_t t_rstride, int T, int D, int slots, float lambda, const float* grad_tab, float* const* grad, int ldg,
                           size_t g_rstride, float* scratch, size_t scratch_floats, float* values, float* part, size_t part_pstride, int max_wg,
                           splice_stream_t stream);
+/* ------------------------------------------------------------------ the key second-moment appearance term.
+ * With lambda > 0 (finite) and one block index `layer` in [0, depth), every step from cls_warmup on -- ordinary and entire-image steps
+ * alike -- adds to the total, word 0 of the losses row,
+ *     lambda * raw,   raw = sum over the crop pairs i < min(nA, nB) of mean over the D * D entries of (G(K_x'_i) - G(K_B'_i))^2,
+ *     G(K) = K^T K / T,   K = the T x D keys of block `layer` (every token, the heads concatenated),
+ * of x' = G(A_crop) against the target pass B', the passes the [CLS] appearance term compares; its key gradient
+ * (4 lambda / (T D^2)) K_x' (G(K_x') - G(K_B')) is ADDED into the block's key-gradient buffer of the x' chain behind the structure term's
+ * store.  raw lives in a buffer of its own (splice_step_key_gram_values); the [P][8] losses row, the trace row and the stop rule keep
+ * their layout.  Three launches (key_gram.hip).  Before the first splice_step_run only and behind splice_step_set_ssim_layers /
+ * splice_step_set_id_layers where they are called; refused on a handle in gradient-only or phase mode or with a leader (which in turn
+ * refuses those calls), with fp8_selfsim, with several pairs whose crop counts nA != nB differ, and a second time.  A handle without the
+ * call launches what it always did. */
+int splice_step_set_key_gram(void* step, float lambda, int layer);
+/* The raw term of the last step that computed it, copied to the host behind a device-wide wait: out[p] = pair p's value, `pairs`
+ * floats.  A pair reads 0 before the first such step. */
+int splice_step_key_gram_values(void* step, float* out);
+/* test hook: the three launches of the term on caller buffers, one crop per pair.  Pair p reads the row-major bf16 keys k_x + p * k_ps
+ * ([T][ldk]), and the token-contiguous copies kT_x + p * tx_ps and kT_b + p * tb_ps ([D][ldt_x] / [D][ldt_b], feature rows of tokens) of the
+ * generated and the target pass.  D % 64 == 0; every bf16 pointer, leading dimension and pair stride a multiple of 16 bytes; ldt_x, ldt_b >=
+ * round_up(T, 8), ldk, lddk >= D; part_ps >= the D / 64 * (D / 64 + 1) / 2 upper-triangular tiles; else refused with nothing launched.  The
+ * contraction of the Gram matrices runs over the tokens < T: what the columns >= T of the transposed copies hold reaches no output bit.
+ *   delta[p][D][D] (bf16)  = G(K_x') - G(K_B'), both triangles -- one fp32 accumulator per entry, [K_x ; K_B]^T [K_x ; -K_B], times 1 / T
+ *   part[p * part_ps + t]  = tile t's fixed-tree sum of the fp32 entries squared, twice off the diagonal, times 1 / D^2
+ *   value[p]               = the partials lane-strided ascending, then the wave tree: the raw term
+ *   dk[p * dk_ps + r * lddk + c] += scale * (K_x' delta)[r][c]   for r < T; rows >= T keep their bits.
+ * Pair p has the bits of its own one-pair call. */
+int splice_key_gram_pairs(const splice_bf16* k_x, int ldk, size_t k_ps, const splice_bf16* kT_x, int ldt_x, size_t tx_ps, const splice_bf16* kT_b,
+                          int ldt_b, size_t tb_ps, int T, int D, int pairs, float scale, splice_bf16* delta, float* part, size_t part_ps, float* value,
+                          float* dk, int lddk, size_t dk_ps, splice_stream_t stream);
 /* splice_total_loss_pairs as a handle with a loss trace launches it (splice_step_set_loss_trace): dev_t (device) holds step index + 1,
  * and words 0-5 of row step index of trace ([capacity][pairs][8], device) receive pair p's out8 values, a row at or beyond capacity
  * left out.  stop (may be NULL; device, [pairs] records) runs the instance of a handle with the stop rule, whose rule is window (>= 1),

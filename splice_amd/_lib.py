@@ -255,6 +255,10 @@ _SIGNATURES = {
     "splice_step_set_id_layers": ([_vp, _i, _vp, _vp], _i),
     "splice_step_id_layer_values": ([_vp, _vp, _i], _i),
     "splice_id_loss_layers": ([_i, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _i, _i, _i, _f, _vp, _vp, _i, _sz, _vp, _sz, _vp, _vp, _sz, _i, _vp], _i),
+    # the key second-moment appearance term
+    "splice_step_set_key_gram": ([_vp, _f, _i], _i),
+    "splice_step_key_gram_values": ([_vp, _vp], _i),
+    "splice_key_gram_pairs": ([_vp, _i, _sz, _vp, _i, _sz, _vp, _i, _sz, _i, _i, _i, _f, _vp, _vp, _sz, _vp, _vp, _i, _sz, _vp], _i),
     "splice_image_terms_value": ([_vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _sz, _i, _vp], _i),
     "splice_image_terms_grad_add": ([_vp, _vp, _vp, _i, _i, _i, _f, _vp], _i),
     "splice_total_loss_pairs_img": ([_vp, _sz, _i, _f, _f, _f, _f, _f, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _f, _f, _vp], _i),

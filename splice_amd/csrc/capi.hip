@@ -226,6 +226,20 @@ int splice_id_loss_layers(int n_layers, const float* const* x, const int* ldx, c
     if (rc != SPLICE_OK) return finish(rc, who);
     return finish(id_layers_finish_launch(tab, slots, grad_tab, scratch, max_wg, values, (size_t)n_layers, part, part_pstride, ST(stream)), who);
 }
+/* the three launches of the key second-moment term (splice_step_set_key_gram) on caller buffers, one crop per pair */
+int splice_key_gram_pairs(const splice_bf16* k_x, int ldk, size_t k_ps, const splice_bf16* kT_x, int ldt_x, size_t tx_ps, const splice_bf16* kT_b,
+                          int ldt_b, size_t tb_ps, int T, int D, int pairs, float scale, splice_bf16* delta, float* part, size_t part_ps, float* value,
+                          float* dk, int lddk, size_t dk_ps, splice_stream_t stream) {
+    const char* who = "splice_key_gram_pairs";
+    KeyGram a = {};
+    a.kT_x = kT_x; a.kT_b = kT_b; a.k_x = k_x; a.ldt_x = ldt_x; a.ldt_b = ldt_b; a.ldk = ldk; a.tx_ps = tx_ps; a.tb_ps = tb_ps; a.k_ps = k_ps;
+    a.T = T; a.D = D; a.delta = delta; a.part = part; a.part_ps = part_ps; a.value = value; a.dk = dk; a.lddk = lddk; a.dk_ps = dk_ps; a.scale = scale;
+    if (!(scale == scale) || scale - scale != 0.f) return finish(SPLICE_ERR_ARG, who);   // (finite)
+    if (int rc = key_gram_check(a, pairs, 1)) return finish(rc, who);   // (nothing launched on a refusal)
+    const int rc = key_gram_loss_launch(a, pairs, 1, ST(stream));
+    if (rc != SPLICE_OK) return finish(rc, who);
+    return finish(key_gram_dk_launch(a, pairs, 1, ST(stream)), who);
+}
 int splice_mse_pairs(const float* a, int lda, size_t a_ps, const float* b, int ldb, size_t b_ps, int rows, int cols, float loss_weight,
                      float grad_weight, float* part, size_t part_ps, float* grad, int ldg, size_t g_ps, int pairs, const float* grad_tab,
                      splice_stream_t stream) {

@@ -209,6 +209,34 @@ int id_layers_launch(const IdLayers& tab, int slots, float g, const float* grad_
 // part[s * part_ps] = the fp32 sum of the slot's values, ascending from 0.
 int id_layers_finish_launch(const IdLayers& tab, int slots, const float* grad_tab, const float* scratch, int max_wg, float* values,
                             size_t values_ps, float* part, size_t part_ps, hipStream_t s);
+// ---- key_gram.hip: the key second-moment appearance term ----
+// Slot s = pair * crops + crop compares the T x D keys of one block of a generated pass with those of its target pass through their
+// D x D second moments.  The Gram operands are the transposed bf16 key copies, feature rows of tokens: slot s's feature f at
+// kT_x + s * tx_ps + f * ldt_x (the target: kT_b, tb_ps, ldt_b); the backward reads the row-major bf16 keys k_x + s * k_ps (rows ldk apart)
+// and adds into dk + s * dk_ps (rows lddk apart).  Every bf16 pointer, leading dimension and slot stride is a multiple of 16 bytes,
+// D of 64, and a transposed row holds round_up(T, 8) columns; what the columns >= T hold reaches no output bit.
+struct KeyGram {
+    const bf16_t* kT_x;
+    const bf16_t* kT_b;
+    const bf16_t* k_x;
+    int ldt_x, ldt_b, ldk;
+    size_t tx_ps, tb_ps, k_ps;
+    int T, D;
+    bf16_t* delta;     // [slots][D][D]: G(K_x') - G(K_B') in bf16, both triangles
+    float* part;       // slot s's tile partials at part + s * part_ps, key_gram_tiles(D) of them, each written exactly once
+    size_t part_ps;
+    float* value;      // [pairs]: the raw term, the pair's crops added in crop order
+    float* dk;
+    int lddk;
+    size_t dk_ps;
+    float scale;       // c = 4 lambda / (T D^2)
+};
+int key_gram_tiles(int D);   // upper-triangular 64 x 64 tiles of D x D; 0: D is no multiple of 64
+int key_gram_check(const KeyGram& a, int pairs, int crops);
+// the loss launch and its one-wave finish: delta, part and value of every slot; dk is not touched
+int key_gram_loss_launch(const KeyGram& a, int pairs, int crops, hipStream_t s);
+// dk[rows < T] += scale * k_x * delta for every slot
+int key_gram_dk_launch(const KeyGram& a, int pairs, int crops, hipStream_t s);
 // 2-D strided MSE: loss_accum[0] += weight * mean((a-b)^2); grad (optional) = weight * 2 (a-b) / (rows*cols)
 int mse_launch(const float* a, int lda, const float* b, int ldb, int rows, int cols, float weight, float* loss_accum,
                float* grad, int ldg, hipStream_t s);

@@ -56,6 +56,12 @@ struct VitView {
     float* dk_id[ID_MAX_LAYERS] = {};
     float* dk_id_own[ID_MAX_LAYERS] = {};
     std::vector<const float*> pk_y;
+    // splice_step_set_key_gram (global view only): the key-gradient buffer the term adds into -- pk's of its block (d_keys at the top, the
+    // structure list's buffer of a block that list names), else one of its own (then also in dk_kg_own: its x' passes are zeroed each step)
+    // -- and the x' chain's key-gradient table on the steps the term runs: pk plus that block
+    float* dk_kg = nullptr;
+    float* dk_kg_own = nullptr;
+    std::vector<const float*> pk_x;
 };
 
 struct SpliceStep {
@@ -191,6 +197,13 @@ struct SpliceStep {
     int id_layers[ID_MAX_LAYERS] = {};
     float id_weights[ID_MAX_LAYERS] = {};
     float *id_scratch = nullptr, *id_values = nullptr;
+    // the key second-moment appearance term (splice_step_set_key_gram): its weight (0: off -- the step launches what it
+    // always did) and block; kg_delta: the bf16 Gram differences, [Pc][D][D]; kg_part: the tile partials, [Pc][tiles]; kg_value: the raw
+    // term, [pairs]
+    float kg_lambda = 0.f;
+    int kg_layer = -1;
+    bf16_t* kg_delta = nullptr;
+    float *kg_part = nullptr, *kg_value = nullptr;
 };
 
 static size_t arena_floats(const SpliceStep* st) { return st->astride ? st->pairs * st->astride : (size_t)st->nparams; }   // of all pairs' arenas
@@ -263,18 +276,21 @@ static int view_init(SpliceStep* st, VitView& v, void* ctx, int want_B) {
 // splice_step_ssim_layer_values reports with), the layers' sums in ascending order, the pair's crops in crop order as before -- so with
 // one crop per pair the reported word IS the float32 sum of the reported per-layer values.  The instances without LYR do not read the
 // three trailing arguments.
+// KG (the key second-moment appearance term): the pair's raw value is read from the term's own buffer, kg_values
+// [pairs] (the finish launch of key_gram.hip has summed it), and enters the total last: fmaf(w_kg, raw, total of everything before).  No word
+// of the row but word 0 moves.  The instances without KG do not read the two trailing arguments.
 __device__ __forceinline__ float ssim_layer_sum(const float* part, int tiles) {
     float acc = 0.f;
     for (int i = 0; i < tiles; ++i) acc += part[i];
     return acc;
 }
-template <bool MONITOR, bool TRACE, bool LRP = false, bool IMG = false, bool LYR = false>
+template <bool MONITOR, bool TRACE, bool LRP = false, bool IMG = false, bool LYR = false, bool KG = false>
 __global__ __launch_bounds__(IMG ? 448 : 320) void total_loss_kernel(float* lbase, size_t lstride, int lp, float w_ssim, float w_essim, float w_ecls, float w_cls,
                                                          float w_id, float* out8, int n_a, int n_b, int n_c, int n_e, const float* wtab, int ssim_on,
                                                          int entire, splice_stop_state* stop, const int* dev_t, StopRule rule, splice_best_state* kb,
                                                          float* means, float* trace, int capacity, LrRule lr_rule, splice_lr_state* lr_state, int* lr_cuts,
                                                          const float* lr_in, int lr_in_stride, float* lr_eff, float w_tv, float w_pix, int n_layers,
-                                                         int tiles_g, int tiles_e) {
+                                                         int tiles_g, int tiles_e, float w_kg, const float* kg_values) {
     static_assert(MONITOR || !LRP, "the lr rule rides on the stop rule");
     __shared__ float raw[8];
     float* l = lbase + (size_t)blockIdx.x * lstride;
@@ -316,6 +332,7 @@ __global__ __launch_bounds__(IMG ? 448 : 320) void total_loss_kernel(float* lbas
             l[L_GLOBAL_TV] = raw[L_GLOBAL_TV]; l[L_GLOBAL_PIX] = raw[L_GLOBAL_PIX];
             l[L_TOTAL] = __builtin_fmaf(w_pix, raw[L_GLOBAL_PIX], __builtin_fmaf(w_tv, raw[L_GLOBAL_TV], l[L_TOTAL]));
         }
+        if (KG) l[L_TOTAL] = __builtin_fmaf(w_kg, kg_values[blockIdx.x], l[L_TOTAL]);
         if (out8) {   // the caller's losses buffer, written here instead of by a copy behind the step
             float* o = out8 + (size_t)blockIdx.x * 8;
             o[0] = l[L_TOTAL];
@@ -352,13 +369,21 @@ __global__ __launch_bounds__(64) void plateau_update_kernel(splice_stop_state* s
 #define NO_IMG_TERMS 0.f, 0.f
 // the three trailing arguments behind those of a launch without structure layers
 #define NO_SSIM_LAYERS 0, 0, 0
+// the two trailing arguments behind those of a launch without the key second-moment term
+#define NO_KEY_GRAM 0.f, (const float*)nullptr
 // the step's instance by what the handle carries (the lr rule rides on the stop rule)
 using TotalLossKernel = decltype(&total_loss_kernel<false, false>);
-template <bool IMG, bool LYR = false>
+template <bool IMG, bool LYR = false, bool KG = false>
 static TotalLossKernel total_loss_instance(bool lr_rule, bool trace, bool stop) {
-    return lr_rule ? (trace ? total_loss_kernel<true, true, true, IMG, LYR> : total_loss_kernel<true, false, true, IMG, LYR>)
-           : trace ? (stop ? total_loss_kernel<true, true, false, IMG, LYR> : total_loss_kernel<false, true, false, IMG, LYR>)
-                   : (stop ? total_loss_kernel<true, false, false, IMG, LYR> : total_loss_kernel<false, false, false, IMG, LYR>);
+    return lr_rule ? (trace ? total_loss_kernel<true, true, true, IMG, LYR, KG> : total_loss_kernel<true, false, true, IMG, LYR, KG>)
+           : trace ? (stop ? total_loss_kernel<true, true, false, IMG, LYR, KG> : total_loss_kernel<false, true, false, IMG, LYR, KG>)
+                   : (stop ? total_loss_kernel<true, false, false, IMG, LYR, KG> : total_loss_kernel<false, false, false, IMG, LYR, KG>);
+}
+// ... and by the step's terms: the image-space terms, structure layers, the key second-moment term
+template <bool KG>
+static TotalLossKernel total_loss_for(bool img, bool layered, bool lr_rule, bool trace, bool stop) {
+    return layered ? (img ? total_loss_instance<true, true, KG>(lr_rule, trace, stop) : total_loss_instance<false, true, KG>(lr_rule, trace, stop))
+                   : (img ? total_loss_instance<true, false, KG>(lr_rule, trace, stop) : total_loss_instance<false, false, KG>(lr_rule, trace, stop));
 }
 // one thread per (layer, pair): the pair's crops' sums of layer i's slot range of `term`, added in crop order (splice_step_ssim_layer_values)
 __global__ __launch_bounds__(64) void ssim_layer_values_kernel(const float* lbase, size_t lstride, int lp, int term, int n_layers, int tiles, int pairs,
@@ -754,7 +779,7 @@ static const char* whole_step_rule(const SpliceStep* st) {
            : st->best ? "that keeps the best weights" : st->trace ? "with a loss trace"
            : (st->lambda_tv > 0.f || st->lambda_pix > 0.f) ? "with image-space loss terms"
            : st->n_ssim_layers > 0 ? "with structure layers" : st->n_cls_layers > 0 ? "with [CLS] layers"
-           : st->n_id_layers > 0 ? "with identity layers" : nullptr;
+           : st->n_id_layers > 0 ? "with identity layers" : st->kg_lambda > 0.f ? "with the key second-moment term" : nullptr;
 }
 // The shared opening of the rule setters below: before the first step only (`what` of the rule, for the error text), and not on a
 // gradient-only or phase-mode handle.  Callers return its code plainly, not through RC(): the message stays the last error.
@@ -1065,6 +1090,7 @@ int splice_step_set_ssim_layers(void* h, int n, const int* layers, const float* 
     if (st->cfg.fp8_selfsim) { splice_set_error("%s: not with fp8_selfsim (the e4m3 Gram path reads the top block alone)", who); return SPLICE_ERR_STATE; }
     if (st->n_ssim_layers) { splice_set_error("%s: the layers are set once", who); return SPLICE_ERR_STATE; }
     if (st->n_id_layers) { splice_set_error("%s: call it in front of splice_step_set_id_layers (the identity term shares this list's key-gradient buffers)", who); return SPLICE_ERR_STATE; }
+    if (st->kg_lambda > 0.f) { splice_set_error("%s: call it in front of splice_step_set_key_gram (that term shares this list's key-gradient buffers)", who); return SPLICE_ERR_STATE; }
     const int Tmax = st->plan_e && st->ve.T > st->vg.T ? st->ve.T : st->vg.T;
     for (VitView* v : {&st->vg, &st->ve}) {
         if (!v->ctx) continue;
@@ -1255,6 +1281,66 @@ int splice_step_id_layer_values(void* h, float* out, int cap) {
     HIPCHK(hipMemcpy(out, st->id_values, (size_t)st->Pb * st->n_id_layers * sizeof(float), hipMemcpyDeviceToHost));
     return SPLICE_OK;
 }
+static unsigned long long key_gram_salt(const SpliceStep* st) {
+    if (!(st->kg_lambda > 0.f)) return 0;
+    unsigned w;
+    memcpy(&w, &st->kg_lambda, sizeof(w));
+    unsigned long long h = 1469598103934665603ull ^ 0xc2b2ae3d27d4eb4full;   // FNV-1a over (block, weight bits), from a basis of its own
+    for (unsigned long long v : {(unsigned long long)st->kg_layer, (unsigned long long)w})
+        for (int k = 0; k < 8; ++k) { h ^= (v >> (8 * k)) & 0xff; h *= 1099511628211ull; }
+    return h | 4ull;   // (never 0: a handle with the term is never keyed like one without)
+}
+// The key second-moment appearance term (include/splice_hip.h has the term): its weight, finite and > 0, and its block.  The global ViT
+// context writes the transposed bf16 copy of a block below the top (splice_vit_ctx_set_transposed_layers: a repeated call before the
+// first forward adds to the blocks already named, so the context ends up with the union of this block and the structure list).  The
+// key gradient is ADDED into the block's buffer of the x' chain: pk's where the block has one (d_keys at the top, the structure
+// list's), else a buffer of its own, zeroed here (padding rows and every other chain's passes read as zero gradient for good) and over
+// its x' passes at every step the term runs; only the x' chain's backward then reads it (pk_x).  Before the first step only; not on a
+// gradient-only or phase-mode handle (which in turn refuses those calls); not with fp8_selfsim; not with several pairs of nA != nB
+// crops; not a second time; and behind splice_step_set_ssim_layers where both are called, so that the shared buffer exists.
+int splice_step_set_key_gram(void* h, float lambda, int layer) {
+    SpliceStep* st = (SpliceStep*)h;
+    const char* who = "splice_step_set_key_gram";
+    if (!st) return SPLICE_ERR_ARG;
+    VitView& v = st->vg;
+    if (!(lambda > 0.f) || !(lambda <= 3.402823466e+38f)) { splice_set_error("%s: lambda must be finite and > 0, got %g", who, (double)lambda); return SPLICE_ERR_ARG; }
+    if (layer < 0 || layer >= v.depth) { splice_set_error("%s: layer must be a block index in [0, %d), got %d", who, v.depth, layer); return SPLICE_ERR_ARG; }
+    if (int rc = rule_setter_ok(st, who, "the term is set")) return rc;
+    if (st->cfg.fp8_selfsim) { splice_set_error("%s: not with fp8_selfsim (the term reads the bf16 key copies of a bf16 forward)", who); return SPLICE_ERR_STATE; }
+    if (st->kg_lambda > 0.f) { splice_set_error("%s: the term is set once", who); return SPLICE_ERR_STATE; }
+    if (v.D % 64) { splice_set_error("%s: needs an embedding width that is a multiple of 64, got %d", who, v.D); return SPLICE_ERR_ARG; }
+    if (st->pairs > 1 && st->na != st->nb) { splice_set_error("%s: not with several pairs of nA != nB crops (%d, %d)", who, st->na, st->nb); return SPLICE_ERR_STATE; }
+    if (layer != v.depth - 1) RC(splice_vit_ctx_set_transposed_layers(v.ctx, 1, &layer));
+    v.pk_x = v.pk;
+    if (v.pk[layer]) v.dk_kg = const_cast<float*>(v.pk[layer]);
+    else {
+        RC(salloc(st, &v.dk_kg_own, (size_t)v.rows * v.D));
+        HIPCHK(hipMemset(v.dk_kg_own, 0, (size_t)v.rows * v.D * sizeof(float)));
+        v.dk_kg = v.dk_kg_own;
+        v.pk_x[layer] = v.dk_kg;
+    }
+    const int slots = st->pairs * (st->na < st->nb ? st->na : st->nb), tiles = key_gram_tiles(v.D);
+    RC(salloc(st, &st->kg_delta, (size_t)slots * v.D * v.D));
+    RC(salloc(st, &st->kg_part, (size_t)slots * tiles));
+    RC(salloc(st, &st->kg_value, (size_t)st->pairs));
+    HIPCHK(hipMemset(st->kg_delta, 0, (size_t)slots * v.D * v.D * sizeof(bf16_t)));
+    HIPCHK(hipMemset(st->kg_part, 0, (size_t)slots * tiles * sizeof(float)));
+    HIPCHK(hipMemset(st->kg_value, 0, (size_t)st->pairs * sizeof(float)));
+    st->graphs.retire();
+    st->kg_lambda = lambda; st->kg_layer = layer;
+    return SPLICE_OK;
+}
+// The raw key second-moment term of the last step that computed it, copied to the HOST behind a device-wide wait: out[p] = pair p's
+// value, `pairs` floats; zeros before the first such step.
+int splice_step_key_gram_values(void* h, float* out) {
+    SpliceStep* st = (SpliceStep*)h;
+    const char* who = "splice_step_key_gram_values";
+    if (!st || !out) { splice_set_error("%s: needs a handle and out", who); return SPLICE_ERR_ARG; }
+    if (!(st->kg_lambda > 0.f)) { splice_set_error("%s: the handle has no key second-moment term (splice_step_set_key_gram)", who); return SPLICE_ERR_STATE; }
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, st->kg_value, (size_t)st->pairs * sizeof(float), hipMemcpyDeviceToHost));
+    return SPLICE_OK;
+}
 // Start the handle at step next_step_idx of a run other handles carried so far (a resumed run, a compacted engine; DESIGN.md section
 // 9g).  What a handle keeps from one step to the next, and this call therefore sets, is two things: ssim_id_on, which only the run of step
 // cls_warmup switches on, and the stop records.  Nothing else in the handle is state: dev_t and the lr(s) are staged by every step's
@@ -1347,7 +1433,7 @@ int splice_total_loss_pairs(float* lbase, size_t lstride, int lp, float w_ssim, 
     const auto kernel = total_loss_kernel<false, false>;
     SPLICE_LAUNCH(kernel, dim3(pairs), dim3(320), 0, (hipStream_t)stream, lbase, lstride, lp, w_ssim, w_essim, w_ecls, w_cls, w_id, out8,
                   n_a, n_b, n_c, n_e, wtab, ssim_on, entire, (splice_stop_state*)nullptr, (const int*)nullptr, StopRule{}, (splice_best_state*)nullptr,
-                  (float*)nullptr, (float*)nullptr, 0, NO_LR_RULE, NO_IMG_TERMS, NO_SSIM_LAYERS);
+                  (float*)nullptr, (float*)nullptr, 0, NO_LR_RULE, NO_IMG_TERMS, NO_SSIM_LAYERS, NO_KEY_GRAM);
     return SPLICE_OK;
 }
 // test hook: the same launch with the image-space terms (the IMG instance, 448 threads): terms 6 / 7 of the partials (lstride >= 8 + 8 lp)
@@ -1361,7 +1447,7 @@ int splice_total_loss_pairs_img(float* lbase, size_t lstride, int lp, float w_ss
     const auto kernel = total_loss_kernel<false, false, false, true>;
     SPLICE_LAUNCH(kernel, dim3(pairs), dim3(448), 0, (hipStream_t)stream, lbase, lstride, lp, w_ssim, w_essim, w_ecls, w_cls, w_id, out8,
                   n_a, n_b, n_c, n_e, wtab, ssim_on, entire, (splice_stop_state*)nullptr, (const int*)nullptr, StopRule{}, (splice_best_state*)nullptr,
-                  (float*)nullptr, (float*)nullptr, 0, NO_LR_RULE, w_tv, w_pix, NO_SSIM_LAYERS);
+                  (float*)nullptr, (float*)nullptr, 0, NO_LR_RULE, w_tv, w_pix, NO_SSIM_LAYERS, NO_KEY_GRAM);
     return SPLICE_OK;
 }
 // test hook: the same launch with the loss trace (the TRACE instances): dev_t holds step index + 1 on the device; stop (optional, with its
@@ -1381,7 +1467,7 @@ int splice_total_loss_pairs_trace(float* lbase, size_t lstride, int lp, float w_
     const auto kernel = stop ? total_loss_kernel<true, true> : total_loss_kernel<false, true>;
     SPLICE_LAUNCH(kernel, dim3(pairs), dim3(320), 0, (hipStream_t)stream, lbase, lstride, lp, w_ssim, w_essim, w_ecls, w_cls, w_id, out8, n_a, n_b, n_c, n_e, wtab,
                   ssim_on, entire, stop, dev_t, stop ? StopRule{window, rel, patience, min_steps} : StopRule{}, (splice_best_state*)nullptr, (float*)nullptr, trace,
-                  capacity, NO_LR_RULE, NO_IMG_TERMS, NO_SSIM_LAYERS);
+                  capacity, NO_LR_RULE, NO_IMG_TERMS, NO_SSIM_LAYERS, NO_KEY_GRAM);
     return SPLICE_OK;
 }
 
@@ -1470,6 +1556,8 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
     const bool layered = st->n_ssim_layers > 0;
     IdLayers idt = {};   // identity layers (splice_step_set_id_layers): the table of the term's two launches
     const bool id_layered = do_v && t[L_GLOBAL_ID].on && st->n_id_layers > 0;
+    // the key second-moment term (splice_step_set_key_gram): on the steps of the structure and identity terms, entire-image steps included
+    const bool kg_on = do_v && ssim_on && st->kg_lambda > 0.f;
     if (do_v) {
         RC(place_passes(vg, src.a_in, c.crop_h, c.crop_w, pA, Pa, s2));
         RC(place_passes(vg, src.b_in, st->cropb_h, st->cropb_w, pB, Pb, s2));
@@ -1479,6 +1567,8 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
         RC(zero_seeds(vg, pX, Pa + Pb, s2));
         for (float* dk : vg.dk_id_own)   // the blocks only the identity list names: their y' passes alone (no x' chain reads them)
             if (dk) RC(dev_zero_launch(dk + pY * passD, Pb * passD * sizeof(float), s2));
+        // a block only the key second-moment term names: its x' passes alone (no other chain reads it), on the steps the term adds into them
+        if (kg_on && vg.dk_kg_own) RC(dev_zero_launch(vg.dk_kg_own + pX * passD, Pa * passD * sizeof(float), s2));
         if (t[L_GLOBAL_SSIM].on) {   // target self-similarity S* of A' (util/losses.py:79)
             RC(ssim_batch(st, vg, pA, pX, Pa, t[L_GLOBAL_SSIM], L_GLOBAL_SSIM, &sb, layered ? &sl : nullptr));
             RC(selfsim_target_launch(sb, s2, layered ? &sl : nullptr));
@@ -1499,6 +1589,22 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
     // ---- losses on the global batch
     if (do_v) {
         if (t[L_GLOBAL_SSIM].on) RC(selfsim_loss_launch(sb, s, layered ? &sl : nullptr));
+        if (kg_on) {   // keys of x' against keys of B', crop i with crop i, through their D x D second moments; behind selfsim_dk_kernel: that stores, this adds
+            const int l = st->kg_layer;
+            bf16_t *qkv = nullptr, *qkvT = nullptr;
+            RC(splice_vit_get_tensor(vg.ctx, 1, l, (void**)&qkv));
+            RC(splice_vit_get_tensor(vg.ctx, l == vg.depth - 1 ? 6 : 8, l, (void**)&qkvT));
+            KeyGram kg = {};
+            kg.kT_x = qkvT + (size_t)vg.D * vg.rows + (size_t)pX * vg.Tld; kg.kT_b = qkvT + (size_t)vg.D * vg.rows + (size_t)pB * vg.Tld;
+            kg.ldt_x = kg.ldt_b = vg.rows; kg.tx_ps = kg.tb_ps = (size_t)vg.Tld;
+            kg.k_x = qkv + (size_t)pX * vg.Tld * 3 * vg.D + vg.D; kg.ldk = 3 * vg.D; kg.k_ps = (size_t)vg.Tld * 3 * vg.D;
+            kg.T = vg.T; kg.D = vg.D;
+            kg.delta = st->kg_delta; kg.part = st->kg_part; kg.part_ps = (size_t)key_gram_tiles(vg.D); kg.value = st->kg_value;
+            kg.dk = vg.dk_kg + pX * passD; kg.lddk = vg.D; kg.dk_ps = passD;
+            kg.scale = 4.0f * st->kg_lambda / ((float)vg.T * (float)vg.D * (float)vg.D);
+            RC(key_gram_loss_launch(kg, pairs, nc, s));
+            RC(key_gram_dk_launch(kg, pairs, nc, s));
+        }
         if (t[L_GLOBAL_CLS].on && st->n_cls_layers) {   // [CLS] of the named blocks: one launch for all of them, the call structure of the plain path below
             const int n = st->n_cls_layers;
             const float g = t[L_GLOBAL_CLS].lambda / (float)(size_t)vg.D;
@@ -1580,13 +1686,12 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
             if (id_layered)
                 RC(id_layers_finish_launch(idt, Pb, t[L_GLOBAL_ID].tab, st->id_scratch, 0, st->id_values, (size_t)st->n_id_layers, loss_part(st, L_GLOBAL_ID),
                                            st->lstride, q));
-            const auto kernel = layered ? (img_on ? total_loss_instance<true, true>(lrp, trc, stop_on) : total_loss_instance<false, true>(lrp, trc, stop_on))
-                                        : (img_on ? total_loss_instance<true>(lrp, trc, stop_on) : total_loss_instance<false>(lrp, trc, stop_on));
+            const auto kernel = kg_on ? total_loss_for<true>(img_on, layered, lrp, trc, stop_on) : total_loss_for<false>(img_on, layered, lrp, trc, stop_on);
             SPLICE_LAUNCH(kernel, dim3(pairs), dim3(img_on ? 448 : 320), 0, q, st->losses, st->lstride, (int)st->lp, t[L_GLOBAL_SSIM].lambda, t[L_ENTIRE_SSIM].lambda,
                           t[L_ENTIRE_CLS].lambda, t[L_GLOBAL_CLS].lambda, t[L_GLOBAL_ID].lambda, st->losses_out, grouped ? st->na : n1, grouped ? st->nb : n1, grouped ? nc : n1,
                           grouped ? 1 : n1, st->pw ? st->pw + (size_t)PW_LAMBDAS * P : nullptr, (int)ssim_on, (int)entire, st->stop, st->dev_t, st->stop_rule, st->best, st->best_means,
                           st->trace, st->trace_cap, st->lr_rule, st->lr_state, st->lr_cuts, (const float*)(st->pair_lr ? st->dev_lrs : st->dev_lr), st->pair_lr ? 1 : 0,
-                          st->lr_eff, st->lambda_tv, st->lambda_pix, st->n_ssim_layers, tri_tiles(vg.T), st->plan_e ? tri_tiles(ve.T) : 0);
+                          st->lr_eff, st->lambda_tv, st->lambda_pix, st->n_ssim_layers, tri_tiles(vg.T), st->plan_e ? tri_tiles(ve.T) : 0, st->kg_lambda, (const float*)st->kg_value);
         }
         if (!st->running || !gen_fwd) return SPLICE_OK;
         void* plans[3] = {st->plan_a, st->plan_b, nullptr};
@@ -1610,7 +1715,7 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
             RC(bookkeeping(s2));
             HIPCHK(hipEventRecord(st->ev(SpliceStep::EV_JOIN2), s2));
         }
-        RC(chain_bwd(vg, pX, pY, true, ip.dx, c.crop_h, c.crop_w, src.dx, st->plan_a, grads, st->accumulate, gen_bwd, L_GLOBAL_TV, L_GLOBAL_CLS, vg.pk, s));
+        RC(chain_bwd(vg, pX, pY, true, ip.dx, c.crop_h, c.crop_w, src.dx, st->plan_a, grads, st->accumulate, gen_bwd, L_GLOBAL_TV, L_GLOBAL_CLS, kg_on ? vg.pk_x : vg.pk, s));
         if (overlap) HIPCHK(hipStreamWaitEvent(s, st->ev(SpliceStep::EV_JOIN2), 0));
         // grads = g(A) + g(B): folded into the Adam kernel on ordinary steps; a separate add when the entire-image branch
         // still has to accumulate into the sum (same association order either way)
@@ -1778,7 +1883,8 @@ int splice_step_run(void* h, float* params, float* grads, float* m, float* v, co
                                             (st->opt_ext_on ? (unsigned long long)(1 + st->opt_kind + 3 * ((st->opt_ext.momentum > 0.f ? 1 : 0) + 2 * (st->opt_ext.amsgrad || st->opt_ext.centered ? 1 : 0))) << 56 : 0);
             // ... and the [CLS] layers: a 64-bit hash of the blocks and their weight bits folded over the word (another loss launch, the seed adds)
             // ... and the identity layers, likewise (two other loss launches, the key-gradient tables of the y' chain, a zeroing launch per own block)
-            ex = st->graphs.adopt(variant, g, salt ^ cls_layers_salt(st) ^ id_layers_salt(st));
+            // ... and the key second-moment term: its block and weight bits (three launches more, a zeroing launch and the x' chain's table)
+            ex = st->graphs.adopt(variant, g, salt ^ cls_layers_salt(st) ^ id_layers_salt(st) ^ key_gram_salt(st));
             if (!ex) return SPLICE_ERR_HIP;
         }
         HIPCHK(hipGraphLaunch(ex, s));

@@ -86,6 +86,16 @@ class MultiPairEngine:
             if fp8_mode(fp8):
                 raise ValueError("'dino_id_layers': not with fp8 -- the e4m3 forward keeps fp32 keys of the top block alone")
             self.cfg.update(dino_id_layers=list(self.id_layers[0]), dino_id_layer_weights=list(self.id_layers[1]))
+        # the key second-moment appearance term: None -- off, today's launches -- or (lambda, block); the config then
+        # holds the block it runs on (what a snapshot is compared on)
+        self.key_gram = key_gram_rule(self.cfg, depth)
+        if self.key_gram is not None:
+            if fp8_mode(fp8):
+                raise ValueError("'lambda_global_key_gram': not with fp8 -- the term reads the bf16 key copies of a bf16 forward")
+            nA_, nB_ = (int(n_crops), int(n_crops)) if isinstance(n_crops, int) else (int(n_crops[0]), int(n_crops[1]))
+            if len(gen_states) > 1 and nA_ != nB_:
+                raise ValueError(f"'lambda_global_key_gram': not with several pairs of different crop counts per side, got n_crops = {(nA_, nB_)}")
+            self.cfg.update(lambda_global_key_gram=self.key_gram[0], dino_gram_layer=self.key_gram[1])
         P_in = len(gen_states)
         self.cfgs = [self.cfg] * P_in
         self._pair_lambdas = self._pair_lr = False
@@ -273,6 +283,10 @@ class MultiPairEngine:
             n = len(self.id_layers[0])
             _lib.check(_lib.lib().splice_step_set_id_layers(self.handle, n, (C.c_int * n)(*self.id_layers[0]), (C.c_float * n)(*self.id_layers[1])),
                        "step_set_id_layers")
+        # the key second-moment term (shared by the slots): three launches on the x' chain from cls_warmup on; before the first step, behind
+        # the structure and identity layers (shared key-gradient buffers).  The default: the call is not made
+        if self.key_gram is not None:
+            _lib.check(_lib.lib().splice_step_set_key_gram(self.handle, C.c_float(self.key_gram[0]), int(self.key_gram[1])), "step_set_key_gram")
         self._lr_scale = [1.0] * P   # the host's copy of every slot's lr scale, refreshed with the stop steps
         self._stopped = [None] * P   # the host's copy of every slot's stop step, refreshed by stop_state()
         self._stop_dirty = False     # a window has closed since the last stop_state(): the copy may be behind
@@ -621,7 +635,34 @@ class MultiPairEngine:
         a list over the pairs for ``pair=None``."""
         rows = self._decoded(lambda t: t.cpu().tolist(), "losses")   # (a parked slot: its last own row)
         acts = self.active_terms(self.step_idx)
-        return self._pick([{k: vals[i] for i, k in enumerate(LOSS_KEYS + IMAGE_LOSS_KEYS) if act[k]} for vals, act in zip(rows, acts)], pair)
+        out = [{k: vals[i] for i, k in enumerate(LOSS_KEYS + IMAGE_LOSS_KEYS) if act[k]} for vals, act in zip(rows, acts)]
+        if self.key_gram is not None and key_gram_active(self.cfg, self.step_idx):   # (its raw value lives beside the row; a parked slot's left with its handle)
+            vals = self._key_gram_host()
+            for p, d in enumerate(out):
+                row = self._row(p)
+                if row is not None:
+                    d[KEY_GRAM_LOSS_KEY] = float(vals[row])
+        return self._pick(out, pair)
+
+    def _key_gram_host(self):
+        buf = (C.c_float * self.P)()
+        _lib.check(_lib.lib().splice_step_key_gram_values(self.handle, buf), "step_key_gram_values")
+        return np.frombuffer(buf, dtype=np.float32).copy()
+
+    def key_gram_value(self, pair=None):
+        """The raw key second-moment term (``lambda_global_key_gram``) of the last step that computed it, copied from
+        the device (waits for the device): ``mean((G(K_x') - G(K_B'))^2)`` over the ``D * D`` entries, summed over the pair's zipped crops --
+        the total, word 0 of the losses row, holds ``lambda`` times it.  0 before the first such step.  One float for ``pair``, a list over
+        the live slots for ``pair=None``."""
+        if self.key_gram is None:
+            raise RuntimeError("key_gram_value: the term is off ('lambda_global_key_gram' is 0)")
+        vals = [float(v) for v in self._key_gram_host()]
+        if pair is None and self.PAIR_NONE is None:
+            return vals
+        row = self._row(self.PAIR_NONE if pair is None else pair)
+        if row is None:
+            raise RuntimeError(f"key_gram_value: slot {pair} is parked (stop_compact): its value left the device with its handle")
+        return vals[row]
 
     def ssim_layer_values(self, pair=None, entire=False):
         """The per-layer addends of the last step's structure term (``dino_ssim_layers``), copied from the device
@@ -865,6 +906,9 @@ class MultiScaleEngine:
                                       "or phase-mode handle, which refuses it")
         if id_layers_rule(self.cfg, vit_engine.depth if vit_engine is not None else synth.DINO_CONFIGS[self.cfg["dino_model_name"]][2]) is not None:
             raise NotImplementedError("dino_id_layers: the layer table is set on a whole fused step; MultiScaleEngine runs each scale as a gradient-only "
+                                      "or phase-mode handle, which refuses it")
+        if key_gram_rule(self.cfg, vit_engine.depth if vit_engine is not None else synth.DINO_CONFIGS[self.cfg["dino_model_name"]][2]) is not None:
+            raise NotImplementedError("lambda_global_key_gram: the term is set on a whole fused step; MultiScaleEngine runs each scale as a gradient-only "
                                       "or phase-mode handle, which refuses it")
         self.ema_rule = ema_rule(self.cfg)
         self.ema = None

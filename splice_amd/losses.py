@@ -8,7 +8,8 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
-from .engine import CLS_LAYER_KEYS, ID_LAYER_KEYS, SSIM_LAYER_KEYS, cls_layers_rule, id_layers_rule, resize_output_size, ssim_layers_rule
+from .engine import (CLS_LAYER_KEYS, ID_LAYER_KEYS, KEY_GRAM_KEYS, KEY_GRAM_LOSS_KEY, SSIM_LAYER_KEYS, cls_layers_rule, id_layers_rule, key_gram_rule,
+                     resize_output_size, ssim_layers_rule)
 from .extractor import VitExtractor
 from .synth import DINO_CONFIGS
 
@@ -100,6 +101,8 @@ class LossG(torch.nn.Module):
         self.cls_layers = cls_layers_rule({k: cfg.get(k) for k in CLS_LAYER_KEYS}, DINO_CONFIGS[cfg['dino_model_name']][2])
         # ... and the blocks of the key-identity term
         self.id_layers = id_layers_rule({k: cfg.get(k) for k in ID_LAYER_KEYS}, DINO_CONFIGS[cfg['dino_model_name']][2])
+        # ... and the key second-moment appearance term: None -- off -- or (lambda, block)
+        self.key_gram = key_gram_rule({k: cfg[k] for k in KEY_GRAM_KEYS if k in cfg}, DINO_CONFIGS[cfg['dino_model_name']][2])
         self._features = {
             "self_sim": lambda img: self.extractor.get_keys_self_sim_from_input(img, layer_num=_LAST_LAYER),
             "cls": lambda img: self.extractor.get_feature_from_input(img)[-1][0, 0, :],
@@ -132,8 +135,28 @@ class LossG(torch.nn.Module):
                 else:
                     losses[key] = sum(F.mse_loss(img, ref.to(img.device)) for img, ref in zip(outputs[out_key], inputs[in_key]))
                 total = total + lam * losses[key]
+        # the key second-moment term, on the steps of the structure and identity terms (from cls_warmup on, entire-image steps included)
+        if self.key_gram is not None and int(inputs['step']) >= self.cfg['cls_warmup']:
+            losses[KEY_GRAM_LOSS_KEY] = self.calculate_key_gram_loss(outputs['x_global'], inputs['B_global'])
+            total = total + self.key_gram[0] * losses[KEY_GRAM_LOSS_KEY]
         losses['loss'] = total
         return losses
+
+    def calculate_key_gram_loss(self, generated, targets):
+        """The raw key second-moment term: sum over the zipped crops of mean((G(K_gen) - G(K_tgt))^2) over the D * D entries, G(K) = K^T K / T of
+        the T x D keys of block ``dino_gram_layer`` (every token, the heads concatenated); target side under no_grad."""
+        layer = self.key_gram[1] if self.key_gram is not None else DINO_CONFIGS[self.cfg['dino_model_name']][2] - 1
+
+        def gram(img):
+            per_head = self.extractor.get_keys_from_input(img, layer_num=layer)   # [heads, T, d]
+            k = per_head.permute(1, 0, 2).reshape(per_head.shape[1], -1)          # [T, heads * d]
+            return k.transpose(0, 1) @ k / k.shape[0]
+        acc = 0.0
+        for gen_img, tgt_img in zip(generated, targets):
+            with torch.no_grad():
+                want = gram(self.global_transform(tgt_img).unsqueeze(0).to(device))
+            acc = acc + F.mse_loss(gram(self.global_transform(gen_img).unsqueeze(0).to(device)), want)
+        return acc
 
     def _feature_mse(self, feature, generated, targets):
         """sum over crops of mse(feature(T(generated_i)), feature(T(target_i))), target side under no_grad."""

@@ -50,13 +50,17 @@ DEFAULT_CFG = dict(  # conf/default/config.yaml of the reference
     # ... and the blocks whose [CLS] row the two appearance terms compare, with a weight each; null: the top block, weight 1
     dino_cls_layers=None, dino_cls_layer_weights=None,
     # ... and the blocks whose keys the identity term compares, with a weight each; null: the top block, weight 1
-    dino_id_layers=None, dino_id_layer_weights=None)
+    dino_id_layers=None, dino_id_layer_weights=None,
+    # ... and the key second-moment appearance term (the D x D Gram of a block's keys over its tokens): its weight and block; off by default
+    lambda_global_key_gram=0.0, dino_gram_layer=None)
 SSIM_LAYER_KEYS = ("dino_ssim_layers", "dino_ssim_layer_weights")
 MAX_SSIM_LAYERS = 12   # SELFSIM_MAX_LAYERS: entries of the loss kernels' by-value layer table
 CLS_LAYER_KEYS = ("dino_cls_layers", "dino_cls_layer_weights")
 MAX_CLS_LAYERS = 12    # CLS_MAX_LAYERS: entries of the layered [CLS] loss kernel's by-value table
 ID_LAYER_KEYS = ("dino_id_layers", "dino_id_layer_weights")
 MAX_ID_LAYERS = 12     # ID_MAX_LAYERS: entries of the layered key-identity kernels' by-value table
+KEY_GRAM_KEYS = ("lambda_global_key_gram", "dino_gram_layer")
+KEY_GRAM_LOSS_KEY = "loss_global_key_gram"   # the term's raw value in engine.losses(), on the steps it is active
 
 SNAPSHOT_FORMAT = 1
 # Keys of a config that do not enter a slot's arithmetic (paths, logging, and how the loop parks and checkpoints): a snapshot is restored
@@ -264,6 +268,38 @@ def id_layers_rule(c, depth):
     as many finite float32 numbers > 0 (null: all 1), refused without ``dino_id_layers``.  Shared by the slots of a sweep
     (``merge_pair_cfgs`` refuses a per-slot value).  Raises ValueError naming the key."""
     return _layers_rule(c, depth, ID_LAYER_KEYS, MAX_ID_LAYERS)
+
+
+def key_gram_rule(c, depth):
+    """The key second-moment appearance term in config ``c`` for a ViT of ``depth`` blocks, checked on the host:
+    ``None`` -- ``lambda_global_key_gram`` is 0 and ``dino_gram_layer`` null: the step launches what it launches without the keys -- or
+    ``(lambda, layer)``.  ``lambda_global_key_gram`` is a finite float32 number >= 0 (0: off); ``dino_gram_layer`` one integer block
+    index in ``[0, depth)`` (null: ``depth - 1``, the top block), refused while the weight is 0.  Shared by the slots of a sweep
+    (``merge_pair_cfgs`` refuses a per-slot value).  Raises ValueError naming the key."""
+    lk, yk = KEY_GRAM_KEYS
+    lam = _number(c, lk, _REAL, lambda v: 0 <= v < float("inf"), "a finite number >= 0")
+    with np.errstate(over="ignore"):
+        if not np.isfinite(np.float32(lam)) or (lam > 0 and not np.float32(lam) > 0):   # (the kernels take it as a float)
+            raise ValueError(f"'{lk}' must be a finite float32 number, 0 or > 0 in float32, got {lam!r}")
+    layer = c.get(yk, DEFAULT_CFG[yk])
+    if layer is None:
+        return None if lam == 0 else (float(lam), depth - 1)
+    if isinstance(layer, bool) or not isinstance(layer, _INT) or not 0 <= layer < depth:
+        raise ValueError(f"'{yk}' must be one integer block index in [0, {depth}) or null, got {layer!r}")
+    if lam == 0:
+        raise ValueError(f"'{yk}' needs '{lk}' > 0 (the term is off), got {layer!r}")
+    return float(lam), int(layer)
+
+
+def np_key_gram(kx, kb, lam):
+    """The key second-moment term restated in NumPy float64: ``kx``, ``kb`` the ``[T][D]`` keys of the generated
+    and of the target pass (every token, the heads concatenated).  With ``G(K) = K^T K / T`` and ``Delta = G(kx) - G(kb)`` returns
+    ``(raw, dK)``: ``raw = mean(Delta^2)`` over the ``D * D`` entries, ``dK = (4 lam / (T D^2)) kx Delta``, the gradient of ``lam * raw``
+    with respect to ``kx``.  The target carries no gradient."""
+    kx, kb = np.asarray(kx, np.float64), np.asarray(kb, np.float64)
+    T, D = kx.shape
+    delta = (kx.T @ kx - kb.T @ kb) / T
+    return float(np.mean(delta * delta)), (4.0 * float(lam) / (T * D * D)) * (kx @ delta)
 
 
 def np_id_layers(values, weights=None):
@@ -606,6 +642,12 @@ def active_terms(c, step_idx, entire_branch):
             "loss_global_id_B": on and c["lambda_global_identity"] > 0,
             # the image-space terms: every step, no schedule
             **{k: c.get(lam, 0.0) > 0 for k, lam in zip(IMAGE_LOSS_KEYS, IMAGE_LAMBDA_KEYS)}}
+
+
+def key_gram_active(c, step_idx):
+    """Whether step ``step_idx`` of a run with config ``c`` computes the key second-moment term (KEY_GRAM_LOSS_KEY; host arithmetic only):
+    from ``cls_warmup`` on, ordinary and entire-image steps alike, with its lambda > 0.  Beside ``active_terms``, whose dict keeps its keys."""
+    return step_idx >= c["cls_warmup"] and c.get("lambda_global_key_gram", 0.0) > 0
 
 
 def resize_output_size(h, w, size, max_size=480):
