@@ -952,6 +952,39 @@ int splice_step_key_gram_values(void* step, float* out);
 int splice_key_gram_pairs(const splice_bf16* k_x, int ldk, size_t k_ps, const splice_bf16* kT_x, int ldt_x, size_t tx_ps, const splice_bf16* kT_b,
                           int ldt_b, size_t tb_ps, int T, int D, int pairs, float scale, splice_bf16* delta, float* part, size_t part_ps, float* value,
                           float* dk, int lddk, size_t dk_ps, splice_stream_t stream);
+/* ------------------------------------------------------------------ the key second-moment term over several blocks, and its centred
+ * form.  n ascending distinct block indices, n finite weights > 0, centered 0 / 1:
+ *     raw = sum over the blocks l, ascending, of w_l * sum over the crop pairs of mean over the D * D entries of (M(K_l,x') - M(K_l,B'))^2,
+ *     M(K) = K^T K / T   (centered 0),      M(K) = K^T K / T - mu mu^T,  mu = K^T 1 / T   (centered 1),
+ * in the place and on the steps of splice_step_set_key_gram's term: lambda * raw enters word 0 last.  Block l's key gradient
+ * (4 lambda w_l / (T D^2)) (K_l,x' Delta_l - 1 (Delta_l mu_l,x')^T) -- the second part where centred -- is ADDED into the block's
+ * key-gradient buffer of the x' chain: the top block's, a structure-list block's, else one of its own that only the x' chain reads and that
+ * is zeroed on the steps the term runs.  The launch count does not depend on n: the loss launch, the finish and the key-gradient launch,
+ * and one launch for the means in front of them where centred (key_gram.hip).  The refusals of splice_step_set_key_gram hold; the two
+ * setters exclude each other, in either order. */
+int splice_step_set_key_gram_layers(void* step, float lambda, int n, const int* layers, const float* weights, int centered);
+/* The per-layer addends of the last step that computed the term, copied to the host behind a device-wide wait: out[p * n + i] = pair p's
+ * w_i * (block i's raw term, the pair's crops added in crop order), pairs * n floats.  splice_step_key_gram_values reports their float32
+ * sum, ascending from 0 -- with one crop per pair the sum of row p exactly.  Zeros before the first such step. */
+int splice_step_key_gram_layer_values(void* step, float* out);
+/* test hook: the launches of the layered term on caller buffers, one crop per pair.  Entry i < n_layers (1..12) reads k_x[i], kT_x[i],
+ * kT_b[i] and writes delta[i] ([pairs][D][D]), part[i] ([pairs][part_ps]) and dk[i], laid out and constrained as splice_key_gram_pairs'
+ * operands of the same names with the shared strides given here; weights[i] finite and > 0, scales[i] finite.  No two entries share a dk, a
+ * delta or a part pointer: refused (two entries adding into one dk would be two unordered read-modify-writes of one launch).  centered: mu
+ * ([n_layers][pairs][2][D] floats) receives the fp32 means over the tokens < T of the generated and the target pass -- a feature's tokens
+ * lane-strided ascending, the wave tree, times the rounded 1 / T -- and
+ *   delta_i = bf16(fl(acc / T - m)),  m = fl(mu_x[r] mu_x[c] - fl(mu_b[r] mu_b[c]))   (two fused multiply-adds; centered 0: fl(acc * fl(1 / T)))
+ *   part as splice_key_gram_pairs;  values[p * n_layers + i] = fl(weights[i] * (the finish sum of entry i's partials));  value[p] = their
+ *   fp32 sum, ascending from 0
+ *   dk_i[r][c] += scales[i] * fl((K_x' delta_i)[r][c] - rr[c]),  rr[c] = sum over j of delta_i[c][j] mu_x[j] in four quarters of fused
+ *   multiply-adds added as (q0 + q1) + (q2 + q3)   (centered 0: scales[i] * (K_x' delta_i)[r][c]),  rows r < T.
+ * With centered 0, entry i's delta, part and dk have the bits of splice_key_gram_pairs on its operands with scale = scales[i], and
+ * values[.][i] is fl(weights[i] * its value).  Tokens >= T reach no output bit.  Refused with nothing launched: n_layers outside 1..12, a
+ * null table or entry pointer, and what splice_key_gram_pairs refuses. */
+int splice_key_gram_layers_pairs(int n_layers, const splice_bf16* const* k_x, const splice_bf16* const* kT_x, const splice_bf16* const* kT_b,
+                                 splice_bf16* const* delta, float* const* part, float* const* dk, const float* weights, const float* scales, int ldk,
+                                 size_t k_ps, int ldt_x, size_t tx_ps, int ldt_b, size_t tb_ps, int T, int D, int pairs, int centered, size_t part_ps,
+                                 float* values, float* value, float* mu, int lddk, size_t dk_ps, splice_stream_t stream);
 /* splice_total_loss_pairs as a handle with a loss trace launches it (splice_step_set_loss_trace): dev_t (device) holds step index + 1,
  * and words 0-5 of row step index of trace ([capacity][pairs][8], device) receive pair p's out8 values, a row at or beyond capacity
  * left out.  stop (may be NULL; device, [pairs] records) runs the instance of a handle with the stop rule, whose rule is window (>= 1),

@@ -259,6 +259,10 @@ _SIGNATURES = {
     "splice_step_set_key_gram": ([_vp, _f, _i], _i),
     "splice_step_key_gram_values": ([_vp, _vp], _i),
     "splice_key_gram_pairs": ([_vp, _i, _sz, _vp, _i, _sz, _vp, _i, _sz, _i, _i, _i, _f, _vp, _vp, _sz, _vp, _vp, _i, _sz, _vp], _i),
+    # ... over several blocks, and centred
+    "splice_step_set_key_gram_layers": ([_vp, _f, _i, _vp, _vp, _i], _i),
+    "splice_step_key_gram_layer_values": ([_vp, _vp], _i),
+    "splice_key_gram_layers_pairs": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _sz, _i, _sz, _i, _sz, _i, _i, _i, _i, _sz, _vp, _vp, _vp, _i, _sz, _vp], _i),
     "splice_image_terms_value": ([_vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _sz, _i, _vp], _i),
     "splice_image_terms_grad_add": ([_vp, _vp, _vp, _i, _i, _i, _f, _vp], _i),
     "splice_total_loss_pairs_img": ([_vp, _sz, _i, _f, _f, _f, _f, _f, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _f, _f, _vp], _i),

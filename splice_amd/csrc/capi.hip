@@ -240,6 +240,26 @@ int splice_key_gram_pairs(const splice_bf16* k_x, int ldk, size_t k_ps, const sp
     if (rc != SPLICE_OK) return finish(rc, who);
     return finish(key_gram_dk_launch(a, pairs, 1, ST(stream)), who);
 }
+/* the launches of the key second-moment term over several blocks (splice_step_set_key_gram_layers) on caller buffers, one crop per pair */
+int splice_key_gram_layers_pairs(int n_layers, const splice_bf16* const* k_x, const splice_bf16* const* kT_x, const splice_bf16* const* kT_b,
+                                 splice_bf16* const* delta, float* const* part, float* const* dk, const float* weights, const float* scales, int ldk,
+                                 size_t k_ps, int ldt_x, size_t tx_ps, int ldt_b, size_t tb_ps, int T, int D, int pairs, int centered, size_t part_ps,
+                                 float* values, float* value, float* mu, int lddk, size_t dk_ps, splice_stream_t stream) {
+    const char* who = "splice_key_gram_layers_pairs";
+    if (n_layers < 1 || n_layers > KEY_GRAM_MAX_LAYERS || !k_x || !kT_x || !kT_b || !delta || !part || !dk || !weights || !scales) return finish(SPLICE_ERR_ARG, who);
+    KeyGramLayers t = {};
+    t.n = n_layers; t.centered = centered ? 1 : 0;
+    t.ldt_x = ldt_x; t.ldt_b = ldt_b; t.ldk = ldk; t.tx_ps = tx_ps; t.tb_ps = tb_ps; t.k_ps = k_ps; t.T = T; t.D = D; t.part_ps = part_ps;
+    t.lddk = lddk; t.dk_ps = dk_ps; t.values = values; t.value = value; t.mu = mu;
+    for (int i = 0; i < n_layers; ++i) {
+        KeyGramLayer& e = t.e[i];
+        e.kT_x = kT_x[i]; e.kT_b = kT_b[i]; e.k_x = k_x[i]; e.dk = dk[i]; e.delta = delta[i]; e.part = part[i]; e.weight = weights[i]; e.scale = scales[i];
+    }
+    if (int rc = key_gram_layers_check(t, pairs, 1)) return finish(rc, who);   // (nothing launched on a refusal)
+    const int rc = key_gram_layers_loss_launch(t, pairs, 1, ST(stream));
+    if (rc != SPLICE_OK) return finish(rc, who);
+    return finish(key_gram_layers_dk_launch(t, pairs, 1, ST(stream)), who);
+}
 int splice_mse_pairs(const float* a, int lda, size_t a_ps, const float* b, int ldb, size_t b_ps, int rows, int cols, float loss_weight,
                      float grad_weight, float* part, size_t part_ps, float* grad, int ldg, size_t g_ps, int pairs, const float* grad_tab,
                      splice_stream_t stream) {

@@ -237,6 +237,39 @@ int key_gram_check(const KeyGram& a, int pairs, int crops);
 int key_gram_loss_launch(const KeyGram& a, int pairs, int crops, hipStream_t s);
 // dk[rows < T] += scale * k_x * delta for every slot
 int key_gram_dk_launch(const KeyGram& a, int pairs, int crops, hipStream_t s);
+// The term over several blocks, optionally centred: the layer is a grid dimension of instances of their own, the
+// table goes by value.  Entry i holds block i's operands (the KeyGram fields of the same names; delta [slots][D][D], part [slots][part_ps]),
+// its weight w_i (finite, > 0) and its scale c_i = fl(fl(4 lambda / (T D^2)) * w_i); strides, T and D are shared.  No two entries share
+// a dk, delta or part pointer (refused).  centered: M(K) = K^T K / T - mu mu^T with mu the fp32 mean of the tokens < T; mu then holds
+// [n][slots][2][D] floats (x' row, target row), written by a launch of its own in front of the loss launch.
+constexpr int KEY_GRAM_MAX_LAYERS = 12;
+struct KeyGramLayer {
+    const bf16_t* kT_x;
+    const bf16_t* kT_b;
+    const bf16_t* k_x;
+    float* dk;
+    bf16_t* delta;
+    float* part;
+    float weight, scale;
+};
+struct KeyGramLayers {
+    int n, centered;
+    int ldt_x, ldt_b, ldk;
+    size_t tx_ps, tb_ps, k_ps;
+    int T, D;
+    size_t part_ps;
+    int lddk;
+    size_t dk_ps;
+    float* values;     // [pairs][n]: w_i * (block i's raw term, the pair's crops added in crop order)
+    float* value;      // [pairs]: the fp32 sum of the pair's values, ascending from 0
+    float* mu;         // centred only
+    KeyGramLayer e[KEY_GRAM_MAX_LAYERS];
+};
+int key_gram_layers_check(const KeyGramLayers& t, int pairs, int crops);
+// (the mean launch where centred,) the loss launch and its one-wave finish: delta and part of every entry, values and value; dk is not touched
+int key_gram_layers_loss_launch(const KeyGramLayers& t, int pairs, int crops, hipStream_t s);
+// dk_i[rows < T] += c_i * (k_x delta_i - 1 (delta_i mu_x)^T) for every entry and slot (the second part where centred)
+int key_gram_layers_dk_launch(const KeyGramLayers& t, int pairs, int crops, hipStream_t s);
 // 2-D strided MSE: loss_accum[0] += weight * mean((a-b)^2); grad (optional) = weight * 2 (a-b) / (rows*cols)
 int mse_launch(const float* a, int lda, const float* b, int ldb, int rows, int cols, float weight, float* loss_accum,
                float* grad, int ldg, hipStream_t s);

@@ -62,6 +62,9 @@ struct VitView {
     float* dk_kg = nullptr;
     float* dk_kg_own = nullptr;
     std::vector<const float*> pk_x;
+    // splice_step_set_key_gram_layers: the same per entry of the list (pk_x then holds pk plus every block of its own)
+    float* dk_kgl[KEY_GRAM_MAX_LAYERS] = {};
+    float* dk_kgl_own[KEY_GRAM_MAX_LAYERS] = {};
 };
 
 struct SpliceStep {
@@ -204,6 +207,13 @@ struct SpliceStep {
     int kg_layer = -1;
     bf16_t* kg_delta = nullptr;
     float *kg_part = nullptr, *kg_value = nullptr;
+    // ... over several blocks (splice_step_set_key_gram_layers): kg_n entries (0: the one-block term above), ascending
+    // blocks, their weights, the centred flag; kg_delta / kg_part then hold [kg_n][Pc]... ; kg_values: the per-layer addends, [pairs][kg_n];
+    // kg_mu: the fp32 means of the centred form, [kg_n][Pc][2][D]
+    int kg_n = 0, kg_centered = 0;
+    int kg_layers[KEY_GRAM_MAX_LAYERS] = {};
+    float kg_weights[KEY_GRAM_MAX_LAYERS] = {};
+    float *kg_values = nullptr, *kg_mu = nullptr;
 };
 
 static size_t arena_floats(const SpliceStep* st) { return st->astride ? st->pairs * st->astride : (size_t)st->nparams; }   // of all pairs' arenas
@@ -1288,6 +1298,12 @@ static unsigned long long key_gram_salt(const SpliceStep* st) {
     unsigned long long h = 1469598103934665603ull ^ 0xc2b2ae3d27d4eb4full;   // FNV-1a over (block, weight bits), from a basis of its own
     for (unsigned long long v : {(unsigned long long)st->kg_layer, (unsigned long long)w})
         for (int k = 0; k < 8; ++k) { h ^= (v >> (8 * k)) & 0xff; h *= 1099511628211ull; }
+    for (int i = 0; i < st->kg_n; ++i) {   // the list: its length and flag, then (block, weight bits) in list order
+        unsigned wi;
+        memcpy(&wi, &st->kg_weights[i], sizeof(wi));
+        for (unsigned long long v : {(unsigned long long)(i == 0 ? 0x100 + 2 * st->kg_n + st->kg_centered : 0), (unsigned long long)st->kg_layers[i], (unsigned long long)wi})
+            for (int k = 0; k < 8; ++k) { h ^= (v >> (8 * k)) & 0xff; h *= 1099511628211ull; }
+    }
     return h | 4ull;   // (never 0: a handle with the term is never keyed like one without)
 }
 // The key second-moment appearance term (include/splice_hip.h has the term): its weight, finite and > 0, and its block.  The global ViT
@@ -1339,6 +1355,77 @@ int splice_step_key_gram_values(void* h, float* out) {
     if (!(st->kg_lambda > 0.f)) { splice_set_error("%s: the handle has no key second-moment term (splice_step_set_key_gram)", who); return SPLICE_ERR_STATE; }
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(out, st->kg_value, (size_t)st->pairs * sizeof(float), hipMemcpyDeviceToHost));
+    return SPLICE_OK;
+}
+// The key second-moment term over several blocks, optionally centred (include/splice_hip.h has the term): the list version of
+// splice_step_set_key_gram, with its refusals; the two exclude each other in either order ("the term is set once").  Every named block
+// below the top gets its transposed bf16 copy (splice_vit_ctx_set_transposed_layers adds to the blocks already named).  Key-gradient
+// buffers are per block as there: pk's where the block has one (d_keys at the top, the structure list's: that term stores, this one adds),
+// else one of its own, zeroed here and over its x' passes on the steps the term runs; only the x' chain's table (pk_x) carries those.
+int splice_step_set_key_gram_layers(void* h, float lambda, int n, const int* layers, const float* weights, int centered) {
+    SpliceStep* st = (SpliceStep*)h;
+    const char* who = "splice_step_set_key_gram_layers";
+    if (!st || !layers || !weights) return SPLICE_ERR_ARG;
+    VitView& v = st->vg;
+    const int depth = v.depth;
+    if (!(lambda > 0.f) || !(lambda <= 3.402823466e+38f)) { splice_set_error("%s: lambda must be finite and > 0, got %g", who, (double)lambda); return SPLICE_ERR_ARG; }
+    if (n < 1 || n > depth || n > KEY_GRAM_MAX_LAYERS) { splice_set_error("%s: needs 1..%d layers, got %d", who, depth < KEY_GRAM_MAX_LAYERS ? depth : KEY_GRAM_MAX_LAYERS, n); return SPLICE_ERR_ARG; }
+    for (int i = 0; i < n; ++i) {
+        if (layers[i] < 0 || layers[i] >= depth || (i > 0 && layers[i] <= layers[i - 1])) {
+            splice_set_error("%s: layers must be ascending distinct block indices in [0, %d), got layers[%d] = %d", who, depth, i, layers[i]);
+            return SPLICE_ERR_ARG;
+        }
+        if (!(weights[i] > 0.f) || !(weights[i] <= 3.402823466e+38f)) {
+            splice_set_error("%s: weights must be finite and > 0, got weights[%d] = %g", who, i, (double)weights[i]);
+            return SPLICE_ERR_ARG;
+        }
+    }
+    if (centered != 0 && centered != 1) { splice_set_error("%s: centered must be 0 or 1, got %d", who, centered); return SPLICE_ERR_ARG; }
+    if (int rc = rule_setter_ok(st, who, "the term is set")) return rc;
+    if (st->cfg.fp8_selfsim) { splice_set_error("%s: not with fp8_selfsim (the term reads the bf16 key copies of a bf16 forward)", who); return SPLICE_ERR_STATE; }
+    if (st->kg_lambda > 0.f) { splice_set_error("%s: the term is set once", who); return SPLICE_ERR_STATE; }
+    if (v.D % 64) { splice_set_error("%s: needs an embedding width that is a multiple of 64, got %d", who, v.D); return SPLICE_ERR_ARG; }
+    if (st->pairs > 1 && st->na != st->nb) { splice_set_error("%s: not with several pairs of nA != nB crops (%d, %d)", who, st->na, st->nb); return SPLICE_ERR_STATE; }
+    int below[KEY_GRAM_MAX_LAYERS], nbelow = 0;
+    for (int i = 0; i < n; ++i)
+        if (layers[i] != depth - 1) below[nbelow++] = layers[i];
+    if (nbelow) RC(splice_vit_ctx_set_transposed_layers(v.ctx, nbelow, below));
+    v.pk_x = v.pk;
+    for (int i = 0; i < n; ++i) {
+        const int l = layers[i];
+        if (v.pk[l]) { v.dk_kgl[i] = const_cast<float*>(v.pk[l]); continue; }
+        RC(salloc(st, &v.dk_kgl_own[i], (size_t)v.rows * v.D));
+        HIPCHK(hipMemset(v.dk_kgl_own[i], 0, (size_t)v.rows * v.D * sizeof(float)));
+        v.dk_kgl[i] = v.dk_kgl_own[i];
+        v.pk_x[l] = v.dk_kgl[i];
+    }
+    const size_t slots = (size_t)st->pairs * (st->na < st->nb ? st->na : st->nb), tiles = key_gram_tiles(v.D);
+    RC(salloc(st, &st->kg_delta, n * slots * v.D * v.D));
+    RC(salloc(st, &st->kg_part, n * slots * tiles));
+    RC(salloc(st, &st->kg_value, (size_t)st->pairs));
+    RC(salloc(st, &st->kg_values, (size_t)st->pairs * n));
+    HIPCHK(hipMemset(st->kg_delta, 0, n * slots * v.D * v.D * sizeof(bf16_t)));
+    HIPCHK(hipMemset(st->kg_part, 0, n * slots * tiles * sizeof(float)));
+    HIPCHK(hipMemset(st->kg_value, 0, (size_t)st->pairs * sizeof(float)));
+    HIPCHK(hipMemset(st->kg_values, 0, (size_t)st->pairs * n * sizeof(float)));
+    if (centered) {
+        RC(salloc(st, &st->kg_mu, n * slots * 2 * v.D));
+        HIPCHK(hipMemset(st->kg_mu, 0, n * slots * 2 * v.D * sizeof(float)));
+    }
+    st->graphs.retire();
+    st->kg_lambda = lambda; st->kg_layer = layers[n - 1]; st->kg_n = n; st->kg_centered = centered;
+    for (int i = 0; i < n; ++i) { st->kg_layers[i] = layers[i]; st->kg_weights[i] = weights[i]; }
+    return SPLICE_OK;
+}
+// The per-layer addends of the term of the last step that computed it, copied to the HOST behind a device-wide wait:
+// out[p * n + i], pairs * n floats; zeros before the first such step.
+int splice_step_key_gram_layer_values(void* h, float* out) {
+    SpliceStep* st = (SpliceStep*)h;
+    const char* who = "splice_step_key_gram_layer_values";
+    if (!st || !out) { splice_set_error("%s: needs a handle and out", who); return SPLICE_ERR_ARG; }
+    if (!st->kg_n) { splice_set_error("%s: the handle has no key second-moment layers (splice_step_set_key_gram_layers)", who); return SPLICE_ERR_STATE; }
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, st->kg_values, (size_t)st->pairs * st->kg_n * sizeof(float), hipMemcpyDeviceToHost));
     return SPLICE_OK;
 }
 // Start the handle at step next_step_idx of a run other handles carried so far (a resumed run, a compacted engine; DESIGN.md section
@@ -1569,6 +1656,9 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
             if (dk) RC(dev_zero_launch(dk + pY * passD, Pb * passD * sizeof(float), s2));
         // a block only the key second-moment term names: its x' passes alone (no other chain reads it), on the steps the term adds into them
         if (kg_on && vg.dk_kg_own) RC(dev_zero_launch(vg.dk_kg_own + pX * passD, Pa * passD * sizeof(float), s2));
+        if (kg_on)
+            for (float* dk : vg.dk_kgl_own)   // ... and of every block only the term's list names
+                if (dk) RC(dev_zero_launch(dk + pX * passD, Pa * passD * sizeof(float), s2));
         if (t[L_GLOBAL_SSIM].on) {   // target self-similarity S* of A' (util/losses.py:79)
             RC(ssim_batch(st, vg, pA, pX, Pa, t[L_GLOBAL_SSIM], L_GLOBAL_SSIM, &sb, layered ? &sl : nullptr));
             RC(selfsim_target_launch(sb, s2, layered ? &sl : nullptr));
@@ -1589,7 +1679,29 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
     // ---- losses on the global batch
     if (do_v) {
         if (t[L_GLOBAL_SSIM].on) RC(selfsim_loss_launch(sb, s, layered ? &sl : nullptr));
-        if (kg_on) {   // keys of x' against keys of B', crop i with crop i, through their D x D second moments; behind selfsim_dk_kernel: that stores, this adds
+        if (kg_on && st->kg_n) {   // the term over its list of blocks: one table, the layer a grid dimension
+            KeyGramLayers kt = {};
+            kt.n = st->kg_n; kt.centered = st->kg_centered;
+            kt.ldt_x = kt.ldt_b = vg.rows; kt.tx_ps = kt.tb_ps = (size_t)vg.Tld; kt.ldk = 3 * vg.D; kt.k_ps = (size_t)vg.Tld * 3 * vg.D;
+            kt.T = vg.T; kt.D = vg.D; kt.part_ps = (size_t)key_gram_tiles(vg.D); kt.lddk = vg.D; kt.dk_ps = passD;
+            kt.values = st->kg_values; kt.value = st->kg_value; kt.mu = st->kg_mu;
+            const size_t slots = (size_t)pairs * nc;
+            const float c0 = 4.0f * st->kg_lambda / ((float)vg.T * (float)vg.D * (float)vg.D);
+            for (int i = 0; i < st->kg_n; ++i) {
+                const int l = st->kg_layers[i];
+                bf16_t *qkv = nullptr, *qkvT = nullptr;
+                RC(splice_vit_get_tensor(vg.ctx, 1, l, (void**)&qkv));
+                RC(splice_vit_get_tensor(vg.ctx, l == vg.depth - 1 ? 6 : 8, l, (void**)&qkvT));
+                KeyGramLayer& e = kt.e[i];
+                e.kT_x = qkvT + (size_t)vg.D * vg.rows + (size_t)pX * vg.Tld; e.kT_b = qkvT + (size_t)vg.D * vg.rows + (size_t)pB * vg.Tld;
+                e.k_x = qkv + (size_t)pX * vg.Tld * 3 * vg.D + vg.D;
+                e.delta = st->kg_delta + i * slots * vg.D * vg.D; e.part = st->kg_part + i * slots * kt.part_ps;
+                e.dk = vg.dk_kgl[i] + pX * passD;
+                e.weight = st->kg_weights[i]; e.scale = c0 * e.weight;   // (one rounding more than the one-block scale; weight 1: its bits)
+            }
+            RC(key_gram_layers_loss_launch(kt, pairs, nc, s));
+            RC(key_gram_layers_dk_launch(kt, pairs, nc, s));
+        } else if (kg_on) {   // keys of x' against keys of B', crop i with crop i, through their D x D second moments; behind selfsim_dk_kernel: that stores, this adds
             const int l = st->kg_layer;
             bf16_t *qkv = nullptr, *qkvT = nullptr;
             RC(splice_vit_get_tensor(vg.ctx, 1, l, (void**)&qkv));

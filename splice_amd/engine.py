@@ -88,6 +88,11 @@ class MultiPairEngine:
             self.cfg.update(dino_id_layers=list(self.id_layers[0]), dino_id_layer_weights=list(self.id_layers[1]))
         # the key second-moment appearance term: None -- off, today's launches -- or (lambda, block); the config then
         # holds the block it runs on (what a snapshot is compared on)
+        # ... over a list of blocks, or centred: key_gram_layers is None -- the one-block term or none, today's launches --
+        # or (lambda, layers, weights, centered); the config holds the canonical spelling (a one-entry list of weight 1, uncentred, IS
+        # dino_gram_layer), and key_gram stays key_gram_rule of that config: not None exactly where the term is on
+        self.cfg.update(key_gram_canonical(self.cfg, depth))
+        self.key_gram_layers = key_gram_layers_rule(self.cfg, depth)
         self.key_gram = key_gram_rule(self.cfg, depth)
         if self.key_gram is not None:
             if fp8_mode(fp8):
@@ -95,7 +100,7 @@ class MultiPairEngine:
             nA_, nB_ = (int(n_crops), int(n_crops)) if isinstance(n_crops, int) else (int(n_crops[0]), int(n_crops[1]))
             if len(gen_states) > 1 and nA_ != nB_:
                 raise ValueError(f"'lambda_global_key_gram': not with several pairs of different crop counts per side, got n_crops = {(nA_, nB_)}")
-            self.cfg.update(lambda_global_key_gram=self.key_gram[0], dino_gram_layer=self.key_gram[1])
+            self.cfg.update(lambda_global_key_gram=self.key_gram[0], dino_gram_layer=None if self.key_gram_layers is not None else self.key_gram[1])
         P_in = len(gen_states)
         self.cfgs = [self.cfg] * P_in
         self._pair_lambdas = self._pair_lr = False
@@ -285,7 +290,12 @@ class MultiPairEngine:
                        "step_set_id_layers")
         # the key second-moment term (shared by the slots): three launches on the x' chain from cls_warmup on; before the first step, behind
         # the structure and identity layers (shared key-gradient buffers).  The default: the call is not made
-        if self.key_gram is not None:
+        if self.key_gram_layers is not None:   # (the list, or the centred form: the layered launches)
+            lam, layers, weights, centered = self.key_gram_layers
+            n = len(layers)
+            _lib.check(_lib.lib().splice_step_set_key_gram_layers(self.handle, C.c_float(lam), n, (C.c_int * n)(*layers), (C.c_float * n)(*weights), int(centered)),
+                       "step_set_key_gram_layers")
+        elif self.key_gram is not None:
             _lib.check(_lib.lib().splice_step_set_key_gram(self.handle, C.c_float(self.key_gram[0]), int(self.key_gram[1])), "step_set_key_gram")
         self._lr_scale = [1.0] * P   # the host's copy of every slot's lr scale, refreshed with the stop steps
         self._stopped = [None] * P   # the host's copy of every slot's stop step, refreshed by stop_state()
@@ -664,6 +674,24 @@ class MultiPairEngine:
             raise RuntimeError(f"key_gram_value: slot {pair} is parked (stop_compact): its value left the device with its handle")
         return vals[row]
 
+    def key_gram_layer_values(self, pair=None):
+        """The per-layer addends of the key second-moment term over ``dino_gram_layers`` of the last step that computed
+        it, copied from the device (waits for the device): a float32 array ``[n]`` for ``pair`` -- ``w_i`` times block i's raw term, the pair's
+        zipped crops added in crop order; ``key_gram_value`` is their float32 sum, ascending from 0 (with one crop per pair exactly) -- a
+        list of such arrays over the live slots for ``pair=None``.  Zeros before the first such step."""
+        if self.key_gram_layers is None:
+            raise RuntimeError("key_gram_layer_values: the term runs on one block or is off ('dino_gram_layers' is null and 'dino_gram_centered' false)")
+        n = len(self.key_gram_layers[1])
+        buf = (C.c_float * (self.P * n))()
+        _lib.check(_lib.lib().splice_step_key_gram_layer_values(self.handle, buf), "step_key_gram_layer_values")
+        vals = np.frombuffer(buf, dtype=np.float32).reshape(self.P, n).copy()
+        if pair is None and self.PAIR_NONE is None:
+            return list(vals)
+        row = self._row(self.PAIR_NONE if pair is None else pair)
+        if row is None:
+            raise RuntimeError(f"key_gram_layer_values: slot {pair} is parked (stop_compact): its values left the device with its handle")
+        return vals[row]
+
     def ssim_layer_values(self, pair=None, entire=False):
         """The per-layer addends of the last step's structure term (``dino_ssim_layers``), copied from the device
         (waits for the current stream): a float32 array with one entry per block of the canonical list, ``w_l * mse(S_l, S*_l)`` as the
@@ -907,7 +935,9 @@ class MultiScaleEngine:
         if id_layers_rule(self.cfg, vit_engine.depth if vit_engine is not None else synth.DINO_CONFIGS[self.cfg["dino_model_name"]][2]) is not None:
             raise NotImplementedError("dino_id_layers: the layer table is set on a whole fused step; MultiScaleEngine runs each scale as a gradient-only "
                                       "or phase-mode handle, which refuses it")
-        if key_gram_rule(self.cfg, vit_engine.depth if vit_engine is not None else synth.DINO_CONFIGS[self.cfg["dino_model_name"]][2]) is not None:
+        key_gram_layers_rule(self.cfg, vit_engine.depth if vit_engine is not None else synth.DINO_CONFIGS[self.cfg["dino_model_name"]][2])   # (a bad value is refused by name here too)
+        if key_gram_rule(dict(self.cfg, dino_gram_layer=None if self.cfg.get("dino_gram_layers") is not None else self.cfg.get("dino_gram_layer")),
+                         vit_engine.depth if vit_engine is not None else synth.DINO_CONFIGS[self.cfg["dino_model_name"]][2]) is not None:
             raise NotImplementedError("lambda_global_key_gram: the term is set on a whole fused step; MultiScaleEngine runs each scale as a gradient-only "
                                       "or phase-mode handle, which refuses it")
         self.ema_rule = ema_rule(self.cfg)

@@ -8,8 +8,8 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
-from .engine import (CLS_LAYER_KEYS, ID_LAYER_KEYS, KEY_GRAM_KEYS, KEY_GRAM_LOSS_KEY, SSIM_LAYER_KEYS, cls_layers_rule, id_layers_rule, key_gram_rule,
-                     resize_output_size, ssim_layers_rule)
+from .engine import (CLS_LAYER_KEYS, ID_LAYER_KEYS, KEY_GRAM_KEYS, KEY_GRAM_LAYER_KEYS, KEY_GRAM_LOSS_KEY, SSIM_LAYER_KEYS, cls_layers_rule, id_layers_rule,
+                     key_gram_canonical, key_gram_layers_rule, key_gram_rule, resize_output_size, ssim_layers_rule)
 from .extractor import VitExtractor
 from .synth import DINO_CONFIGS
 
@@ -102,7 +102,11 @@ class LossG(torch.nn.Module):
         # ... and the blocks of the key-identity term
         self.id_layers = id_layers_rule({k: cfg.get(k) for k in ID_LAYER_KEYS}, DINO_CONFIGS[cfg['dino_model_name']][2])
         # ... and the key second-moment appearance term: None -- off -- or (lambda, block)
-        self.key_gram = key_gram_rule({k: cfg[k] for k in KEY_GRAM_KEYS if k in cfg}, DINO_CONFIGS[cfg['dino_model_name']][2])
+        # ... over a list of blocks, or centred: None, or (lambda, layers, weights, centered)
+        kg_cfg = {k: cfg[k] for k in KEY_GRAM_KEYS + KEY_GRAM_LAYER_KEYS if k in cfg}
+        kg_cfg.update(key_gram_canonical(kg_cfg, DINO_CONFIGS[cfg['dino_model_name']][2]))
+        self.key_gram_layers = key_gram_layers_rule(kg_cfg, DINO_CONFIGS[cfg['dino_model_name']][2])
+        self.key_gram = key_gram_rule(kg_cfg, DINO_CONFIGS[cfg['dino_model_name']][2])
         self._features = {
             "self_sim": lambda img: self.extractor.get_keys_self_sim_from_input(img, layer_num=_LAST_LAYER),
             "cls": lambda img: self.extractor.get_feature_from_input(img)[-1][0, 0, :],
@@ -146,16 +150,26 @@ class LossG(torch.nn.Module):
         """The raw key second-moment term: sum over the zipped crops of mean((G(K_gen) - G(K_tgt))^2) over the D * D entries, G(K) = K^T K / T of
         the T x D keys of block ``dino_gram_layer`` (every token, the heads concatenated); target side under no_grad."""
         layer = self.key_gram[1] if self.key_gram is not None else DINO_CONFIGS[self.cfg['dino_model_name']][2] - 1
+        # over ``dino_gram_layers`` (DESIGN.md section 9o): the sum over the blocks, ascending, of weight * that; ``dino_gram_centered``: G(K) less
+        # the outer product of the mean key
+        layers, weights, centered = ([layer], [1.0], False) if getattr(self, "key_gram_layers", None) is None else self.key_gram_layers[1:]
 
-        def gram(img):
-            per_head = self.extractor.get_keys_from_input(img, layer_num=layer)   # [heads, T, d]
+        def gram(img, l):
+            per_head = self.extractor.get_keys_from_input(img, layer_num=l)       # [heads, T, d]
             k = per_head.permute(1, 0, 2).reshape(per_head.shape[1], -1)          # [T, heads * d]
-            return k.transpose(0, 1) @ k / k.shape[0]
+            g = k.transpose(0, 1) @ k / k.shape[0]
+            if centered:
+                mu = k.mean(0)
+                g = g - torch.outer(mu, mu)
+            return g
         acc = 0.0
-        for gen_img, tgt_img in zip(generated, targets):
-            with torch.no_grad():
-                want = gram(self.global_transform(tgt_img).unsqueeze(0).to(device))
-            acc = acc + F.mse_loss(gram(self.global_transform(gen_img).unsqueeze(0).to(device)), want)
+        for l, w in zip(layers, weights):
+            term = 0.0
+            for gen_img, tgt_img in zip(generated, targets):
+                with torch.no_grad():
+                    want = gram(self.global_transform(tgt_img).unsqueeze(0).to(device), l)
+                term = term + F.mse_loss(gram(self.global_transform(gen_img).unsqueeze(0).to(device), l), want)
+            acc = acc + (term if w == 1.0 else w * term)
         return acc
 
     def _feature_mse(self, feature, generated, targets):

@@ -52,7 +52,9 @@ DEFAULT_CFG = dict(  # conf/default/config.yaml of the reference
     # ... and the blocks whose keys the identity term compares, with a weight each; null: the top block, weight 1
     dino_id_layers=None, dino_id_layer_weights=None,
     # ... and the key second-moment appearance term (the D x D Gram of a block's keys over its tokens): its weight and block; off by default
-    lambda_global_key_gram=0.0, dino_gram_layer=None)
+    lambda_global_key_gram=0.0, dino_gram_layer=None,
+    # ... over a list of blocks with a weight each, and its centred (covariance) form; null / false: the one-block uncentred term
+    dino_gram_layers=None, dino_gram_layer_weights=None, dino_gram_centered=False)
 SSIM_LAYER_KEYS = ("dino_ssim_layers", "dino_ssim_layer_weights")
 MAX_SSIM_LAYERS = 12   # SELFSIM_MAX_LAYERS: entries of the loss kernels' by-value layer table
 CLS_LAYER_KEYS = ("dino_cls_layers", "dino_cls_layer_weights")
@@ -60,6 +62,8 @@ MAX_CLS_LAYERS = 12    # CLS_MAX_LAYERS: entries of the layered [CLS] loss kerne
 ID_LAYER_KEYS = ("dino_id_layers", "dino_id_layer_weights")
 MAX_ID_LAYERS = 12     # ID_MAX_LAYERS: entries of the layered key-identity kernels' by-value table
 KEY_GRAM_KEYS = ("lambda_global_key_gram", "dino_gram_layer")
+KEY_GRAM_LAYER_KEYS = ("dino_gram_layers", "dino_gram_layer_weights", "dino_gram_centered")
+MAX_KEY_GRAM_LAYERS = 12   # KEY_GRAM_MAX_LAYERS: entries of the layered key second-moment kernels' by-value table
 KEY_GRAM_LOSS_KEY = "loss_global_key_gram"   # the term's raw value in engine.losses(), on the steps it is active
 
 SNAPSHOT_FORMAT = 1
@@ -289,6 +293,82 @@ def key_gram_rule(c, depth):
     if lam == 0:
         raise ValueError(f"'{yk}' needs '{lk}' > 0 (the term is off), got {layer!r}")
     return float(lam), int(layer)
+
+
+def key_gram_layers_rule(c, depth):
+    """The key second-moment term over several blocks, or centred, in config ``c`` for a ViT of ``depth`` blocks,
+    checked on the host: ``None`` -- the three KEY_GRAM_LAYER_KEYS at their defaults, or a one-entry ``dino_gram_layers`` with weight 1 and
+    ``dino_gram_centered`` false, which IS the one-block term of ``key_gram_rule`` (``key_gram_canonical`` spells it that way) -- or
+    ``(lambda, layers, weights, centered)``, the canonical form: the block indices ascending, each weight beside its block.
+    ``dino_gram_layers`` is a list of 1..``min(depth, MAX_KEY_GRAM_LAYERS)`` distinct integers in ``[0, depth)``, the top block not required,
+    refused together with a non-null ``dino_gram_layer``; ``dino_gram_layer_weights`` a list of as many finite float32 numbers > 0 (null: all
+    1), refused without the list; ``dino_gram_centered`` a bool: with it and no list the term runs centred on ``dino_gram_layer`` (null: the
+    top block).  The list and ``dino_gram_centered: true`` are refused while ``lambda_global_key_gram`` is 0.  Shared by the slots of a
+    sweep (``merge_pair_cfgs`` refuses a per-slot value).  Raises ValueError naming the key."""
+    lk, wk, ck = KEY_GRAM_LAYER_KEYS
+    centered = c.get(ck, DEFAULT_CFG[ck])
+    if not isinstance(centered, (bool, np.bool_)):
+        raise ValueError(f"'{ck}' must be true or false, got {centered!r}")
+    centered = bool(centered)
+    listed = c.get(lk, DEFAULT_CFG[lk]) is not None
+    canon = _layers_rule(c, depth, (lk, wk), MAX_KEY_GRAM_LAYERS)   # (None for [depth - 1] with weight 1 too)
+    single = c.get(KEY_GRAM_KEYS[1], DEFAULT_CFG[KEY_GRAM_KEYS[1]])
+    if listed and single is not None:
+        raise ValueError(f"'{lk}' and '{KEY_GRAM_KEYS[1]}' name the blocks of one term: give one of them, got {c.get(lk)!r} and {single!r}")
+    base = key_gram_rule({KEY_GRAM_KEYS[0]: c.get(KEY_GRAM_KEYS[0], DEFAULT_CFG[KEY_GRAM_KEYS[0]]), KEY_GRAM_KEYS[1]: None if listed else single}, depth)
+    if base is None:
+        for key, on in ((lk, listed), (ck, centered)):
+            if on:
+                raise ValueError(f"'{key}' needs '{KEY_GRAM_KEYS[0]}' > 0 (the term is off), got {c.get(key)!r}")
+        return None
+    if not listed:
+        return (base[0], [base[1]], [1.0], True) if centered else None
+    layers, weights = canon if canon is not None else ([depth - 1], [1.0])
+    if len(layers) == 1 and weights == [1.0] and not centered:
+        return None
+    return base[0], layers, weights, centered
+
+
+def key_gram_canonical(c, depth):
+    """The values of KEY_GRAM_KEYS[1] and KEY_GRAM_LAYER_KEYS a run with config ``c`` is recorded (and a snapshot compared) under: a
+    one-entry list with weight 1, uncentred, becomes ``dino_gram_layer``; any other list or the centred form becomes the canonical list with
+    ``dino_gram_layer`` null; a config without the new keys keeps what ``key_gram_rule`` makes of it.  Checks what the two rules check."""
+    lk, wk, ck = KEY_GRAM_LAYER_KEYS
+    rule = key_gram_layers_rule(c, depth)
+    if rule is not None:
+        return {KEY_GRAM_KEYS[1]: None, lk: list(rule[1]), wk: list(rule[2]), ck: rule[3]}
+    out = {lk: None, wk: None, ck: False}
+    layers = c.get(lk, DEFAULT_CFG[lk])
+    if layers is not None:
+        out[KEY_GRAM_KEYS[1]] = int(layers[0])
+    else:
+        base = key_gram_rule(c, depth)
+        out[KEY_GRAM_KEYS[1]] = None if base is None else base[1]
+    return out
+
+
+def np_key_gram_layers(kx_list, kb_list, lam, weights=None, centered=False):
+    """The term over several blocks restated in NumPy float64: ``kx_list[i]``, ``kb_list[i]`` the ``[T][D]`` keys of
+    block i of the generated and of the target pass; ``weights`` one number per block (None: all 1).  With ``M(K) = K^T K / T`` --
+    ``centered``: ``- mu mu^T``, ``mu = K^T 1 / T`` -- and ``Delta_i = M(kx_i) - M(kb_i)`` returns ``(raw, addends, dK)``:
+    ``addends[i] = w_i mean(Delta_i^2)`` over the ``D * D`` entries, ``raw`` their sum ascending, ``dK[i] = (4 lam w_i / (T D^2))
+    (kx_i Delta_i - 1 (Delta_i mu_i)^T)`` (the second part where centred), the gradient of ``lam * raw`` with respect to ``kx_i``."""
+    n = len(kx_list)
+    weights = [1.0] * n if weights is None else [float(w) for w in weights]
+    raw, addends, grads = 0.0, [], []
+    for kx, kb, w in zip(kx_list, kb_list, weights):
+        kx, kb = np.asarray(kx, np.float64), np.asarray(kb, np.float64)
+        T, D = kx.shape
+        delta = (kx.T @ kx - kb.T @ kb) / T
+        g = kx @ delta
+        if centered:
+            mx, mb = kx.mean(0), kb.mean(0)
+            delta = delta - (np.outer(mx, mx) - np.outer(mb, mb))
+            g = kx @ delta - np.outer(np.ones(T), delta @ mx)
+        addends.append(w * float(np.mean(delta * delta)))
+        raw += addends[-1]
+        grads.append((4.0 * float(lam) * w / (T * D * D)) * g)
+    return raw, addends, grads
 
 
 def np_key_gram(kx, kb, lam):

@@ -433,6 +433,9 @@ def key_gram_fields(engine):
     """What ``result.json`` / ``variant.json`` say about the key second-moment appearance term of a run (shared by the slots; DESIGN.md
     section 9n): ``lambda_global_key_gram`` and the block it ran on, ``dino_gram_layer``, where the term was on."""
     rule = getattr(engine, "key_gram", None)
+    listed = getattr(engine, "key_gram_layers", None)   # (DESIGN.md section 9o: the list, its weights and the centred flag in place of the block)
+    if rule is not None and listed is not None:
+        return {"lambda_global_key_gram": listed[0], "dino_gram_layers": list(listed[1]), "dino_gram_layer_weights": list(listed[2]), "dino_gram_centered": listed[3]}
     return {} if rule is None else {"lambda_global_key_gram": rule[0], "dino_gram_layer": rule[1]}
 
 

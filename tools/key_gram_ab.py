@@ -1,6 +1,7 @@
-"""usage (GPU box): python tools/key_gram_ab.py [--pairs 1] [--rounds 4] [--steps 80] [--warmup 15] [--layer 11] [--lam 1.0] [--only off|on]
+"""usage (GPU box): python tools/key_gram_ab.py [--pairs 1] [--rounds 4] [--steps 80] [--warmup 15] [--layer 11 | --layers 2,7,11] [--centered] [--lam 1.0] [--only off|on]
 The step without the key second-moment appearance term (`off`: the keys absent) and with it on block `--layer` (`on`:
-`lambda_global_key_gram`, `dino_gram_layer`), alternating on one box: engines as bench.py builds them (synthetic weights, 224 x 224 pairs,
+`lambda_global_key_gram`, `dino_gram_layer`) or over the blocks `--layers` (`dino_gram_layers`, all weights 1; a one-entry list runs the
+layered launches only with `--centered`, `dino_gram_centered`: else it is the one-block term), alternating on one box: engines as bench.py builds them (synthetic weights, 224 x 224 pairs,
 ViT-B/8, every step with the entire image handed over, `cls_warmup` 0 so that the term runs from the first step), `--steps` steps timed
 between two events behind `--warmup` steps, `--rounds` rounds.  `--only` runs one arm alone (one arm per process; also for a rocprofv3
 --kernel-trace --stats run of one arm: the launches' own time)."""
@@ -21,16 +22,21 @@ ap.add_argument("--rounds", type=int, default=4)
 ap.add_argument("--steps", type=int, default=80)
 ap.add_argument("--warmup", type=int, default=15)
 ap.add_argument("--layer", type=int, default=11)
+ap.add_argument("--layers", default="", help="comma list of blocks (dino_gram_layers) in place of --layer")
+ap.add_argument("--centered", action="store_true", help="dino_gram_centered")
 ap.add_argument("--lam", type=float, default=1.0)
 ap.add_argument("--only", choices=ARMS, default=None)
 a = ap.parse_args()
 
+on_keys = {"lambda_global_key_gram": a.lam, **({"dino_gram_layers": [int(l) for l in a.layers.split(",")]} if a.layers else {"dino_gram_layer": a.layer}),
+           **({"dino_gram_centered": True} if a.centered else {})}
+on_name = ("blocks " + a.layers if a.layers else "block %d" % a.layer) + (" centred" if a.centered else "")
 vit = None
 for rnd in range(1, a.rounds + 1):
     for arm in (ARMS if rnd % 2 else ARMS[::-1]):   # (the order swapped every round)
         if a.only and arm != a.only:
             continue
-        cfg = dict(n_epochs=10000, cls_warmup=0, **({"lambda_global_key_gram": a.lam, "dino_gram_layer": a.layer} if arm == "on" else {}))
+        cfg = dict(n_epochs=10000, cls_warmup=0, **(on_keys if arm == "on" else {}))
         eng, A, B = synthetic_engine(cfg, pairs=a.pairs, vit_engine=vit)
         vit = eng.vit
         for _ in range(a.warmup):
@@ -50,5 +56,5 @@ for rnd in range(1, a.rounds + 1):
         if arm == "on":
             vals = eng.key_gram_value()
             note += f" key_gram {[round(float(v), 6) for v in (vals if isinstance(vals, list) else [vals])]}"
-        print(f"round {rnd} key_gram={'off' if arm == 'off' else 'block %d' % a.layer:8s} P={a.pairs} steps/s {1e3 / ms:.3f} ms/step {ms:.4f} wall steps/s {a.steps / wall:.3f}{note}", flush=True)
+        print(f"round {rnd} key_gram={'off' if arm == 'off' else on_name:8s} P={a.pairs} steps/s {1e3 / ms:.3f} ms/step {ms:.4f} wall steps/s {a.steps / wall:.3f}{note}", flush=True)
         del eng
