@@ -112,14 +112,13 @@ def _slot_fields(eng, slot=None):
     ``train.clip_fields`` / ``train.best_fields`` / ``train.trace_fields`` / ``train.lr_fields``.  The optimiser: ``optimizer`` and every
     ``optimizer_*`` option that is not at its default (``train.optim_fields``).  The image-space loss terms: each of their two lambdas that
     is not 0 (``train.image_terms_fields``).  The blocks of the structure terms: ``dino_ssim_layers`` / ``dino_ssim_layer_weights`` where the
-    run named other blocks than the top one (``train.ssim_layers_fields``), and of the appearance terms likewise (``dino_cls_layers`` /
-    ``dino_cls_layer_weights``, ``train.cls_layers_fields``) and of the identity term (``dino_id_layers`` / ``dino_id_layer_weights``,
-    ``train.id_layers_fields``).  The key second-moment appearance term: ``lambda_global_key_gram`` / ``dino_gram_layer`` where it was on
+    run named other blocks than the top one, and of the appearance terms likewise (``dino_cls_layers`` / ``dino_cls_layer_weights``) and of
+    the identity term (``dino_id_layers`` / ``dino_id_layer_weights``): ``train.layer_list_fields``.  The key second-moment appearance term: ``lambda_global_key_gram`` / ``dino_gram_layer`` where it was on
     (``train.key_gram_fields``)."""
-    from .train import best_fields, clip_fields, cls_layers_fields, id_layers_fields, image_terms_fields, key_gram_fields, lr_fields, optim_fields, ssim_layers_fields, trace_fields
+    from .train import best_fields, clip_fields, image_terms_fields, key_gram_fields, layer_list_fields, lr_fields, optim_fields, trace_fields
     at = eng.stopped_at if slot is None else eng.stopped_at[slot]
     return {"steps_run": eng.step_idx + 1 if at is None else at + 1, "stopped_at": at, "ema_decay": eng.ema_rule[0],
-            **clip_fields(eng, slot), **best_fields(eng, slot), **trace_fields(eng), **lr_fields(eng, slot), **optim_fields(eng), **image_terms_fields(eng), **ssim_layers_fields(eng), **cls_layers_fields(eng), **id_layers_fields(eng), **key_gram_fields(eng)}
+            **clip_fields(eng, slot), **best_fields(eng, slot), **trace_fields(eng), **lr_fields(eng, slot), **optim_fields(eng), **image_terms_fields(eng), **layer_list_fields(eng), **key_gram_fields(eng)}
 
 
 def _timed(train, *args, **kw):

@@ -11,6 +11,7 @@
 // generator plans hold P independent generators (own parameter / gradient / Adam arenas, own BatchNorm statistics), the
 // loss kernels take the pair as a grid dimension.  Every per-pair quantity is computed exactly as in a P = 1 step (no
 // policy depends on P), so a pair's trajectory is bit-identical whichever batch it rides in.
+#include <algorithm>
 #include <memory>
 #include <vector>
 
@@ -56,15 +57,31 @@ struct VitView {
     float* dk_id[ID_MAX_LAYERS] = {};
     float* dk_id_own[ID_MAX_LAYERS] = {};
     std::vector<const float*> pk_y;
-    // splice_step_set_key_gram (global view only): the key-gradient buffer the term adds into -- pk's of its block (d_keys at the top, the
-    // structure list's buffer of a block that list names), else one of its own (then also in dk_kg_own: its x' passes are zeroed each step)
-    // -- and the x' chain's key-gradient table on the steps the term runs: pk plus that block
-    float* dk_kg = nullptr;
-    float* dk_kg_own = nullptr;
-    std::vector<const float*> pk_x;
-    // splice_step_set_key_gram_layers: the same per entry of the list (pk_x then holds pk plus every block of its own)
+    // splice_step_set_key_gram_layers (global view only): the key-gradient buffer entry i of the list adds into -- pk's of its block (d_keys
+    // at the top, the structure list's buffer of a block that list names), else one of its own (then also in dk_kgl_own: its x' passes are
+    // zeroed each step) -- and the x' chain's key-gradient table on the steps the term runs: pk plus the blocks of its own.  The one block of
+    // splice_step_set_key_gram is entry 0.
     float* dk_kgl[KEY_GRAM_MAX_LAYERS] = {};
     float* dk_kgl_own[KEY_GRAM_MAX_LAYERS] = {};
+    std::vector<const float*> pk_x;
+};
+
+// The blocks a per-layer loss term reads and their weights (splice_step_set_ssim_layers, ..._cls_layers, ..._id_layers,
+// ..._key_gram_layers): n ascending distinct block indices, n finite weights > 0; 0 entries: the term has no list.  One record for the four
+// terms, sized by the largest of their caps; no term's kernel table may hold fewer entries than it.
+constexpr int LAYER_LIST_MAX = std::max({SELFSIM_MAX_LAYERS, CLS_MAX_LAYERS, ID_MAX_LAYERS, (int)KEY_GRAM_MAX_LAYERS});
+static_assert(SELFSIM_MAX_LAYERS >= LAYER_LIST_MAX, "SelfSimLayers holds fewer entries than a LayerList");
+static_assert(CLS_MAX_LAYERS >= LAYER_LIST_MAX, "ClsLayers holds fewer entries than a LayerList");
+static_assert(ID_MAX_LAYERS >= LAYER_LIST_MAX, "IdLayers holds fewer entries than a LayerList");
+static_assert(KEY_GRAM_MAX_LAYERS >= LAYER_LIST_MAX, "KeyGramLayers holds fewer entries than a LayerList");
+struct LayerList {
+    int n = 0;
+    int layers[LAYER_LIST_MAX] = {};
+    float weights[LAYER_LIST_MAX] = {};
+    void set(int count, const int* l, const float* w) {
+        n = count;
+        for (int i = 0; i < count; ++i) { layers[i] = l[i]; weights[i] = w[i]; }
+    }
 };
 
 struct SpliceStep {
@@ -181,24 +198,17 @@ struct SpliceStep {
     // the image-space terms (splice_step_set_image_terms): lambda_global_tv on x' = G(A_crop), lambda_global_pixel_identity on y' = G(B_crop)
     // against B_crop; both 0: off -- the step launches what it always did
     float lambda_tv = 0.f, lambda_pix = 0.f;
-    // the blocks whose keys the two structure terms read (splice_step_set_ssim_layers): ascending block indices, their
-    // weights, and one SelfSimBatch workspace per entry (entry 0: ssim_ws); 0 entries: off -- the top block alone, the step launches what it
-    // always did
-    int n_ssim_layers = 0;
-    int ssim_layers[SELFSIM_MAX_LAYERS] = {};
-    float ssim_weights[SELFSIM_MAX_LAYERS] = {};
+    // the blocks whose keys the two structure terms read (splice_step_set_ssim_layers), and one SelfSimBatch workspace
+    // per entry (entry 0: ssim_ws); 0 entries: off -- the top block alone, the step launches what it always did
+    LayerList ssim_list;
     void* ssim_ws_layer[SELFSIM_MAX_LAYERS] = {};
-    // the blocks whose [CLS] row the two appearance terms read (splice_step_set_cls_layers): ascending block indices and
-    // their weights; 0 entries: off -- the top block alone, the step launches what it always did
-    int n_cls_layers = 0;
-    int cls_layers[CLS_MAX_LAYERS] = {};
-    float cls_weights[CLS_MAX_LAYERS] = {};
-    // the blocks whose keys the identity term reads (splice_step_set_id_layers): ascending block indices and their
-    // weights; 0 entries: off -- the top block alone, the step launches what it always did.  id_scratch: the workgroup partials of the term's
-    // main launch, [Pb][n][G]; id_values: the per-layer addends, [Pb][n]
-    int n_id_layers = 0;
-    int id_layers[ID_MAX_LAYERS] = {};
-    float id_weights[ID_MAX_LAYERS] = {};
+    // the blocks whose [CLS] row the two appearance terms read (splice_step_set_cls_layers); 0 entries: off -- the
+    // top block alone, the step launches what it always did
+    LayerList cls_list;
+    // the blocks whose keys the identity term reads (splice_step_set_id_layers); 0 entries: off -- the top block
+    // alone, the step launches what it always did.  id_scratch: the workgroup partials of the term's main launch, [Pb][n][G]; id_values: the
+    // per-layer addends, [Pb][n]
+    LayerList id_list;
     float *id_scratch = nullptr, *id_values = nullptr;
     // the key second-moment appearance term (splice_step_set_key_gram): its weight (0: off -- the step launches what it
     // always did) and block; kg_delta: the bf16 Gram differences, [Pc][D][D]; kg_part: the tile partials, [Pc][tiles]; kg_value: the raw
@@ -207,15 +217,17 @@ struct SpliceStep {
     int kg_layer = -1;
     bf16_t* kg_delta = nullptr;
     float *kg_part = nullptr, *kg_value = nullptr;
-    // ... over several blocks (splice_step_set_key_gram_layers): kg_n entries (0: the one-block term above), ascending
-    // blocks, their weights, the centred flag; kg_delta / kg_part then hold [kg_n][Pc]... ; kg_values: the per-layer addends, [pairs][kg_n];
-    // kg_mu: the fp32 means of the centred form, [kg_n][Pc][2][D]
-    int kg_n = 0, kg_centered = 0;
-    int kg_layers[KEY_GRAM_MAX_LAYERS] = {};
-    float kg_weights[KEY_GRAM_MAX_LAYERS] = {};
+    // ... over several blocks (splice_step_set_key_gram_layers): the list of n entries (0: the one-block term above) and
+    // the centred flag; kg_delta / kg_part then hold [n][Pc]... ; kg_values: the per-layer addends, [pairs][n]; kg_mu: the fp32 means of the
+    // centred form, [n][Pc][2][D]
+    LayerList kg_list;
+    int kg_centered = 0;
     float *kg_values = nullptr, *kg_mu = nullptr;
 };
 
+// the key second-moment term runs over a list of blocks (splice_step_set_key_gram_layers: the list launches) rather than over its one block
+// (splice_step_set_key_gram: the one-block launches, which round their scale differently)
+static bool kg_listed(const SpliceStep* st) { return st->kg_list.n > 0; }
 static size_t arena_floats(const SpliceStep* st) { return st->astride ? st->pairs * st->astride : (size_t)st->nparams; }   // of all pairs' arenas
 static bool create_events(SpliceStep* st) {
     for (auto& set : st->evs)
@@ -564,10 +576,10 @@ static int ssim_batch(SpliceStep* st, VitView& v, int pass_tgt, int pass_x, int 
                       SelfSimLayers* tab = nullptr) {
     bf16_t *qkv = nullptr, *qkvT = nullptr;
     if (tab) {
-        tab->n = st->n_ssim_layers;
+        tab->n = st->ssim_list.n;
         const size_t pass_rows = (size_t)v.Tld * 3 * v.D;
         for (int i = 0; i < tab->n; ++i) {
-            const int l = st->ssim_layers[i];
+            const int l = st->ssim_list.layers[i];
             SelfSimBatch w = {};
             RC(splice_vit_get_tensor(v.ctx, 1, l, (void**)&qkv));
             RC(splice_vit_get_tensor(v.ctx, 8, l, (void**)&qkvT));
@@ -578,7 +590,7 @@ static int ssim_batch(SpliceStep* st, VitView& v, int pass_tgt, int pass_x, int 
             e.kT_x = qkvT + (size_t)v.D * v.rows + (size_t)pass_x * v.Tld;
             e.S_tgt = w.S_tgt; e.wmat = w.wmat; e.norm_x = w.norm_x; e.rpart = w.rpart;
             e.dk = v.dk_layer[i] + (size_t)pass_x * v.Tld * v.D;
-            e.weight = st->ssim_weights[i];
+            e.weight = st->ssim_list.weights[i];
         }
     }
     RC(splice_vit_get_tensor(v.ctx, 1, v.depth - 1, (void**)&qkv));
@@ -605,17 +617,17 @@ static int ssim_batch(SpliceStep* st, VitView& v, int pass_tgt, int pass_x, int 
 static int cls_table(SpliceStep* st, VitView& vx, int pass_x, int x_step, int pass_t, int t_step, ClsLayers* tab) {
     VitView& vg = st->vg;
     const size_t xpass = (size_t)vx.Tld * vx.D, tpass = (size_t)vg.Tld * vg.D;
-    tab->n = st->n_cls_layers; tab->D = vx.D;
+    tab->n = st->cls_list.n; tab->D = vx.D;
     tab->x_ps = (size_t)x_step * xpass; tab->t_ps = (size_t)t_step * tpass; tab->seed_step = x_step;
     for (int i = 0; i < tab->n; ++i) {
         float *bx = nullptr, *bt = nullptr;
-        RC(splice_vit_get_tensor(vx.ctx, 0, st->cls_layers[i], (void**)&bx));
-        RC(splice_vit_get_tensor(vg.ctx, 0, st->cls_layers[i], (void**)&bt));
+        RC(splice_vit_get_tensor(vx.ctx, 0, st->cls_list.layers[i], (void**)&bx));
+        RC(splice_vit_get_tensor(vg.ctx, 0, st->cls_list.layers[i], (void**)&bt));
         ClsLayer& e = tab->e[i];
         e.x = bx + (size_t)pass_x * xpass; e.tgt = bt + (size_t)pass_t * tpass;
         if (vx.cls_seed[i]) { e.seed = vx.cls_seed[i] + (size_t)pass_x * vx.D; e.seed_ps = (size_t)vx.D; }
         else { e.seed = vx.d_block + (size_t)pass_x * xpass; e.seed_ps = xpass; }
-        e.weight = st->cls_weights[i];
+        e.weight = st->cls_list.weights[i];
     }
     return SPLICE_OK;
 }
@@ -626,10 +638,10 @@ static int cls_table(SpliceStep* st, VitView& vx, int pass_x, int x_step, int pa
 // key-gradient buffer.
 static int id_table(SpliceStep* st, int pass_y, int pass_b, IdLayers* tab) {
     VitView& v = st->vg;
-    tab->n = st->n_id_layers; tab->T = v.T; tab->D = v.D;
+    tab->n = st->id_list.n; tab->T = v.T; tab->D = v.D;
     tab->x_rs = tab->t_rs = tab->g_rs = (size_t)v.Tld;
     for (int i = 0; i < tab->n; ++i) {
-        const int l = st->id_layers[i];
+        const int l = st->id_list.layers[i];
         IdLayer& e = tab->e[i];
         float* k = nullptr;
         if (l == v.depth - 1) {
@@ -640,7 +652,7 @@ static int id_table(SpliceStep* st, int pass_y, int pass_b, IdLayers* tab) {
             e.x = k + (size_t)pass_y * v.Tld * v.D; e.tgt = k + (size_t)pass_b * v.Tld * v.D; e.ldx = e.ldt = v.D;
         }
         e.grad = v.dk_id[i] + (size_t)pass_y * v.Tld * v.D; e.ldg = v.D;
-        e.weight = st->id_weights[i];
+        e.weight = st->id_list.weights[i];
     }
     return SPLICE_OK;
 }
@@ -788,8 +800,8 @@ static const char* whole_step_rule(const SpliceStep* st) {
     return st->stop_rule.window > 0 ? "with a stop rule" : st->ema ? "with a weight average" : st->clip ? "with gradient clipping"
            : st->best ? "that keeps the best weights" : st->trace ? "with a loss trace"
            : (st->lambda_tv > 0.f || st->lambda_pix > 0.f) ? "with image-space loss terms"
-           : st->n_ssim_layers > 0 ? "with structure layers" : st->n_cls_layers > 0 ? "with [CLS] layers"
-           : st->n_id_layers > 0 ? "with identity layers" : st->kg_lambda > 0.f ? "with the key second-moment term" : nullptr;
+           : st->ssim_list.n > 0 ? "with structure layers" : st->cls_list.n > 0 ? "with [CLS] layers"
+           : st->id_list.n > 0 ? "with identity layers" : st->kg_lambda > 0.f ? "with the key second-moment term" : nullptr;
 }
 // The shared opening of the rule setters below: before the first step only (`what` of the rule, for the error text), and not on a
 // gradient-only or phase-mode handle.  Callers return its code plainly, not through RC(): the message stays the last error.
@@ -1061,15 +1073,65 @@ int splice_step_set_image_terms(void* h, float lambda_tv, float lambda_pix) {
     st->lambda_tv = lambda_tv; st->lambda_pix = lambda_pix;
     return SPLICE_OK;
 }
-static unsigned long long ssim_layers_salt(const SpliceStep* st) {
-    if (!st->n_ssim_layers) return 0;
-    unsigned long long h = 1469598103934665603ull;   // FNV-1a over (block, weight bits) in list order
-    for (int i = 0; i < st->n_ssim_layers; ++i) {
-        unsigned w;
-        memcpy(&w, &st->ssim_weights[i], sizeof(w));
-        for (unsigned long long v : {(unsigned long long)st->ssim_layers[i], (unsigned long long)w})
-            for (int k = 0; k < 8; ++k) { h ^= (v >> (8 * k)) & 0xff; h *= 1099511628211ull; }
+// ---- what the four per-layer terms share on the host (DESIGN.md section 9k has the overview): the record above, the argument checks of
+// their setters, the hash their graph keys are built from, the key-gradient buffers of the two terms that add into a chain's table, and the
+// host copy of their per-layer values.
+// The argument checks of a layer list for `who`: n in 1..min(depth, most), ascending distinct blocks of a depth-block ViT, finite weights > 0.
+static bool layer_list_check(const char* who, int depth, int most, int n, const int* layers, const float* weights) {
+    if (n < 1 || n > depth || n > most) { splice_set_error("%s: needs 1..%d layers, got %d", who, depth < most ? depth : most, n); return false; }
+    for (int i = 0; i < n; ++i) {
+        if (layers[i] < 0 || layers[i] >= depth || (i > 0 && layers[i] <= layers[i - 1])) {
+            splice_set_error("%s: layers must be ascending distinct block indices in [0, %d), got layers[%d] = %d", who, depth, i, layers[i]);
+            return false;
+        }
+        if (!(weights[i] > 0.f) || !(weights[i] <= 3.402823466e+38f)) {
+            splice_set_error("%s: weights must be finite and > 0, got weights[%d] = %g", who, i, (double)weights[i]);
+            return false;
+        }
     }
+    return true;
+}
+static const unsigned long long FNV_BASIS = 1469598103934665603ull;
+static unsigned long long fnv1a_word(unsigned long long h, unsigned long long v) {   // the eight bytes of v, low byte first
+    for (int k = 0; k < 8; ++k) { h ^= (v >> (8 * k)) & 0xff; h *= 1099511628211ull; }
+    return h;
+}
+// FNV-1a from `basis` over (block, weight bits) in list order.  head >= 0 (the key second-moment list): every entry opens with a word more,
+// `head` at entry 0 and 0 at the later ones.
+static unsigned long long layer_list_hash(const LayerList& list, unsigned long long basis, long long head = -1) {
+    unsigned long long h = basis;
+    for (int i = 0; i < list.n; ++i) {
+        unsigned w;
+        memcpy(&w, &list.weights[i], sizeof(w));
+        if (head >= 0) h = fnv1a_word(h, i == 0 ? (unsigned long long)head : 0);
+        h = fnv1a_word(fnv1a_word(h, (unsigned long long)list.layers[i]), (unsigned long long)w);
+    }
+    return h;
+}
+// The key-gradient buffers of a term that ADDS into the blocks `layers` of one chain of the global view (the identity list on the y' chain,
+// the key second-moment term on the x' chain): dk[i] = the buffer pk already has for the block (d_keys at the top, the structure list's),
+// else a zeroed one of the handle's own -- then also in dk_own[i], for the step's zeroing of the chain's passes, and in `tab`, the chain's
+// table, which starts as a copy of pk.
+static int key_grad_buffers(SpliceStep* st, VitView& v, int n, const int* layers, float** dk, float** dk_own, std::vector<const float*>& tab) {
+    tab = v.pk;
+    for (int i = 0; i < n; ++i) {
+        const int l = layers[i];
+        if (v.pk[l]) { dk[i] = const_cast<float*>(v.pk[l]); continue; }
+        RC(salloc(st, &dk_own[i], (size_t)v.rows * v.D));
+        HIPCHK(hipMemset(dk_own[i], 0, (size_t)v.rows * v.D * sizeof(float)));   // padding rows and every other chain's passes read as zero gradient for good
+        tab[l] = dk[i] = dk_own[i];
+    }
+    return SPLICE_OK;
+}
+// `count` floats of a term's values to the HOST behind a device-wide wait (the *_values readers)
+static int values_to_host(float* out, const float* dev, size_t count) {
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, dev, count * sizeof(float), hipMemcpyDeviceToHost));
+    return SPLICE_OK;
+}
+static unsigned long long ssim_layers_salt(const SpliceStep* st) {
+    if (!st->ssim_list.n) return 0;
+    const unsigned long long h = layer_list_hash(st->ssim_list, FNV_BASIS);
     return ((h ^ (h >> 15) ^ (h >> 30) ^ (h >> 45)) & 0x7fffull) << 40 | 1ull << 55;
 }
 // The blocks whose keys the two structure terms read, and their weights (include/splice_hip.h has the term): n ascending distinct block
@@ -1084,22 +1146,11 @@ int splice_step_set_ssim_layers(void* h, int n, const int* layers, const float* 
     SpliceStep* st = (SpliceStep*)h;
     const char* who = "splice_step_set_ssim_layers";
     if (!st || !layers || !weights) return SPLICE_ERR_ARG;
-    const int depth = st->vg.depth;
-    if (n < 1 || n > depth || n > SELFSIM_MAX_LAYERS) { splice_set_error("%s: needs 1..%d layers, got %d", who, depth < SELFSIM_MAX_LAYERS ? depth : SELFSIM_MAX_LAYERS, n); return SPLICE_ERR_ARG; }
-    for (int i = 0; i < n; ++i) {
-        if (layers[i] < 0 || layers[i] >= depth || (i > 0 && layers[i] <= layers[i - 1])) {
-            splice_set_error("%s: layers must be ascending distinct block indices in [0, %d), got layers[%d] = %d", who, depth, i, layers[i]);
-            return SPLICE_ERR_ARG;
-        }
-        if (!(weights[i] > 0.f) || !(weights[i] <= 3.402823466e+38f)) {
-            splice_set_error("%s: weights must be finite and > 0, got weights[%d] = %g", who, i, (double)weights[i]);
-            return SPLICE_ERR_ARG;
-        }
-    }
+    if (!layer_list_check(who, st->vg.depth, SELFSIM_MAX_LAYERS, n, layers, weights)) return SPLICE_ERR_ARG;
     if (int rc = rule_setter_ok(st, who, "the layers are set")) return rc;
     if (st->cfg.fp8_selfsim) { splice_set_error("%s: not with fp8_selfsim (the e4m3 Gram path reads the top block alone)", who); return SPLICE_ERR_STATE; }
-    if (st->n_ssim_layers) { splice_set_error("%s: the layers are set once", who); return SPLICE_ERR_STATE; }
-    if (st->n_id_layers) { splice_set_error("%s: call it in front of splice_step_set_id_layers (the identity term shares this list's key-gradient buffers)", who); return SPLICE_ERR_STATE; }
+    if (st->ssim_list.n) { splice_set_error("%s: the layers are set once", who); return SPLICE_ERR_STATE; }
+    if (st->id_list.n) { splice_set_error("%s: call it in front of splice_step_set_id_layers (the identity term shares this list's key-gradient buffers)", who); return SPLICE_ERR_STATE; }
     if (st->kg_lambda > 0.f) { splice_set_error("%s: call it in front of splice_step_set_key_gram (that term shares this list's key-gradient buffers)", who); return SPLICE_ERR_STATE; }
     const int Tmax = st->plan_e && st->ve.T > st->vg.T ? st->ve.T : st->vg.T;
     for (VitView* v : {&st->vg, &st->ve}) {
@@ -1125,8 +1176,7 @@ int splice_step_set_ssim_layers(void* h, int n, const int* layers, const float* 
         st->losses = wider; st->lp = need; st->lstride = 8 + 8 * need;   // (the narrower buffer stays with the handle until it goes)
     }
     st->graphs.retire();
-    st->n_ssim_layers = n;
-    for (int i = 0; i < n; ++i) { st->ssim_layers[i] = layers[i]; st->ssim_weights[i] = weights[i]; }
+    st->ssim_list.set(n, layers, weights);
     return SPLICE_OK;
 }
 // The per-layer values of the last step's structure term `term` (1: global, 2: entire-image): out[i * pairs + p] (device, [n][pairs]) =
@@ -1136,24 +1186,17 @@ int splice_step_ssim_layer_values(void* h, int term, float* out, splice_stream_t
     SpliceStep* st = (SpliceStep*)h;
     const char* who = "splice_step_ssim_layer_values";
     if (!st || !out || (term != L_GLOBAL_SSIM && term != L_ENTIRE_SSIM)) { splice_set_error("%s: needs a handle, out and term 1 or 2", who); return SPLICE_ERR_ARG; }
-    if (!st->n_ssim_layers) { splice_set_error("%s: the handle has no structure layers (splice_step_set_ssim_layers)", who); return SPLICE_ERR_STATE; }
+    if (!st->ssim_list.n) { splice_set_error("%s: the handle has no structure layers (splice_step_set_ssim_layers)", who); return SPLICE_ERR_STATE; }
     if (term == L_ENTIRE_SSIM && !st->plan_e) { splice_set_error("%s: the handle has no entire-image branch", who); return SPLICE_ERR_STATE; }
-    const int n = st->n_ssim_layers, tiles = tri_tiles(term == L_GLOBAL_SSIM ? st->vg.T : st->ve.T);
+    const int n = st->ssim_list.n, tiles = tri_tiles(term == L_GLOBAL_SSIM ? st->vg.T : st->ve.T);
     const int n_slots = term == L_GLOBAL_SSIM && st->crops_mode ? (st->pairs > 1 ? st->na : st->P) : 1;
     SPLICE_LAUNCH(ssim_layer_values_kernel, dim3((n * st->pairs + 63) / 64), dim3(64), 0, (hipStream_t)stream, (const float*)st->losses, st->lstride, (int)st->lp, term, n,
                   tiles, st->pairs, n_slots, out);
     return SPLICE_OK;
 }
 static unsigned long long cls_layers_salt(const SpliceStep* st) {
-    if (!st->n_cls_layers) return 0;
-    unsigned long long h = 1469598103934665603ull;   // FNV-1a over (block, weight bits) in list order
-    for (int i = 0; i < st->n_cls_layers; ++i) {
-        unsigned w;
-        memcpy(&w, &st->cls_weights[i], sizeof(w));
-        for (unsigned long long v : {(unsigned long long)st->cls_layers[i], (unsigned long long)w})
-            for (int k = 0; k < 8; ++k) { h ^= (v >> (8 * k)) & 0xff; h *= 1099511628211ull; }
-    }
-    return h | 1ull;   // (never 0: a handle with layers is never keyed like one without)
+    if (!st->cls_list.n) return 0;
+    return layer_list_hash(st->cls_list, FNV_BASIS) | 1ull;   // (never 0: a handle with layers is never keyed like one without)
 }
 // The blocks whose [CLS] row the two appearance terms read, and their weights (include/splice_hip.h has the term): n ascending distinct
 // block indices, n finite weights > 0.  One launch per appearance term then covers every named block (cls_layers.hip) in place of the
@@ -1166,21 +1209,10 @@ int splice_step_set_cls_layers(void* h, int n, const int* layers, const float* w
     SpliceStep* st = (SpliceStep*)h;
     const char* who = "splice_step_set_cls_layers";
     if (!st || !layers || !weights) return SPLICE_ERR_ARG;
-    const int depth = st->vg.depth;
-    if (n < 1 || n > depth || n > CLS_MAX_LAYERS) { splice_set_error("%s: needs 1..%d layers, got %d", who, depth < CLS_MAX_LAYERS ? depth : CLS_MAX_LAYERS, n); return SPLICE_ERR_ARG; }
-    for (int i = 0; i < n; ++i) {
-        if (layers[i] < 0 || layers[i] >= depth || (i > 0 && layers[i] <= layers[i - 1])) {
-            splice_set_error("%s: layers must be ascending distinct block indices in [0, %d), got layers[%d] = %d", who, depth, i, layers[i]);
-            return SPLICE_ERR_ARG;
-        }
-        if (!(weights[i] > 0.f) || !(weights[i] <= 3.402823466e+38f)) {
-            splice_set_error("%s: weights must be finite and > 0, got weights[%d] = %g", who, i, (double)weights[i]);
-            return SPLICE_ERR_ARG;
-        }
-    }
+    if (!layer_list_check(who, st->vg.depth, CLS_MAX_LAYERS, n, layers, weights)) return SPLICE_ERR_ARG;
     if (int rc = rule_setter_ok(st, who, "the layers are set")) return rc;
     if (st->cfg.fp8_selfsim) { splice_set_error("%s: not with fp8 (the e4m3 forward is validated against the top block's [CLS] row alone)", who); return SPLICE_ERR_STATE; }
-    if (st->n_cls_layers) { splice_set_error("%s: the layers are set once", who); return SPLICE_ERR_STATE; }
+    if (st->cls_list.n) { splice_set_error("%s: the layers are set once", who); return SPLICE_ERR_STATE; }
     for (VitView* v : {&st->vg, &st->ve}) {
         if (!v->ctx) continue;
         v->cls_seed_tab.assign(v->depth, nullptr);
@@ -1196,8 +1228,7 @@ int splice_step_set_cls_layers(void* h, int n, const int* layers, const float* w
         HIPCHK(hipMemset(v->cls_values, 0, (size_t)st->P * n * sizeof(float)));
     }
     st->graphs.retire();
-    st->n_cls_layers = n;
-    for (int i = 0; i < n; ++i) { st->cls_layers[i] = layers[i]; st->cls_weights[i] = weights[i]; }
+    st->cls_list.set(n, layers, weights);
     return SPLICE_OK;
 }
 // The per-layer addends of the appearance term of the last step that computed it (entire = 0: loss_global_cls, word 4; else
@@ -1208,24 +1239,16 @@ int splice_step_cls_layer_values(void* h, int entire, float* out, int cap) {
     SpliceStep* st = (SpliceStep*)h;
     const char* who = "splice_step_cls_layer_values";
     if (!st || !out) { splice_set_error("%s: needs a handle and out", who); return SPLICE_ERR_ARG; }
-    if (!st->n_cls_layers) { splice_set_error("%s: the handle has no [CLS] layers (splice_step_set_cls_layers)", who); return SPLICE_ERR_STATE; }
+    if (!st->cls_list.n) { splice_set_error("%s: the handle has no [CLS] layers (splice_step_set_cls_layers)", who); return SPLICE_ERR_STATE; }
     if (entire && !st->plan_e) { splice_set_error("%s: the handle has no entire-image branch", who); return SPLICE_ERR_STATE; }
     const int nc = st->na < st->nb ? st->na : st->nb, slots = entire ? st->pairs : st->pairs * nc;
-    if (cap < slots * st->n_cls_layers) { splice_set_error("%s: out holds %d floats, needs %d", who, cap, slots * st->n_cls_layers); return SPLICE_ERR_ARG; }
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, entire ? st->ve.cls_values : st->vg.cls_values, (size_t)slots * st->n_cls_layers * sizeof(float), hipMemcpyDeviceToHost));
-    return SPLICE_OK;
+    if (cap < slots * st->cls_list.n) { splice_set_error("%s: out holds %d floats, needs %d", who, cap, slots * st->cls_list.n); return SPLICE_ERR_ARG; }
+    return values_to_host(out, entire ? st->ve.cls_values : st->vg.cls_values, (size_t)slots * st->cls_list.n);
 }
 static unsigned long long id_layers_salt(const SpliceStep* st) {
-    if (!st->n_id_layers) return 0;
-    unsigned long long h = 1469598103934665603ull ^ 0x9e3779b97f4a7c15ull;   // FNV-1a over (block, weight bits) in list order, from a basis of its own
-    for (int i = 0; i < st->n_id_layers; ++i) {
-        unsigned w;
-        memcpy(&w, &st->id_weights[i], sizeof(w));
-        for (unsigned long long v : {(unsigned long long)st->id_layers[i], (unsigned long long)w})
-            for (int k = 0; k < 8; ++k) { h ^= (v >> (8 * k)) & 0xff; h *= 1099511628211ull; }
-    }
-    return h | 2ull;   // (never 0: a handle with layers is never keyed like one without)
+    if (!st->id_list.n) return 0;
+    // (from a basis of its own; never 0: a handle with layers is never keyed like one without)
+    return layer_list_hash(st->id_list, FNV_BASIS ^ 0x9e3779b97f4a7c15ull) | 2ull;
 }
 // The blocks whose keys the identity term reads, and their weights (include/splice_hip.h has the term): n ascending distinct block indices,
 // n finite weights > 0.  Two launches then cover every named block (id_layers.hip) in place of the term's mse_batched_launch; the global
@@ -1241,40 +1264,20 @@ int splice_step_set_id_layers(void* h, int n, const int* layers, const float* we
     const char* who = "splice_step_set_id_layers";
     if (!st || !layers || !weights) return SPLICE_ERR_ARG;
     VitView& v = st->vg;
-    const int depth = v.depth;
-    if (n < 1 || n > depth || n > ID_MAX_LAYERS) { splice_set_error("%s: needs 1..%d layers, got %d", who, depth < ID_MAX_LAYERS ? depth : ID_MAX_LAYERS, n); return SPLICE_ERR_ARG; }
-    for (int i = 0; i < n; ++i) {
-        if (layers[i] < 0 || layers[i] >= depth || (i > 0 && layers[i] <= layers[i - 1])) {
-            splice_set_error("%s: layers must be ascending distinct block indices in [0, %d), got layers[%d] = %d", who, depth, i, layers[i]);
-            return SPLICE_ERR_ARG;
-        }
-        if (!(weights[i] > 0.f) || !(weights[i] <= 3.402823466e+38f)) {
-            splice_set_error("%s: weights must be finite and > 0, got weights[%d] = %g", who, i, (double)weights[i]);
-            return SPLICE_ERR_ARG;
-        }
-    }
+    if (!layer_list_check(who, v.depth, ID_MAX_LAYERS, n, layers, weights)) return SPLICE_ERR_ARG;
     if (int rc = rule_setter_ok(st, who, "the layers are set")) return rc;
     if (st->cfg.fp8_selfsim) { splice_set_error("%s: not with fp8 (the e4m3 forward keeps fp32 keys of the top block alone)", who); return SPLICE_ERR_STATE; }
-    if (st->n_id_layers) { splice_set_error("%s: the layers are set once", who); return SPLICE_ERR_STATE; }
+    if (st->id_list.n) { splice_set_error("%s: the layers are set once", who); return SPLICE_ERR_STATE; }
     if (v.D % 4) { splice_set_error("%s: needs an embedding width that is a multiple of 4, got %d", who, v.D); return SPLICE_ERR_ARG; }
     RC(splice_vit_ctx_set_key_f32_layers(v.ctx, n, layers));
-    v.pk_y = v.pk;
-    for (int i = 0; i < n; ++i) {
-        const int l = layers[i];
-        if (v.pk[l]) { v.dk_id[i] = const_cast<float*>(v.pk[l]); continue; }   // the top block (d_keys), or a block of the structure list
-        RC(salloc(st, &v.dk_id_own[i], (size_t)v.rows * v.D));
-        HIPCHK(hipMemset(v.dk_id_own[i], 0, (size_t)v.rows * v.D * sizeof(float)));
-        v.dk_id[i] = v.dk_id_own[i];
-        v.pk_y[l] = v.dk_id[i];
-    }
+    if (int rc = key_grad_buffers(st, v, n, layers, v.dk_id, v.dk_id_own, v.pk_y)) return rc;
     const int G = id_layers_wg(v.T, v.D, 0);
     RC(salloc(st, &st->id_scratch, (size_t)st->Pb * n * G));
     RC(salloc(st, &st->id_values, (size_t)st->Pb * n));
     HIPCHK(hipMemset(st->id_scratch, 0, (size_t)st->Pb * n * G * sizeof(float)));
     HIPCHK(hipMemset(st->id_values, 0, (size_t)st->Pb * n * sizeof(float)));
     st->graphs.retire();
-    st->n_id_layers = n;
-    for (int i = 0; i < n; ++i) { st->id_layers[i] = layers[i]; st->id_weights[i] = weights[i]; }
+    st->id_list.set(n, layers, weights);
     return SPLICE_OK;
 }
 // The per-layer addends of the identity term (loss_global_id_B, word 5) of the last step that computed it, copied to the HOST behind a
@@ -1285,26 +1288,17 @@ int splice_step_id_layer_values(void* h, float* out, int cap) {
     SpliceStep* st = (SpliceStep*)h;
     const char* who = "splice_step_id_layer_values";
     if (!st || !out) { splice_set_error("%s: needs a handle and out", who); return SPLICE_ERR_ARG; }
-    if (!st->n_id_layers) { splice_set_error("%s: the handle has no identity layers (splice_step_set_id_layers)", who); return SPLICE_ERR_STATE; }
-    if (cap < st->Pb * st->n_id_layers) { splice_set_error("%s: out holds %d floats, needs %d", who, cap, st->Pb * st->n_id_layers); return SPLICE_ERR_ARG; }
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, st->id_values, (size_t)st->Pb * st->n_id_layers * sizeof(float), hipMemcpyDeviceToHost));
-    return SPLICE_OK;
+    if (!st->id_list.n) { splice_set_error("%s: the handle has no identity layers (splice_step_set_id_layers)", who); return SPLICE_ERR_STATE; }
+    if (cap < st->Pb * st->id_list.n) { splice_set_error("%s: out holds %d floats, needs %d", who, cap, st->Pb * st->id_list.n); return SPLICE_ERR_ARG; }
+    return values_to_host(out, st->id_values, (size_t)st->Pb * st->id_list.n);
 }
 static unsigned long long key_gram_salt(const SpliceStep* st) {
     if (!(st->kg_lambda > 0.f)) return 0;
     unsigned w;
     memcpy(&w, &st->kg_lambda, sizeof(w));
-    unsigned long long h = 1469598103934665603ull ^ 0xc2b2ae3d27d4eb4full;   // FNV-1a over (block, weight bits), from a basis of its own
-    for (unsigned long long v : {(unsigned long long)st->kg_layer, (unsigned long long)w})
-        for (int k = 0; k < 8; ++k) { h ^= (v >> (8 * k)) & 0xff; h *= 1099511628211ull; }
-    for (int i = 0; i < st->kg_n; ++i) {   // the list: its length and flag, then (block, weight bits) in list order
-        unsigned wi;
-        memcpy(&wi, &st->kg_weights[i], sizeof(wi));
-        for (unsigned long long v : {(unsigned long long)(i == 0 ? 0x100 + 2 * st->kg_n + st->kg_centered : 0), (unsigned long long)st->kg_layers[i], (unsigned long long)wi})
-            for (int k = 0; k < 8; ++k) { h ^= (v >> (8 * k)) & 0xff; h *= 1099511628211ull; }
-    }
-    return h | 4ull;   // (never 0: a handle with the term is never keyed like one without)
+    // FNV-1a over (block, weight bits), from a basis of its own; then the list, headed by its length and flag
+    const unsigned long long h = fnv1a_word(fnv1a_word(FNV_BASIS ^ 0xc2b2ae3d27d4eb4full, (unsigned long long)st->kg_layer), (unsigned long long)w);
+    return layer_list_hash(st->kg_list, h, 0x100 + 2 * st->kg_list.n + st->kg_centered) | 4ull;   // (never 0: a handle with the term is never keyed like one without)
 }
 // The key second-moment appearance term (include/splice_hip.h has the term): its weight, finite and > 0, and its block.  The global ViT
 // context writes the transposed bf16 copy of a block below the top (splice_vit_ctx_set_transposed_layers: a repeated call before the
@@ -1327,14 +1321,7 @@ int splice_step_set_key_gram(void* h, float lambda, int layer) {
     if (v.D % 64) { splice_set_error("%s: needs an embedding width that is a multiple of 64, got %d", who, v.D); return SPLICE_ERR_ARG; }
     if (st->pairs > 1 && st->na != st->nb) { splice_set_error("%s: not with several pairs of nA != nB crops (%d, %d)", who, st->na, st->nb); return SPLICE_ERR_STATE; }
     if (layer != v.depth - 1) RC(splice_vit_ctx_set_transposed_layers(v.ctx, 1, &layer));
-    v.pk_x = v.pk;
-    if (v.pk[layer]) v.dk_kg = const_cast<float*>(v.pk[layer]);
-    else {
-        RC(salloc(st, &v.dk_kg_own, (size_t)v.rows * v.D));
-        HIPCHK(hipMemset(v.dk_kg_own, 0, (size_t)v.rows * v.D * sizeof(float)));
-        v.dk_kg = v.dk_kg_own;
-        v.pk_x[layer] = v.dk_kg;
-    }
+    if (int rc = key_grad_buffers(st, v, 1, &layer, v.dk_kgl, v.dk_kgl_own, v.pk_x)) return rc;   // (a list of the one block: entry 0)
     const int slots = st->pairs * (st->na < st->nb ? st->na : st->nb), tiles = key_gram_tiles(v.D);
     RC(salloc(st, &st->kg_delta, (size_t)slots * v.D * v.D));
     RC(salloc(st, &st->kg_part, (size_t)slots * tiles));
@@ -1353,9 +1340,7 @@ int splice_step_key_gram_values(void* h, float* out) {
     const char* who = "splice_step_key_gram_values";
     if (!st || !out) { splice_set_error("%s: needs a handle and out", who); return SPLICE_ERR_ARG; }
     if (!(st->kg_lambda > 0.f)) { splice_set_error("%s: the handle has no key second-moment term (splice_step_set_key_gram)", who); return SPLICE_ERR_STATE; }
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, st->kg_value, (size_t)st->pairs * sizeof(float), hipMemcpyDeviceToHost));
-    return SPLICE_OK;
+    return values_to_host(out, st->kg_value, (size_t)st->pairs);
 }
 // The key second-moment term over several blocks, optionally centred (include/splice_hip.h has the term): the list version of
 // splice_step_set_key_gram, with its refusals; the two exclude each other in either order ("the term is set once").  Every named block
@@ -1369,17 +1354,7 @@ int splice_step_set_key_gram_layers(void* h, float lambda, int n, const int* lay
     VitView& v = st->vg;
     const int depth = v.depth;
     if (!(lambda > 0.f) || !(lambda <= 3.402823466e+38f)) { splice_set_error("%s: lambda must be finite and > 0, got %g", who, (double)lambda); return SPLICE_ERR_ARG; }
-    if (n < 1 || n > depth || n > KEY_GRAM_MAX_LAYERS) { splice_set_error("%s: needs 1..%d layers, got %d", who, depth < KEY_GRAM_MAX_LAYERS ? depth : KEY_GRAM_MAX_LAYERS, n); return SPLICE_ERR_ARG; }
-    for (int i = 0; i < n; ++i) {
-        if (layers[i] < 0 || layers[i] >= depth || (i > 0 && layers[i] <= layers[i - 1])) {
-            splice_set_error("%s: layers must be ascending distinct block indices in [0, %d), got layers[%d] = %d", who, depth, i, layers[i]);
-            return SPLICE_ERR_ARG;
-        }
-        if (!(weights[i] > 0.f) || !(weights[i] <= 3.402823466e+38f)) {
-            splice_set_error("%s: weights must be finite and > 0, got weights[%d] = %g", who, i, (double)weights[i]);
-            return SPLICE_ERR_ARG;
-        }
-    }
+    if (!layer_list_check(who, depth, KEY_GRAM_MAX_LAYERS, n, layers, weights)) return SPLICE_ERR_ARG;
     if (centered != 0 && centered != 1) { splice_set_error("%s: centered must be 0 or 1, got %d", who, centered); return SPLICE_ERR_ARG; }
     if (int rc = rule_setter_ok(st, who, "the term is set")) return rc;
     if (st->cfg.fp8_selfsim) { splice_set_error("%s: not with fp8_selfsim (the term reads the bf16 key copies of a bf16 forward)", who); return SPLICE_ERR_STATE; }
@@ -1390,15 +1365,7 @@ int splice_step_set_key_gram_layers(void* h, float lambda, int n, const int* lay
     for (int i = 0; i < n; ++i)
         if (layers[i] != depth - 1) below[nbelow++] = layers[i];
     if (nbelow) RC(splice_vit_ctx_set_transposed_layers(v.ctx, nbelow, below));
-    v.pk_x = v.pk;
-    for (int i = 0; i < n; ++i) {
-        const int l = layers[i];
-        if (v.pk[l]) { v.dk_kgl[i] = const_cast<float*>(v.pk[l]); continue; }
-        RC(salloc(st, &v.dk_kgl_own[i], (size_t)v.rows * v.D));
-        HIPCHK(hipMemset(v.dk_kgl_own[i], 0, (size_t)v.rows * v.D * sizeof(float)));
-        v.dk_kgl[i] = v.dk_kgl_own[i];
-        v.pk_x[l] = v.dk_kgl[i];
-    }
+    if (int rc = key_grad_buffers(st, v, n, layers, v.dk_kgl, v.dk_kgl_own, v.pk_x)) return rc;
     const size_t slots = (size_t)st->pairs * (st->na < st->nb ? st->na : st->nb), tiles = key_gram_tiles(v.D);
     RC(salloc(st, &st->kg_delta, n * slots * v.D * v.D));
     RC(salloc(st, &st->kg_part, n * slots * tiles));
@@ -1413,8 +1380,8 @@ int splice_step_set_key_gram_layers(void* h, float lambda, int n, const int* lay
         HIPCHK(hipMemset(st->kg_mu, 0, n * slots * 2 * v.D * sizeof(float)));
     }
     st->graphs.retire();
-    st->kg_lambda = lambda; st->kg_layer = layers[n - 1]; st->kg_n = n; st->kg_centered = centered;
-    for (int i = 0; i < n; ++i) { st->kg_layers[i] = layers[i]; st->kg_weights[i] = weights[i]; }
+    st->kg_lambda = lambda; st->kg_layer = layers[n - 1]; st->kg_centered = centered;
+    st->kg_list.set(n, layers, weights);
     return SPLICE_OK;
 }
 // The per-layer addends of the term of the last step that computed it, copied to the HOST behind a device-wide wait:
@@ -1423,10 +1390,8 @@ int splice_step_key_gram_layer_values(void* h, float* out) {
     SpliceStep* st = (SpliceStep*)h;
     const char* who = "splice_step_key_gram_layer_values";
     if (!st || !out) { splice_set_error("%s: needs a handle and out", who); return SPLICE_ERR_ARG; }
-    if (!st->kg_n) { splice_set_error("%s: the handle has no key second-moment layers (splice_step_set_key_gram_layers)", who); return SPLICE_ERR_STATE; }
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, st->kg_values, (size_t)st->pairs * st->kg_n * sizeof(float), hipMemcpyDeviceToHost));
-    return SPLICE_OK;
+    if (!kg_listed(st)) { splice_set_error("%s: the handle has no key second-moment layers (splice_step_set_key_gram_layers)", who); return SPLICE_ERR_STATE; }
+    return values_to_host(out, st->kg_values, (size_t)st->pairs * st->kg_list.n);
 }
 // Start the handle at step next_step_idx of a run other handles carried so far (a resumed run, a compacted engine; DESIGN.md section
 // 9g).  What a handle keeps from one step to the next, and this call therefore sets, is two things: ssim_id_on, which only the run of step
@@ -1606,7 +1571,7 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
     auto chain_bwd = [&](VitView& vw, int p0, int p1, bool vit, float* d_img, int h, int w, float* d_lead, void* plan, float* arena, int accumulate,
                          bool gen, int img_term, int cls_term, const std::vector<const float*>& pk, hipStream_t q) -> int {
         if (do_v) {
-            if (vit && st->n_cls_layers) RC(splice_vit_ctx_set_cls_seeds(vw.ctx, cls_term && t[cls_term].on ? vw.cls_seed_tab.data() : nullptr, p0, p1));
+            if (vit && st->cls_list.n) RC(splice_vit_ctx_set_cls_seeds(vw.ctx, cls_term && t[cls_term].on ? vw.cls_seed_tab.data() : nullptr, p0, p1));
             if (vit) RC(splice_vit_backward(vw.ctx, p0, p1, vw.pb.data(), nullptr, pk.data(), vw.d_imgs, 1, q));
             RC(unplace_grads(vw.d_imgs + (size_t)p0 * 3 * vw.H * vw.W, vw.H, vw.W, d_img, h, w, p1 - p0, q));
             if (st->leader) RC(add_f32_launch(d_lead, d_img, (size_t)(p1 - p0) * 3 * h * w, q));
@@ -1640,9 +1605,9 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
     SelfSimBatch sb = {};
     // structure layers (splice_step_set_ssim_layers): the tables of the two views' launches; null: the top block alone, the plain launches
     SelfSimLayers sl = {}, sle = {};
-    const bool layered = st->n_ssim_layers > 0;
+    const bool layered = st->ssim_list.n > 0;
     IdLayers idt = {};   // identity layers (splice_step_set_id_layers): the table of the term's two launches
-    const bool id_layered = do_v && t[L_GLOBAL_ID].on && st->n_id_layers > 0;
+    const bool id_layered = do_v && t[L_GLOBAL_ID].on && st->id_list.n > 0;
     // the key second-moment term (splice_step_set_key_gram): on the steps of the structure and identity terms, entire-image steps included
     const bool kg_on = do_v && ssim_on && st->kg_lambda > 0.f;
     if (do_v) {
@@ -1654,10 +1619,9 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
         RC(zero_seeds(vg, pX, Pa + Pb, s2));
         for (float* dk : vg.dk_id_own)   // the blocks only the identity list names: their y' passes alone (no x' chain reads them)
             if (dk) RC(dev_zero_launch(dk + pY * passD, Pb * passD * sizeof(float), s2));
-        // a block only the key second-moment term names: its x' passes alone (no other chain reads it), on the steps the term adds into them
-        if (kg_on && vg.dk_kg_own) RC(dev_zero_launch(vg.dk_kg_own + pX * passD, Pa * passD * sizeof(float), s2));
+        // the blocks only the key second-moment term names: their x' passes alone (no other chain reads them), on the steps the term adds into them
         if (kg_on)
-            for (float* dk : vg.dk_kgl_own)   // ... and of every block only the term's list names
+            for (float* dk : vg.dk_kgl_own)
                 if (dk) RC(dev_zero_launch(dk + pX * passD, Pa * passD * sizeof(float), s2));
         if (t[L_GLOBAL_SSIM].on) {   // target self-similarity S* of A' (util/losses.py:79)
             RC(ssim_batch(st, vg, pA, pX, Pa, t[L_GLOBAL_SSIM], L_GLOBAL_SSIM, &sb, layered ? &sl : nullptr));
@@ -1679,16 +1643,16 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
     // ---- losses on the global batch
     if (do_v) {
         if (t[L_GLOBAL_SSIM].on) RC(selfsim_loss_launch(sb, s, layered ? &sl : nullptr));
-        if (kg_on && st->kg_n) {   // the term over its list of blocks: one table, the layer a grid dimension
+        if (kg_on && kg_listed(st)) {   // the term over its list of blocks: one table, the layer a grid dimension
             KeyGramLayers kt = {};
-            kt.n = st->kg_n; kt.centered = st->kg_centered;
+            kt.n = st->kg_list.n; kt.centered = st->kg_centered;
             kt.ldt_x = kt.ldt_b = vg.rows; kt.tx_ps = kt.tb_ps = (size_t)vg.Tld; kt.ldk = 3 * vg.D; kt.k_ps = (size_t)vg.Tld * 3 * vg.D;
             kt.T = vg.T; kt.D = vg.D; kt.part_ps = (size_t)key_gram_tiles(vg.D); kt.lddk = vg.D; kt.dk_ps = passD;
             kt.values = st->kg_values; kt.value = st->kg_value; kt.mu = st->kg_mu;
             const size_t slots = (size_t)pairs * nc;
             const float c0 = 4.0f * st->kg_lambda / ((float)vg.T * (float)vg.D * (float)vg.D);
-            for (int i = 0; i < st->kg_n; ++i) {
-                const int l = st->kg_layers[i];
+            for (int i = 0; i < st->kg_list.n; ++i) {
+                const int l = st->kg_list.layers[i];
                 bf16_t *qkv = nullptr, *qkvT = nullptr;
                 RC(splice_vit_get_tensor(vg.ctx, 1, l, (void**)&qkv));
                 RC(splice_vit_get_tensor(vg.ctx, l == vg.depth - 1 ? 6 : 8, l, (void**)&qkvT));
@@ -1697,7 +1661,7 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
                 e.k_x = qkv + (size_t)pX * vg.Tld * 3 * vg.D + vg.D;
                 e.delta = st->kg_delta + i * slots * vg.D * vg.D; e.part = st->kg_part + i * slots * kt.part_ps;
                 e.dk = vg.dk_kgl[i] + pX * passD;
-                e.weight = st->kg_weights[i]; e.scale = c0 * e.weight;   // (one rounding more than the one-block scale; weight 1: its bits)
+                e.weight = st->kg_list.weights[i]; e.scale = c0 * e.weight;   // (one rounding more than the one-block scale; weight 1: its bits)
             }
             RC(key_gram_layers_loss_launch(kt, pairs, nc, s));
             RC(key_gram_layers_dk_launch(kt, pairs, nc, s));
@@ -1712,13 +1676,13 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
             kg.k_x = qkv + (size_t)pX * vg.Tld * 3 * vg.D + vg.D; kg.ldk = 3 * vg.D; kg.k_ps = (size_t)vg.Tld * 3 * vg.D;
             kg.T = vg.T; kg.D = vg.D;
             kg.delta = st->kg_delta; kg.part = st->kg_part; kg.part_ps = (size_t)key_gram_tiles(vg.D); kg.value = st->kg_value;
-            kg.dk = vg.dk_kg + pX * passD; kg.lddk = vg.D; kg.dk_ps = passD;
+            kg.dk = vg.dk_kgl[0] + pX * passD; kg.lddk = vg.D; kg.dk_ps = passD;
             kg.scale = 4.0f * st->kg_lambda / ((float)vg.T * (float)vg.D * (float)vg.D);
             RC(key_gram_loss_launch(kg, pairs, nc, s));
             RC(key_gram_dk_launch(kg, pairs, nc, s));
         }
-        if (t[L_GLOBAL_CLS].on && st->n_cls_layers) {   // [CLS] of the named blocks: one launch for all of them, the call structure of the plain path below
-            const int n = st->n_cls_layers;
+        if (t[L_GLOBAL_CLS].on && st->cls_list.n) {   // [CLS] of the named blocks: one launch for all of them, the call structure of the plain path below
+            const int n = st->cls_list.n;
             const float g = t[L_GLOBAL_CLS].lambda / (float)(size_t)vg.D;
             ClsLayers ct = {};
             if (pairs > 1 && st->na != st->nb) {
@@ -1744,7 +1708,7 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
                                       loss_part(st, L_GLOBAL_CLS), st->lstride, vg.d_block + pX * passD, vg.D, passD, Pc, s, t[L_GLOBAL_CLS].tab));
             }
         }
-        if (t[L_GLOBAL_ID].on && st->n_id_layers) {   // keys of the named blocks: one launch for all of them; its finish launch rides in bookkeeping
+        if (t[L_GLOBAL_ID].on && st->id_list.n) {   // keys of the named blocks: one launch for all of them; its finish launch rides in bookkeeping
             RC(id_table(st, pY, pB, &idt));
             RC(id_layers_launch(idt, Pb, t[L_GLOBAL_ID].lambda / (float)((size_t)vg.T * vg.D), t[L_GLOBAL_ID].tab, st->id_scratch, 0, s));
         } else if (t[L_GLOBAL_ID].on)    // keys of y' against keys of B' (util/losses.py:96-105): mean over h*T*d = T*D
@@ -1773,11 +1737,11 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
                 RC(selfsim_target_launch(se, s, layered ? &sle : nullptr));
                 RC(selfsim_loss_launch(se, s, layered ? &sle : nullptr));
             }
-            if (t[L_ENTIRE_CLS].on && st->n_cls_layers) {   // the same over the named blocks (one launch)
+            if (t[L_ENTIRE_CLS].on && st->cls_list.n) {   // the same over the named blocks (one launch)
                 ClsLayers ct = {};
                 RC(cls_table(st, ve, pairs, 1, pB, st->nb, &ct));
                 RC(cls_layers_launch(ct, pairs, t[L_ENTIRE_CLS].lambda / (float)(size_t)ve.D, t[L_ENTIRE_CLS].tab, loss_part(st, L_ENTIRE_CLS), st->lstride,
-                                     ve.cls_values, (size_t)st->n_cls_layers, s));
+                                     ve.cls_values, (size_t)st->cls_list.n, s));
             } else if (t[L_ENTIRE_CLS].on)   // target is the B_global crop's CLS (util/losses.py:60; with n_crops > 1 the zip pairs x_entire with the FIRST crop of its pair)
                 RC(mse_batched_launch(blk_e + pairs * epassD, ve.D, epassD, blk_g + pB * passD, vg.D, st->nb * passD, 1, ve.D, 1.0f, t[L_ENTIRE_CLS].lambda,
                                       loss_part(st, L_ENTIRE_CLS), st->lstride, ve.d_block + pairs * epassD, ve.D, epassD, pairs, s, t[L_ENTIRE_CLS].tab));
@@ -1796,14 +1760,14 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
             const bool lrp = st->lr_state != nullptr, trc = st->trace != nullptr;
             // the identity layers' finish launch: the slots' addends, and their sum into partial slot 0 of the term's zeroed row
             if (id_layered)
-                RC(id_layers_finish_launch(idt, Pb, t[L_GLOBAL_ID].tab, st->id_scratch, 0, st->id_values, (size_t)st->n_id_layers, loss_part(st, L_GLOBAL_ID),
+                RC(id_layers_finish_launch(idt, Pb, t[L_GLOBAL_ID].tab, st->id_scratch, 0, st->id_values, (size_t)st->id_list.n, loss_part(st, L_GLOBAL_ID),
                                            st->lstride, q));
             const auto kernel = kg_on ? total_loss_for<true>(img_on, layered, lrp, trc, stop_on) : total_loss_for<false>(img_on, layered, lrp, trc, stop_on);
             SPLICE_LAUNCH(kernel, dim3(pairs), dim3(img_on ? 448 : 320), 0, q, st->losses, st->lstride, (int)st->lp, t[L_GLOBAL_SSIM].lambda, t[L_ENTIRE_SSIM].lambda,
                           t[L_ENTIRE_CLS].lambda, t[L_GLOBAL_CLS].lambda, t[L_GLOBAL_ID].lambda, st->losses_out, grouped ? st->na : n1, grouped ? st->nb : n1, grouped ? nc : n1,
                           grouped ? 1 : n1, st->pw ? st->pw + (size_t)PW_LAMBDAS * P : nullptr, (int)ssim_on, (int)entire, st->stop, st->dev_t, st->stop_rule, st->best, st->best_means,
                           st->trace, st->trace_cap, st->lr_rule, st->lr_state, st->lr_cuts, (const float*)(st->pair_lr ? st->dev_lrs : st->dev_lr), st->pair_lr ? 1 : 0,
-                          st->lr_eff, st->lambda_tv, st->lambda_pix, st->n_ssim_layers, tri_tiles(vg.T), st->plan_e ? tri_tiles(ve.T) : 0, st->kg_lambda, (const float*)st->kg_value);
+                          st->lr_eff, st->lambda_tv, st->lambda_pix, st->ssim_list.n, tri_tiles(vg.T), st->plan_e ? tri_tiles(ve.T) : 0, st->kg_lambda, (const float*)st->kg_value);
         }
         if (!st->running || !gen_fwd) return SPLICE_OK;
         void* plans[3] = {st->plan_a, st->plan_b, nullptr};

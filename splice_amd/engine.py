@@ -66,26 +66,17 @@ class MultiPairEngine:
         self.opt_ext = fused_optimizer_ext(self.cfg)   # None: the plain rules, today's launches
         self.w = None
         self.image_terms = image_terms_rule(self.cfg)
-        # the blocks of the structure terms: None -- the top block, today's launches -- or the canonical (layers, weights),
-        # which the config then holds too (what a snapshot is compared on)
+        # the blocks of the structure terms, the two appearance terms and the key-identity term (LAYER_LIST_TERMS; DESIGN.md sections 9k, 9l,
+        # 9m): ssim_layers / cls_layers / id_layers are None -- the top block, today's launches -- or the canonical (layers, weights), which the
+        # config then holds too (what a snapshot is compared on)
         depth = vit_engine.depth if vit_engine is not None else synth.DINO_CONFIGS[self.cfg["dino_model_name"]][2]
-        self.ssim_layers = ssim_layers_rule(self.cfg, depth)
-        if self.ssim_layers is not None:
-            if fp8_mode(fp8):
-                raise ValueError("'dino_ssim_layers': not with fp8 -- the e4m3 Gram path of the structure term reads the top block alone")
-            self.cfg.update(dino_ssim_layers=list(self.ssim_layers[0]), dino_ssim_layer_weights=list(self.ssim_layers[1]))
-        # the blocks of the two appearance terms, likewise: None -- the top block's [CLS] row, today's launches
-        self.cls_layers = cls_layers_rule(self.cfg, depth)
-        if self.cls_layers is not None:
-            if fp8_mode(fp8):
-                raise ValueError("'dino_cls_layers': not with fp8 -- the e4m3 forward is validated against the top block's [CLS] row alone")
-            self.cfg.update(dino_cls_layers=list(self.cls_layers[0]), dino_cls_layer_weights=list(self.cls_layers[1]))
-        # the blocks of the key-identity term, likewise: None -- the top block's keys, today's launches
-        self.id_layers = id_layers_rule(self.cfg, depth)
-        if self.id_layers is not None:
-            if fp8_mode(fp8):
-                raise ValueError("'dino_id_layers': not with fp8 -- the e4m3 forward keeps fp32 keys of the top block alone")
-            self.cfg.update(dino_id_layers=list(self.id_layers[0]), dino_id_layer_weights=list(self.id_layers[1]))
+        for term in LAYER_LIST_TERMS:
+            rule = layer_list_rule(term, self.cfg, depth)
+            setattr(self, term.attr, rule)
+            if rule is not None:
+                if fp8_mode(fp8):
+                    raise ValueError(f"'{term.keys[0]}': not with fp8 -- {term.fp8}")
+                self.cfg.update(zip(term.keys, (list(rule[0]), list(rule[1]))))
         # the key second-moment appearance term: None -- off, today's launches -- or (lambda, block); the config then
         # holds the block it runs on (what a snapshot is compared on)
         # ... over a list of blocks, or centred: key_gram_layers is None -- the one-block term or none, today's launches --
@@ -270,24 +261,15 @@ class MultiPairEngine:
         # the first step.  Both 0: the call is not made and the handle launches what it always did
         if max(self.image_terms) > 0:
             _lib.check(_lib.lib().splice_step_set_image_terms(self.handle, *self.image_terms), "step_set_image_terms")
-        # the blocks of the structure terms (shared by the slots): the layer is one more grid dimension of the three self-similarity launches;
-        # before the first step.  The default: the call is not made and the handle launches what it always did
-        if self.ssim_layers is not None:
-            n = len(self.ssim_layers[0])
-            _lib.check(_lib.lib().splice_step_set_ssim_layers(self.handle, n, (C.c_int * n)(*self.ssim_layers[0]), (C.c_float * n)(*self.ssim_layers[1])),
-                       "step_set_ssim_layers")
-        # the blocks of the appearance terms (shared by the slots): one layered launch per term, [CLS]-row seeds into the ViT backward; before
-        # the first step.  The default: the call is not made and the handle launches what it always did
-        if self.cls_layers is not None:
-            n = len(self.cls_layers[0])
-            _lib.check(_lib.lib().splice_step_set_cls_layers(self.handle, n, (C.c_int * n)(*self.cls_layers[0]), (C.c_float * n)(*self.cls_layers[1])),
-                       "step_set_cls_layers")
-        # the blocks of the identity term (shared by the slots): two layered launches, fp32 keys and key gradients of the named blocks on the
-        # y' chain; before the first step, behind the structure layers (shared buffers).  The default: the call is not made
-        if self.id_layers is not None:
-            n = len(self.id_layers[0])
-            _lib.check(_lib.lib().splice_step_set_id_layers(self.handle, n, (C.c_int * n)(*self.id_layers[0]), (C.c_float * n)(*self.id_layers[1])),
-                       "step_set_id_layers")
+        # the blocks of the three plain per-layer terms (shared by the slots), before the first step: the structure terms (the layer is one
+        # more grid dimension of the three self-similarity launches), the appearance terms (one layered launch per term, [CLS]-row seeds into
+        # the ViT backward), then the identity term (two layered launches, fp32 keys and key gradients of the named blocks on the y' chain),
+        # behind the structure layers whose buffers it shares.  The default: the call is not made and the handle launches what it always did
+        for term in LAYER_LIST_TERMS:
+            rule = getattr(self, term.attr)
+            if rule is not None:
+                n = len(rule[0])
+                _lib.check(getattr(_lib.lib(), term.setter)(self.handle, n, (C.c_int * n)(*rule[0]), (C.c_float * n)(*rule[1])), term.setter[len("splice_"):])
         # the key second-moment term (shared by the slots): three launches on the x' chain from cls_warmup on; before the first step, behind
         # the structure and identity layers (shared key-gradient buffers).  The default: the call is not made
         if self.key_gram_layers is not None:   # (the list, or the centred form: the layered launches)
@@ -684,13 +666,24 @@ class MultiPairEngine:
         n = len(self.key_gram_layers[1])
         buf = (C.c_float * (self.P * n))()
         _lib.check(_lib.lib().splice_step_key_gram_layer_values(self.handle, buf), "step_key_gram_layer_values")
-        vals = np.frombuffer(buf, dtype=np.float32).reshape(self.P, n).copy()
+        return self._layer_rows(np.frombuffer(buf, dtype=np.float32).reshape(self.P, 1, n), pair, "key_gram_layer_values", "values")
+
+    def _layer_rows(self, host, pair, who, noun):
+        """The shared tail of the ``*_layer_values`` methods.  ``host``: float32 ``[P][slots][n]``, a pair's crops (slots) in crop order.  Per
+        pair the slots are added per layer in float32 in slot order; then one array for ``pair``, a list over the live slots for
+        ``pair=None``.  ``who`` / ``noun``: the method and what a parked slot lost, for the error text."""
+        rows = []
+        for slots in host:
+            acc = slots[0].copy()
+            for row in slots[1:]:
+                acc = (acc + row).astype(np.float32)
+            rows.append(acc)
         if pair is None and self.PAIR_NONE is None:
-            return list(vals)
+            return rows
         row = self._row(self.PAIR_NONE if pair is None else pair)
         if row is None:
-            raise RuntimeError(f"key_gram_layer_values: slot {pair} is parked (stop_compact): its values left the device with its handle")
-        return vals[row]
+            raise RuntimeError(f"{who}: slot {pair} is parked (stop_compact): its {noun} left the device with its handle")
+        return rows[row]
 
     def ssim_layer_values(self, pair=None, entire=False):
         """The per-layer addends of the last step's structure term (``dino_ssim_layers``), copied from the device
@@ -704,14 +697,7 @@ class MultiPairEngine:
             raise RuntimeError("ssim_layer_values: the engine has no entire-image branch")
         out = torch.zeros(len(self.ssim_layers[0]), self.P, device=self.device)
         _lib.check(_lib.lib().splice_step_ssim_layer_values(self.handle, 2 if entire else 1, _lib.ptr(out), _lib.current_stream()), "step_ssim_layer_values")
-        host = out.cpu().numpy()
-        rows = [host[:, i].copy() for i in range(self.P)]
-        if pair is None and self.PAIR_NONE is None:
-            return rows
-        row = self._row(self.PAIR_NONE if pair is None else pair)
-        if row is None:
-            raise RuntimeError(f"ssim_layer_values: slot {pair} is parked (stop_compact): its partials left the device with its handle")
-        return rows[row]
+        return self._layer_rows(out.cpu().numpy().T[:, None, :], pair, "ssim_layer_values", "partials")
 
     def cls_layer_values(self, pair=None, entire=False):
         """The per-layer addends of the appearance term (``dino_cls_layers``) of the last step that computed it, copied
@@ -727,19 +713,7 @@ class MultiPairEngine:
         nc = 1 if entire or self.n_crops == 1 else min(self.n_crops_ab)
         buf = (C.c_float * (self.P * nc * n))()
         _lib.check(_lib.lib().splice_step_cls_layer_values(self.handle, 1 if entire else 0, buf, len(buf)), "step_cls_layer_values")
-        host = np.frombuffer(buf, dtype=np.float32).reshape(self.P, nc, n)
-        rows = []
-        for p in range(self.P):
-            acc = host[p, 0].copy()
-            for i in range(1, nc):
-                acc = (acc + host[p, i]).astype(np.float32)
-            rows.append(acc)
-        if pair is None and self.PAIR_NONE is None:
-            return rows
-        row = self._row(self.PAIR_NONE if pair is None else pair)
-        if row is None:
-            raise RuntimeError(f"cls_layer_values: slot {pair} is parked (stop_compact): its values left the device with its handle")
-        return rows[row]
+        return self._layer_rows(np.frombuffer(buf, dtype=np.float32).reshape(self.P, nc, n), pair, "cls_layer_values", "values")
 
     def id_layer_values(self, pair=None):
         """The per-layer addends of the key-identity term (``dino_id_layers``) of the last step that computed it, copied
@@ -753,19 +727,7 @@ class MultiPairEngine:
         nb = self.n_crops_ab[1]
         buf = (C.c_float * (self.P * nb * n))()
         _lib.check(_lib.lib().splice_step_id_layer_values(self.handle, buf, len(buf)), "step_id_layer_values")
-        host = np.frombuffer(buf, dtype=np.float32).reshape(self.P, nb, n)
-        rows = []
-        for p in range(self.P):
-            acc = host[p, 0].copy()
-            for i in range(1, nb):
-                acc = (acc + host[p, i]).astype(np.float32)
-            rows.append(acc)
-        if pair is None and self.PAIR_NONE is None:
-            return rows
-        row = self._row(self.PAIR_NONE if pair is None else pair)
-        if row is None:
-            raise RuntimeError(f"id_layer_values: slot {pair} is parked (stop_compact): its values left the device with its handle")
-        return rows[row]
+        return self._layer_rows(np.frombuffer(buf, dtype=np.float32).reshape(self.P, nb, n), pair, "id_layer_values", "values")
 
     def active_terms(self, step_idx):
         """Per slot: which of LOSS_KEYS and IMAGE_LOSS_KEYS step ``step_idx`` computes (``engine.active_terms``; a slot's terms follow that slot's own
@@ -926,18 +888,13 @@ class MultiScaleEngine:
             if lam > 0:
                 raise NotImplementedError(f"{key} > 0: the term's gradient is added to a whole fused step's image gradient; MultiScaleEngine's per-scale "
                                           "follower handles add theirs into the leader's, which would count the term once per scale")
-        if ssim_layers_rule(self.cfg, vit_engine.depth if vit_engine is not None else synth.DINO_CONFIGS[self.cfg["dino_model_name"]][2]) is not None:
-            raise NotImplementedError("dino_ssim_layers: the layer table is set on a whole fused step; MultiScaleEngine runs each scale as a gradient-only "
-                                      "or phase-mode handle, which refuses it")
-        if cls_layers_rule(self.cfg, vit_engine.depth if vit_engine is not None else synth.DINO_CONFIGS[self.cfg["dino_model_name"]][2]) is not None:
-            raise NotImplementedError("dino_cls_layers: the layer table is set on a whole fused step; MultiScaleEngine runs each scale as a gradient-only "
-                                      "or phase-mode handle, which refuses it")
-        if id_layers_rule(self.cfg, vit_engine.depth if vit_engine is not None else synth.DINO_CONFIGS[self.cfg["dino_model_name"]][2]) is not None:
-            raise NotImplementedError("dino_id_layers: the layer table is set on a whole fused step; MultiScaleEngine runs each scale as a gradient-only "
-                                      "or phase-mode handle, which refuses it")
-        key_gram_layers_rule(self.cfg, vit_engine.depth if vit_engine is not None else synth.DINO_CONFIGS[self.cfg["dino_model_name"]][2])   # (a bad value is refused by name here too)
-        if key_gram_rule(dict(self.cfg, dino_gram_layer=None if self.cfg.get("dino_gram_layers") is not None else self.cfg.get("dino_gram_layer")),
-                         vit_engine.depth if vit_engine is not None else synth.DINO_CONFIGS[self.cfg["dino_model_name"]][2]) is not None:
+        depth = vit_engine.depth if vit_engine is not None else synth.DINO_CONFIGS[self.cfg["dino_model_name"]][2]
+        for term in LAYER_LIST_TERMS:
+            if layer_list_rule(term, self.cfg, depth) is not None:
+                raise NotImplementedError(f"{term.keys[0]}: the layer table is set on a whole fused step; MultiScaleEngine runs each scale as a gradient-only "
+                                          "or phase-mode handle, which refuses it")
+        key_gram_layers_rule(self.cfg, depth)   # (a bad value is refused by name here too)
+        if key_gram_rule(dict(self.cfg, dino_gram_layer=None if self.cfg.get("dino_gram_layers") is not None else self.cfg.get("dino_gram_layer")), depth) is not None:
             raise NotImplementedError("lambda_global_key_gram: the term is set on a whole fused step; MultiScaleEngine runs each scale as a gradient-only "
                                       "or phase-mode handle, which refuses it")
         self.ema_rule = ema_rule(self.cfg)

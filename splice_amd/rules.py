@@ -3,6 +3,8 @@
 In this order: the config's defaults and key groups; the checks of every rule's keys (``*_rule``: ValueError naming the key); the NumPy
 restatements of the rules' arithmetic (``np_*``); the decoders of the device records; the step arithmetic.  Nothing here launches
 anything: the module needs neither the generator nor the ViT engine.  ``splice_amd.engine`` hands every public name on."""
+from collections import namedtuple
+
 import numpy as np
 import torch
 
@@ -55,12 +57,20 @@ DEFAULT_CFG = dict(  # conf/default/config.yaml of the reference
     lambda_global_key_gram=0.0, dino_gram_layer=None,
     # ... over a list of blocks with a weight each, and its centred (covariance) form; null / false: the one-block uncentred term
     dino_gram_layers=None, dino_gram_layer_weights=None, dino_gram_centered=False)
-SSIM_LAYER_KEYS = ("dino_ssim_layers", "dino_ssim_layer_weights")
-MAX_SSIM_LAYERS = 12   # SELFSIM_MAX_LAYERS: entries of the loss kernels' by-value layer table
-CLS_LAYER_KEYS = ("dino_cls_layers", "dino_cls_layer_weights")
-MAX_CLS_LAYERS = 12    # CLS_MAX_LAYERS: entries of the layered [CLS] loss kernel's by-value table
-ID_LAYER_KEYS = ("dino_id_layers", "dino_id_layer_weights")
-MAX_ID_LAYERS = 12     # ID_MAX_LAYERS: entries of the layered key-identity kernels' by-value table
+# The three plain per-layer terms -- a list of blocks with a weight each and nothing else -- in the order the engine sets them (the identity
+# list behind the structure list, whose key-gradient buffers it shares).  keys: the two config keys; most: entries of the term's by-value
+# kernel table (SELFSIM_MAX_LAYERS / CLS_MAX_LAYERS / ID_MAX_LAYERS); attr: the engine attribute that holds the canonical (layers,
+# weights) or None; setter: the C call that takes them; fp8: why the engine refuses the keys with fp8; section: of DESIGN.md.
+LayerListTerm = namedtuple("LayerListTerm", "keys most attr setter fp8 section")
+LAYER_LIST_TERMS = (
+    LayerListTerm(("dino_ssim_layers", "dino_ssim_layer_weights"), 12, "ssim_layers", "splice_step_set_ssim_layers",
+                  "the e4m3 Gram path of the structure term reads the top block alone", "9k"),
+    LayerListTerm(("dino_cls_layers", "dino_cls_layer_weights"), 12, "cls_layers", "splice_step_set_cls_layers",
+                  "the e4m3 forward is validated against the top block's [CLS] row alone", "9l"),
+    LayerListTerm(("dino_id_layers", "dino_id_layer_weights"), 12, "id_layers", "splice_step_set_id_layers",
+                  "the e4m3 forward keeps fp32 keys of the top block alone", "9m"))
+SSIM_LAYER_KEYS, CLS_LAYER_KEYS, ID_LAYER_KEYS = (t.keys for t in LAYER_LIST_TERMS)
+MAX_SSIM_LAYERS, MAX_CLS_LAYERS, MAX_ID_LAYERS = (t.most for t in LAYER_LIST_TERMS)
 KEY_GRAM_KEYS = ("lambda_global_key_gram", "dino_gram_layer")
 KEY_GRAM_LAYER_KEYS = ("dino_gram_layers", "dino_gram_layer_weights", "dino_gram_centered")
 MAX_KEY_GRAM_LAYERS = 12   # KEY_GRAM_MAX_LAYERS: entries of the layered key second-moment kernels' by-value table
@@ -220,7 +230,12 @@ def ssim_layers_rule(c, depth):
     float32 numbers > 0 (null: all 1), refused without ``dino_ssim_layers``.  ``[depth - 1]`` with weight 1 is the default and also
     returns ``None``.  Shared by the slots of a sweep (``merge_pair_cfgs`` refuses a per-slot value).  Raises ValueError naming the
     key."""
-    return _layers_rule(c, depth, SSIM_LAYER_KEYS, MAX_SSIM_LAYERS)
+    return layer_list_rule(LAYER_LIST_TERMS[0], c, depth)
+
+
+def layer_list_rule(term, c, depth):
+    """The rule of one of LAYER_LIST_TERMS (``ssim_layers_rule`` / ``cls_layers_rule`` / ``id_layers_rule`` state it) on config ``c``."""
+    return _layers_rule(c, depth, term.keys, term.most)
 
 
 def _layers_rule(c, depth, keys, most):
@@ -261,7 +276,7 @@ def cls_layers_rule(c, depth):
     1..``min(depth, MAX_CLS_LAYERS)`` distinct integers in ``[0, depth)``, the top block not required; ``dino_cls_layer_weights`` a list of
     as many finite float32 numbers > 0 (null: all 1), refused without ``dino_cls_layers``.  Shared by the slots of a sweep
     (``merge_pair_cfgs`` refuses a per-slot value).  Raises ValueError naming the key."""
-    return _layers_rule(c, depth, CLS_LAYER_KEYS, MAX_CLS_LAYERS)
+    return layer_list_rule(LAYER_LIST_TERMS[1], c, depth)
 
 
 def id_layers_rule(c, depth):
@@ -271,7 +286,7 @@ def id_layers_rule(c, depth):
     1..``min(depth, MAX_ID_LAYERS)`` distinct integers in ``[0, depth)``, the top block not required; ``dino_id_layer_weights`` a list of
     as many finite float32 numbers > 0 (null: all 1), refused without ``dino_id_layers``.  Shared by the slots of a sweep
     (``merge_pair_cfgs`` refuses a per-slot value).  Raises ValueError naming the key."""
-    return _layers_rule(c, depth, ID_LAYER_KEYS, MAX_ID_LAYERS)
+    return layer_list_rule(LAYER_LIST_TERMS[2], c, depth)
 
 
 def key_gram_rule(c, depth):
@@ -382,26 +397,18 @@ def np_key_gram(kx, kb, lam):
     return float(np.mean(delta * delta)), (4.0 * float(lam) / (T * D * D)) * (kx @ delta)
 
 
-def np_id_layers(values, weights=None):
-    """Word 5 of a losses row from the per-layer addends ``engine.id_layer_values`` reports (already weighted; ``weights`` given:
-    unweighted values, multiplied in float32 first): their float32 sum over the blocks ascending, one rounding per addition, from 0."""
-    return np_ssim_layers(values, weights)
-
-
-def np_cls_layers(values, weights=None):
-    """Word 4 / 3 of a losses row from the per-layer addends ``engine.cls_layer_values`` reports (already weighted; ``weights`` given:
-    unweighted values, multiplied in float32 first): their float32 sum over the blocks ascending, one rounding per addition, from 0."""
-    return np_ssim_layers(values, weights)
-
-
 def np_ssim_layers(values, weights=None):
-    """Word 1 / 2 of a losses row from the per-layer addends ``engine.ssim_layer_values`` reports (already weighted; ``weights`` given:
-    unweighted values, multiplied in float32 first): their float32 sum over the blocks ascending, one rounding per addition, from 0."""
+    """A word of a losses row -- 1 / 2, 4 / 3, 5 -- from the per-layer addends ``engine.ssim_layer_values`` / ``cls_layer_values`` /
+    ``id_layer_values`` report (already weighted; ``weights`` given: unweighted values, multiplied in float32 first): their float32 sum over
+    the blocks ascending, one rounding per addition, from 0."""
     f = np.float32
     acc = f(0)
     for i, v in enumerate(values):
         acc = f(acc + (f(v) if weights is None else f(f(weights[i]) * f(v))))
     return acc
+
+
+np_cls_layers = np_id_layers = np_ssim_layers
 
 
 def snapshot_cfg_mismatch(a, b):

@@ -408,25 +408,30 @@ def image_terms_fields(engine):
     return {k: cfg[k] for k in IMAGE_LAMBDA_KEYS if cfg.get(k, 0) != 0}
 
 
+def layer_list_fields(engine, only=None):
+    """What ``result.json`` / ``variant.json`` say about the blocks of the structure, appearance and key-identity terms of a run (shared by
+    the slots; ``rules.LAYER_LIST_TERMS``, DESIGN.md sections 9k, 9l, 9m): a term's two config keys -- ``dino_ssim_layers`` /
+    ``dino_ssim_layer_weights`` and so on -- in canonical order where the run named other blocks than the default.  ``only``: the engine
+    attribute of the one term to report (None: all three)."""
+    from .rules import LAYER_LIST_TERMS
+    out = {}
+    for term in LAYER_LIST_TERMS:
+        rule = getattr(engine, term.attr, None) if only in (None, term.attr) else None
+        if rule is not None:
+            out.update(zip(term.keys, (list(rule[0]), list(rule[1]))))
+    return out
+
+
 def ssim_layers_fields(engine):
-    """What ``result.json`` / ``variant.json`` say about the blocks of the structure terms of a run (shared by the slots; DESIGN.md
-    section 9k): ``dino_ssim_layers`` / ``dino_ssim_layer_weights`` in canonical order where the run named other blocks than the default."""
-    rule = getattr(engine, "ssim_layers", None)
-    return {} if rule is None else {"dino_ssim_layers": list(rule[0]), "dino_ssim_layer_weights": list(rule[1])}
+    return layer_list_fields(engine, "ssim_layers")
 
 
 def cls_layers_fields(engine):
-    """What ``result.json`` / ``variant.json`` say about the blocks of the appearance terms of a run (shared by the slots; DESIGN.md
-    section 9l): ``dino_cls_layers`` / ``dino_cls_layer_weights`` in canonical order where the run named other blocks than the default."""
-    rule = getattr(engine, "cls_layers", None)
-    return {} if rule is None else {"dino_cls_layers": list(rule[0]), "dino_cls_layer_weights": list(rule[1])}
+    return layer_list_fields(engine, "cls_layers")
 
 
 def id_layers_fields(engine):
-    """What ``result.json`` / ``variant.json`` say about the blocks of the key-identity term of a run (shared by the slots; DESIGN.md
-    section 9m): ``dino_id_layers`` / ``dino_id_layer_weights`` in canonical order where the run named other blocks than the default."""
-    rule = getattr(engine, "id_layers", None)
-    return {} if rule is None else {"dino_id_layers": list(rule[0]), "dino_id_layer_weights": list(rule[1])}
+    return layer_list_fields(engine, "id_layers")
 
 
 def key_gram_fields(engine):
@@ -574,7 +579,7 @@ def train_sweep(dataroot, variants, cfg_overrides=None, vit_state=None, callback
     losses = engine.losses() if engine.step_idx >= 0 else [{} for _ in range(K)]
     for k in range(K):
         with open(os.path.join(out_dirs[k], 'variant.json'), 'w') as f:
-            json.dump({"index": k, "overrides": variants[k], "seed": seeds[k], "losses": losses[k], "stopped_at": engine.stopped_at[k], **trace_fields(engine), **lr_fields(engine, k), **optim_fields(engine), **image_terms_fields(engine), **ssim_layers_fields(engine), **cls_layers_fields(engine), **id_layers_fields(engine), **key_gram_fields(engine)}, f)
+            json.dump({"index": k, "overrides": variants[k], "seed": seeds[k], "losses": losses[k], "stopped_at": engine.stopped_at[k], **trace_fields(engine), **lr_fields(engine, k), **optim_fields(engine), **image_terms_fields(engine), **layer_list_fields(engine), **key_gram_fields(engine)}, f)
     return engine
 
 
