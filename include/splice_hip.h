@@ -985,6 +985,47 @@ int splice_key_gram_layers_pairs(int n_layers, const splice_bf16* const* k_x, co
                                  splice_bf16* const* delta, float* const* part, float* const* dk, const float* weights, const float* scales, int ldk,
                                  size_t k_ps, int ldt_x, size_t tx_ps, int ldt_b, size_t tb_ps, int T, int D, int pairs, int centered, size_t part_ps,
                                  float* values, float* value, float* mu, int lddk, size_t dk_ps, splice_stream_t stream);
+/* ------------------------------------------------------------------ the nearest-neighbour key appearance term.
+ * With lambda > 0 (finite) and one block index `layer` in [0, depth), every step from cls_warmup on -- ordinary and entire-image steps
+ * alike, the steps of the key second-moment term -- adds to the total, word 0 of the losses row, lambda * raw,
+ *     raw = sum over the crop pairs i < min(nA, nB) of (1 / T) sum over the tokens t of (1 - c_t,j*(t)),
+ *     c_tj = (k_t . b_j) / max(|k_t| |b_j|, eps),  eps = 1e-8,   j*(t) = the LOWEST j among those with the largest c_tj,
+ * k_t / b_j the bf16 key rows of block `layer` (every token, the heads concatenated) of x' = G(A_crop) and of the target pass B'.  It
+ * enters word 0 last, behind the key second-moment term where both are on.  The target carries no gradient; the key gradient, that of
+ * autograd through clamp and max, is ADDED into the block's key-gradient buffer of the x' chain behind the structure term's store and the
+ * key second-moment term's add: the top block's, a structure-list or key-second-moment block's, else one of its own that only the x' chain
+ * reads and that is zeroed on the steps the term runs.  Four launches (key_nn.hip) whatever the number of pairs and crops.  Before the
+ * first splice_step_run only and behind splice_step_set_ssim_layers / _id_layers / _key_gram / _key_gram_layers where they are called;
+ * refused on a handle in gradient-only or phase mode or with a leader (which in turn refuses those calls), with fp8_selfsim, with several
+ * pairs whose crop counts nA != nB differ, and a second time.  A handle without the call launches what it always did. */
+int splice_step_set_key_nn(void* step, float lambda, int layer);
+/* The raw term of the last step that computed it, copied to the host behind a device-wide wait: out[p] = pair p's value, `pairs`
+ * floats.  A pair reads 0 before the first such step. */
+int splice_step_key_nn_values(void* step, float* out);
+/* The assignment of that step, copied to the host behind a device-wide wait: match ([pairs][crops][T] int32) and cos (the same shape,
+ * floats), crops = min(nA, nB).  Zeros before the first such step.  Either pointer may be NULL. */
+int splice_step_key_nn_match(void* step, int* match, float* cos);
+/* test hook: the four launches of the term on caller buffers, one crop per pair.  Pair p reads the row-major bf16 keys k_x + p * kx_ps
+ * (generated) and k_b + p * kb_ps (target), [T][ldk] each.  D % 64 == 0; T, pairs >= 1; both key pointers, ldk and the pair strides
+ * multiples of 16 bytes; ldk, lddk >= D; part_ps >= ceil(T / 4); scale finite, eps finite and > 0; no null pointer; else refused with
+ * SPLICE_ERR_ARG and nothing launched.  ws: splice_key_nn_ws_bytes(T, D, pairs) bytes of device scratch.  Rows >= T of either key array are
+ * never read.  All arithmetic is fp32; fl() is one rounding to nearest; x_d are the bf16 values widened exactly.
+ *   norms    n_t = sqrt(s),  s = the row's squares x_d^2 added by fused multiply-adds on 64 lanes (lane l: d = l, l + 64, ..., ascending,
+ *            from 0), then the wave tree (offsets 32, 16, ..., 1);  m_j likewise of the target rows.
+ *   cosines  a_tj = the fp32 MFMA accumulation of the D exact products k_td b_jd (16x16x32 bf16, K slices ascending);
+ *            c_tj = fl(a_tj / max(fl(n_t m_j), eps))   for j < T.
+ *   match    per 64-column tile the (maximum, lowest column of the maximum) of row t; the tiles ascending with a strict >:
+ *            match[p][t] = j*(t),  cos[p][t] = c_t,j*   (all-zero row t: every c is 0, match 0).
+ *   dk       with j = j*(t), q = fl(n_t m_j), f = max(q, eps), wb = fl(-scale / f), wk = q > eps ? fl(fl(scale * c_tj) / fl(n_t n_t)) : 0:
+ *            dk[p * dk_ps + t * lddk + d] = fma(wb, b_jd, fma(wk, k_td, dk[...]))   for t < T, d < D; rows >= T keep their bits.
+ *   part     part[p * part_ps + g] = (r_0 + r_1) + (r_2 + r_3),  r_w = fl(1 - c_t,j*) of row t = 4 g + w, 0 for t >= T;  g < ceil(T / 4).
+ *   value    value[p] = fl(S * fl(1 / T)),  S = the partials added on 64 lanes (lane l: g = l, l + 64, ..., ascending, from 0), then the
+ *            wave tree (the step: the pair's crops' S added in crop order from 0 first).
+ * scale is lambda / T as the caller rounded it.  Pair p has the bits of its own one-pair call. */
+size_t splice_key_nn_ws_bytes(int T, int D, int pairs);
+int splice_key_nn_pairs(const splice_bf16* k_x, const splice_bf16* k_b, int ldk, size_t kx_ps, size_t kb_ps, int T, int D, int pairs, float scale,
+                        float eps, int* match, float* cos, float* part, size_t part_ps, float* value, float* dk, int lddk, size_t dk_ps, void* ws,
+                        splice_stream_t stream);
 /* splice_total_loss_pairs as a handle with a loss trace launches it (splice_step_set_loss_trace): dev_t (device) holds step index + 1,
  * and words 0-5 of row step index of trace ([capacity][pairs][8], device) receive pair p's out8 values, a row at or beyond capacity
  * left out.  stop (may be NULL; device, [pairs] records) runs the instance of a handle with the stop rule, whose rule is window (>= 1),

@@ -260,6 +260,12 @@ _SIGNATURES = {
     "splice_step_key_gram_values": ([_vp, _vp], _i),
     "splice_key_gram_pairs": ([_vp, _i, _sz, _vp, _i, _sz, _vp, _i, _sz, _i, _i, _i, _f, _vp, _vp, _sz, _vp, _vp, _i, _sz, _vp], _i),
     # ... over several blocks, and centred
+    # the nearest-neighbour key appearance term
+    "splice_step_set_key_nn": ([_vp, _f, _i], _i),
+    "splice_step_key_nn_values": ([_vp, _vp], _i),
+    "splice_step_key_nn_match": ([_vp, _vp, _vp], _i),
+    "splice_key_nn_ws_bytes": ([_i, _i, _i], _sz),
+    "splice_key_nn_pairs": ([_vp, _vp, _i, _sz, _sz, _i, _i, _i, _f, _f, _vp, _vp, _vp, _sz, _vp, _vp, _i, _sz, _vp, _vp], _i),
     "splice_step_set_key_gram_layers": ([_vp, _f, _i, _vp, _vp, _i], _i),
     "splice_step_key_gram_layer_values": ([_vp, _vp], _i),
     "splice_key_gram_layers_pairs": ([_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _sz, _i, _sz, _i, _sz, _i, _i, _i, _i, _sz, _vp, _vp, _vp, _i, _sz, _vp], _i),

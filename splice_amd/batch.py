@@ -114,11 +114,11 @@ def _slot_fields(eng, slot=None):
     is not 0 (``train.image_terms_fields``).  The blocks of the structure terms: ``dino_ssim_layers`` / ``dino_ssim_layer_weights`` where the
     run named other blocks than the top one, and of the appearance terms likewise (``dino_cls_layers`` / ``dino_cls_layer_weights``) and of
     the identity term (``dino_id_layers`` / ``dino_id_layer_weights``): ``train.layer_list_fields``.  The key second-moment appearance term: ``lambda_global_key_gram`` / ``dino_gram_layer`` where it was on
-    (``train.key_gram_fields``)."""
-    from .train import best_fields, clip_fields, image_terms_fields, key_gram_fields, layer_list_fields, lr_fields, optim_fields, trace_fields
+    (``train.key_gram_fields``), and the nearest-neighbour key term likewise: ``lambda_global_key_nn`` / ``dino_nn_layer`` (``train.key_nn_fields``)."""
+    from .train import best_fields, clip_fields, image_terms_fields, key_gram_fields, key_nn_fields, layer_list_fields, lr_fields, optim_fields, trace_fields
     at = eng.stopped_at if slot is None else eng.stopped_at[slot]
     return {"steps_run": eng.step_idx + 1 if at is None else at + 1, "stopped_at": at, "ema_decay": eng.ema_rule[0],
-            **clip_fields(eng, slot), **best_fields(eng, slot), **trace_fields(eng), **lr_fields(eng, slot), **optim_fields(eng), **image_terms_fields(eng), **layer_list_fields(eng), **key_gram_fields(eng)}
+            **clip_fields(eng, slot), **best_fields(eng, slot), **trace_fields(eng), **lr_fields(eng, slot), **optim_fields(eng), **image_terms_fields(eng), **layer_list_fields(eng), **key_gram_fields(eng), **key_nn_fields(eng)}
 
 
 def _timed(train, *args, **kw):

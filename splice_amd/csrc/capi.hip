@@ -260,6 +260,19 @@ int splice_key_gram_layers_pairs(int n_layers, const splice_bf16* const* k_x, co
     if (rc != SPLICE_OK) return finish(rc, who);
     return finish(key_gram_layers_dk_launch(t, pairs, 1, ST(stream)), who);
 }
+/* the four launches of the nearest-neighbour key term (splice_step_set_key_nn) on caller buffers, one crop per pair */
+size_t splice_key_nn_ws_bytes(int T, int D, int pairs) { return key_nn_ws_bytes(T, D, pairs); }
+int splice_key_nn_pairs(const splice_bf16* k_x, const splice_bf16* k_b, int ldk, size_t kx_ps, size_t kb_ps, int T, int D, int pairs, float scale,
+                        float eps, int* match, float* cos, float* part, size_t part_ps, float* value, float* dk, int lddk, size_t dk_ps, void* ws,
+                        splice_stream_t stream) {
+    const char* who = "splice_key_nn_pairs";
+    KeyNn a = {};
+    a.k_x = k_x; a.k_b = k_b; a.ldk = ldk; a.kx_ps = kx_ps; a.kb_ps = kb_ps; a.T = T; a.D = D; a.scale = scale; a.eps = eps;
+    a.inv_t = T > 0 ? 1.0f / (float)T : 0.f;
+    a.match = match; a.cos = cos; a.part = part; a.part_ps = part_ps; a.value = value; a.dk = dk; a.lddk = lddk; a.dk_ps = dk_ps; a.ws = ws;
+    if (int rc = key_nn_check(a, pairs, 1)) return finish(rc, who);   // (nothing launched on a refusal)
+    return finish(key_nn_launch(a, pairs, 1, ST(stream)), who);
+}
 int splice_mse_pairs(const float* a, int lda, size_t a_ps, const float* b, int ldb, size_t b_ps, int rows, int cols, float loss_weight,
                      float grad_weight, float* part, size_t part_ps, float* grad, int ldg, size_t g_ps, int pairs, const float* grad_tab,
                      splice_stream_t stream) {

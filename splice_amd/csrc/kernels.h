@@ -270,6 +270,34 @@ int key_gram_layers_check(const KeyGramLayers& t, int pairs, int crops);
 int key_gram_layers_loss_launch(const KeyGramLayers& t, int pairs, int crops, hipStream_t s);
 // dk_i[rows < T] += c_i * (k_x delta_i - 1 (delta_i mu_x)^T) for every entry and slot (the second part where centred)
 int key_gram_layers_dk_launch(const KeyGramLayers& t, int pairs, int crops, hipStream_t s);
+// ---- key_nn.hip: the nearest-neighbour key appearance term ----
+// Slot s = pair * crops + crop pulls every key row of a generated pass towards the most similar key row, in cosine, of its target pass.
+// Both operands are row-major bf16 keys, rows ldk apart: slot s's generated keys at k_x + s * kx_ps, its target keys at k_b + s * kb_ps.
+// Every bf16 pointer, ldk and the slot strides are multiples of 16 bytes, D of 64.  Rows >= T of either array reach no output bit.
+struct KeyNn {
+    const bf16_t* k_x;
+    const bf16_t* k_b;
+    int ldk;
+    size_t kx_ps, kb_ps;
+    int T, D;
+    float scale;       // lambda / T, rounded once on the host
+    float eps;
+    float inv_t;       // 1 / T, rounded once on the host
+    int* match;        // [slots][T]: j*(i)
+    float* cos;        // [slots][T]: c_i,j*(i)
+    float* part;       // slot s's row-kernel partials at part + s * part_ps, key_nn_parts(T) of them, each written exactly once
+    size_t part_ps;
+    float* value;      // [pairs]: the raw term, the pair's crops added in crop order
+    float* dk;         // slot s's key gradient at dk + s * dk_ps, rows lddk apart: ADDED into, rows < T
+    int lddk;
+    size_t dk_ps;
+    void* ws;          // key_nn_ws_bytes(T, D, slots) bytes of scratch: the norms and the column-tile partials
+};
+int key_nn_parts(int T);                             // ceil(T / 4): workgroups of the row launch
+size_t key_nn_ws_bytes(int T, int D, int slots);     // 0: T, D or slots < 1
+int key_nn_check(const KeyNn& a, int pairs, int crops);
+// the four launches: norms, match, row (match, cos, dk, part), finish (value)
+int key_nn_launch(const KeyNn& a, int pairs, int crops, hipStream_t s);
 // 2-D strided MSE: loss_accum[0] += weight * mean((a-b)^2); grad (optional) = weight * 2 (a-b) / (rows*cols)
 int mse_launch(const float* a, int lda, const float* b, int ldb, int rows, int cols, float weight, float* loss_accum,
                float* grad, int ldg, hipStream_t s);

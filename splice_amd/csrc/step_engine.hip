@@ -64,6 +64,10 @@ struct VitView {
     float* dk_kgl[KEY_GRAM_MAX_LAYERS] = {};
     float* dk_kgl_own[KEY_GRAM_MAX_LAYERS] = {};
     std::vector<const float*> pk_x;
+    // splice_step_set_key_nn (global view only): the key-gradient buffer the nearest-neighbour term adds into -- pk_x's of its block (pk's,
+    // or the key second-moment term's own), else one of its own (then also in dk_nn_own, zeroed over its x' passes like dk_kgl_own's)
+    float* dk_nn = nullptr;
+    float* dk_nn_own = nullptr;
 };
 
 // The blocks a per-layer loss term reads and their weights (splice_step_set_ssim_layers, ..._cls_layers, ..._id_layers,
@@ -223,6 +227,13 @@ struct SpliceStep {
     LayerList kg_list;
     int kg_centered = 0;
     float *kg_values = nullptr, *kg_mu = nullptr;
+    // the nearest-neighbour key appearance term (splice_step_set_key_nn): its weight (0: off -- the step launches what
+    // it always did) and block; nn_match / nn_cos: the assignment, [Pc][T]; nn_part: the row launch's partials, [Pc][ceil(T / 4)]; nn_value:
+    // the raw term, [pairs]; nn_ws: the scratch of key_nn.hip
+    float nn_lambda = 0.f;
+    int nn_layer = -1;
+    int* nn_match = nullptr;
+    float *nn_cos = nullptr, *nn_part = nullptr, *nn_value = nullptr, *nn_ws = nullptr;
 };
 
 // the key second-moment term runs over a list of blocks (splice_step_set_key_gram_layers: the list launches) rather than over its one block
@@ -306,6 +317,10 @@ __device__ __forceinline__ float ssim_layer_sum(const float* part, int tiles) {
     for (int i = 0; i < tiles; ++i) acc += part[i];
     return acc;
 }
+// NN (the nearest-neighbour key appearance term): its raw value, nn_values[pair] (the finish launch of key_nn.hip), enters
+// behind that: fmaf(w_nn, raw, total).  With the key second-moment term off the step launches the KG instance on this term's weight and
+// buffer -- the same one fused multiply-add, no new code; with both on, total_loss_nn_kernel below: the same body
+// (total_loss_body.h, included into both) with KG and NN, two arguments more.  total_loss_kernel keeps its name, its arguments and its code.
 template <bool MONITOR, bool TRACE, bool LRP = false, bool IMG = false, bool LYR = false, bool KG = false>
 __global__ __launch_bounds__(IMG ? 448 : 320) void total_loss_kernel(float* lbase, size_t lstride, int lp, float w_ssim, float w_essim, float w_ecls, float w_cls,
                                                          float w_id, float* out8, int n_a, int n_b, int n_c, int n_e, const float* wtab, int ssim_on,
@@ -313,70 +328,21 @@ __global__ __launch_bounds__(IMG ? 448 : 320) void total_loss_kernel(float* lbas
                                                          float* means, float* trace, int capacity, LrRule lr_rule, splice_lr_state* lr_state, int* lr_cuts,
                                                          const float* lr_in, int lr_in_stride, float* lr_eff, float w_tv, float w_pix, int n_layers,
                                                          int tiles_g, int tiles_e, float w_kg, const float* kg_values) {
-    static_assert(MONITOR || !LRP, "the lr rule rides on the stop rule");
-    __shared__ float raw[8];
-    float* l = lbase + (size_t)blockIdx.x * lstride;
-    const int k = 1 + (threadIdx.x >> 6), lane = threadIdx.x & 63;   // wave k-1 owns term k (5 waves; 7 with IMG)
-    const int n_slots = k == L_GLOBAL_SSIM ? n_a : k == L_GLOBAL_ID ? n_b : k == L_GLOBAL_CLS ? n_c : (IMG && k == L_GLOBAL_TV) ? n_a : (IMG && k == L_GLOBAL_PIX) ? n_b : n_e;
-    const float* lp0 = lbase + (size_t)blockIdx.x * n_slots * lstride;   // the pair's first slot of this term
-    float tot = 0.f;
-    for (int slot = 0; slot < n_slots; ++slot) {
-        const float* part = lp0 + (size_t)slot * lstride + 8 + (size_t)k * lp;
-        if (LYR && (k == L_GLOBAL_SSIM || k == L_ENTIRE_SSIM)) {   // (wave-uniform: every lane walks the same slots)
-            const int tiles = k == L_GLOBAL_SSIM ? tiles_g : tiles_e;
-            float v = 0.f;
-            for (int i = 0; i < n_layers; ++i) v += ssim_layer_sum(part + (size_t)i * tiles, tiles);
-            tot += v;
-            continue;
-        }
-        float acc = 0.f;
-        for (int i = lane; i < lp; i += 64) acc += part[i];
-        tot += wave_sum(acc);
-    }
-    const float acc = tot;
-    if (lane == 0) raw[k] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        if (wtab) {
-            const float* w = wtab + (size_t)blockIdx.x * 5;
-            w_cls = w[0];
-            w_ssim = ssim_on ? w[1] : 0.f;
-            w_id = ssim_on ? w[2] : 0.f;
-            w_ecls = entire ? w[3] : 0.f;
-            w_essim = entire ? w[4] : 0.f;
-        }
-        for (int t = 1; t <= 5; ++t) l[t] = raw[t];
-        // (the sum of five products with its contraction spelled out -- one product, then four fused multiply-adds: what the compiler made
-        // of `w_ssim * raw_1 + w_essim * raw_2 + ...` in every instance before the lr rule, and would not make of it in the LRP instances)
-        l[L_TOTAL] = __builtin_fmaf(w_id, raw[L_GLOBAL_ID], __builtin_fmaf(w_cls, raw[L_GLOBAL_CLS], __builtin_fmaf(w_ecls, raw[L_ENTIRE_CLS],
-                         __builtin_fmaf(w_ssim, raw[L_GLOBAL_SSIM], w_essim * raw[L_ENTIRE_SSIM]))));
-        if (IMG) {
-            l[L_GLOBAL_TV] = raw[L_GLOBAL_TV]; l[L_GLOBAL_PIX] = raw[L_GLOBAL_PIX];
-            l[L_TOTAL] = __builtin_fmaf(w_pix, raw[L_GLOBAL_PIX], __builtin_fmaf(w_tv, raw[L_GLOBAL_TV], l[L_TOTAL]));
-        }
-        if (KG) l[L_TOTAL] = __builtin_fmaf(w_kg, kg_values[blockIdx.x], l[L_TOTAL]);
-        if (out8) {   // the caller's losses buffer, written here instead of by a copy behind the step
-            float* o = out8 + (size_t)blockIdx.x * 8;
-            o[0] = l[L_TOTAL];
-            for (int t = 1; t <= 5; ++t) o[t] = raw[t];
-            o[6] = IMG ? raw[L_GLOBAL_TV] : 0.f; o[7] = IMG ? raw[L_GLOBAL_PIX] : 0.f;
-        }
-        if (TRACE) {
-            const int row = *dev_t - 1;
-            if (row >= 0 && row < capacity && !(MONITOR && stop_frozen(stop + blockIdx.x, row))) {
-                float* tr = trace + ((size_t)row * gridDim.x + blockIdx.x) * 8;
-                tr[0] = l[L_TOTAL];
-                for (int t = 1; t <= 5; ++t) tr[t] = raw[t];
-            }
-        }
-        if (LRP)
-            lr_plateau_step(stop + blockIdx.x, lr_state + blockIdx.x, lr_cuts + (size_t)blockIdx.x * SPLICE_STOP_HISTORY, l[L_TOTAL], ssim_on && !entire, rule,
-                            lr_rule, *dev_t - 1, lr_in[(size_t)blockIdx.x * lr_in_stride], lr_eff + blockIdx.x, kb ? kb + blockIdx.x : nullptr,
-                            means ? means + (size_t)blockIdx.x * SPLICE_STOP_HISTORY : nullptr);
-        else if (MONITOR && ssim_on && !entire)
-            plateau_update(stop + blockIdx.x, l[L_TOTAL], rule, *dev_t - 1, kb ? kb + blockIdx.x : nullptr,
-                           means ? means + (size_t)blockIdx.x * SPLICE_STOP_HISTORY : nullptr);
-    }
+    constexpr bool NN = false;
+    constexpr float w_nn = 0.f;
+    constexpr const float* nn_values = nullptr;
+#include "total_loss_body.h"
+}
+// the instance of a step with both key terms
+template <bool MONITOR, bool TRACE, bool LRP = false, bool IMG = false, bool LYR = false>
+__global__ __launch_bounds__(IMG ? 448 : 320) void total_loss_nn_kernel(float* lbase, size_t lstride, int lp, float w_ssim, float w_essim, float w_ecls, float w_cls,
+                                                            float w_id, float* out8, int n_a, int n_b, int n_c, int n_e, const float* wtab, int ssim_on,
+                                                            int entire, splice_stop_state* stop, const int* dev_t, StopRule rule, splice_best_state* kb,
+                                                            float* means, float* trace, int capacity, LrRule lr_rule, splice_lr_state* lr_state, int* lr_cuts,
+                                                            const float* lr_in, int lr_in_stride, float* lr_eff, float w_tv, float w_pix, int n_layers,
+                                                            int tiles_g, int tiles_e, float w_kg, const float* kg_values, float w_nn, const float* nn_values) {
+    constexpr bool KG = true, NN = true;
+#include "total_loss_body.h"
 }
 // the rule alone on a caller's [pairs][8] losses (splice_plateau_update): one thread per slot
 __global__ __launch_bounds__(64) void plateau_update_kernel(splice_stop_state* stop, const float* losses8, int pairs, StopRule rule, int step_idx,
@@ -406,6 +372,17 @@ template <bool KG>
 static TotalLossKernel total_loss_for(bool img, bool layered, bool lr_rule, bool trace, bool stop) {
     return layered ? (img ? total_loss_instance<true, true, KG>(lr_rule, trace, stop) : total_loss_instance<false, true, KG>(lr_rule, trace, stop))
                    : (img ? total_loss_instance<true, false, KG>(lr_rule, trace, stop) : total_loss_instance<false, false, KG>(lr_rule, trace, stop));
+}
+using TotalLossNnKernel = decltype(&total_loss_nn_kernel<false, false>);
+template <bool IMG, bool LYR>
+static TotalLossNnKernel total_loss_nn_instance(bool lr_rule, bool trace, bool stop) {
+    return lr_rule ? (trace ? total_loss_nn_kernel<true, true, true, IMG, LYR> : total_loss_nn_kernel<true, false, true, IMG, LYR>)
+           : trace ? (stop ? total_loss_nn_kernel<true, true, false, IMG, LYR> : total_loss_nn_kernel<false, true, false, IMG, LYR>)
+                   : (stop ? total_loss_nn_kernel<true, false, false, IMG, LYR> : total_loss_nn_kernel<false, false, false, IMG, LYR>);
+}
+static TotalLossNnKernel total_loss_nn_for(bool img, bool layered, bool lr_rule, bool trace, bool stop) {
+    return layered ? (img ? total_loss_nn_instance<true, true>(lr_rule, trace, stop) : total_loss_nn_instance<false, true>(lr_rule, trace, stop))
+                   : (img ? total_loss_nn_instance<true, false>(lr_rule, trace, stop) : total_loss_nn_instance<false, false>(lr_rule, trace, stop));
 }
 // one thread per (layer, pair): the pair's crops' sums of layer i's slot range of `term`, added in crop order (splice_step_ssim_layer_values)
 __global__ __launch_bounds__(64) void ssim_layer_values_kernel(const float* lbase, size_t lstride, int lp, int term, int n_layers, int tiles, int pairs,
@@ -801,7 +778,8 @@ static const char* whole_step_rule(const SpliceStep* st) {
            : st->best ? "that keeps the best weights" : st->trace ? "with a loss trace"
            : (st->lambda_tv > 0.f || st->lambda_pix > 0.f) ? "with image-space loss terms"
            : st->ssim_list.n > 0 ? "with structure layers" : st->cls_list.n > 0 ? "with [CLS] layers"
-           : st->id_list.n > 0 ? "with identity layers" : st->kg_lambda > 0.f ? "with the key second-moment term" : nullptr;
+           : st->id_list.n > 0 ? "with identity layers" : st->kg_lambda > 0.f ? "with the key second-moment term"
+           : st->nn_lambda > 0.f ? "with the nearest-neighbour key term" : nullptr;
 }
 // The shared opening of the rule setters below: before the first step only (`what` of the rule, for the error text), and not on a
 // gradient-only or phase-mode handle.  Callers return its code plainly, not through RC(): the message stays the last error.
@@ -1152,6 +1130,7 @@ int splice_step_set_ssim_layers(void* h, int n, const int* layers, const float* 
     if (st->ssim_list.n) { splice_set_error("%s: the layers are set once", who); return SPLICE_ERR_STATE; }
     if (st->id_list.n) { splice_set_error("%s: call it in front of splice_step_set_id_layers (the identity term shares this list's key-gradient buffers)", who); return SPLICE_ERR_STATE; }
     if (st->kg_lambda > 0.f) { splice_set_error("%s: call it in front of splice_step_set_key_gram (that term shares this list's key-gradient buffers)", who); return SPLICE_ERR_STATE; }
+    if (st->nn_lambda > 0.f) { splice_set_error("%s: call it in front of splice_step_set_key_nn (that term shares this list's key-gradient buffers)", who); return SPLICE_ERR_STATE; }
     const int Tmax = st->plan_e && st->ve.T > st->vg.T ? st->ve.T : st->vg.T;
     for (VitView* v : {&st->vg, &st->ve}) {
         if (!v->ctx) continue;
@@ -1268,6 +1247,7 @@ int splice_step_set_id_layers(void* h, int n, const int* layers, const float* we
     if (int rc = rule_setter_ok(st, who, "the layers are set")) return rc;
     if (st->cfg.fp8_selfsim) { splice_set_error("%s: not with fp8 (the e4m3 forward keeps fp32 keys of the top block alone)", who); return SPLICE_ERR_STATE; }
     if (st->id_list.n) { splice_set_error("%s: the layers are set once", who); return SPLICE_ERR_STATE; }
+    if (st->nn_lambda > 0.f) { splice_set_error("%s: call it in front of splice_step_set_key_nn", who); return SPLICE_ERR_STATE; }
     if (v.D % 4) { splice_set_error("%s: needs an embedding width that is a multiple of 4, got %d", who, v.D); return SPLICE_ERR_ARG; }
     RC(splice_vit_ctx_set_key_f32_layers(v.ctx, n, layers));
     if (int rc = key_grad_buffers(st, v, n, layers, v.dk_id, v.dk_id_own, v.pk_y)) return rc;
@@ -1318,6 +1298,7 @@ int splice_step_set_key_gram(void* h, float lambda, int layer) {
     if (int rc = rule_setter_ok(st, who, "the term is set")) return rc;
     if (st->cfg.fp8_selfsim) { splice_set_error("%s: not with fp8_selfsim (the term reads the bf16 key copies of a bf16 forward)", who); return SPLICE_ERR_STATE; }
     if (st->kg_lambda > 0.f) { splice_set_error("%s: the term is set once", who); return SPLICE_ERR_STATE; }
+    if (st->nn_lambda > 0.f) { splice_set_error("%s: call it in front of splice_step_set_key_nn (that term shares this one's key-gradient buffers)", who); return SPLICE_ERR_STATE; }
     if (v.D % 64) { splice_set_error("%s: needs an embedding width that is a multiple of 64, got %d", who, v.D); return SPLICE_ERR_ARG; }
     if (st->pairs > 1 && st->na != st->nb) { splice_set_error("%s: not with several pairs of nA != nB crops (%d, %d)", who, st->na, st->nb); return SPLICE_ERR_STATE; }
     if (layer != v.depth - 1) RC(splice_vit_ctx_set_transposed_layers(v.ctx, 1, &layer));
@@ -1359,6 +1340,7 @@ int splice_step_set_key_gram_layers(void* h, float lambda, int n, const int* lay
     if (int rc = rule_setter_ok(st, who, "the term is set")) return rc;
     if (st->cfg.fp8_selfsim) { splice_set_error("%s: not with fp8_selfsim (the term reads the bf16 key copies of a bf16 forward)", who); return SPLICE_ERR_STATE; }
     if (st->kg_lambda > 0.f) { splice_set_error("%s: the term is set once", who); return SPLICE_ERR_STATE; }
+    if (st->nn_lambda > 0.f) { splice_set_error("%s: call it in front of splice_step_set_key_nn (that term shares this one's key-gradient buffers)", who); return SPLICE_ERR_STATE; }
     if (v.D % 64) { splice_set_error("%s: needs an embedding width that is a multiple of 64, got %d", who, v.D); return SPLICE_ERR_ARG; }
     if (st->pairs > 1 && st->na != st->nb) { splice_set_error("%s: not with several pairs of nA != nB crops (%d, %d)", who, st->na, st->nb); return SPLICE_ERR_STATE; }
     int below[KEY_GRAM_MAX_LAYERS], nbelow = 0;
@@ -1392,6 +1374,76 @@ int splice_step_key_gram_layer_values(void* h, float* out) {
     if (!st || !out) { splice_set_error("%s: needs a handle and out", who); return SPLICE_ERR_ARG; }
     if (!kg_listed(st)) { splice_set_error("%s: the handle has no key second-moment layers (splice_step_set_key_gram_layers)", who); return SPLICE_ERR_STATE; }
     return values_to_host(out, st->kg_values, (size_t)st->pairs * st->kg_list.n);
+}
+static unsigned long long key_nn_salt(const SpliceStep* st) {
+    if (!(st->nn_lambda > 0.f)) return 0;
+    unsigned w;
+    memcpy(&w, &st->nn_lambda, sizeof(w));
+    // FNV-1a over (block, weight bits), from a basis of its own
+    return fnv1a_word(fnv1a_word(FNV_BASIS ^ 0x165667b19e3779f9ull, (unsigned long long)st->nn_layer), (unsigned long long)w) | 8ull;   // (never 0)
+}
+// The nearest-neighbour key appearance term (include/splice_hip.h has the term): its weight, finite and > 0, and its block.  It reads the
+// row-major bf16 qkv of the block, which every block keeps for its backward: the ViT context needs no call.  The key gradient is ADDED
+// into the block's buffer of the x' chain: pk_x's where the block has one (pk's -- d_keys at the top, the structure list's -- or the key
+// second-moment term's own), else a buffer of its own, zeroed here and over its x' passes at every step the term runs; only the x' chain's
+// backward reads it (pk_x).  Before the first step only; not on a gradient-only or phase-mode handle (which in turn refuses those calls);
+// not with fp8_selfsim; not with several pairs of nA != nB crops; not a second time; and behind the setters of the structure, identity
+// and key second-moment layers where they are called, so that the shared buffers exist.
+int splice_step_set_key_nn(void* h, float lambda, int layer) {
+    SpliceStep* st = (SpliceStep*)h;
+    const char* who = "splice_step_set_key_nn";
+    if (!st) return SPLICE_ERR_ARG;
+    VitView& v = st->vg;
+    if (!(lambda > 0.f) || !(lambda <= 3.402823466e+38f)) { splice_set_error("%s: lambda must be finite and > 0, got %g", who, (double)lambda); return SPLICE_ERR_ARG; }
+    if (layer < 0 || layer >= v.depth) { splice_set_error("%s: layer must be a block index in [0, %d), got %d", who, v.depth, layer); return SPLICE_ERR_ARG; }
+    if (int rc = rule_setter_ok(st, who, "the term is set")) return rc;
+    if (st->cfg.fp8_selfsim) { splice_set_error("%s: not with fp8_selfsim (the term reads the bf16 keys of a bf16 forward)", who); return SPLICE_ERR_STATE; }
+    if (st->nn_lambda > 0.f) { splice_set_error("%s: the term is set once", who); return SPLICE_ERR_STATE; }
+    if (v.D % 64) { splice_set_error("%s: needs an embedding width that is a multiple of 64, got %d", who, v.D); return SPLICE_ERR_ARG; }
+    if (st->pairs > 1 && st->na != st->nb) { splice_set_error("%s: not with several pairs of nA != nB crops (%d, %d)", who, st->na, st->nb); return SPLICE_ERR_STATE; }
+    if (v.pk_x.empty()) v.pk_x = v.pk;
+    if (v.pk_x[layer]) v.dk_nn = const_cast<float*>(v.pk_x[layer]);
+    else {
+        RC(salloc(st, &v.dk_nn_own, (size_t)v.rows * v.D));
+        HIPCHK(hipMemset(v.dk_nn_own, 0, (size_t)v.rows * v.D * sizeof(float)));   // padding rows and every other chain's passes read as zero gradient for good
+        v.pk_x[layer] = v.dk_nn = v.dk_nn_own;
+    }
+    const size_t slots = (size_t)st->pairs * (st->na < st->nb ? st->na : st->nb), parts = (size_t)key_nn_parts(v.T);
+    const size_t ws = key_nn_ws_bytes(v.T, v.D, (int)slots) / sizeof(float);
+    RC(salloc(st, &st->nn_match, slots * v.T));
+    RC(salloc(st, &st->nn_cos, slots * v.T));
+    RC(salloc(st, &st->nn_part, slots * parts));
+    RC(salloc(st, &st->nn_value, (size_t)st->pairs));
+    RC(salloc(st, &st->nn_ws, ws));
+    HIPCHK(hipMemset(st->nn_match, 0, slots * v.T * sizeof(int)));
+    HIPCHK(hipMemset(st->nn_cos, 0, slots * v.T * sizeof(float)));
+    HIPCHK(hipMemset(st->nn_part, 0, slots * parts * sizeof(float)));
+    HIPCHK(hipMemset(st->nn_value, 0, (size_t)st->pairs * sizeof(float)));
+    HIPCHK(hipMemset(st->nn_ws, 0, ws * sizeof(float)));
+    st->graphs.retire();
+    st->nn_lambda = lambda; st->nn_layer = layer;
+    return SPLICE_OK;
+}
+// The raw nearest-neighbour term of the last step that computed it, copied to the HOST behind a device-wide wait: out[p] = pair p's
+// value, `pairs` floats; zeros before the first such step.
+int splice_step_key_nn_values(void* h, float* out) {
+    SpliceStep* st = (SpliceStep*)h;
+    const char* who = "splice_step_key_nn_values";
+    if (!st || !out) { splice_set_error("%s: needs a handle and out", who); return SPLICE_ERR_ARG; }
+    if (!(st->nn_lambda > 0.f)) { splice_set_error("%s: the handle has no nearest-neighbour key term (splice_step_set_key_nn)", who); return SPLICE_ERR_STATE; }
+    return values_to_host(out, st->nn_value, (size_t)st->pairs);
+}
+// ... and its assignment: match / cos, [pairs][crops][T] each (either may be null)
+int splice_step_key_nn_match(void* h, int* match, float* cos) {
+    SpliceStep* st = (SpliceStep*)h;
+    const char* who = "splice_step_key_nn_match";
+    if (!st || (!match && !cos)) { splice_set_error("%s: needs a handle and match or cos", who); return SPLICE_ERR_ARG; }
+    if (!(st->nn_lambda > 0.f)) { splice_set_error("%s: the handle has no nearest-neighbour key term (splice_step_set_key_nn)", who); return SPLICE_ERR_STATE; }
+    const size_t n = (size_t)st->pairs * (st->na < st->nb ? st->na : st->nb) * st->vg.T;
+    HIPCHK(hipDeviceSynchronize());
+    if (match) HIPCHK(hipMemcpy(match, st->nn_match, n * sizeof(int), hipMemcpyDeviceToHost));
+    if (cos) HIPCHK(hipMemcpy(cos, st->nn_cos, n * sizeof(float), hipMemcpyDeviceToHost));
+    return SPLICE_OK;
 }
 // Start the handle at step next_step_idx of a run other handles carried so far (a resumed run, a compacted engine; DESIGN.md section
 // 9g).  What a handle keeps from one step to the next, and this call therefore sets, is two things: ssim_id_on, which only the run of step
@@ -1610,6 +1662,8 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
     const bool id_layered = do_v && t[L_GLOBAL_ID].on && st->id_list.n > 0;
     // the key second-moment term (splice_step_set_key_gram): on the steps of the structure and identity terms, entire-image steps included
     const bool kg_on = do_v && ssim_on && st->kg_lambda > 0.f;
+    // the nearest-neighbour key term (splice_step_set_key_nn): on the same steps
+    const bool nn_on = do_v && ssim_on && st->nn_lambda > 0.f;
     if (do_v) {
         RC(place_passes(vg, src.a_in, c.crop_h, c.crop_w, pA, Pa, s2));
         RC(place_passes(vg, src.b_in, st->cropb_h, st->cropb_w, pB, Pb, s2));
@@ -1623,6 +1677,7 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
         if (kg_on)
             for (float* dk : vg.dk_kgl_own)
                 if (dk) RC(dev_zero_launch(dk + pX * passD, Pa * passD * sizeof(float), s2));
+        if (nn_on && vg.dk_nn_own) RC(dev_zero_launch(vg.dk_nn_own + pX * passD, Pa * passD * sizeof(float), s2));   // likewise the nearest-neighbour term's
         if (t[L_GLOBAL_SSIM].on) {   // target self-similarity S* of A' (util/losses.py:79)
             RC(ssim_batch(st, vg, pA, pX, Pa, t[L_GLOBAL_SSIM], L_GLOBAL_SSIM, &sb, layered ? &sl : nullptr));
             RC(selfsim_target_launch(sb, s2, layered ? &sl : nullptr));
@@ -1680,6 +1735,17 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
             kg.scale = 4.0f * st->kg_lambda / ((float)vg.T * (float)vg.D * (float)vg.D);
             RC(key_gram_loss_launch(kg, pairs, nc, s));
             RC(key_gram_dk_launch(kg, pairs, nc, s));
+        }
+        if (nn_on) {   // every key of x' towards its nearest key of B', crop i with crop i; behind the structure term's store and the key second-moment add
+            bf16_t* qkv = nullptr;
+            RC(splice_vit_get_tensor(vg.ctx, 1, st->nn_layer, (void**)&qkv));
+            KeyNn kn = {};
+            kn.k_x = qkv + (size_t)pX * vg.Tld * 3 * vg.D + vg.D; kn.k_b = qkv + (size_t)pB * vg.Tld * 3 * vg.D + vg.D;
+            kn.ldk = 3 * vg.D; kn.kx_ps = kn.kb_ps = (size_t)vg.Tld * 3 * vg.D;
+            kn.T = vg.T; kn.D = vg.D; kn.scale = st->nn_lambda / (float)vg.T; kn.eps = 1e-8f; kn.inv_t = 1.0f / (float)vg.T;
+            kn.match = st->nn_match; kn.cos = st->nn_cos; kn.part = st->nn_part; kn.part_ps = (size_t)key_nn_parts(vg.T); kn.value = st->nn_value;
+            kn.dk = vg.dk_nn + pX * passD; kn.lddk = vg.D; kn.dk_ps = passD; kn.ws = st->nn_ws;
+            RC(key_nn_launch(kn, pairs, nc, s));
         }
         if (t[L_GLOBAL_CLS].on && st->cls_list.n) {   // [CLS] of the named blocks: one launch for all of them, the call structure of the plain path below
             const int n = st->cls_list.n;
@@ -1762,12 +1828,24 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
             if (id_layered)
                 RC(id_layers_finish_launch(idt, Pb, t[L_GLOBAL_ID].tab, st->id_scratch, 0, st->id_values, (size_t)st->id_list.n, loss_part(st, L_GLOBAL_ID),
                                            st->lstride, q));
-            const auto kernel = kg_on ? total_loss_for<true>(img_on, layered, lrp, trc, stop_on) : total_loss_for<false>(img_on, layered, lrp, trc, stop_on);
-            SPLICE_LAUNCH(kernel, dim3(pairs), dim3(img_on ? 448 : 320), 0, q, st->losses, st->lstride, (int)st->lp, t[L_GLOBAL_SSIM].lambda, t[L_ENTIRE_SSIM].lambda,
-                          t[L_ENTIRE_CLS].lambda, t[L_GLOBAL_CLS].lambda, t[L_GLOBAL_ID].lambda, st->losses_out, grouped ? st->na : n1, grouped ? st->nb : n1, grouped ? nc : n1,
-                          grouped ? 1 : n1, st->pw ? st->pw + (size_t)PW_LAMBDAS * P : nullptr, (int)ssim_on, (int)entire, st->stop, st->dev_t, st->stop_rule, st->best, st->best_means,
-                          st->trace, st->trace_cap, st->lr_rule, st->lr_state, st->lr_cuts, (const float*)(st->pair_lr ? st->dev_lrs : st->dev_lr), st->pair_lr ? 1 : 0,
-                          st->lr_eff, st->lambda_tv, st->lambda_pix, st->ssim_list.n, tri_tiles(vg.T), st->plan_e ? tri_tiles(ve.T) : 0, st->kg_lambda, (const float*)st->kg_value);
+            // the trailing pair (weight, values) of the one key term that is on: the nearest-neighbour term alone rides on the KG instance
+            const bool key_one = kg_on != nn_on;
+            const float w_key = kg_on ? st->kg_lambda : nn_on ? st->nn_lambda : st->kg_lambda;
+            const float* v_key = kg_on ? st->kg_value : nn_on ? st->nn_value : st->kg_value;
+#define TOTAL_LOSS_STEP_ARGS                                                                                                                                         \
+    st->losses, st->lstride, (int)st->lp, t[L_GLOBAL_SSIM].lambda, t[L_ENTIRE_SSIM].lambda, t[L_ENTIRE_CLS].lambda, t[L_GLOBAL_CLS].lambda, t[L_GLOBAL_ID].lambda, \
+        st->losses_out, grouped ? st->na : n1, grouped ? st->nb : n1, grouped ? nc : n1, grouped ? 1 : n1, st->pw ? st->pw + (size_t)PW_LAMBDAS * P : nullptr,     \
+        (int)ssim_on, (int)entire, st->stop, st->dev_t, st->stop_rule, st->best, st->best_means, st->trace, st->trace_cap, st->lr_rule, st->lr_state, st->lr_cuts, \
+        (const float*)(st->pair_lr ? st->dev_lrs : st->dev_lr), st->pair_lr ? 1 : 0, st->lr_eff, st->lambda_tv, st->lambda_pix, st->ssim_list.n, tri_tiles(vg.T),  \
+        st->plan_e ? tri_tiles(ve.T) : 0, w_key, v_key
+            if (kg_on && nn_on) {
+                const auto kernel = total_loss_nn_for(img_on, layered, lrp, trc, stop_on);
+                SPLICE_LAUNCH(kernel, dim3(pairs), dim3(img_on ? 448 : 320), 0, q, TOTAL_LOSS_STEP_ARGS, st->nn_lambda, (const float*)st->nn_value);
+            } else {
+                const auto kernel = key_one ? total_loss_for<true>(img_on, layered, lrp, trc, stop_on) : total_loss_for<false>(img_on, layered, lrp, trc, stop_on);
+                SPLICE_LAUNCH(kernel, dim3(pairs), dim3(img_on ? 448 : 320), 0, q, TOTAL_LOSS_STEP_ARGS);
+            }
+#undef TOTAL_LOSS_STEP_ARGS
         }
         if (!st->running || !gen_fwd) return SPLICE_OK;
         void* plans[3] = {st->plan_a, st->plan_b, nullptr};
@@ -1791,7 +1869,7 @@ static int step_body(SpliceStep* st, float* params, float* grads, float* m, floa
             RC(bookkeeping(s2));
             HIPCHK(hipEventRecord(st->ev(SpliceStep::EV_JOIN2), s2));
         }
-        RC(chain_bwd(vg, pX, pY, true, ip.dx, c.crop_h, c.crop_w, src.dx, st->plan_a, grads, st->accumulate, gen_bwd, L_GLOBAL_TV, L_GLOBAL_CLS, kg_on ? vg.pk_x : vg.pk, s));
+        RC(chain_bwd(vg, pX, pY, true, ip.dx, c.crop_h, c.crop_w, src.dx, st->plan_a, grads, st->accumulate, gen_bwd, L_GLOBAL_TV, L_GLOBAL_CLS, kg_on || nn_on ? vg.pk_x : vg.pk, s));
         if (overlap) HIPCHK(hipStreamWaitEvent(s, st->ev(SpliceStep::EV_JOIN2), 0));
         // grads = g(A) + g(B): folded into the Adam kernel on ordinary steps; a separate add when the entire-image branch
         // still has to accumulate into the sum (same association order either way)
@@ -1960,7 +2038,7 @@ int splice_step_run(void* h, float* params, float* grads, float* m, float* v, co
             // ... and the [CLS] layers: a 64-bit hash of the blocks and their weight bits folded over the word (another loss launch, the seed adds)
             // ... and the identity layers, likewise (two other loss launches, the key-gradient tables of the y' chain, a zeroing launch per own block)
             // ... and the key second-moment term: its block and weight bits (three launches more, a zeroing launch and the x' chain's table)
-            ex = st->graphs.adopt(variant, g, salt ^ cls_layers_salt(st) ^ id_layers_salt(st) ^ key_gram_salt(st));
+            ex = st->graphs.adopt(variant, g, salt ^ cls_layers_salt(st) ^ id_layers_salt(st) ^ key_gram_salt(st) ^ key_nn_salt(st));
             if (!ex) return SPLICE_ERR_HIP;
         }
         HIPCHK(hipGraphLaunch(ex, s));

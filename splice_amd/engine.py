@@ -92,6 +92,16 @@ class MultiPairEngine:
             if len(gen_states) > 1 and nA_ != nB_:
                 raise ValueError(f"'lambda_global_key_gram': not with several pairs of different crop counts per side, got n_crops = {(nA_, nB_)}")
             self.cfg.update(lambda_global_key_gram=self.key_gram[0], dino_gram_layer=None if self.key_gram_layers is not None else self.key_gram[1])
+        # the nearest-neighbour key appearance term: None -- off, today's launches -- or (lambda, block); the config then
+        # holds the block it runs on (what a snapshot is compared on)
+        self.key_nn = key_nn_rule(self.cfg, depth)
+        if self.key_nn is not None:
+            if fp8_mode(fp8):
+                raise ValueError("'lambda_global_key_nn': not with fp8 -- the term reads the bf16 keys of a bf16 forward")
+            nA_, nB_ = (int(n_crops), int(n_crops)) if isinstance(n_crops, int) else (int(n_crops[0]), int(n_crops[1]))
+            if len(gen_states) > 1 and nA_ != nB_:
+                raise ValueError(f"'lambda_global_key_nn': not with several pairs of different crop counts per side, got n_crops = {(nA_, nB_)}")
+            self.cfg.update(lambda_global_key_nn=self.key_nn[0], dino_nn_layer=self.key_nn[1])
         P_in = len(gen_states)
         self.cfgs = [self.cfg] * P_in
         self._pair_lambdas = self._pair_lr = False
@@ -279,6 +289,10 @@ class MultiPairEngine:
                        "step_set_key_gram_layers")
         elif self.key_gram is not None:
             _lib.check(_lib.lib().splice_step_set_key_gram(self.handle, C.c_float(self.key_gram[0]), int(self.key_gram[1])), "step_set_key_gram")
+        # the nearest-neighbour key term (shared by the slots): four launches on the x' chain from cls_warmup on; before the first step, behind
+        # the setters above (shared key-gradient buffers).  The default: the call is not made
+        if self.key_nn is not None:
+            _lib.check(_lib.lib().splice_step_set_key_nn(self.handle, C.c_float(self.key_nn[0]), int(self.key_nn[1])), "step_set_key_nn")
         self._lr_scale = [1.0] * P   # the host's copy of every slot's lr scale, refreshed with the stop steps
         self._stopped = [None] * P   # the host's copy of every slot's stop step, refreshed by stop_state()
         self._stop_dirty = False     # a window has closed since the last stop_state(): the copy may be behind
@@ -634,7 +648,47 @@ class MultiPairEngine:
                 row = self._row(p)
                 if row is not None:
                     d[KEY_GRAM_LOSS_KEY] = float(vals[row])
+        if self.key_nn is not None and key_nn_active(self.cfg, self.step_idx):   # (likewise the nearest-neighbour term's)
+            vals = self._key_nn_host()
+            for p, d in enumerate(out):
+                row = self._row(p)
+                if row is not None:
+                    d[KEY_NN_LOSS_KEY] = float(vals[row])
         return self._pick(out, pair)
+
+    def _key_nn_host(self):
+        buf = (C.c_float * self.P)()
+        _lib.check(_lib.lib().splice_step_key_nn_values(self.handle, buf), "step_key_nn_values")
+        return np.frombuffer(buf, dtype=np.float32).copy()
+
+    def _key_nn_row(self, pair, who):
+        if self.key_nn is None:
+            raise RuntimeError(f"{who}: the term is off ('lambda_global_key_nn' is 0)")
+        if pair is None and self.PAIR_NONE is None:
+            return None
+        row = self._row(self.PAIR_NONE if pair is None else pair)
+        if row is None:
+            raise RuntimeError(f"{who}: slot {pair} is parked (stop_compact): its value left the device with its handle")
+        return row
+
+    def key_nn_value(self, pair=None):
+        """The raw nearest-neighbour key term (``lambda_global_key_nn``) of the last step that computed it, copied from
+        the device (waits for the device): ``mean over the tokens of 1 - cos(k_i, b_j*(i))``, summed over the pair's zipped crops -- the
+        total, word 0 of the losses row, holds ``lambda`` times it.  0 before the first such step.  One float for ``pair``, a list over the
+        live slots for ``pair=None``."""
+        row = self._key_nn_row(pair, "key_nn_value")
+        vals = [float(v) for v in self._key_nn_host()]
+        return vals if row is None else vals[row]
+
+    def key_nn_match(self, pair=None):
+        """The assignment of that step, copied from the device (waits for the device): ``(match, cos)``, an int32 and a float32 array
+        ``[crops][T]`` for ``pair`` (``[slots][crops][T]`` over the live slots for ``pair=None``): ``match[c][i]`` the token of crop c of the
+        target pass that key i of G(A_crop c) was pulled towards -- the lowest index among the most similar -- and ``cos`` that cosine."""
+        row = self._key_nn_row(pair, "key_nn_match")
+        nc, T = (min(self.n_crops_ab) if self.n_crops > 1 else 1), self.ctx_g.T
+        m, c = np.zeros((self.P, nc, T), np.int32), np.zeros((self.P, nc, T), np.float32)
+        _lib.check(_lib.lib().splice_step_key_nn_match(self.handle, m.ctypes.data_as(C.c_void_p), c.ctypes.data_as(C.c_void_p)), "step_key_nn_match")
+        return (m, c) if row is None else (m[row], c[row])
 
     def _key_gram_host(self):
         buf = (C.c_float * self.P)()
@@ -896,6 +950,9 @@ class MultiScaleEngine:
         key_gram_layers_rule(self.cfg, depth)   # (a bad value is refused by name here too)
         if key_gram_rule(dict(self.cfg, dino_gram_layer=None if self.cfg.get("dino_gram_layers") is not None else self.cfg.get("dino_gram_layer")), depth) is not None:
             raise NotImplementedError("lambda_global_key_gram: the term is set on a whole fused step; MultiScaleEngine runs each scale as a gradient-only "
+                                      "or phase-mode handle, which refuses it")
+        if key_nn_rule(self.cfg, depth) is not None:
+            raise NotImplementedError("lambda_global_key_nn: the term is set on a whole fused step; MultiScaleEngine runs each scale as a gradient-only "
                                       "or phase-mode handle, which refuses it")
         self.ema_rule = ema_rule(self.cfg)
         self.ema = None

@@ -8,8 +8,8 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
-from .engine import (CLS_LAYER_KEYS, ID_LAYER_KEYS, KEY_GRAM_KEYS, KEY_GRAM_LAYER_KEYS, KEY_GRAM_LOSS_KEY, SSIM_LAYER_KEYS, cls_layers_rule, id_layers_rule,
-                     key_gram_canonical, key_gram_layers_rule, key_gram_rule, resize_output_size, ssim_layers_rule)
+from .engine import (CLS_LAYER_KEYS, ID_LAYER_KEYS, KEY_GRAM_KEYS, KEY_GRAM_LAYER_KEYS, KEY_GRAM_LOSS_KEY, KEY_NN_KEYS, KEY_NN_LOSS_KEY, SSIM_LAYER_KEYS,
+                     cls_layers_rule, id_layers_rule, key_gram_canonical, key_gram_layers_rule, key_gram_rule, key_nn_rule, resize_output_size, ssim_layers_rule)
 from .extractor import VitExtractor
 from .synth import DINO_CONFIGS
 
@@ -107,6 +107,8 @@ class LossG(torch.nn.Module):
         kg_cfg.update(key_gram_canonical(kg_cfg, DINO_CONFIGS[cfg['dino_model_name']][2]))
         self.key_gram_layers = key_gram_layers_rule(kg_cfg, DINO_CONFIGS[cfg['dino_model_name']][2])
         self.key_gram = key_gram_rule(kg_cfg, DINO_CONFIGS[cfg['dino_model_name']][2])
+        # ... and the nearest-neighbour key appearance term: None -- off -- or (lambda, block)
+        self.key_nn = key_nn_rule({k: cfg[k] for k in KEY_NN_KEYS if k in cfg}, DINO_CONFIGS[cfg['dino_model_name']][2])
         self._features = {
             "self_sim": lambda img: self.extractor.get_keys_self_sim_from_input(img, layer_num=_LAST_LAYER),
             "cls": lambda img: self.extractor.get_feature_from_input(img)[-1][0, 0, :],
@@ -143,8 +145,31 @@ class LossG(torch.nn.Module):
         if self.key_gram is not None and int(inputs['step']) >= self.cfg['cls_warmup']:
             losses[KEY_GRAM_LOSS_KEY] = self.calculate_key_gram_loss(outputs['x_global'], inputs['B_global'])
             total = total + self.key_gram[0] * losses[KEY_GRAM_LOSS_KEY]
+        # the nearest-neighbour key term, on the same steps, behind it
+        if self.key_nn is not None and int(inputs['step']) >= self.cfg['cls_warmup']:
+            losses[KEY_NN_LOSS_KEY] = self.calculate_key_nn_loss(outputs['x_global'], inputs['B_global'])
+            total = total + self.key_nn[0] * losses[KEY_NN_LOSS_KEY]
         losses['loss'] = total
         return losses
+
+    def calculate_key_nn_loss(self, generated, targets, eps=1e-8):
+        """The raw nearest-neighbour key term: sum over the zipped crops of mean over the tokens i of 1 - max_j cos(k_i, b_j), k / b the T x D
+        keys of block ``dino_nn_layer`` (every token, the heads concatenated) of the generated and of the target crop, the cosine as the key
+        self-similarity forms it (the product of the norms clamped at ``eps``); target side under no_grad.  ``max`` hands the gradient to
+        the first index among equals, the engine's choice."""
+        layer = self.key_nn[1] if self.key_nn is not None else DINO_CONFIGS[self.cfg['dino_model_name']][2] - 1
+
+        def keys(img):
+            per_head = self.extractor.get_keys_from_input(img, layer_num=layer)   # [heads, T, d]
+            return per_head.permute(1, 0, 2).reshape(per_head.shape[1], -1)       # [T, heads * d]
+        acc = 0.0
+        for gen_img, tgt_img in zip(generated, targets):
+            with torch.no_grad():
+                b = keys(self.global_transform(tgt_img).unsqueeze(0).to(device))
+            k = keys(self.global_transform(gen_img).unsqueeze(0).to(device))
+            cos = (k @ b.transpose(0, 1)) / torch.clamp(k.norm(dim=1)[:, None] * b.norm(dim=1)[None, :], min=eps)
+            acc = acc + (1.0 - cos.max(dim=1).values).mean()
+        return acc
 
     def calculate_key_gram_loss(self, generated, targets):
         """The raw key second-moment term: sum over the zipped crops of mean((G(K_gen) - G(K_tgt))^2) over the D * D entries, G(K) = K^T K / T of

@@ -56,7 +56,10 @@ DEFAULT_CFG = dict(  # conf/default/config.yaml of the reference
     # ... and the key second-moment appearance term (the D x D Gram of a block's keys over its tokens): its weight and block; off by default
     lambda_global_key_gram=0.0, dino_gram_layer=None,
     # ... over a list of blocks with a weight each, and its centred (covariance) form; null / false: the one-block uncentred term
-    dino_gram_layers=None, dino_gram_layer_weights=None, dino_gram_centered=False)
+    dino_gram_layers=None, dino_gram_layer_weights=None, dino_gram_centered=False,
+    # ... and the nearest-neighbour key appearance term (every key of G(A_crop) towards its most similar key of the B crop, in cosine;
+    # DESIGN.md section 9p): its weight and block; off by default
+    lambda_global_key_nn=0.0, dino_nn_layer=None)
 # The three plain per-layer terms -- a list of blocks with a weight each and nothing else -- in the order the engine sets them (the identity
 # list behind the structure list, whose key-gradient buffers it shares).  keys: the two config keys; most: entries of the term's by-value
 # kernel table (SELFSIM_MAX_LAYERS / CLS_MAX_LAYERS / ID_MAX_LAYERS); attr: the engine attribute that holds the canonical (layers,
@@ -75,6 +78,9 @@ KEY_GRAM_KEYS = ("lambda_global_key_gram", "dino_gram_layer")
 KEY_GRAM_LAYER_KEYS = ("dino_gram_layers", "dino_gram_layer_weights", "dino_gram_centered")
 MAX_KEY_GRAM_LAYERS = 12   # KEY_GRAM_MAX_LAYERS: entries of the layered key second-moment kernels' by-value table
 KEY_GRAM_LOSS_KEY = "loss_global_key_gram"   # the term's raw value in engine.losses(), on the steps it is active
+
+KEY_NN_KEYS = ("lambda_global_key_nn", "dino_nn_layer")
+KEY_NN_LOSS_KEY = "loss_global_key_nn"   # the term's raw value in engine.losses(), on the steps it is active
 
 SNAPSHOT_FORMAT = 1
 # Keys of a config that do not enter a slot's arithmetic (paths, logging, and how the loop parks and checkpoints): a snapshot is restored
@@ -308,6 +314,52 @@ def key_gram_rule(c, depth):
     if lam == 0:
         raise ValueError(f"'{yk}' needs '{lk}' > 0 (the term is off), got {layer!r}")
     return float(lam), int(layer)
+
+
+def key_nn_rule(c, depth):
+    """The nearest-neighbour key appearance term in config ``c`` for a ViT of ``depth`` blocks, checked on the host:
+    ``None`` -- ``lambda_global_key_nn`` is 0 and ``dino_nn_layer`` null: the step launches what it launches without the keys -- or
+    ``(lambda, layer)``.  ``lambda_global_key_nn`` is a finite float32 number >= 0 (0: off); ``dino_nn_layer`` one integer block index in
+    ``[0, depth)`` (null: ``depth - 1``, the top block), refused while the weight is 0.  Shared by the slots of a sweep
+    (``merge_pair_cfgs`` refuses a per-slot value).  Raises ValueError naming the key."""
+    lk, yk = KEY_NN_KEYS
+    lam = _number(c, lk, _REAL, lambda v: 0 <= v < float("inf"), "a finite number >= 0")
+    with np.errstate(over="ignore"):
+        if not np.isfinite(np.float32(lam)) or (lam > 0 and not np.float32(lam) > 0):   # (the kernels take it as a float)
+            raise ValueError(f"'{lk}' must be a finite float32 number, 0 or > 0 in float32, got {lam!r}")
+    layer = c.get(yk, DEFAULT_CFG[yk])
+    if layer is None:
+        return None if lam == 0 else (float(lam), depth - 1)
+    if isinstance(layer, bool) or not isinstance(layer, _INT) or not 0 <= layer < depth:
+        raise ValueError(f"'{yk}' must be one integer block index in [0, {depth}) or null, got {layer!r}")
+    if lam == 0:
+        raise ValueError(f"'{yk}' needs '{lk}' > 0 (the term is off), got {layer!r}")
+    return float(lam), int(layer)
+
+
+def np_key_nn(kx, kb, lam, eps=1e-8, match=None):
+    """The nearest-neighbour key term restated in NumPy float64: ``kx``, ``kb`` the ``[T][D]`` keys of the generated
+    and of the target pass (every token, the heads concatenated).  With ``c_ij = kx_i . kb_j / max(|kx_i| |kb_j|, eps)`` and ``m(i)`` the
+    lowest ``j`` among those with the largest ``c_ij`` -- or ``match`` where given: that assignment instead of the arg-max -- returns
+    ``(raw, m, cos, dK)``: ``cos[i] = c_i,m(i)``, ``raw = mean(1 - cos)``, ``dK`` the gradient of ``lam * raw`` with respect to ``kx`` as
+    autograd takes it through ``clamp`` and ``max``: ``dK_i = -(lam / T) (kb_m / f - [n_i n_m > eps] cos_i kx_i / n_i^2)``,
+    ``f = max(n_i n_m, eps)``.  The target carries no gradient."""
+    kx, kb = np.asarray(kx, np.float64), np.asarray(kb, np.float64)
+    T = kx.shape[0]
+    nx, nb = np.sqrt((kx * kx).sum(1)), np.sqrt((kb * kb).sum(1))
+    if match is None:
+        c = (kx @ kb.T) / np.maximum(np.outer(nx, nb), eps)
+        m = np.argmax(c, axis=1)   # (the first occurrence: the lowest index among equals)
+    else:
+        m = np.asarray(match, np.int64)
+    bm, nm = kb[m], nb[m]
+    prod = nx * nm
+    f = np.maximum(prod, eps)
+    cos = (kx * bm).sum(1) / f
+    with np.errstate(divide="ignore", invalid="ignore"):
+        own = np.where(prod > eps, cos / np.where(nx > 0, nx * nx, 1.0), 0.0)
+    dK = -(float(lam) / T) * (bm / f[:, None] - own[:, None] * kx)
+    return float(np.mean(1.0 - cos)), m.astype(np.int64), cos, dK
 
 
 def key_gram_layers_rule(c, depth):
@@ -735,6 +787,12 @@ def key_gram_active(c, step_idx):
     """Whether step ``step_idx`` of a run with config ``c`` computes the key second-moment term (KEY_GRAM_LOSS_KEY; host arithmetic only):
     from ``cls_warmup`` on, ordinary and entire-image steps alike, with its lambda > 0.  Beside ``active_terms``, whose dict keeps its keys."""
     return step_idx >= c["cls_warmup"] and c.get("lambda_global_key_gram", 0.0) > 0
+
+
+def key_nn_active(c, step_idx):
+    """Whether step ``step_idx`` of a run with config ``c`` computes the nearest-neighbour key term (KEY_NN_LOSS_KEY; host arithmetic only):
+    the steps of the key second-moment term -- from ``cls_warmup`` on, ordinary and entire-image steps alike -- with its lambda > 0."""
+    return step_idx >= c["cls_warmup"] and c.get("lambda_global_key_nn", 0.0) > 0
 
 
 def resize_output_size(h, w, size, max_size=480):

@@ -444,6 +444,13 @@ def key_gram_fields(engine):
     return {} if rule is None else {"lambda_global_key_gram": rule[0], "dino_gram_layer": rule[1]}
 
 
+def key_nn_fields(engine):
+    """What ``result.json`` / ``variant.json`` say about the nearest-neighbour key appearance term of a run (shared by the slots; DESIGN.md
+    section 9p): ``lambda_global_key_nn`` and the block it ran on, ``dino_nn_layer``, where the term was on."""
+    rule = getattr(engine, "key_nn", None)
+    return {} if rule is None else {"lambda_global_key_nn": rule[0], "dino_nn_layer": rule[1]}
+
+
 def best_fields(engine, slot=None):
     """What ``result.json`` says about the stop rule's windows (``splice_amd.batch``) of a run with ``stop_keep_best``: ``best_step`` (the
     step whose weights ``output_best.png`` shows; None: no window closed, they are the initial weights), ``best_window_mean`` and
@@ -579,7 +586,7 @@ def train_sweep(dataroot, variants, cfg_overrides=None, vit_state=None, callback
     losses = engine.losses() if engine.step_idx >= 0 else [{} for _ in range(K)]
     for k in range(K):
         with open(os.path.join(out_dirs[k], 'variant.json'), 'w') as f:
-            json.dump({"index": k, "overrides": variants[k], "seed": seeds[k], "losses": losses[k], "stopped_at": engine.stopped_at[k], **trace_fields(engine), **lr_fields(engine, k), **optim_fields(engine), **image_terms_fields(engine), **layer_list_fields(engine), **key_gram_fields(engine)}, f)
+            json.dump({"index": k, "overrides": variants[k], "seed": seeds[k], "losses": losses[k], "stopped_at": engine.stopped_at[k], **trace_fields(engine), **lr_fields(engine, k), **optim_fields(engine), **image_terms_fields(engine), **layer_list_fields(engine), **key_gram_fields(engine), **key_nn_fields(engine)}, f)
     return engine
 
 
